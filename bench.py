@@ -20,9 +20,14 @@ kernels.
 
 Prints ONE JSON line on rank 0 (see the driver contract): value = candidate sites (pileup columns evaluated) per
 second, whole job, over the full step time; roofline = the pileup stage's algorithmic bytes / its HIP-event time
-(k1 alone beside it), roofline.traffic = HBM bytes of the stage's kernels from two rocprofv3 --pmc passes run by this
-script over the same batch; cpu_baseline = the CPU oracle (a C++ restatement of the reference, NOT the Rust binary) on a
-native thread pool over the same batch, rank 0 at N = 1 only.
+(k1 alone beside it), from the events of the timed steps.
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds everything else, as
+the line had it before: roofline.traffic = HBM bytes of the stage's kernels from two rocprofv3 --pmc passes run by this
+script over the same batch, roofline.isolated, `stages` (per-call and per-kernel times of extra passes, the side
+workloads) and cpu_baseline = the CPU oracle (a C++ restatement of the reference, NOT the Rust binary) on a native
+thread pool over the same batch, rank 0 at N = 1 only; --quick / --no-extras / --no-traffic / --no-cpu-baseline trim it.
+--dump-outputs DIR: what the last timed step delivered to its caller, one float64 DIR/<name>.npy per array (seeded
+inputs: two builds compare output for output).
 --inflight N: N contexts on N host threads keep N batches in flight per GPU (default 1).
 """
 import argparse
@@ -166,6 +171,39 @@ def run_steps_simple(E, dev_batch, n, sink=None, have=None, stamps=None):
         consume(E.collect_phase(), sink); have[0] = False
     E.sync()
     return sink
+
+
+DUMP_BYTES = 60 * 10 ** 6   # (--dump-outputs: under 64 MB in all with the .npy headers)
+
+
+def record_columns(prefix, rec):
+    """One array per field of a structured record array (padding fields left out)."""
+    return {"%s_%s" % (prefix, f): rec[f] for f in rec.dtype.names if not f.endswith("_")}
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES, seed=0):
+    """Writes every array as <path>/<name>.npy in float64 (the integers here are exact in it), every value finite: an array with
+    non-finite entries (GQ is +inf where two genotype probabilities underflow to 0, candidate.rs:330-335) has them written as 0
+    and gets <path>/<name>_nonfinite.npy beside it (float32, same shape: 0 finite, 1 +inf, -1 -inf, 2 NaN).  Above `budget`
+    bytes in all, the offset arrays (*_off) stay whole and every other array keeps the same fraction of its rows, drawn from a
+    fixed seed and kept in order; arrays with the same number of rows (the fields of one record type) keep the same rows.
+    The same outputs give the same files.  Returns the bytes of the full outputs."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    for name in sorted(arrays):
+        v = arrays[name]
+        if not np.isfinite(v).all():
+            arrays[name + "_nonfinite"] = np.select([np.isnan(v), v == np.inf, v == -np.inf], [2, 1, -1], 0).astype(np.float32)
+            arrays[name] = np.where(np.isfinite(v), v, 0.0)
+    total = sum(v.nbytes for v in arrays.values())
+    whole = sum(v.nbytes for k, v in arrays.items() if k.endswith("_off"))
+    keep = min(1.0, max(budget - whole, 0) / max(total - whole, 1)) if total > budget else 1.0
+    for name, v in sorted(arrays.items()):
+        if keep < 1.0 and not name.endswith("_off") and v.ndim and v.shape[0] > 1:
+            idx = np.sort(np.random.default_rng(seed).choice(v.shape[0], max(1, int(v.shape[0] * keep)), replace=False))
+            v = v[idx]
+        np.save(os.path.join(path, name + ".npy"), v)
+    return total
 
 
 def step_stats(stamps, t0):
@@ -618,10 +656,15 @@ def main():
     ap.add_argument("--seed", type=int, default=1, help="generator seed of the synthetic genes (SURVEY §8(d): seeds 1..5)")
     ap.add_argument("--gene-len", type=int, default=None)
     ap.add_argument("--depth", type=float, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beside the headline figure: roofline.traffic / isolated, `stages` (extra passes "
+                         "and side workloads), cpu_baseline; the four options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (what its caller receives) as float64 DIR/<name>.npy, under 64 MB in all")
     ap.add_argument("--no-c5", action="store_true", help="alias of --no-extras")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline workload (+ cpu_baseline, + traffic)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline workload (+ cpu_baseline, + traffic)")
     ap.add_argument("--quick", action="store_true", help="--no-extras --no-cpu-baseline --no-traffic")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes behind roofline.traffic")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the two rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: smoke-test the N > 1 path on a box with fewer GPUs than ranks (ranks share GPUs, records travel "
                          "through host memory); the numbers of such a run mean nothing")
@@ -652,8 +695,10 @@ def main():
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        # (the ranks are child processes: this one has opened the GPU runtime to count the devices)
+        r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
+                            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(128 - r.returncode if r.returncode < 0 else r.returncode)   # (killed by signal N: 128 + N, as a shell reports it)
 
     rank = int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -712,6 +757,7 @@ def main():
     gstat = {"wait_s": 0.0, "bytes": 0, "batches": 0}   # this rank's share of the final gathers: time spent waiting for them, bytes sent
 
     sink, have, stamps = [0, 0, 0], {}, []   # results read per step (consume), "this context has a batch's results to collect"
+    last = {}   # the last batch's results as the caller receives them, per context (N > 1: "gathered"), for --dump-outputs
 
     def step(Ej):
         # bind batch k, queue its pileup, collect and read batch k - 1's results (lcr_collect_phase: the pipelined getter, valid across the
@@ -727,9 +773,10 @@ def main():
         return (Ej.kernel_ms(_abi.K_PILEUP), Ej.kernel_ms(_abi.K_SPANS) + Ej.kernel_ms(_abi.K_BIND) + Ej.kernel_ms(_abi.K_BIND_TABLE))
 
     def collect_last():   # the last batch's results: collected and read before the clock stops
-        for Ej in engines:
+        for j, Ej in enumerate(engines):
             if G is None and have.get(id(Ej)):
-                consume(Ej.collect_phase(), sink)
+                last[j] = Ej.collect_phase()
+                consume(last[j], sink)
                 have[id(Ej)] = False
 
     def read_records_host(Ej):
@@ -761,6 +808,7 @@ def main():
             gstat["wait_s"] += time.perf_counter() - tw
             if c is not None:
                 gathered[0], gathered[1] = int(c.size), int(r.size)
+                last["gathered"] = (c, r)
             pending[0] = None
 
     def run_steps(n):
@@ -854,37 +902,48 @@ def main():
                     "backend": dist.get_backend(), "world_size": int(dist.get_world_size()),
                     "note": "ms_per_step = a rank's own K steps incl. its share of the gathers, before the closing barrier; `value` uses the slowest rank"}
 
-    # stage breakdown (untimed extra pass: wall clock per ABI call with a sync after each, + HIP events)
+    if a.dump_outputs and rank == 0:   # before anything else runs on the contexts: the collected arrays are their buffers
+        if "gathered" in last:
+            res = dict(record_columns("cand", last["gathered"][0]), **record_columns("read", last["gathered"][1]))
+        else:
+            res = dict(last[(a.steps - 1) % F])   # (pass k runs on context k mod F)
+            res.update(record_columns("cand", res.pop("cand")))
+            del res["dev_cand"], res["dev_read_rec"]
+        dump_outputs(a.dump_outputs, res)
+
     step_ms = step_stats(stamps, t0) if (F == 1 and stamps) else None
     collected = (sink[0] // max(sink[2], 1), sink[1] // max(sink[2], 1), sink[2])
     if G is None and F == 1:
         assert sink[2] == a.steps, (sink, a.steps)
     iso_ms = None
-    if async_phase:   # the pileup stage's kernels once more WITHOUT the previous step's tails beside them: five synchronous steps
-        E.set_async_phase(False)
-        iso = [step(E) for _ in range(5)]
-        E.sync()
-        iso_ms = float(np.mean([t[0] + t[1] for t in iso[1:]]))
-    api_ms = {}
-    def timed(name, fn):
-        ts = time.perf_counter(); fn(); E.sync(); api_ms[name] = (time.perf_counter() - ts) * 1e3
-    timed("lcr_load_batch", lambda: E.load_batch((reads, regions, keep)))
-    timed("lcr_pileup", E.fill_data_into_freq_vec)
-    timed("lcr_candidates", E.get_candidate_snps)
-    timed("lcr_fragments", E.get_fragments)
-    timed("lcr_phase", E.phase)
-    t_call = (api_ms["lcr_load_batch"] + api_ms["lcr_pileup"] + api_ms["lcr_candidates"]) * 1e-3
-    t_phase = (api_ms["lcr_fragments"] + api_ms["lcr_phase"]) * 1e-3
-    fm = E.fragmat()
+    if a.full:
+        # stage breakdown (untimed extra pass: wall clock per ABI call with a sync after each, + HIP events)
+        if async_phase:   # the pileup stage's kernels once more WITHOUT the previous step's tails beside them: five synchronous steps
+            E.set_async_phase(False)
+            iso = [step(E) for _ in range(5)]
+            E.sync()
+            iso_ms = float(np.mean([t[0] + t[1] for t in iso[1:]]))
+        api_ms = {}
+        def timed(name, fn):
+            ts = time.perf_counter(); fn(); E.sync(); api_ms[name] = (time.perf_counter() - ts) * 1e3
+        timed("lcr_load_batch", lambda: E.load_batch((reads, regions, keep)))
+        timed("lcr_pileup", E.fill_data_into_freq_vec)
+        timed("lcr_candidates", E.get_candidate_snps)
+        timed("lcr_fragments", E.get_fragments)
+        timed("lcr_phase", E.phase)
+        t_call = (api_ms["lcr_load_batch"] + api_ms["lcr_pileup"] + api_ms["lcr_candidates"]) * 1e-3
+        t_phase = (api_ms["lcr_fragments"] + api_ms["lcr_phase"]) * 1e-3
+    fm = E.fragmat()   # (plain run: the last timed step's batch, still bound)
     n_phased = int(fm["row_for_phasing"].sum())
     cands = E.candidates()[0]
-    E.debug_set("timing_mask", 0)   # one more step with every kernel group timed
-    step(E)
-    E.sync()
-    kms = {n: E.kernel_ms(k) for n, k in (("k0_ops", _abi.K_SPANS), ("k1_tiles_bin_pileup", _abi.K_PILEUP),
-                                          ("k2_filter", _abi.K_CAND_FILTER), ("k2_hist", _abi.K_CAND_HIST),
-                                          ("k2_gt", _abi.K_CAND_GT), ("k3_count", _abi.K_FRAG_COUNT),
-                                          ("k3_fill", _abi.K_FRAG_FILL))}
+    if a.full:
+        E.debug_set("timing_mask", 0)   # one more step with every kernel group timed
+        step(E)
+        E.sync()
+        kms = {n: E.kernel_ms(k) for n, k in (("k0_ops", _abi.K_SPANS), ("k1_tiles_bin_pileup", _abi.K_PILEUP),
+                                              ("k2_filter", _abi.K_CAND_FILTER), ("k2_hist", _abi.K_CAND_HIST),
+                                              ("k2_gt", _abi.K_CAND_GT), ("k3_count", _abi.K_FRAG_COUNT),
+                                              ("k3_fill", _abi.K_FRAG_FILL))}
 
     # whole-job totals (the shards of an LPT partition differ slightly in size)
     tot = np.array([int(batch.col_off[-1]), int(batch.bases.size), batch.n_reads, int(cands.size), int(fm["col"].size), n_phased], dtype=np.int64)
@@ -894,8 +953,8 @@ def main():
         tot = tt.cpu().numpy()
     if rank == 0:
         cols = int(batch.col_off[-1])
-        # covered sites (depth >= min_depth on A+C+G+T, candidate.rs:90-94) of this rank's batch
-        covered = int((E.columns()[:4].sum(axis=0) >= params.min_depth).sum())
+        if a.full:   # covered sites (depth >= min_depth on A+C+G+T, candidate.rs:90-94) of this rank's batch
+            covered = int((E.columns()[:4].sum(axis=0) >= params.min_depth).sum())
         pbytes = E.pileup_bytes()
         avg_ms = float(np.mean([t[0] for t in pile_ms]))
         avg_k0_ms = float(np.mean([t[1] for t in pile_ms]))
@@ -906,8 +965,8 @@ def main():
         n_items = int((pbytes - int(batch.bases.size) - 53 * cols) // 8)
         for Ej in engines[1:]:
             Ej.close()
-        traffic, traffic_note = (None, "skipped (--no-traffic, or N > 1)")
-        if world == 1 and not a.no_traffic:
+        traffic, traffic_note = (None, "skipped (--no-traffic, or N > 1)" if a.full else "not measured (bench.py --full)")
+        if a.full and world == 1 and not a.no_traffic:
             traffic, traffic_note = measure_traffic(batch, preset)
         out = {
             "metric": "candidate_sites_per_sec", "value": int(tot[0]) * a.steps / dt, "unit": "sites/s",
@@ -934,7 +993,7 @@ def main():
                                        "behind its restarts and runs beside its resolve / post-phase tails; every batch's results collected by lcr_collect_phase before the next lcr_candidates); "
                                        "GPU_MAX_HW_QUEUES=%s" % os.environ.get("GPU_MAX_HW_QUEUES")) if async_phase else "synchronous",
                        "scaling_reference": ("the N = 1 point of THIS workload (one GPU's 1 000-gene share of C4) is `stages.c4_share.sites_per_sec` of the "
-                                             "N = 1 line; the N = 1 headline `value` is C3, a different workload") if world > 1 else None},
+                                             "N = 1 line with --full; the N = 1 headline `value` is C3, a different workload") if world > 1 else None},
             "roofline": {"bound": "hbm", "kernel": "pileup stage = k0_bind_a/b (read headers, tables) + k0_ops + k1_tiles_a/b + k0_desc_bin + k1_pileup + k1_empty_tiles (+ k1_zonefix on HiFi presets): what replaces fill_data_into_freq_vec",
                          "achieved": stage_bytes / (stage_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
                          "frac": stage_bytes / (stage_ms * 1e-3) / 1e9 / 8000.0,
@@ -951,23 +1010,24 @@ def main():
                                     "note": "4C + 64R read, 8 B per record item written; avg_ms includes the two bind kernels of lcr_load_batch"},
                          "k1": {"algorithmic_bytes": pbytes, "avg_ms": avg_ms, "achieved": achieved, "frac": achieved / 8000.0,
                                 "note": "the tally with its tile passes and the chunk binning (k1_tiles_a/b + k0_desc_bin + k1_pileup + k1_empty_tiles): bases once + 8 B per record item + 53 B/column"}},
-            "stages": {"pileup_plus_candidates_s": t_call, "fragments_plus_phase_s": t_phase,
-                       "sites_per_sec_pileup_gt": cols / t_call, "covered_sites_per_sec_pileup_gt": covered / t_call,
-                       "candidates_per_sec_pileup_gt": int(cands.size) / t_call, "phased_reads_per_sec": n_phased / t_phase,
-                       "covered_sites_rank0": covered,
-                       "k3_fragment_bytes": {"algorithmic_bytes": 4 * int(batch.cigar.size) + 64 * batch.n_reads + 15 * nnz,
-                                             "ms": kms["k3_count"] + kms["k3_fill"],
-                                             "achieved_GBps": (4 * int(batch.cigar.size) + 64 * batch.n_reads + 15 * nnz) / ((kms["k3_count"] + kms["k3_fill"]) * 1e-3 + 1e-12) / 1e9},
-                       "k4_phase": {"ms": api_ms["lcr_phase"], "nnz": nnz, "phasing_reads": n_phased,
-                                    "note": "per-kernel times: profiles/ (rocprofv3 --kernel-trace --stats of this command)"},
-                       "api_ms": api_ms, "kernel_ms": kms},
         }
-        extras = world == 1 and not a.no_extras
+        if a.full:
+            out["stages"] = {"pileup_plus_candidates_s": t_call, "fragments_plus_phase_s": t_phase,
+                             "sites_per_sec_pileup_gt": cols / t_call, "covered_sites_per_sec_pileup_gt": covered / t_call,
+                             "candidates_per_sec_pileup_gt": int(cands.size) / t_call, "phased_reads_per_sec": n_phased / t_phase,
+                             "covered_sites_rank0": covered,
+                             "k3_fragment_bytes": {"algorithmic_bytes": 4 * int(batch.cigar.size) + 64 * batch.n_reads + 15 * nnz,
+                                                   "ms": kms["k3_count"] + kms["k3_fill"],
+                                                   "achieved_GBps": (4 * int(batch.cigar.size) + 64 * batch.n_reads + 15 * nnz) / ((kms["k3_count"] + kms["k3_fill"]) * 1e-3 + 1e-12) / 1e9},
+                             "k4_phase": {"ms": api_ms["lcr_phase"], "nnz": nnz, "phasing_reads": n_phased,
+                                          "note": "per-kernel times: profiles/ (rocprofv3 --kernel-trace --stats of this command)"},
+                             "api_ms": api_ms, "kernel_ms": kms}
+        extras = a.full and world == 1 and not a.no_extras
         cpu = None
-        if not a.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only: the other ranks of a node would sit idle behind it
+        if a.full and not a.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only: the other ranks of a node would sit idle behind it
             cpu = cpu_baseline(batch, params, a.cpu_budget)
             out["cpu_baseline"] = cpu
-        st = out["stages"]
+        st = out.get("stages")
         if extras and F == 1:
             st["batches_in_flight"] = batches_in_flight_stage(api, torch, local, params, (reads, regions, keep), cols)
             st["end_to_end_from_bam"] = end_to_end_stage(api, _abi, torch, local, batch, params,

@@ -1607,30 +1607,44 @@ def test_nccl_group_gathers_device_records():
     assert r.returncode == 0 and "NCCL-GATHER-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
-def test_bench_under_the_launcher_with_one_rank():
+def test_bench_under_the_launcher_with_one_rank(tmp_path):
     """`bench.py --gpus 1` under torch.distributed.run, as the driver launches N > 1: the nccl group, the device-pointer
-    gathers of every step, the world-size / backend asserts and the per-rank block of the JSON line all execute."""
+    gathers of every step, the world-size / backend asserts and the per-rank block of the JSON line all execute; --dump-outputs
+    writes the records rank 0 gathered from the last step.  Once more with --full --quick: the stage breakdown (timed per-call
+    passes, the step with every kernel group timed) behind the gathers, and the same totals as the plain line."""
     import json
     import os
     bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
-    r = _torchrun([bench, "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm", "2", "--quick", "--genes", "24", "--gene-len", "12000"])
+    common = [bench, "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm", "2", "--quick", "--genes", "24", "--gene-len", "12000"]
+    rf = _torchrun(common + ["--full"])
+    assert rf.returncode == 0, rf.stdout[-2000:] + rf.stderr[-4000:]
+    full = json.loads([x for x in rf.stdout.splitlines() if x.startswith("{")][-1])
+    assert full["config"]["per_rank"]["backend"] == "nccl" and full["stages"]["api_ms"]["lcr_phase"] > 0 and "k3_fill" in full["stages"]["kernel_ms"]
+    r = _torchrun(common + ["--dump-outputs", str(tmp_path)])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert "stages" not in line
+    for k in ("columns", "aligned_bases", "reads", "candidates", "fragment_nnz", "phasing_reads"):
+        assert line["config"][k] == full["config"][k], k
     pr = line["config"]["per_rank"]
     assert pr["backend"] == "nccl" and pr["world_size"] == 1 and len(pr["ms_per_step"]) == 1
     assert pr["gather_bytes_per_step"][0] > 0 and line["config"]["gathered_records_last_batch"]["candidates"] > 0
     assert line["n_gpus"] == 1 and line["value"] > 0
+    g = line["config"]["gathered_records_last_batch"]
+    pos, tag = np.load(tmp_path / "cand_pos.npy"), np.load(tmp_path / "read_haplotag.npy")
+    assert pos.dtype == np.float64 and pos.size == g["candidates"] and tag.size == g["reads"]
+    assert all(np.isfinite(np.load(tmp_path / f)).all() for f in os.listdir(tmp_path))
 
 
 def test_bench_dry_run_at_eight_ranks():
     """The first real 8-GPU line must not fail on shard construction or capacity negotiation (thread.rs:77,204-221):
-    `bench.py --gpus 8 --dist-backend gloo --quick` -- EIGHT ranks sharing the one GPU, one list of 8 x 16 distinct MAS-Seq genes through
+    `bench.py --gpus 8 --dist-backend gloo --full --quick` -- EIGHT ranks sharing the one GPU, one list of 8 x 16 distinct MAS-Seq genes through
     shard.assign_regions (LPT on len x max_coverage), both RecordGathers every step, the per-rank block with eight entries -- and the records
     gathered on rank 0 == what ONE rank gathers over the whole list (same genes: the list depends on world x genes only)."""
     import json
     import os
     bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
-    common = ["--dist-backend", "gloo", "--quick", "--workload", "c4", "--steps", "2", "--warmup", "1", "--prewarm", "1", "--gene-len", "12000"]
+    common = ["--dist-backend", "gloo", "--full", "--quick", "--workload", "c4", "--steps", "2", "--warmup", "1", "--prewarm", "1", "--gene-len", "12000"]
     r8 = _torchrun([bench, "--gpus", "8", "--genes", "16"] + common, nproc=8, timeout=900)
     assert r8.returncode == 0, r8.stdout[-2000:] + r8.stderr[-4000:]
     l8 = json.loads([x for x in r8.stdout.splitlines() if x.startswith("{")][-1])
@@ -1815,12 +1829,12 @@ def test_poly_a_mask_zone_sizes(engine_cls, orc, dist_to_end, polya_len):
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line with the fields the driver reads: metric / value / unit / n_gpus / steps /
+    """`python bench.py --full` prints ONE JSON line with the fields the driver reads: metric / value / unit / n_gpus / steps /
     warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, a `roofline` object
     (bound, achieved, peak, unit, frac = achieved / peak, traffic) and -- without --no-cpu-baseline -- `cpu_baseline`."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--prewarm", "1", "--no-c5",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--prewarm", "1", "--no-c5",
                           "--cpu-budget", "2"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -1843,10 +1857,42 @@ def test_bench_several_batches_in_flight():
     """`bench.py --inflight 2`: two contexts on two host threads share the GPU; the line keeps its contract and says so."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--prewarm", "2", "--no-c5",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--prewarm", "2", "--no-c5",
                           "--no-cpu-baseline", "--no-traffic", "--inflight", "2"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["config"]["batches_in_flight_per_gpu"] == 2 and d["steps"] == 4 and d["value"] > 0 and "cpu_baseline" not in d
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run is set-up, warm-up, the timed steps and the line (the rest is --full's); --dump-outputs writes what the
+    last timed step handed its caller (lcr_collect_phase) as float64 .npy files under 64 MB, the same in two runs over the same inputs."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumped = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--prewarm", "1", "--genes", "24",
+                              "--gene-len", "12000", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "roofline"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["higher_is_better"] is True and "stages" not in line and "cpu_baseline" not in line
+        assert abs(line["value"] - line["config"]["columns"] / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
+        files = sorted(os.listdir(d))
+        arrays = {f: np.load(d / f) for f in files}
+        assert files and all(f.endswith(".npy") and a.dtype == (np.float32 if f.endswith("_nonfinite.npy") else np.float64) for f, a in arrays.items())
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        n_cand = line["results_collected_per_step"]["candidates"]
+        assert arrays["cand_pos.npy"].size == n_cand == line["config"]["candidates"] > 0
+        assert arrays["cand_loglik.npy"].shape == (n_cand, 3) and arrays["haplotag.npy"].size == arrays["row_region_off.npy"][-1]
+        dumped.append(arrays)
+    assert dumped[0].keys() == dumped[1].keys()
+    for f in dumped[0]:
+        assert np.array_equal(dumped[0][f], dumped[1][f]), f

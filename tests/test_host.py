@@ -176,3 +176,38 @@ def test_bench_shards_partition_one_region_list():
                 assert sb.bases[int(sb.seq_off[r0]):int(sb.seq_off[r1 - 1] + sb.seq_len[r1 - 1])].tobytes() == \
                     big.bases[int(big.seq_off[q0]):int(big.seq_off[q1 - 1] + big.seq_len[q1 - 1])].tobytes()
 
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """bench.py --dump-outputs: record fields as float64 columns; under the byte budget every array in full, above it the offset
+    arrays whole and the same seeded share of every other array's rows, in order (the same rows for arrays of one length), and
+    the same files on every call."""
+    import bench
+    rec = np.zeros(5, dtype=_abi.READ_REC_DTYPE)
+    rec["row"], rec["phase_set"] = np.arange(5), 7
+    cols = bench.record_columns("read", rec)
+    assert sorted(cols) == ["read_assignment", "read_haplotag", "read_phase_set", "read_row"]
+    small = dict(cols, objective=np.array([1.5, -2.0]))
+    assert bench.dump_outputs(str(tmp_path / "s"), small) == 4 * 5 * 8 + 2 * 8
+    for k, v in small.items():
+        got = np.load(tmp_path / "s" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    big = dict(a=np.arange(100000, dtype=np.int64), twice_a=2 * np.arange(100000), b=np.arange(30000, dtype=np.uint32).reshape(10000, 3),
+               a_off=np.arange(0, 100001, 100))
+    for d in ("b1", "b2"):
+        assert bench.dump_outputs(str(tmp_path / d), big, budget=200000) == 2 * 100000 * 8 + 30000 * 8 + 1001 * 8
+    got = {k: np.load(tmp_path / "b1" / (k + ".npy")) for k in big}
+    keep = (200000 - 1001 * 8) / (2 * 100000 * 8 + 30000 * 8)
+    a1 = got["a"]
+    assert np.array_equal(a1, np.load(tmp_path / "b2" / "a.npy")) and a1.size == int(100000 * keep) and np.all(np.diff(a1) > 0)
+    assert np.array_equal(got["twice_a"], 2 * a1)                                 # same length: the same rows
+    assert got["b"].shape == (int(10000 * keep), 3) and np.all(got["b"][:, 0] % 3 == 0)
+    assert np.array_equal(got["a_off"], big["a_off"])                             # offsets whole
+    assert sum(v.nbytes for v in got.values()) <= 200000
+    # non-finite entries: written as 0, their kind in <name>_nonfinite.npy; arrays without any get no such file
+    gq = np.array([3.5, np.inf, -np.inf, np.nan, 0.25])
+    bench.dump_outputs(str(tmp_path / "n"), dict(gq=gq, pos=np.arange(5)))
+    assert sorted(os.listdir(tmp_path / "n")) == ["gq.npy", "gq_nonfinite.npy", "pos.npy"]
+    got, kind = np.load(tmp_path / "n" / "gq.npy"), np.load(tmp_path / "n" / "gq_nonfinite.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, [3.5, 0.0, 0.0, 0.0, 0.25])
+    assert kind.dtype == np.float32 and np.array_equal(kind, [0, 1, -1, 2, 0])

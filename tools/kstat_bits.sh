@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 W=${1:-c3}
 for v in 0 1; do
-rm -rf /tmp/ks; LCR_ENUM_BITS=$v rocprofv3 --kernel-trace --stats -d /tmp/ks -o p --output-format csv -- python bench.py --no-extras --no-cpu-baseline --no-traffic --sync-phase --workload $W --steps 30 > /tmp/ks.log 2>&1
+rm -rf /tmp/ks; LCR_ENUM_BITS=$v rocprofv3 --kernel-trace --stats -d /tmp/ks -o p --output-format csv -- python bench.py --full --no-extras --no-cpu-baseline --no-traffic --sync-phase --workload $W --steps 30 > /tmp/ks.log 2>&1
 echo "== enum_bits=$v"; python - <<'PY'
 import csv,glob
 for f in glob.glob("/tmp/ks/*kernel_stats.csv"):

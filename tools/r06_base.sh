@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 > $O/pytest_gpu_base.txt
 cat $O/pytest_gpu_base.txt
-python bench.py > $O/bench_base.json 2> $O/bench_base.err
+python bench.py --full > $O/bench_base.json 2> $O/bench_base.err
 tail -3 $O/bench_base.err
 python - <<'PY'
 import json

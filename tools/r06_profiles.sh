@@ -6,8 +6,8 @@ TAG=${1:-r06p}
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-Q="--no-extras --no-cpu-baseline --no-traffic"
+python bench.py --full > $O/bench.json 2> $O/bench.err
+Q="--full --no-extras --no-cpu-baseline --no-traffic"
 rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python bench.py $Q > $O/prof.log 2>&1
 cp $O/prof/p_kernel_stats.csv $O/bench_kernel_stats.csv
 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o p --output-format csv -- python bench.py $Q --workload c4 --steps 30 > $O/bench_c4_one_gpu.json 2> $O/prof_c4.log

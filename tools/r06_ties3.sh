@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests -m gpu -q -x -k "chain_ties or tie_arithmetic
   timeout 900 python tools/fuzz_chain.py 5000 5080 2>&1 | grep -v amdgpu | tail -3 ) > $O/fuzz_chain_ties.txt 2>&1
 cat $O/fuzz_chain_ties.txt
 for ct in 1 0 1 0; do
-  LCR_CHAIN_TIES=$ct timeout 600 python bench.py --steps 60 --warmup 10 2>/dev/null | tail -1 > $O/bench_ct$ct.json
+  LCR_CHAIN_TIES=$ct timeout 600 python bench.py --full --steps 60 --warmup 10 2>/dev/null | tail -1 > $O/bench_ct$ct.json
   python - <<PY
 import json
 d=json.load(open("$O/bench_ct$ct.json"))
