@@ -401,17 +401,15 @@ int lcr_ctx_set_async_phase(lcr_ctx*, int on);
 int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
 
 /* Debug / test switches (the library reads no environment variable): key = "phase_prof", "post_host", "grid_min_entries",
- * "grid_generic", "grid_spec_lanes", "post_half", "enum_force_big", "enum_force_stream", "host_threads", "tie_arith", "timing_mask",
+ * "grid_generic", "grid_spec_lanes", "post_half", "enum_force_big", "enum_force_stream" (1: every LDS-resident enumeration region by the
+ * streaming kernel, one restart per wave), "host_threads", "tie_arith", "timing_mask",
  * "k3_hits" (0: the fragment stage walks the CIGARs itself), "async_phase" (1: lcr_phase returns with its kernels in flight),
- * "enum_bits" (0: the enumeration restarts one per wave, the kernels of rounds 2-4; default 1: eight per wave as bit states),
  * "grid_spec_batch" (0: the all-CU chain kernel's speculative half-rounds side by side on sub-grids; default 1: as eight bits of one state)
  * (bit k: only the kernel groups LCR_K_* k are timed when timing is enabled; 0 = all) (see PhaseDebug in
  * csrc/lcr_phase_host.h), "hist_tiles" (quality histograms from K0's records: 0 = when the survivors are dense, 1 = whenever the
  * preset allows, -1 = never); round 6: "chain_ties" (0: chain regions of workgroup scope keep the tie contract of round 5: sigma ties
  * only), "redo_lds" (bytes of dynamic LDS of the enumeration branch's repair pass; 0: its matrices in global memory), "fuse_filter",
- * "bg_tiles", "zonefix_overlap", "zonefix_fused" (measurement switches of the pileup stage), "spec_compact" (0: lcr_candidates waits for the
- * survivors' number before it queues their compaction), "phase_prio", "no_gate" (measurement switches of the asynchronous stage),
- * "own_fill" (0: hipMemsetAsync instead of the
+ * "spec_compact" (0: lcr_candidates waits for the survivors' number before it queues their compaction), "own_fill" (0: hipMemsetAsync instead of the
  * library's fill kernels), "fill_selftest" (checks those kernels against the host; LCR_E_DEVICE on a difference), "host_trace" (1: a
  * "[host]" line of wall-clock marks per lcr_phase on stderr; process-wide like own_fill).  Unknown key: LCR_E_ARG.  The defaults are the
  * product behaviour. */

@@ -10,9 +10,7 @@
 // workgroup per span.
 struct EnumSpan { int32_t slot; uint32_t tile0; };
 constexpr int ENUM_WAVES = 4;
-constexpr uint32_t ENUM_TILE_JOBS = 16;
-constexpr uint32_t ENUM_LDS_BYTES = 48 * 1024;   // image of a region of the register / streaming classes (three workgroups per CU)
-constexpr uint32_t ENUM_LDS_MAX = 63 * 1024;     // ... of the large-image streaming class (a launch of its own; 64 KB less the kernels' static arrays)
+constexpr uint32_t ENUM_LDS_MAX = 63 * 1024;     // LDS image of a region of the LDS-resident classes (64 KB less the kernels' static arrays)
 
 // LDS image: wl2[32] {lo23, hi24 (signed)} | lut64[64] (log10 eps_q, log10 (1 - eps_q): the f64 tie path) | csr[E] {lo | meta << 24,
 //            hi | row_in_lane << 24} | csc[E] | rp[R+1] u16 | first_row[65] u16 | ent16[E] (row-order entries of the f64 tie paths) |
@@ -80,11 +78,14 @@ __host__ __device__ inline ResolveLayout resolve_layout(uint32_t R, uint32_t E, 
 // lane l owns the rows whose first entry index lies in [l*c, (l+1)*c), c = ceil(E / 64)
 __host__ __device__ inline uint32_t enum_chunk(uint32_t E) { return E ? (E + 63) / 64 : 1; }
 
-// CK = 32 | 0: k4_enum_reg<CK> (the per-lane share of the region's entries held in registers; 0 = streamed from LDS); -1: k4_enum_bits
+// k4_enum_reg (one restart per wave, the entries streamed from LDS) / k4_enum_bits (eight restarts per wave as bit states)
 // st_base[slot]: first word of the region's 2^S saved states in st_words
-void launch_k4_enum_reg(int ck, unsigned n_blocks, size_t dyn_lds, hipStream_t s, const PhaseDev& P, const EnumSpan* spans, int32_t n_spans,
+void launch_k4_enum_reg(unsigned n_blocks, size_t dyn_lds, hipStream_t s, const PhaseDev& P, const EnumSpan* spans, int32_t n_spans,
                         uint32_t per, const int64_t* job_base, long long* job_obj, const int64_t* st_base, unsigned long long* st_words,
                         long long* region_best, uint32_t* redo /* repair list: [0] count (zeroed), [4 ..] (slot, restart) pairs; nullptr: none */, uint32_t redo_cap);
+void launch_k4_enum_bits(unsigned n_blocks, size_t dyn_lds, hipStream_t s, const PhaseDev& P, const EnumSpan* spans, int32_t n_spans,
+                         uint32_t per, const int64_t* job_base, long long* job_obj, const int64_t* st_base, unsigned long long* st_words,
+                         long long* region_best, uint32_t* redo, uint32_t redo_cap);
 void launch_k4_enum_redo(unsigned n_blocks, hipStream_t s, const PhaseDev& P, const uint32_t* redo, uint32_t redo_cap, int8_t* scratch /* n_blocks x stride */,
                          int32_t scratch_stride, double* qrow /* n_blocks x qrow_stride */, int64_t qrow_stride, const int64_t* job_base, long long* job_obj,
                          const int64_t* st_base, unsigned long long* st_words, uint32_t lds_bytes /* dynamic LDS: state + matrix of a restart's region, where they fit */);

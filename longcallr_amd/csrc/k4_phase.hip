@@ -454,14 +454,7 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
   // lcr_candidates has to wait for this stage anyway, and a fourth stream of the process pushes `side` and `aux` onto one hardware
   // queue: 2.19 -> 2.12 ms per step, and the pileup kernels' own durations (the roofline's measurement) grow by half.
   const bool async_mode = dbg.async_phase != 0;
-  auto new_queue = [&](hipStream_t* q) -> hipError_t {
-    if (!dbg.phase_prio) return hipStreamCreateWithFlags(q, hipStreamNonBlocking);
-    int least = 0, greatest = 0;
-    const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e != hipSuccess) return e;
-    return hipStreamCreateWithPriority(q, hipStreamNonBlocking, greatest);
-  };
-  if (async_mode && !main_q) PCHK(new_queue(&main_q));
+  if (async_mode && !main_q) PCHK(hipStreamCreateWithFlags(&main_q, hipStreamNonBlocking));
   if (!ev_user) { PCHK(hipEventCreateWithFlags(&ev_user, hipEventDisableTiming)); PCHK(hipEventCreateWithFlags(&ev_gate[0], hipEventDisableTiming)); PCHK(hipEventCreateWithFlags(&ev_gate[1], hipEventDisableTiming)); }
   gate_set[0] = gate_set[1] = false;
   hipStream_t const stream = async_mode ? main_q : user_stream;
@@ -471,10 +464,10 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
   hipStream_t const sq = user_stream;
   q_first = stream;
   if (!side) {
-    PCHK(new_queue(&side));
+    PCHK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
     PCHK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
     PCHK(hipEventCreateWithFlags(&ev_csr, hipEventDisableTiming));
-    PCHK(new_queue(&aux));
+    PCHK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
     PCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     PCHK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
   }
@@ -807,63 +800,46 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
     P.scratch_stride = stride;
     const bool force_big = dbg.enum_force_big != 0;        // test hooks: exercise the fallback kernels
     const bool force_stream = dbg.enum_force_stream != 0;
-    // class 2: register-resident kernel (<= 32 entries per lane; smaller instantiations were measured: separate
-    // launches each pay their own tail, one CK=32 launch with early exits is faster); class 3: same kernel
-    // streaming its entries from LDS (any share size); class 4: global-memory kernel (matrix larger than the
-    // LDS budget); classes 0 / 1 unused.  (A second register-resident instantiation with 40 entries per lane -- three
-    // quarters of C4's restarts sit at 33 .. 36 -- needs 207 VGPRs, two waves per SIMD, and is slower than streaming
-    // from LDS at six: 0.61 vs 0.51 ms per launch pair on C4, 0.23 vs 0.13 on C3.)
-    constexpr int NCLS = 5;
+    // kernel classes: CL_BITS = k4_enum_bits (eight restarts per wave as bit states) where its image (a sigma byte per row and wave)
+    // fits LDS; CL_STREAM = k4_enum_reg (one restart per wave, the entries streamed from LDS) for the LDS-resident regions beyond that
+    // image, in a launch of its own beside CL_BITS (behind it on one queue they were 0.68 ms of the C4 share's critical path);
+    // CL_BIG = k4_enum_big, global memory (matrix larger than the LDS budget)
+    enum { CL_STREAM, CL_BITS, CL_BIG, NCLS };
     std::vector<EnumSpan> spans[NCLS];
-    for (int k = 1; k < 4; k++) spans[k].reserve(enum_slots.size());
-    size_t n_t[NCLS] = {0, 0, 0, 0, 0};   // tiles per class = grid of the class's kernel
+    spans[CL_STREAM].reserve(enum_slots.size()); spans[CL_BITS].reserve(enum_slots.size());
+    size_t n_t[NCLS] = {0, 0, 0};   // tiles per class = grid of the class's kernel
 #ifndef ENUM_PER3
 #define ENUM_PER3 2u
 #endif
-    const bool ebits = dbg.enum_bits != 0;   // classes 1 - 3 by k4_enum_bits: eight restarts per wave
-    const uint32_t per_of[NCLS] = {1u, ENUM_PER3 * ENUM_WAVES, ENUM_TILE_JOBS, ebits ? ENUM_BITS_PER : ENUM_PER3 * ENUM_WAVES, 1u};
-    std::vector<int64_t>& job_base = enum_job_base; std::vector<int64_t>& st_base = enum_st_base;   // st_base: first word of the region's saved restart states (classes 1 - 3)
+    const uint32_t per_of[NCLS] = {ENUM_PER3 * ENUM_WAVES, ENUM_BITS_PER, 1u};
+    std::vector<int64_t>& job_base = enum_job_base; std::vector<int64_t>& st_base = enum_st_base;   // st_base: first word of the region's saved restart states
     job_base.assign(ng, 0); st_base.assign(ng, 0);
     int64_t nj = 0, st_words = 0, big_words = 0, big_emax = 0;
-    uint32_t lds_need[NCLS] = {0, 0, 0, 0, 0}, res_lds[NCLS] = {0, 0, 0, 0, 0};   // (res_lds: k4_enum_resolve's image of the class's largest region)
-    // enumeration regions with the device epilogue: those of the streaming class (the largest matrices, so the longest epilogues)
-    // are post-processed on their own queue right behind their resolve kernel, beside the register class's resolve; the others
-    // behind everything on `stream`
+    uint32_t lds_need[NCLS] = {0, 0, 0}, res_lds[NCLS] = {0, 0, 0};   // (res_lds: k4_enum_resolve's image of the class's largest region)
+    // enumeration regions with the device epilogue: those of the bit-state class are post-processed on its queue right behind its
+    // resolve kernel, beside the streaming class's; the others behind everything on `stream`
     std::vector<int32_t> post_slots, post_slots_b, post_slots_c;   // (c: the global-memory class, behind its winners' second launch)
     post_slots.reserve(enum_slots.size());
     for (int g : enum_slots) {
       const int S = in.cand_region_off[g + 1] - in.cand_region_off[g];
       const StageStat& st = stat[g];
-      const EnumLayout EL_old = enum_layout(st.R, st.E), EL_bits = enum_layout(st.R, st.E, true, (uint32_t)std::min(S, 32));
-      // k4_enum_bits where its image (a sigma byte per row and wave) fits; regions beyond it keep the streaming kernel (class 1, a launch of its own)
-      const bool use_bits = ebits && S <= 31 && EL_bits.total <= ENUM_LDS_MAX;
-      const EnumLayout EL = use_bits ? EL_bits : EL_old;
+      const EnumLayout EL_stream = enum_layout(st.R, st.E), EL_bits = enum_layout(st.R, st.E, true, (uint32_t)std::min(S, 32));
+      const bool use_bits = !force_stream && S <= 31 && EL_bits.total <= ENUM_LDS_MAX;
+      const EnumLayout EL = use_bits ? EL_bits : EL_stream;
       const uint32_t RL = resolve_layout((uint32_t)st.R, (uint32_t)st.E, (uint32_t)S).total;
-      int cls = 4;
+      int cls = CL_BIG;
       if (!force_big && st.R < 65536 && st.E < 65536 && S <= 31 && EL.total <= ENUM_LDS_MAX && RL <= ENUM_LDS_MAX && st.max_rows <= 64)
-#ifdef ENUM_MASK64
-        cls = force_stream ? 3 : (st.max_n <= 32 ? 2 : 3);
-#else
-        cls = force_stream ? 3 : (st.max_n <= 32 && st.max_rows <= 32 ? 2 : 3);
-#endif   // (register-resident form: <= 32 entries and <= 32 rows per lane)   // (the 8 / 16 instantiations: one launch has one tail; a 40-entry one: below)
-      // class 1: the streaming kernel for the few regions whose image needs more than ENUM_LDS_BYTES (up to the 64 KB a launch gets
-      // without opting in): a launch of their own, so that their LDS does not set the occupancy of class 3's tiles
-      // (C4 share: three such regions used to take the global-memory kernel BEHIND class 3 on its queue, 0.68 ms of the critical
-      // path: step 5.49 -> 4.97 ms; a queue of their own was measured too: HIP maps a fourth stream onto one of the first three's
-      // hardware queues, no difference)
-      // with k4_enum_bits: class 3 = its regions (one launch), class 1 = the LDS-resident regions beyond its image (streaming kernel)
-      if (ebits && cls < 4) cls = use_bits ? 3 : 1;
-      if (!ebits && (cls == 2 || cls == 3) && (std::max(EL.total, RL) > ENUM_LDS_BYTES || dbg.enum_force_stream == 2 /* test hook */)) cls = 1;
+        cls = use_bits ? CL_BITS : CL_STREAM;
       //  the saved restart states of the LDS classes are allocated up front: a raised max_enum_snps (2^20 restarts x
       // R / 64 + 3 words) goes to the global-memory class instead, whose states are kept only inside a budget
-      if (cls < 4 && (int64_t)((uint64_t)1 << std::min(S, 62)) * enum_state_words((uint32_t)st.R) > ((int64_t)1 << 27)) cls = 4;
-      if (cls < 4) { lds_need[cls] = std::max(lds_need[cls], EL.total); res_lds[cls] = std::max(res_lds[cls], RL); }
+      if (cls != CL_BIG && (int64_t)((uint64_t)1 << std::min(S, 62)) * enum_state_words((uint32_t)st.R) > ((int64_t)1 << 27)) cls = CL_BIG;
+      if (cls != CL_BIG) { lds_need[cls] = std::max(lds_need[cls], EL.total); res_lds[cls] = std::max(res_lds[cls], RL); }
       job_base[g] = nj;
       const uint64_t n = 1ull << S;
-      // saved restart states: every region of classes 1 - 3; of the global-memory class while they fit a budget of 2^26 words
+      // saved restart states: every region of the LDS classes; of the global-memory class while they fit a budget of 2^26 words
       // (512 MB -- beyond it that region's equal-objective restarts fall to "first maximum", counted as unresolved)
       st_base[g] = -1;
-      if (cls < 4) { st_base[g] = st_words; st_words += (int64_t)n * enum_state_words((uint32_t)st.R); }
+      if (cls != CL_BIG) { st_base[g] = st_words; st_words += (int64_t)n * enum_state_words((uint32_t)st.R); }
       else if ((int64_t)n * enum_state_words((uint32_t)st.R) <= ((int64_t)1 << 26) - big_words) {
         st_base[g] = st_words; st_words += (int64_t)n * enum_state_words((uint32_t)st.R); big_words += (int64_t)n * enum_state_words((uint32_t)st.R);
         big_emax = std::max<int64_t>(big_emax, st.E);
@@ -872,10 +848,11 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
       spans[cls].push_back({g, (uint32_t)n_t[cls]});
       n_t[cls] += (size_t)((n + per_of[cls] - 1) / per_of[cls]);
       nj += (int64_t)n;
-      if (!host_post[g] && !grid_post[g]) (cls == 3 ? post_slots_b : (cls == 4 ? post_slots_c : post_slots)).push_back(g);
-      if (prof && cls == 4) fprintf(stderr, "[phase]   global-memory enumeration region %d: R %d E %d S %d max_rows %d max_n %d, LDS image %u B\n", g, st.R, st.E, S, st.max_rows, st.max_n, EL.total);
+      if (!host_post[g] && !grid_post[g]) (cls == CL_BITS ? post_slots_b : (cls == CL_BIG ? post_slots_c : post_slots)).push_back(g);
+      if (prof && cls == CL_BIG) fprintf(stderr, "[phase]   global-memory enumeration region %d: R %d E %d S %d max_rows %d max_n %d, LDS image %u B\n", g, st.R, st.E, S, st.max_rows, st.max_n, EL.total);
     }
-    if (prof) fprintf(stderr, "[phase]   enumeration classes: register %zu regions / %zu tiles, streaming %zu / %zu, streaming with a large image %zu / %zu, global %zu / %zu\n", spans[2].size(), n_t[2], spans[3].size(), n_t[3], spans[1].size(), n_t[1], spans[4].size(), n_t[4]);
+    if (prof) fprintf(stderr, "[phase]   enumeration classes: bit states %zu regions / %zu tiles, streaming %zu / %zu, global %zu / %zu\n",
+                      spans[CL_BITS].size(), n_t[CL_BITS], spans[CL_STREAM].size(), n_t[CL_STREAM], spans[CL_BIG].size(), n_t[CL_BIG]);
     // one upload: spans of every class | job_base | slots | post slots ; then job objectives and winners
     size_t n_w[NCLS], s_off[NCLS], n_spans = 0;
     for (int k = 0; k < NCLS; k++) { n_w[k] = spans[k].size(); s_off[k] = n_spans; n_spans += n_w[k]; }
@@ -905,7 +882,7 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
     const int32_t* d_psl = d_sl + ns;
     long long* d_obj = b_obj.as<long long>();
     uint32_t* d_win = (uint32_t*)(d_obj + nj);
-    const size_t n_big_blocks = std::max(n_t[4], n_w[4]);
+    const size_t n_big_blocks = std::max(n_t[CL_BIG], n_w[CL_BIG]);
     // the repair pass (tie classes 2 / 4 met by a fast kernel's restart): per launch queue a list of REDO_CAP restarts and REDO_GRID
     // workgroups' worth of state scratch + score scratch (2 doubles per row), behind the global-memory class's own
     const bool full_ties = dbg.tie_arith >= 3;
@@ -918,66 +895,63 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
     if (full_ties) {
       PCHK(b_qrow.reserve((size_t)qstride * n_scr_blocks * 8 + 64));
     }
-    uint32_t* const redo_a = full_ties ? b_redo.as<uint32_t>() : nullptr;                          // classes 1 / 2 (first queue)
-    uint32_t* const redo_b = full_ties ? b_redo.as<uint32_t>() + 4 + 2 * REDO_CAP : nullptr;       // class 3 (`aux`)
+    uint32_t* const redo_a = full_ties ? b_redo.as<uint32_t>() : nullptr;                          // the streaming class (first queue)
+    uint32_t* const redo_b = full_ties ? b_redo.as<uint32_t>() + 4 + 2 * REDO_CAP : nullptr;       // the bit-state class (`aux`)
     double* const qrow_all = full_ties ? b_qrow.as<double>() : nullptr;
     auto launch_redo = [&](uint32_t* redo, int which, hipStream_t q) {
       if (!redo) return;
       const size_t b0 = n_big_blocks + (size_t)which * REDO_GRID;
       launch_k4_enum_redo(REDO_GRID, q, P, redo, REDO_CAP, b_scr.as<int8_t>() + (size_t)stride * b0, stride, qrow_all + (size_t)qstride * b0, qstride,
                           d_jb, d_obj, d_sb, d_enum_st.as<unsigned long long>(),
-                          // (the matrix in LDS where it fits -- not for the queue that, with k4_enum_bits, only carries the regions beyond ITS image: their
-                          // matrices are the largest, and that launch runs beside the bit-state kernel, where 512 workgroups asking for 64 KB each wait for
-                          // it to drain even when the list is empty: 5 us -> 0.98 ms on the C4 share)
-                          (which == 0 && ebits) ? 0u : (uint32_t)std::max(0, dbg.redo_lds));
+                          // (the matrix in LDS where it fits -- not for the streaming class's queue: its matrices are the largest, and that
+                          // launch runs beside the bit-state kernel, where 512 workgroups asking for 64 KB each wait for it to drain even
+                          // when the list is empty: 5 us -> 0.98 ms on the C4 share)
+                          which == 0 ? 0u : (uint32_t)std::max(0, dbg.redo_lds));
     };
-    // the classes touch disjoint regions: class 2 on `stream`, classes 3 / 4 beside it on `aux` (their tails overlap)
+    // the classes touch disjoint regions: the streaming class on `stream`, the bit-state and global-memory classes beside it on `aux`
+    // (their tails overlap)
     long long* const d_rbest = d_rbest_buf.as<long long>();   // (filled in front of the staging kernel)
+    unsigned long long* const d_st = d_enum_st.as<unsigned long long>();
     auto launch = [&](const size_t* cnt, const uint32_t* win) -> hipError_t {
-      const bool fork = (cnt[2] || (ebits && cnt[1])) && (cnt[3] || cnt[4]);   // (with k4_enum_bits: the streaming kernel's few large regions beside its launch)
-      hipStream_t s34 = fork ? aux : stream, s1 = stream;
+      const bool fork = cnt[CL_STREAM] && (cnt[CL_BITS] || cnt[CL_BIG]);
+      hipStream_t const qb = fork ? aux : stream;
       hipError_t e = hipSuccess;
       if (fork) { if ((e = hipEventRecord(ev_fork, stream)) != hipSuccess) return e; if ((e = hipStreamWaitEvent(aux, ev_fork, 0)) != hipSuccess) return e; }
-      if (cnt[1]) {   // (first, ahead of class 2 on its queue: the largest matrices have the longest restarts)
-        launch_k4_enum_reg(0, (unsigned)cnt[1], lds_need[1], s1, P, d_sp + s_off[1], (int32_t)n_w[1], per_of[1], d_jb, d_obj, d_sb, d_enum_st.as<unsigned long long>(), d_rbest, redo_a, REDO_CAP);
-        if (!win && !cnt[2]) launch_redo(redo_a, 0, s1);   // (with a class 2 launch behind it on this queue: one repair pass for both, below)
-        if (!win && !cnt[2]) launch_k4_enum_resolve((unsigned)n_w[1], res_lds[1], s1, P, d_sp + s_off[1], d_jb, d_obj, d_sb, d_enum_st.as<unsigned long long>());
+      // per class all restarts, then `prob > largest_prob` over each region's restarts from the objectives, signatures and states they
+      // left (phase.rs:1113-1119; ties between configurations of maximal objective by their f64 sums) -- a workgroup per region -- and
+      // the post-phase kernel of the class's regions, each behind its own restarts on its own queue
+      if (cnt[CL_STREAM]) {   // (first: the largest matrices have the longest restarts)
+        launch_k4_enum_reg((unsigned)cnt[CL_STREAM], lds_need[CL_STREAM], stream, P, d_sp + s_off[CL_STREAM], (int32_t)n_w[CL_STREAM], per_of[CL_STREAM], d_jb, d_obj, d_sb, d_st, d_rbest, redo_a, REDO_CAP);
+        if (!win) {
+          launch_redo(redo_a, 0, stream);
+          launch_k4_enum_resolve((unsigned)n_w[CL_STREAM], res_lds[CL_STREAM], stream, P, d_sp + s_off[CL_STREAM], d_jb, d_obj, d_sb, d_st);
+        }
       }
-      // classes 2 / 3: all restarts (both kernels queued first), then per class `prob > largest_prob` over each region's restarts from
-      // the objectives, signatures and states they left (phase.rs:1113-1119; ties between configurations of maximal objective by
-      // their f64 sums) -- a workgroup per region -- and the post-phase kernel of the class's regions, each behind its own
-      // restarts on its own queue (the streaming class has the largest matrices, so the longest epilogues: they run beside the
-      // register class's resolve instead of behind it)
-      unsigned long long* const d_st = d_enum_st.as<unsigned long long>();
-      if (cnt[2]) launch_k4_enum_reg(32, (unsigned)cnt[2], lds_need[2], stream, P, d_sp + s_off[2], (int32_t)n_w[2], per_of[2], d_jb, d_obj, d_sb, d_st, d_rbest, redo_a, REDO_CAP);
-      if (cnt[3]) launch_k4_enum_reg(ebits ? -1 : 0, (unsigned)cnt[3], lds_need[3], s34, P, d_sp + s_off[3], (int32_t)n_w[3], per_of[3], d_jb, d_obj, d_sb, d_st, d_rbest, redo_b, REDO_CAP);
+      if (cnt[CL_BITS]) launch_k4_enum_bits((unsigned)cnt[CL_BITS], lds_need[CL_BITS], qb, P, d_sp + s_off[CL_BITS], (int32_t)n_w[CL_BITS], per_of[CL_BITS], d_jb, d_obj, d_sb, d_st, d_rbest, redo_b, REDO_CAP);
       if (!win && async_mode) {   // (the dense part of the stage ends here on both queues: the next batch's pileup waits for these)
-        if (cnt[1] || cnt[2]) { if ((e = hipEventRecord(ev_gate[0], stream)) != hipSuccess) return e; gate_set[0] = true; }
-        if (fork && cnt[3]) { if ((e = hipEventRecord(ev_gate[1], s34)) != hipSuccess) return e; gate_set[1] = true; }
-        else if (!fork && cnt[3]) { if ((e = hipEventRecord(ev_gate[0], stream)) != hipSuccess) return e; gate_set[0] = true; }
+        if (cnt[CL_STREAM]) { if ((e = hipEventRecord(ev_gate[0], stream)) != hipSuccess) return e; gate_set[0] = true; }
+        if (fork && cnt[CL_BITS]) { if ((e = hipEventRecord(ev_gate[1], qb)) != hipSuccess) return e; gate_set[1] = true; }
+        else if (!fork && cnt[CL_BITS]) { if ((e = hipEventRecord(ev_gate[0], stream)) != hipSuccess) return e; gate_set[0] = true; }
       }
       if (!win) {
-        if (cnt[2]) launch_redo(redo_a, 0, stream);
-        if (cnt[1] && cnt[2]) launch_k4_enum_resolve((unsigned)n_w[1], res_lds[1], s1, P, d_sp + s_off[1], d_jb, d_obj, d_sb, d_enum_st.as<unsigned long long>());
-        if (cnt[2]) launch_k4_enum_resolve((unsigned)n_w[2], res_lds[2], stream, P, d_sp + s_off[2], d_jb, d_obj, d_sb, d_st);
         // eight waves per region: the slowest region (most rows) sets the kernel's length, and every row sweep of the
         // epilogue is a pass of <threads> rows (148 -> 103 us on C3)
         if (nps_a && (e = launch_k4_post(2 * LCR_BLOCK, (unsigned)nps_a, post_lds, stream, pin, d_psl, (int32_t)nps_a, plut)) != hipSuccess) return e;
-        if (cnt[3]) { launch_redo(redo_b, 1, s34); launch_k4_enum_resolve((unsigned)n_w[3], res_lds[3], s34, P, d_sp + s_off[3], d_jb, d_obj, d_sb, d_st); }
-        if (nps_b && (e = launch_k4_post(2 * LCR_BLOCK, (unsigned)nps_b, post_lds, s34, pin, d_psl + nps_a, (int32_t)nps_b, plut)) != hipSuccess) return e;
+        if (cnt[CL_BITS]) { launch_redo(redo_b, 1, qb); launch_k4_enum_resolve((unsigned)n_w[CL_BITS], res_lds[CL_BITS], qb, P, d_sp + s_off[CL_BITS], d_jb, d_obj, d_sb, d_st); }
+        if (nps_b && (e = launch_k4_post(2 * LCR_BLOCK, (unsigned)nps_b, post_lds, qb, pin, d_psl + nps_a, (int32_t)nps_b, plut)) != hipSuccess) return e;
       }
-      if (cnt[4]) launch_k4_enum_big((unsigned)cnt[4], s34, P, d_sp + s_off[4], (int32_t)n_w[4], per_of[4], d_jb, d_obj, win, d_sb, d_enum_st.as<unsigned long long>(), qrow_all, qstride);
+      if (cnt[CL_BIG]) launch_k4_enum_big((unsigned)cnt[CL_BIG], qb, P, d_sp + s_off[CL_BIG], (int32_t)n_w[CL_BIG], per_of[CL_BIG], d_jb, d_obj, win, d_sb, d_st, qrow_all, qstride);
       if (fork) { if ((e = hipEventRecord(ev_join, aux)) != hipSuccess) return e; if ((e = hipStreamWaitEvent(stream, ev_join, 0)) != hipSuccess) return e; }
       return e;
     };
     PCHK(launch(n_t, nullptr));
     HT("en:launched");
-    if (n_w[4]) {   // the global-memory class: its own resolve kernel (equal objectives by the f64 sums) and the winners' second launch
-      const size_t only4[NCLS] = {0, 0, 0, 0, n_w[4]};
+    if (n_w[CL_BIG]) {   // the global-memory class: its own resolve kernel (equal objectives by the f64 sums) and the winners' second launch
+      const size_t only_big[NCLS] = {0, 0, n_w[CL_BIG]};
       const int64_t tstride = (big_emax + 63) & ~(int64_t)63;
-      PCHK(b_terms.reserve((size_t)std::max<int64_t>(tstride, 64) * n_w[4] * 8 + 64));
-      launch_k4_enum_resolve_big((int32_t)n_w[4], stream, P, d_sp + s_off[4], d_jb, d_obj, d_sb, d_enum_st.as<unsigned long long>(), d_win, b_terms.as<double>(), tstride);
-      PCHK(launch(only4, d_win));
+      PCHK(b_terms.reserve((size_t)std::max<int64_t>(tstride, 64) * n_w[CL_BIG] * 8 + 64));
+      launch_k4_enum_resolve_big((int32_t)n_w[CL_BIG], stream, P, d_sp + s_off[CL_BIG], d_jb, d_obj, d_sb, d_st, d_win, b_terms.as<double>(), tstride);
+      PCHK(launch(only_big, d_win));
     }
     if (nps_c) PCHK(launch_k4_post(2 * LCR_BLOCK, (unsigned)nps_c, post_lds, stream, pin, d_psl + nps_a + nps_b, (int32_t)nps_c, plut));
     PCHK(hipGetLastError());

@@ -31,8 +31,6 @@ struct lcr_ctx {
   hipStream_t up_stream = nullptr;
   hipEvent_t ev_dl = nullptr, ev_cand_dl = nullptr;   // lcr_candidates: the candidate records' download on the phase stage's second queue
   bool cand_dl_other = false;
-  hipStream_t fill_stream = nullptr;           // zero fill of the count planes beside K0 (lcr_pileup)
-  hipEvent_t ev_fill0 = nullptr, ev_fill1 = nullptr;
   int bound_slot = -1;
   bool bound_host = false;   // the bound batch was copied into in_[] (LCR_MEM_HOST)
   DevBuf scan_tmp, read_region, read_bin, read_rend, tile_region, tile_col0, first_tile, k0_tile_fill, k0_items, tile_nbase, tile_order;
@@ -63,11 +61,7 @@ struct lcr_ctx {
   DevBuf flags, tile_count, tile_off, total, survivors, sv_region_off, hist, cand_tmp, keep;
   DevBuf hit_cnt, hit_list, ovf_list;   // k2_hist's (read, survivor) hits for K3; the overflow counter sits behind the histograms
   bool hits_valid = false; int32_t hits_n_sv = 0;
-  int dbg_bg_tiles = 0;     // lcr_debug_set("bg_tiles"): > 0 = the record-free tiles' stores by this many workgroups on a second queue beside the tally
-  int dbg_prefill = 0;      // lcr_debug_set("plane_prefill"): 1 = the count planes are zeroed on a second queue while K0 runs -- measured: 0.69 instead of 0.63 ms for the stage; 0: k1_empty_tiles writes the record-free tiles
   int dbg_hist_tiles = 0;   // lcr_debug_set("hist_tiles"): 0 = by survivor density, 1 = the tile form whenever it applies, -1 = never
-  int dbg_zf_fused = 0;     // lcr_debug_set("zonefix_fused", 1) (measurement switch): HiFi presets -- the poly-A pass and the record-free tiles' stores in one launch; measured slower (HISTORY.md Appendix C)
-  int dbg_zf_overlap = 0;   // lcr_debug_set("zonefix_overlap", 1) (measurement switch): HiFi presets -- the record-free tiles' stores on a second queue beside the poly-A pass; measured slower with the asynchronous phase stage (HISTORY.md Appendix C)
   int dbg_spec_compact = 1; // lcr_debug_set("spec_compact"): 0 = lcr_candidates waits for the survivors' number before it queues their compaction
   int dbg_fuse_filter = 1;  // lcr_debug_set("fuse_filter"): 0 = pass 1 of the candidate filters always by k2_filter (its own pass over the planes)
   bool flt_fused = false;   // the last lcr_pileup left k2_filter's flags and per-tile counts (ONT presets: no poly-A pass behind the tally)
@@ -376,9 +370,6 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
   if (c->ev_dl) (void)hipEventDestroy(c->ev_dl);
   if (c->ev_cand_dl) (void)hipEventDestroy(c->ev_cand_dl);
-  if (c->fill_stream) { (void)hipStreamSynchronize(c->fill_stream); (void)hipStreamDestroy(c->fill_stream); }
-  if (c->ev_fill0) (void)hipEventDestroy(c->ev_fill0);
-  if (c->ev_fill1) (void)hipEventDestroy(c->ev_fill1);
   DevBuf* bufs[] = {&c->rd_start, &c->rd_end, &c->rd_diff, &c->rd_ex, &c->rd_cnt, &c->rd_off, &c->rd_s, &c->rd_e, &c->rd_max,
                     &c->scan_tmp, &c->read_region, &c->read_bin, &c->read_rend, &c->tile_region, &c->tile_col0, &c->first_tile, &c->desc_tile, &c->desc_val, &c->chunks, &c->chunk_off,
                     &c->k0_tile_fill, &c->k0_items, &c->region_e_off, &c->frag_tmp_col, &c->frag_tmp_val, &c->tile_nbase, &c->blk_first_read, &c->read_scan, &c->cig_compact, &c->cig_off_new, &c->cig_new_off32, &c->planes, &c->flags,
@@ -694,24 +685,6 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   HIPCHK(c, c->read_scan.reserve(std::max<size_t>(b.n_reads, 1) * 8));
   HIPCHK(c, c->h_stage[0].reserve(64));
   int32_t n_recs = 0, bad = 0, n_ops = 0;
-  // Three quarters of a spliced batch's tiles hold no record: all their planes are zeros (the intron plane: a constant).  That
-  // store stream (52 B per column) is the stage's largest HBM write, and K0 -- instruction-bound -- leaves the memory system idle:
-  // ALL planes are zeroed on a second queue while K0 runs, K1 then writes the tiles with records and the intron constants.
-  // (Under the tally the same stream hurts: the tiles' dependent loads queue behind it.  DESIGN.md K1.)
-  const bool prefill = c->dbg_prefill != 0 && nt > 0;
-  // (measurement switch) HiFi presets: the record-free tiles' stores in ONE launch with the poly-A pass
-  const bool zf_fused = c->dbg_zf_fused != 0 && !c->dp.ont && c->dp.dist_to_end > 0 && c->dp.dist_to_end <= 63 && c->dp.polya_len >= 2 && c->dp.polya_len <= 16 &&
-                        nt > 0 && !prefill && c->dbg_bg_tiles == 0 && c->dbg_zf_overlap == 0 && b.n_reads > 0;
-  // (measurement switch) HiFi presets: the record-free tiles' stores beside the poly-A pass
-  const bool zf_overlap = c->dbg_zf_overlap != 0 && !c->dp.ont && c->dp.dist_to_end > 0 && nt > 0 && !prefill && c->dbg_bg_tiles == 0;
-  if ((prefill || c->dbg_bg_tiles > 0 || c->dbg_bg_tiles == -1 || zf_overlap) && !c->fill_stream) { HIPCHK(c, hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_fill0, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_fill1, hipEventDisableTiming)); }
-  if (prefill) {
-    if (!c->fill_stream) { HIPCHK(c, hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_fill0, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_fill1, hipEventDisableTiming)); }
-    HIPCHK(c, hipEventRecord(c->ev_fill0, c->stream));            // (the planes' last readers of the previous batch are ahead in the ctx stream)
-    HIPCHK(c, hipStreamWaitEvent(c->fill_stream, c->ev_fill0, 0));
-    HIPCHK(c, hipMemsetAsync(c->planes.p, 0, (size_t)c->n_cols * LCR_NPLANES * 4, c->fill_stream));
-    HIPCHK(c, hipEventRecord(c->ev_fill1, c->fill_stream));
-  }
   // pass 1 of the candidate filters inside the tally's epilogue (k2_eval.h): presets whose planes are final when K1 stores them (ONT: the
   // HiFi presets subtract the poly-A mask afterwards, k1_zonefix); lcr_candidates uses the flags if it is called with the same filters
   const bool fuse = c->dbg_fuse_filter != 0 && c->dp.ont && nt > 0;
@@ -752,26 +725,16 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
       HIPCHK(c, hipEventRecord(c->ev_ctl, c->stream));
       if (nt > 0) launch_k1_tiles_b(nt, fill, fill + o_ndiff, fill + o_nch, fill + o_tmp, c->tile_nbase.as<int32_t>(), c->chunk_off.as<int32_t>(),
                                     c->tile_order.as<int32_t>(), c->stream);
-      const bool early_empty = c->dbg_bg_tiles == -1 && nt > 0 && !prefill;
-      if (early_empty)   // (measurement switch) the record-free tiles' store stream beside k0_desc_bin and the start of the tally
-        launch_k1_empty_early(b, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols, c->tile_nbase.as<int32_t>(), c->planes.as<uint32_t>(),
-                              c->tile_order.as<int32_t>(), fill + o_tmp, c->stream, c->fill_stream, c->ev_fill0, c->ev_fill1, fuse ? c->tile_count.as<int32_t>() : nullptr);
       if (nt > 0 && c->n_ops > 0)
         launch_k0_desc_bin(fill + nt + 1, (const unsigned int*)(fill + o_acct), desc_sub, c->desc_tile.as<uint32_t>(), c->desc_val.p, c->chunk_off.as<int32_t>(), fill + o_cur,
                            c->chunks.p, n_blocks / 8 + 1, c->stream);
-      // ---- K1: per-tile tally from the records (leaves at once if K0 flagged an error); K1z: poly-A / homopolymer
-      // mask of the HiFi presets
-      if (prefill) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_fill1, 0));
+      // ---- K1: per-tile tally from the records (leaves at once if K0 flagged an error), the record-free tiles; K1z: poly-A /
+      // homopolymer mask of the HiFi presets
       launch_k1_pileup(b, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols, fill, c->chunk_off.as<int32_t>(),
                        c->chunks.p, c->k0_items.as<unsigned long long>(), c->tile_nbase.as<int32_t>(), c->planes.as<uint32_t>(),
-                       c->tile_order.as<int32_t>(), fill + o_tmp, prefill ? 1 : 0, c->stream, (c->dbg_bg_tiles > 0 || c->dbg_bg_tiles == -1 || zf_overlap) ? c->fill_stream : nullptr, c->ev_fill0, c->ev_fill1, zf_fused ? -4 : zf_overlap ? -3 : c->dbg_bg_tiles,
-                       fuse ? c->flags.as<uint8_t>() : nullptr, fuse ? c->tile_count.as<int32_t>() : nullptr);
-      if (zf_fused)
-        (void)launch_k1_zonefix_tiles(b, c->dp.dist_to_end, c->dp.polya_len, c->n_cols, c->planes.as<uint32_t>(), c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt,
-                                      c->tile_nbase.as<int32_t>(), c->tile_order.as<int32_t>(), fill + o_tmp, fuse ? c->tile_count.as<int32_t>() : nullptr, c->stream);
-      else if (!c->dp.ont && c->dp.dist_to_end > 0)
-        launch_k1_zonefix(b, c->read_bin.as<ReadBin>(), c->dp.dist_to_end, c->dp.polya_len, c->n_cols, c->planes.as<uint32_t>(), c->stream);
-      if (zf_overlap) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_fill1, 0)); }
+                       c->tile_order.as<int32_t>(), fill + o_tmp, c->stream, fuse ? c->flags.as<uint8_t>() : nullptr, fuse ? c->tile_count.as<int32_t>() : nullptr);
+      if (!c->dp.ont && c->dp.dist_to_end > 0)
+        launch_k1_zonefix(b, c->read_bin.as<ReadBin>(), c->dp.dist_to_end, c->dp.polya_len, c->n_cols, c->planes.as<uint32_t>(), c->stream); }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventSynchronize(c->ev_ctl));
   HT("pile:ctl");
@@ -1307,21 +1270,14 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
       }
   }
   else if (k == "chain_ties") d.chain_ties = value != 0;
-  else if (k == "phase_prio") d.phase_prio = value != 0;
-  else if (k == "no_gate") d.no_gate = value != 0;
   else if (k == "redo_lds") d.redo_lds = (int)std::max<int64_t>(0, std::min<int64_t>(value, 128 * 1024));
   else if (k == "tie_arith") d.tie_arith = (int)std::max<int64_t>(0, std::min<int64_t>(value, 3));   // (3 = the default: all four classes in the enumeration branch)
   else if (k == "timing_mask") c->timing_mask = (uint32_t)value;
-  else if (k == "plane_prefill") c->dbg_prefill = value != 0;
-  else if (k == "bg_tiles") c->dbg_bg_tiles = (int)std::max<int64_t>(-2, std::min<int64_t>(value, 4096));
   else if (k == "hist_tiles") c->dbg_hist_tiles = value > 0 ? 1 : value < 0 ? -1 : 0;
   else if (k == "k3_hits") c->dbg_k3_hits = value != 0;
   else if (k == "fuse_filter") c->dbg_fuse_filter = value != 0;
   else if (k == "spec_compact") c->dbg_spec_compact = value != 0;
-  else if (k == "zonefix_overlap") c->dbg_zf_overlap = value != 0;
-  else if (k == "zonefix_fused") c->dbg_zf_fused = value != 0;
   else if (k == "grid_spec_batch") d.spec_batch = (int)value;
-  else if (k == "enum_bits") d.enum_bits = (int)value;
   else if (k == "grid_spec_lanes") d.spec_lanes = (int)std::max<int64_t>(1, std::min<int64_t>(value, 16));
   else { c->err = "lcr_debug_set: unknown key " + k; return LCR_E_ARG; }
   return LCR_OK;

@@ -119,12 +119,9 @@ struct PhaseDebug {
   int grid_generic = 0;         // "grid_generic": fenced grid barriers only
   int post_half = 0;            // "post_half": the eight-wave epilogue of the chain regions
   int enum_force_big = 0;       // "enum_force_big" / "enum_force_stream": the fallback enumeration kernels
-  int enum_force_stream = 0;    // (2: the large-image launch of the streaming kernel)
-  int enum_bits = 1;            // "enum_bits": the enumeration restarts of the LDS classes eight per wave as bit states (k4_enum_bits)
+  int enum_force_stream = 0;    // (every LDS-resident region by the streaming kernel, k4_enum_reg)
   int spec_batch = 1;           // "grid_spec_batch": eight speculative half-rounds per pass over the matrix (k4_grid_batch.h); 0: the side-by-side lanes below
   int spec_lanes = 8;           // "grid_spec_lanes": half-rounds of the perturbation loop run at once at grid scope (1: one after the other; C5 with packed entries: 454 / 370 / 348 / 366 ms with 2 / 4 / 8 / 16 -- eight lanes = one XCD each)
-  int phase_prio = 0;           // "phase_prio" (measurement switch): 1 = the stage's own queues are created at the device's greatest priority
-  int no_gate = 0;              // "no_gate" (measurement switch): 1 = the next batch's K0 does not wait for the restarts of the stage in flight
   int redo_lds = 64 * 1024;     // "redo_lds": bytes of dynamic LDS of the enumeration branch's repair pass (k4_enum_redo: state + matrix of a restart's region where they fit; 0: global memory)
   int chain_ties = 1;           // "chain_ties": chain regions of workgroup scope that meet a class-2 / class-4 tie run again under the complete tie contract (0: counted as unresolved)
   int tie_arith = 3;            // "tie_arith": which exact fixed-point ties the reference-order f64 arithmetic decides (PhaseDev::tie_arith; 3 = all that liblcr resolves)
@@ -154,7 +151,7 @@ struct PhaseHost {
   HostBuf h_pin[12];   // pinned staging: row_ptr, col, val, links, enum state, region sizes, chain state, results, job tables, chain start
   hipStream_t side = nullptr;   // second queue: fragment matrix download + chain regions
   hipEvent_t ev_in = nullptr, ev_csr = nullptr, ev_fork = nullptr, ev_join = nullptr;
-  hipStream_t aux = nullptr;   // enumeration classes 3 / 4 beside class 2
+  hipStream_t aux = nullptr;   // the bit-state and global-memory enumeration classes beside the streaming class
   // lcr_debug_set("async_phase", 1) (round 5, opt-in): the stage's FIRST queue is its own too, lcr_phase returns when everything is
   // queued, the caller's stream is free for the next batch's lcr_load_batch / lcr_pileup, and the results are collected by
   // settle(): every getter, lcr_ctx_sync, the next lcr_candidates / lcr_phase call it.  Persistent all-CU launches (device
@@ -167,7 +164,7 @@ struct PhaseHost {
   bool gate_set[2] = {false, false};
   // makes `s` wait for the dense part of a stage in flight (no-op otherwise)
   hipError_t gate_stream(hipStream_t s) {
-    if (!pending || dbg.no_gate) return hipSuccess;
+    if (!pending) return hipSuccess;
     for (int k = 0; k < 2; k++) if (gate_set[k]) { hipError_t e = hipStreamWaitEvent(s, ev_gate[k], 0); if (e != hipSuccess) return e; }
     return hipSuccess;
   }
