@@ -360,34 +360,17 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->cand_pending && c->cand_dl_other && c->ev_cand_dl) (void)hipEventSynchronize(c->ev_cand_dl);   // (the candidate download on the phase stage's queue writes h_stage[1..2], freed below)
   (void)c->phase.settle(nullptr);   // (an lcr_phase whose results nobody collected: its queues are drained before anything is freed)
-  if (c->phase.main_q) (void)hipStreamSynchronize(c->phase.main_q);
-  if (c->phase.side) (void)hipStreamSynchronize(c->phase.side);
-  if (c->phase.aux) (void)hipStreamSynchronize(c->phase.aux);
+  for (hipStream_t q : {c->phase.main_q, c->phase.side, c->phase.aux}) if (q) (void)hipStreamSynchronize(q);
   (void)hipStreamSynchronize(c->stream);
-  for (auto& b : c->in_) b.release();
   if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
-  for (auto& u : c->up) { for (auto& b : u.buf) b.release(); if (u.ev) (void)hipEventDestroy(u.ev); }
+  for (auto& u : c->up) if (u.ev) (void)hipEventDestroy(u.ev);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  if (c->ev_dl) (void)hipEventDestroy(c->ev_dl);
-  if (c->ev_cand_dl) (void)hipEventDestroy(c->ev_cand_dl);
-  DevBuf* bufs[] = {&c->rd_start, &c->rd_end, &c->rd_diff, &c->rd_ex, &c->rd_cnt, &c->rd_off, &c->rd_s, &c->rd_e, &c->rd_max,
-                    &c->scan_tmp, &c->read_region, &c->read_bin, &c->read_rend, &c->tile_region, &c->tile_col0, &c->first_tile, &c->desc_tile, &c->desc_val, &c->chunks, &c->chunk_off,
-                    &c->k0_tile_fill, &c->k0_items, &c->region_e_off, &c->frag_tmp_col, &c->frag_tmp_val, &c->tile_nbase, &c->blk_first_read, &c->read_scan, &c->cig_compact, &c->cig_off_new, &c->cig_new_off32, &c->planes, &c->flags,
-                    &c->tile_count, &c->tile_off, &c->total, &c->survivors, &c->sv_region_off, &c->hist, &c->cand_tmp,
-                    &c->keep, &c->d_cand, &c->d_cand_off, &c->region_rows, &c->row_region_off, &c->row_cnt,
-                    &c->row_links, &c->row_ptr, &c->col, &c->val, &c->tile_order, &c->hit_cnt, &c->hit_list, &c->ovf_list};
-  for (auto* b : bufs) b->release();
-  if (c->ev_nnz) (void)hipEventDestroy(c->ev_nnz);
-  if (c->ev_cand) (void)hipEventDestroy(c->ev_cand);
-  if (c->ev_sv) (void)hipEventDestroy(c->ev_sv);
-  if (c->ev_ctl) (void)hipEventDestroy(c->ev_ctl);
-  for (int k = 0; k < 2 * lcr_ctx::UP_LANES; k++) { if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]); c->h_up[k].release(); }
-  HostBuf* hb[] = {&c->h_order, &c->h_nnz, &c->h_stage[0], &c->h_stage[1], &c->h_stage[2], &c->h_stage[3], &c->h_planes, &c->h_row_ptr, &c->h_row_read, &c->h_col, &c->h_val, &c->h_row_fp, &c->h_row_links};
-  for (auto* b : hb) b->release();
+  for (hipEvent_t e : {c->ev_dl, c->ev_cand_dl, c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl}) if (e) (void)hipEventDestroy(e);
+  for (int k = 0; k < 2 * lcr_ctx::UP_LANES; k++) if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
   c->phase.release();
   for (int k = 0; k < LCR_NKERNELS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;   // (every queue is drained: the buffers give their blocks back)
 }
 
 const char* lcr_last_error(const lcr_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
@@ -1248,7 +1231,9 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "fill_selftest") {   // lcr_fill_async / lcr_fill_multi_async against the host on every alignment of both ends (a test hook: returns LCR_E_DEVICE on a difference)
     HIPCHK(c, hipSetDevice(c->device));
     const size_t N = 4096;
-    DevBuf buf; HIPCHK(c, buf.reserve(4 * N));
+    DevBuf buf;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{c->stream};   // (destroyed before `buf`: no fill is in flight when it is freed)
+    HIPCHK(c, buf.reserve(4 * N));
     std::vector<uint8_t> host(4 * N), want(4 * N);
     for (size_t off = 0; off < 18; off++)
       for (size_t len : {(size_t)0, (size_t)1, (size_t)15, (size_t)16, (size_t)17, (size_t)255, (size_t)1000 + off, (size_t)2049}) {

@@ -102,7 +102,6 @@ struct Survivor {
 void* lcr_cache_take(int host, size_t want, size_t* cap);   // a cached block with want <= cap <= 2 * want + 1 MiB of the current device, or nullptr
 bool lcr_cache_put(int host, void* p, size_t cap);          // false: the cache is full, the caller frees the block
 
-// growable device buffer
 // Measurement aid (lcr_debug_set("host_trace", 1)): wall-clock marks of the calling thread inside the stage calls, printed to stderr by
 // lcr_host_trace_flush (end of lcr_phase) as microseconds since the first mark -- where does the host wait, when does it queue what.
 extern int g_lcr_host_trace;
@@ -117,9 +116,13 @@ extern int g_lcr_own_fill;
 hipError_t lcr_fill_async(void* p, int byte, size_t bytes, hipStream_t s);
 hipError_t lcr_fill_multi_async(int n /* <= 4 */, void* const* ptrs, const int* bytes_val, const size_t* sizes, hipStream_t s);
 
+// Growable buffers that own their block: the destructor gives it back (the owner has drained its queues by then: lcr_ctx_destroy)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p && !lcr_cache_put(0, p, cap)) (void)hipFree(p); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     // (hipFree waits for the device before it releases a block: so does handing one to the cache -- a kernel in flight may still read it)
@@ -132,13 +135,14 @@ struct DevBuf {
     if (e == hipSuccess) cap = want; else p = nullptr;
     return e;
   }
-  // (the owner has drained its queues: lcr_ctx_destroy)
-  void release() { if (p && !lcr_cache_put(0, p, cap)) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 struct HostBuf {  // pinned
   void* p = nullptr;
   size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete; HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { if (p && !lcr_cache_put(1, p, cap)) (void)hipHostFree(p); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) { (void)hipDeviceSynchronize(); if (!lcr_cache_put(1, p, cap)) (void)hipHostFree(p); }
@@ -150,7 +154,6 @@ struct HostBuf {  // pinned
     if (e == hipSuccess) cap = want; else p = nullptr;
     return e;
   }
-  void release() { if (p && !lcr_cache_put(1, p, cap)) (void)hipHostFree(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 

@@ -2,10 +2,8 @@
 #pragma once
 #include <string>
 #include <atomic>
-#include <condition_variable>
 #include <functional>
 #include <memory>
-#include <mutex>
 #include <semaphore.h>
 #include <thread>
 
@@ -28,6 +26,7 @@ struct PhaseInputs {
   const int32_t* d_cand_off = nullptr;       // device, n_regions+1
   const int32_t* d_row_region_off = nullptr; // device, n_regions+1
   const int64_t* d_start0 = nullptr;         // device, region start columns
+  int snps(int g) const { return cand_region_off[g + 1] - cand_region_off[g]; }   // SNPs (candidates) of region g
 };
 
 // Persistent host worker pool: regions are independent units of host-side work (the reference runs
@@ -84,32 +83,6 @@ class HostPool {
   std::atomic<bool> stop_{false};
 };
 
-// One persistent helper thread per context: runs a job beside the calling thread (creating a thread per call costs
-// tens of microseconds at the head of the chain regions' critical path).
-class HelperThread {
- public:
-  HelperThread() {
-    sem_init(&go_, 0, 0); sem_init(&done_, 0, 0);
-    t_ = std::thread([this]() {
-      for (;;) {
-        while (sem_wait(&go_) != 0) {}
-        if (stop_) return;
-        job_();
-        sem_post(&done_);
-      }
-    });
-  }
-  ~HelperThread() { stop_ = true; sem_post(&go_); t_.join(); sem_destroy(&go_); sem_destroy(&done_); }
-  void start(std::function<void()> job) { job_ = std::move(job); busy_ = true; sem_post(&go_); }
-  void join() { if (busy_) { while (sem_wait(&done_) != 0) {} busy_ = false; } }
- private:
-  std::thread t_;
-  sem_t go_, done_;
-  std::function<void()> job_;
-  bool busy_ = false;
-  std::atomic<bool> stop_{false};
-};
-
 // Debug / test switches of the phase stage (lcr_debug_set, include/lcr.h): none of them is read from the environment inside
 // the library; the defaults are the product behaviour.
 struct PhaseDebug {
@@ -129,6 +102,8 @@ struct PhaseDebug {
   int async_phase = 0;          // "async_phase": lcr_phase returns when its kernels are queued (on a queue of its own); settle() collects the results
 };
 
+struct PhaseCall;   // k4_phase.hip
+
 struct PhaseHost {
   PhaseDebug dbg;
   std::string lock_dir;          // directory of the per-GPU lock file of persistent launches ("" = /tmp/liblcr-<uid>)
@@ -139,16 +114,28 @@ struct PhaseHost {
   const int8_t* r_haplotag = nullptr;      // results of the last run (host vectors above or pinned buffers)
   const uint8_t* r_assignment = nullptr;
   const uint32_t* r_phase_set = nullptr;
-  DevBuf d_state[40];
-  DevBuf d_tie_flag, d_tie_q, d_tie_ch, d_tie_terms;
-  DevBuf d_rbest_buf;   // enumeration branch: best objective seen per region (filled before the staging kernel)   // k4_chain_wg: regions that met a class-2 / class-4 tie, scratch of their second run
-  DevBuf d_spec_sig, d_spec_de, d_spec_res, d_pk, d_bt;   // working states / results of the speculative half-rounds (k4_grid.hip)
-  DevBuf d_read_rec;             // per-row results as 12-byte records in HBM, written by k4_post
-  DevBuf d_lut64, d_tie, d_enum_st;   // f64 table of the tie paths (PostLut), census counters, final states of the enumeration restarts
+  // ---- buffers, by the step that uses them (each grows to the largest batch seen; freed with the context)
+  // staging matrices (k4_stage): region table, row / column-major phase matrices, per-SNP bytes and constants, cursors, source rows
+  DevBuf d_reg, d_prow_ptr, d_pcol, d_pval, d_ccol_ptr, d_crow, d_cval, d_snp, d_snp_const, d_cur, d_prow_src;
+  DevBuf d_grid_ctl, d_grid_tot;   // grid-scope launches: barrier blocks, k4_stage's per-workgroup totals
+  // result state: sigma | delta | eta | objective of the enumeration and of the chain regions, per-row records in HBM (k4_post),
+  // f64 table of the tie paths (PostLut), tie census counters; k4_post's step clocks (phase_prof)
+  DevBuf d_st_enum, d_st_chain, d_read_rec, d_lut64, d_tie, d_prof_clk;
   bool lut64_ready = false;
+  // chain-region scratch: descriptors, post-phase slots, LD pair table, adjacency, partial counts, per-SNP ints / bytes / doubles,
+  // block info, per-row / per-entry ints, working state, accumulators, sigma words
+  DevBuf d_ch_desc, d_ch_slots, d_ch_tbl, d_ch_adj, d_ch_part, d_ch_snpi, d_ch_snpb, d_ch_q, d_ch_info, d_ch_rowi, d_ch_enti, d_ch_work, d_ch_macc, d_ch_sig;
+  DevBuf d_spec_sig, d_spec_de, d_spec_res, d_pk, d_bt;   // working states / results of the speculative half-rounds (k4_grid.hip)
+  DevBuf d_tie_flag, d_tie_q, d_tie_ch, d_tie_terms;      // k4_chain_wg: regions that met a class-2 / class-4 tie, scratch of their second run
+  // enumeration jobs: upload table, objectives | winners, final states of the restarts, best objective seen per region (filled
+  // before the staging kernel), state scratch, row scores and repair lists of the repair pass, f64 terms of the global-memory class
+  DevBuf d_en_job, d_en_obj, d_en_st, d_en_rbest, d_en_scr, d_en_qrow, d_en_redo, d_en_terms;
+  DevBuf d_gp_snp, d_gp_ent, d_gp_part;   // k4_gpost scratch: per SNP and row, per entry, partial counts
+  // pinned: region sizes (k4_stage), k4_post's results and candidate mirror | objectives, tie census, the two upload tables
+  HostBuf h_stat, h_res, h_cand_obj, h_census, h_en_up, h_ch_up;
+  HostBuf h_row_ptr, h_col, h_val, h_links, h_st_enum, h_st_chain;   // host-epilogue copies: fragment matrix, both states
   unsigned long long tie_census[TIE_NCTR] = {0, 0, 0, 0, 0, 0, 0, 0};   // of the last run (lcr_get_tie_census)
   bool read_rec_stale = false;   // some regions took the host epilogue: the records are rebuilt from the host arrays on demand
-  HostBuf h_pin[12];   // pinned staging: row_ptr, col, val, links, enum state, region sizes, chain state, results, job tables, chain start
   hipStream_t side = nullptr;   // second queue: fragment matrix download + chain regions
   hipEvent_t ev_in = nullptr, ev_csr = nullptr, ev_fork = nullptr, ev_join = nullptr;
   hipStream_t aux = nullptr;   // the bit-state and global-memory enumeration classes beside the streaming class
@@ -178,7 +165,6 @@ struct PhaseHost {
   } pend;
   int settle(std::string* err);
   HostPool* pool = nullptr;
-  HelperThread* helper_thread = nullptr;
   void* work = nullptr;   // PhaseWork (k4_phase.hip): per-region host state reused across calls
   ChainDev chain_dev{};                // chain-region buffers of the last run (LD blocks are read back from them)
   std::vector<ChainDesc> chain_desc;
@@ -188,22 +174,16 @@ struct PhaseHost {
   int ld_blocks(const PhaseInputs& in, int region, std::vector<int32_t>* off, std::vector<int32_t>* snps, hipStream_t s, std::string* err);
   void free_work();
   int run(const PhaseInputs& in, const lcr_params& p, hipStream_t s, std::string* err);
+  // the steps of run(), in order (k4_phase.hip); PhaseCall holds the values of one call
+  int open_queues(PhaseCall& c), size_buffers(PhaseCall& c), stage(PhaseCall& c), classify(PhaseCall& c), wait_sizes(PhaseCall& c);
+  int launch_enum(PhaseCall& c), launch_chain(PhaseCall& c), launch_gpost(PhaseCall& c), report_prof(PhaseCall& c), host_epilogue(PhaseCall& c);
+  bool mark_pending(PhaseCall& c);
+  // queues, events, host pool and host work (the buffers free themselves; the owner has drained the queues: lcr_ctx_destroy)
   void release() {
-    for (auto& b : d_state) b.release();
-    d_lut64.release(); d_tie.release(); d_enum_st.release(); lut64_ready = false;
-    d_read_rec.release(); d_spec_sig.release(); d_spec_de.release(); d_spec_res.release(); d_pk.release(); d_bt.release();
-    for (auto& b : h_pin) b.release();
-    if (side) { (void)hipStreamDestroy(side); side = nullptr; }
-    if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
-    if (ev_csr) { (void)hipEventDestroy(ev_csr); ev_csr = nullptr; }
-    if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
-    if (ev_join) { (void)hipEventDestroy(ev_join); ev_join = nullptr; }
-    if (aux) { (void)hipStreamDestroy(aux); aux = nullptr; }
-    if (main_q) { (void)hipStreamDestroy(main_q); main_q = nullptr; }
-    if (ev_user) { (void)hipEventDestroy(ev_user); ev_user = nullptr; }
-    for (int k = 0; k < 2; k++) { if (ev_gate[k]) (void)hipEventDestroy(ev_gate[k]); ev_gate[k] = nullptr; gate_set[k] = false; }
+    for (hipStream_t* q : {&side, &aux, &main_q}) { if (*q) (void)hipStreamDestroy(*q); *q = nullptr; }
+    for (hipEvent_t* e : {&ev_in, &ev_csr, &ev_fork, &ev_join, &ev_user, &ev_gate[0], &ev_gate[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    gate_set[0] = gate_set[1] = false;
     pending = false;
-    delete helper_thread; helper_thread = nullptr;
     delete pool; pool = nullptr;
     free_work();
   }

@@ -381,13 +381,15 @@ def test_k0_thousands_of_records_beyond_the_tile_window(engine_cls, orc):
     assert c.size >= 2
 
 
-@pytest.mark.parametrize("hook", ["LCR_ENUM_FORCE_STREAM", "LCR_ENUM_FORCE_BIG", "LCR_POST_HOST", "LCR_POST_HALF", "LCR_K3_HITS=0"])
+@pytest.mark.parametrize("hook", ["LCR_ENUM_FORCE_STREAM", "LCR_ENUM_FORCE_BIG", "LCR_POST_HOST", "LCR_POST_HALF", "LCR_K3_HITS=0",
+                                  "LCR_PHASE_PROF=2+LCR_GRID_MIN_ENTRIES=0"])
 def test_fallback_device_paths(engine_cls, orc, monkeypatch, hook):
     """The size-dependent fallbacks of the phase stage give the same results as the default kernels: the enumeration restarts one
     per wave with LDS-streamed entries (LCR_ENUM_FORCE_STREAM: every LDS-resident region, in the launch of the regions beyond the
     bit-state kernel's image) / from global memory, post-phase epilogue on the host, the eight-wave epilogue of the chain regions (taken when a batch has more chain
     regions than the device has CUs), the fragment matrix's count pass walking the CIGARs itself instead of taking the hits
-    the candidate stage's walk left (LCR_K3_HITS=0: the path of batches whose histograms came from the tiles)."""
+    the candidate stage's walk left (LCR_K3_HITS=0: the path of batches whose histograms came from the tiles), and a profiled run
+    (LCR_PHASE_PROF=2: the phase stage's step report, here with every chain region at grid scope and through k4_gpost)."""
     for h in hook.split("+"):
         name, _, value = h.partition("=")
         monkeypatch.setenv(name, value or "1")
