@@ -229,6 +229,28 @@ int lcr_get_candidates(lcr_ctx*, lcr_candidate_list* out);
  * is valid until the next lcr_candidates / lcr_load_batch on this ctx. */
 int lcr_get_candidates_device(lcr_ctx*, const lcr_candidate** dev_cand, int32_t* n_cand);
 
+/* replaces SNPFrag::import_external_candidates (candidate.rs:530-613, min_variant_qual = 0.0): the candidate stage of a run with
+ * user-provided sites (longcallR -v, thread.rs:107-116), in place of lcr_candidates.  Sites of the batch (one batch's or a whole
+ * contig's; those outside every region are ignored): pos0 0-based, ascending and unique; genotype codes of vcf.rs:440-446
+ * (0 = 0/0, 1 = 0/1 | 1/0, 2 = 1/1, 3 = 1/2 | 2/1, 4 = anything else); qual = QUAL (NaN when missing).  Positions carry no
+ * contig, and neither do the regions: the call is defined for a batch whose regions all lie on ONE contig, with that contig's
+ * sites (pipeline.run batches per contig; a caller that mixes contigs in a batch must import per contig batch).
+ * mem = LCR_MEM_HOST: the arrays are copied before the call returns (no host wait).  mem = LCR_MEM_DEVICE: the arrays are read
+ * in place on the context's stream -- they must be complete with respect to that stream when the call is made (written by it,
+ * or the writer's stream synchronised) and stay valid and unchanged until the candidate stage has been consumed (lcr_fragments,
+ * lcr_get_candidates*, lcr_ctx_sync); they are checked by a kernel whose verdict the call waits for (its one host wait).
+ * A site at column c of region g with
+ * genotype 1-3 and a qual that is not < 0 (NaN is kept) becomes a record; codes 0 and 4 and negative quals none.  Record fields:
+ *   pos, region; ref_base = the reference byte as stored (case kept); allele1 / cnt1, allele2 / cnt2 = get_two_major_alleles of
+ *   the column's A/C/G/T counts; depth = a + c + g + t; af1 / af2 = cnt / depth as f32 (NaN when depth is 0); qual = gq = the
+ *   site's qual; genotype 1: variant_type 1, genotype 0, flags HET | FOR_PHASING; 2: variant_type 2, genotype -1, HOM | FOR_PHASING;
+ *   3: variant_type 3, genotype -1, HOM.  n_alt, haplotype, phase_set, loglik, gt_prob and phase_score are 0.  No dense-cluster
+ *   sweep, no RNA-edit or low-fraction class.  Needs lcr_pileup (LCR_E_STATE); unsorted / duplicate positions or a code above 4:
+ *   LCR_E_ARG.  Afterwards lcr_get_candidates*, lcr_fragments and lcr_phase work as after lcr_candidates; lcr_candidates on the same
+ *   pileup is unaffected. */
+int lcr_import_candidates(lcr_ctx*, const lcr_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* genotype,
+                          const float* qual);
+
 /* replaces SNPFrag::get_fragments (fragment.rs:10-309); thread.rs:136-143 */
 int lcr_fragments(lcr_ctx*, const lcr_params*);
 int lcr_get_fragmat(lcr_ctx*, lcr_fragmat* out);
@@ -356,6 +378,23 @@ int lcr_bam_batch(lcr_bam*, int32_t ref_id, const lcr_read_filter*, int32_t n_re
                   const int32_t* len, lcr_reads* reads, const int32_t** read_begin, const uint64_t** name_off,
                   const char** names);
 
+/* ---- user-provided candidates: VCF reader, replaces get_genotype_quality_phase_from_vcf (vcf.rs:400-462) ----------------------
+ * Reads a plain-text VCF or a gzip / BGZF .vcf.gz (every gzip member) into per-contig site lists for lcr_import_candidates.  For
+ * every record and every sample whose GT has exactly two alleles: genotype code as in lcr_import_candidates (a missing allele counts
+ * as 3, so ./. and 0/. give 4); qual = QUAL as f32, NaN for '.'.  A later sample or a later record at the same position overwrites
+ * the earlier value (a code 4 included).  Samples with another GT length are skipped, a sites-only file yields no sites.  The phase
+ * bit, REF and ALT are not used; an indel is a site at its POS.  BCF input and records without a GT key fail with LCR_E_ARG (the
+ * reference panics).  No GPU is involved; *out is set even when the call fails (unless out of memory): lcr_vcf_last_error explains,
+ * lcr_vcf_close frees.  n_threads is reserved (the reader runs on the calling thread). */
+typedef struct lcr_vcf lcr_vcf;
+int lcr_vcf_open(const char* path, int32_t n_threads, lcr_vcf** out);
+void lcr_vcf_close(lcr_vcf*);
+const char* lcr_vcf_last_error(const lcr_vcf*);
+/* contig names that hold at least one site, in the order of their first record */
+int lcr_vcf_contigs(lcr_vcf*, int32_t* n, const char* const** names);
+/* the sites of one contig sorted by position (n = 0 for a contig without sites); pointers valid until lcr_vcf_close */
+int lcr_vcf_contig(lcr_vcf*, const char* name, int32_t* n, const int64_t** pos0, const uint8_t** genotype, const float** qual);
+
 /* ---- phased BAM, replaces thread.rs:307-361 ------------------------------------------------
  * Writes to out_path the header of the opened file and, region by region in the order given (region i = columns
  * [start0[i], start0[i] + len[i]) of contig region_ref[i]), the records the reference's loop keeps: fetched by the
@@ -420,7 +459,8 @@ int lcr_debug_set(lcr_ctx*, const char* key, int64_t value);
 enum { LCR_K_SPANS = 0 /* K0: CIGAR decode + binning */, LCR_K_PILEUP, LCR_K_CAND_FILTER, LCR_K_CAND_HIST, LCR_K_CAND_GT,
        LCR_K_FRAG_COUNT, LCR_K_FRAG_FILL, LCR_K_PHASE,
        LCR_K_BIND /* lcr_load_batch: read headers, read / tile -> region tables, op blocks' first reads (part of the pileup stage) */,
-       LCR_K_BIND_TABLE /* lcr_load_batch of a device batch: region table + CIGAR layout check, before its one host wait */, LCR_NKERNELS };
+       LCR_K_BIND_TABLE /* lcr_load_batch of a device batch: region table + CIGAR layout check, before its one host wait */,
+       LCR_K_CAND_IMPORT /* lcr_import_candidates: count, scan, emit */, LCR_NKERNELS };
 int lcr_enable_timing(lcr_ctx*, int on);
 int lcr_kernel_ms(lcr_ctx*, int kernel, float* ms);
 /* Bytes the pileup tally kernel (K1) of the last lcr_pileup has to move: read bases once (B) + 8-byte

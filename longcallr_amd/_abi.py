@@ -18,7 +18,7 @@ F_RNA_EDIT, F_DENSE, F_HET, F_FOR_PHASING, F_HOM, F_SINGLE, F_NON_SELECTED, F_CA
     1, 2, 4, 8, 16, 32, 64, 128)
 
 (K_SPANS, K_PILEUP, K_CAND_FILTER, K_CAND_HIST, K_CAND_GT, K_FRAG_COUNT, K_FRAG_FILL, K_PHASE, K_BIND, K_BIND_TABLE,
- NKERNELS) = range(11)
+ K_CAND_IMPORT, NKERNELS) = range(12)
 
 
 class LcrReads(C.Structure):

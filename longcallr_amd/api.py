@@ -3,6 +3,7 @@ the C ABI.  Names follow the reference methods they replace:
 
     Engine.fill_data_into_freq_vec  -> Profile::fill_data_into_freq_vec   (util.rs:621)
     Engine.get_candidate_snps       -> SNPFrag::get_candidate_snps        (candidate.rs:54)
+    Engine.import_external_candidates -> SNPFrag::import_external_candidates (candidate.rs:530)
     Engine.get_fragments            -> SNPFrag::get_fragments             (fragment.rs:10)
     Engine.phase                    -> SNPFrag::phase + post-phase steps  (phase.rs:1087, snpfrags.rs)
 
@@ -45,7 +46,9 @@ class Engine:
             raise LcrError("lcr_ctx_create(device=%d) failed with %d: no usable HIP device; "
                            "liblcr has no CPU fallback" % (device, rc))
         self.h = h
+        self.device = device
         self.params = params if params is not None else _abi.make_params()
+        self._sites = None   # device tensors of the last import_external_candidates: its kernels read them after the call returns
         self._keep = None
         if timing:
             self.lib.lcr_enable_timing(self.h, 1)
@@ -80,6 +83,7 @@ class Engine:
 
     def sync(self):
         self._chk(self.lib.lcr_ctx_sync(self.h), "lcr_ctx_sync")
+        self._sites = None
 
     def set_async_phase(self, on=True):
         """lcr_ctx_set_async_phase: phase() returns with its kernels in flight; getters / sync() collect the results (include/lcr.h)"""
@@ -134,8 +138,51 @@ class Engine:
         self._chk(self.lib.lcr_candidates(self.h, C.byref(self.params)), "lcr_candidates")
         return self
 
+    def import_external_candidates(self, pos0, genotype, qual):
+        """SNPFrag::import_external_candidates (candidate.rs:530-613): the candidate stage from user-provided sites instead of
+        get_candidate_snps -- pos0 ascending and unique, genotype codes 0-4, qual f32 (vcf.read_sites gives them per contig).
+        numpy arrays (converted), or contiguous int64 / uint8 / float32 tensors on this engine's device, used in place
+        (LCR_MEM_DEVICE): they are made ready on the context's stream (the current torch stream is waited for) and held by the
+        engine until the stage's kernels have read them (get_fragments, candidates, sync or the next import)."""
+        if any(getattr(t, "is_cuda", False) for t in (pos0, genotype, qual)):
+            import torch
+            ts = (pos0, genotype, qual)
+            want = (torch.int64, torch.uint8, torch.float32)
+            if not all(getattr(t, "is_cuda", False) for t in ts):
+                raise ValueError("device sites: pos0, genotype and qual must all be device tensors")
+            for name, t, dt in zip(("pos0", "genotype", "qual"), ts, want):
+                if t.dtype != dt:
+                    raise ValueError("device sites: %s must be %s, got %s" % (name, dt, t.dtype))
+                if t.device.index != self.device:
+                    raise ValueError("device sites: %s is on %s, the engine on device %d" % (name, t.device, self.device))
+                if t.dim() != 1 or not t.is_contiguous():
+                    raise ValueError("device sites: %s must be a contiguous 1-d tensor" % name)
+            if len({t.numel() for t in ts}) != 1:
+                raise ValueError("pos0, genotype and qual must have the same length")
+            self._release_sites()
+            torch.cuda.current_stream(self.device).synchronize()   # (the tensors may still be being written on torch's stream)
+            self._chk(self.lib.lcr_import_candidates(self.h, C.byref(self.params), _abi.LCR_MEM_DEVICE, int(pos0.numel()),
+                                                     *[C.c_void_p(t.data_ptr()) for t in ts]), "lcr_import_candidates")
+            self._sites = ts
+            return self
+        p = np.ascontiguousarray(pos0, dtype=np.int64)
+        g = np.ascontiguousarray(genotype, dtype=np.uint8)
+        q = np.ascontiguousarray(qual, dtype=np.float32)
+        if not (p.size == g.size == q.size):
+            raise ValueError("pos0, genotype and qual must have the same length")
+        self._release_sites()
+        self._chk(self.lib.lcr_import_candidates(self.h, C.byref(self.params), _abi.LCR_MEM_HOST, int(p.size), p.ctypes.data, g.ctypes.data,
+                                                 q.ctypes.data), "lcr_import_candidates")   # (host arrays are copied before the call returns)
+        return self
+
+    def _release_sites(self):
+        """drop the device sites of the last import once its kernels are done (they are queued behind the call's return)"""
+        if self._sites is not None:
+            self.sync()
+
     def get_fragments(self):
         self._chk(self.lib.lcr_fragments(self.h, C.byref(self.params)), "lcr_fragments")
+        self._sites = None   # (lcr_fragments has waited for the candidate stage: the imported sites are read)
         return self
 
     def phase(self):
@@ -154,6 +201,7 @@ class Engine:
     def candidates(self):
         o = _abi.LcrCandidateList()
         self._chk(self.lib.lcr_get_candidates(self.h, C.byref(o)), "lcr_get_candidates")
+        self._sites = None   # (the getter has waited for the candidate stage)
         return (_view(o.cand, _abi.CAND_DTYPE, o.n_cand), _view(o.region_off, np.int32, o.n_regions + 1))
 
     def candidates_device(self):

@@ -70,6 +70,9 @@ struct lcr_ctx {
   std::vector<lcr_candidate> h_cand;
   std::vector<int32_t> h_cand_off;
   DevBuf d_cand, d_cand_off;
+  DevBuf imp_pos, imp_gt, imp_q, imp_cnt;   // lcr_import_candidates: host sites copied to HBM, sites kept per region
+  HostBuf h_imp_bad;                         // ... verdict of the check of device-resident sites
+  hipEvent_t ev_imp = nullptr;
 
   // K3
   bool have_frag = false;
@@ -365,7 +368,7 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
   for (auto& u : c->up) if (u.ev) (void)hipEventDestroy(u.ev);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  for (hipEvent_t e : {c->ev_dl, c->ev_cand_dl, c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_dl, c->ev_cand_dl, c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp}) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2 * lcr_ctx::UP_LANES; k++) if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
   c->phase.release();
   for (int k = 0; k < LCR_NKERNELS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);
@@ -884,6 +887,82 @@ int lcr_candidates(lcr_ctx* c, const lcr_params* p) {
   c->have_cand = true;
   HT("cand:ret");
   c->have_frag = c->have_phase = false;
+  return LCR_OK;
+}
+
+// replaces SNPFrag::import_external_candidates (candidate.rs:530-613) -- the candidate stage of thread.rs:107-116 -- for sites the
+// caller brings (a VCF, lcr_vcf_*).  Leaves the context as lcr_candidates does for the stages behind it; the regular path's own state
+// (pass-1 flags and tile counts of lcr_pileup, the survivors' size guess) is not touched, so lcr_candidates can follow on the same pileup.
+int lcr_import_candidates(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* genotype,
+                          const float* qual) {
+  HT("import");
+  if (!c) return LCR_E_ARG;
+  if (!p || n_sites < 0 || (mem != LCR_MEM_HOST && mem != LCR_MEM_DEVICE)) {
+    c->err = "lcr_import_candidates: null params, n_sites < 0 or mem not LCR_MEM_HOST / LCR_MEM_DEVICE";
+    return LCR_E_ARG;
+  }
+  if (n_sites > 0 && (!pos0 || !genotype || !qual)) { c->err = "lcr_import_candidates: null site array"; return LCR_E_ARG; }
+  if (!c->have_planes) { c->err = "lcr_import_candidates before lcr_pileup"; return LCR_E_STATE; }
+  if (mem == LCR_MEM_HOST)
+    for (int32_t i = 0; i < n_sites; i++)
+      if (genotype[i] > 4 || (i > 0 && pos0[i - 1] >= pos0[i])) {
+        c->err = "lcr_import_candidates: sites must be sorted by position without duplicates, genotype codes 0-4 (site " + std::to_string(i) + ")";
+        return LCR_E_ARG;
+      }
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = phase_settle(c); if (rc) return rc; }   // (the previous batch's phase stage reads the candidate / fragment buffers rewritten from here on)
+  if (c->cand_pending && c->cand_dl_other) HIPCHK(c, hipEventSynchronize(c->ev_cand_dl));
+  const int ng = c->bv.n_regions;
+  const int64_t* d_pos = nullptr; const uint8_t* d_gt = nullptr; const float* d_q = nullptr;
+  { int rc = upload(c, c->imp_pos, pos0, (size_t)n_sites, &d_pos, mem); if (rc) return rc; }
+  { int rc = upload(c, c->imp_gt, genotype, (size_t)n_sites, &d_gt, mem); if (rc) return rc; }
+  { int rc = upload(c, c->imp_q, qual, (size_t)n_sites, &d_q, mem); if (rc) return rc; }
+  if (mem == LCR_MEM_DEVICE && n_sites > 0) {   // (the one host wait of a device-resident list: its contract, as lcr_load_batch checks a device batch)
+    HIPCHK(c, c->h_imp_bad.reserve(64));
+    int32_t* bad = c->h_imp_bad.as<int32_t>();
+    *bad = 0;
+    int32_t* d_bad = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer((void**)&d_bad, bad, 0));
+    launch_k2_import_check(d_pos, d_gt, n_sites, d_bad, c->stream);
+    if (!c->ev_imp) HIPCHK(c, hipEventCreateWithFlags(&c->ev_imp, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_imp, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev_imp));
+    if (*(volatile int32_t*)bad) { c->err = "lcr_import_candidates: sites must be sorted by position without duplicates, genotype codes 0-4"; return LCR_E_ARG; }
+  }
+  c->res_valid = false;   // (the last lcr_phase's results are rewritten from here on: lcr_collect_phase had to come before this call)
+  // records <= sites: every buffer is sized by n_sites, no count comes back to the host
+  HIPCHK(c, c->imp_cnt.reserve(std::max(ng, 1) * 4));
+  HIPCHK(c, c->d_cand.reserve(std::max<size_t>(n_sites, 1) * sizeof(lcr_candidate)));
+  HIPCHK(c, c->d_cand_off.reserve((ng + 1) * 4));
+  HIPCHK(c, c->h_stage[1].reserve(std::max<size_t>(n_sites, 1) * sizeof(lcr_candidate)));
+  HIPCHK(c, c->h_stage[2].reserve((size_t)(ng + 1) * 4));
+  c->h_cand.clear();
+  c->h_cand_off.assign(ng + 1, 0);
+  c->hits_valid = false;   // (no hit lists: K3 walks the CIGARs)
+  { lcr_candidate* hp = nullptr; int32_t* ho = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer((void**)&hp, c->h_stage[1].p, 0));
+    HIPCHK(c, hipHostGetDevicePointer((void**)&ho, c->h_stage[2].p, 0));
+    if (ng == 0) c->h_stage[2].as<int32_t>()[0] = 0;
+    Timer t(c, LCR_K_CAND_IMPORT);
+    launch_k2_import_count(c->bv, d_pos, d_gt, d_q, n_sites, c->imp_cnt.as<int32_t>(), c->stream);
+    launch_scan_i32(c->scan_tmp, c->imp_cnt.as<int32_t>(), c->d_cand_off.as<int32_t>(), ng, c->d_cand_off.as<int32_t>() + ng, c->stream);
+    launch_k2_import_emit(c->bv, c->n_cols, c->planes.as<uint32_t>(), d_pos, d_gt, d_q, n_sites, c->d_cand_off.as<int32_t>(),
+                          c->d_cand.as<lcr_candidate>(), c->stream, hp, ho); }
+  c->cand_dl_other = false;
+  // rows of the fragment matrix per region, as lcr_candidates leaves them
+  HIPCHK(c, c->region_rows.reserve(std::max(ng, 1) * 4));
+  HIPCHK(c, c->h_stage[3].reserve(std::max(ng, 1) * 4));
+  HIPCHK(c, c->row_region_off.reserve((ng + 1) * 4));
+  { int32_t* d_rr = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer((void**)&d_rr, c->h_stage[3].p, 0));
+    launch_k3_rows_offsets(c->bv, c->d_cand.as<lcr_candidate>(), c->d_cand_off.as<int32_t>(), c->region_rows.as<int32_t>(), c->row_region_off.as<int32_t>(), c->stream, d_rr); }
+  if (!c->ev_cand) HIPCHK(c, hipEventCreateWithFlags(&c->ev_cand, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->ev_cand, c->stream));
+  HIPCHK(c, hipGetLastError());
+  c->cand_pending = true;
+  c->have_cand = true;
+  c->have_frag = c->have_phase = false;
+  HT("import:ret");
   return LCR_OK;
 }
 

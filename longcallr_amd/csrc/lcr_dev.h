@@ -225,6 +225,12 @@ void launch_k2_gt(const DevParams& p, const Survivor* sv, int32_t n_sv, const ui
 void launch_k2_finish(DevBuf& scan_tmp, const lcr_candidate* tmp, const int32_t* keep, int32_t n_sv, const int32_t* sv_region_off,
                       int32_t n_regions, int32_t* pos, int32_t* idx, lcr_candidate* out, int32_t* cand_off, uint32_t dense_win,
                       uint32_t min_dense_cnt, hipStream_t s, lcr_candidate* h_cand = nullptr, int32_t* h_off = nullptr);
+// k2_import.hip: the candidate stage of caller-provided sites (lcr_import_candidates, candidate.rs:530-613)
+void launch_k2_import_count(const BatchView& b, const int64_t* pos0, const uint8_t* gt, const float* qual, int32_t n_sites, int32_t* count /* n_regions */, hipStream_t s);
+void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int64_t* pos0, const uint8_t* gt, const float* qual,
+                           int32_t n_sites, const int32_t* cand_off /* n_regions + 1 */, lcr_candidate* out, hipStream_t s,
+                           lcr_candidate* h_cand /* pinned (device pointer): the records and ... */, int32_t* h_off /* ... their offsets, or nullptr */);
+void launch_k2_import_check(const int64_t* pos0, const uint8_t* gt, int32_t n_sites, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k3_row_offsets(const int32_t* region_rows, int32_t ng, int32_t* row_region_off, hipStream_t s);
 void launch_k3_region_entries(const int64_t* row_ptr, const int32_t* row_region_off, int32_t ng, int64_t* region_e_off, hipStream_t s, int64_t* host_out = nullptr);
 struct K3Hits {   // what k2_hist left for K3 (hit_cnt == nullptr: nothing -- K3 walks every read's CIGAR itself)

@@ -11,8 +11,9 @@ the five hot-path calls, with one context per GPU instead of one rayon task per 
   thread.rs:223-305 VCF header + records                     -> write_vcf (records from vcf.format_records)
   thread.rs:307-361 phased BAM                               -> lcr_bam_write_phased
 
-Not here (out of scope): gene annotation / exon filter, external VCF candidates, down-sampling,
-region truncation, the somatic model.  Records are written in contig order of the .fai and position order inside
+  thread.rs:70-74,107-116 user-provided candidates (-v)   -> vcf.read_sites once + lcr_import_candidates per chunk
+
+Not here (out of scope): gene annotation / exon filter, down-sampling, region truncation, the somatic model.  Records are written in contig order of the .fai and position order inside
 a contig (the reference writes them in region-completion order, thread.rs:216-221: compare as a set)."""
 import os
 
@@ -105,7 +106,7 @@ def _gather_names(name_off, blob, rows):
 
 
 def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs=None, device=0, threads=0, seed=2025,
-        read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, **param_overrides):
+        read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -113,7 +114,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     chunks are then in flight on it, each filling the queue gaps of the others' host round trips (bench.py
     stages.batches_in_flight: +25 % at three).  async_phase: the engines run the asynchronous phase stage (a chunk's upload + pileup
     beside the previous chunk's resolve / post-phase tails, results through lcr_collect_phase).  The output does not depend on devices,
-    chunk_cost or async_phase."""
+    chunk_cost or async_phase.
+    input_vcf: phase the sites of this VCF / .vcf.gz instead of calling candidates (longcallR -v, thread.rs:107-116): the file is read
+    once (vcf.read_sites), every chunk takes its contig's sites inside its span (none when the contig is not in the file) through
+    lcr_import_candidates.  Adds the stats input_sites (sites read) and imported_sites (sites handed to the candidate stage)."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     fai = ref_path + ".fai"
@@ -134,6 +138,12 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     free = list(range(len(engines)))
     free_lock = threading.Condition()
     stats = dict(contigs=0, regions=0, reads=0, candidates=0, vcf_records=0, chunks=0)
+    sites = None
+    if input_vcf is not None:
+        sites = vcf.read_sites(input_vcf)      # vcf.rs:400-462, once for the whole run (thread.rs:70-74)
+        stats["input_sites"] = sum(int(v[0].size) for v in sites.values())
+        stats["imported_sites"] = 0
+    no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
     # Every engine is a long-lived worker with the ASYNCHRONOUS phase stage (lcr_ctx_set_async_phase, include/lcr.h): a chunk is uploaded
     # into one of the context's two staging slots (lcr_load_batch_async + lcr_bind_batch: the device-resident form, which does not wait
@@ -161,7 +171,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
         results[idx] = out
 
-    def work(idx, batch, name, want_reads):   # one chunk on whichever engine is free
+    def work(idx, batch, name, want_reads, imp):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates)
         with free_lock:
             while not free:
                 free_lock.wait()
@@ -174,7 +184,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             E.fill_data_into_freq_vec()
             if in_flight[k] is not None:
                 finish(k)
-            E.get_candidate_snps().get_fragments()
+            if imp is None:
+                E.get_candidate_snps()
+            else:
+                E.import_external_candidates(*imp)
+            E.get_fragments()
             fm = None
             if want_reads:      # rows of the fragment matrix (read of every row, num_hete_links >= min_linkers): known before the phase stage
                 f = E.fragmat()
@@ -209,9 +223,15 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                         for s, l, _ in chunk]
                 batch = nb.batch(rid, [(s, l) for s, l, _ in chunk], wins, name_format="blob", **flt)
                 stats["reads"] += batch.n_reads; stats["chunks"] += 1
+                imp = None
+                if sites is not None:       # thread.rs:108: a contig the VCF does not name gets no candidates
+                    sp, sg, sq = sites.get(name, no_sites)
+                    lo, hi = np.searchsorted(sp, [chunk[0][0], chunk[-1][0] + chunk[-1][1]])
+                    imp = (sp[lo:hi], sg[lo:hi], sq[lo:hi])
+                    stats["imported_sites"] += int(hi - lo)
                 while len(pending) > len(engines):     # bounded: at most one batch waiting per engine
                     pending.pop(0).result()
-                pending.append(pool.submit(work, n_chunks, batch, name, out_bam is not None))
+                pending.append(pool.submit(work, n_chunks, batch, name, out_bam is not None, imp))
                 n_chunks += 1
                 regions_out.extend((rid, s, l) for s, l, _ in chunk)
         for f in pending:

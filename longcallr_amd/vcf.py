@@ -1,9 +1,50 @@
-"""VCF body text of the phased candidates — the parity diff surface.
+"""VCF body text of the phased candidates — the parity diff surface — and the reader of user-provided sites.
 
 Host formatting only; mirrors SNPFrag::output_phased_vcf (reference src/vcf.rs:27-306) and the
 record writer of src/thread.rs:266-303 (records without an ALT allele are silently skipped).
+read_sites wraps liblcr's VCF reader (lcr_vcf_*, include/lcr.h: get_genotype_quality_phase_from_vcf, vcf.rs:400-462).
 """
+import ctypes as C
+import os
+
+import numpy as np
+
 from . import _abi
+
+
+def read_sites(path):
+    """A VCF / .vcf.gz -> {contig: (pos0 int64, genotype uint8, qual float32)}, every array sorted by position: the sites
+    lcr_import_candidates takes (genotype codes 0-4 and the overwrite rules of vcf.rs:400-462, see include/lcr.h)."""
+    from . import _lib
+    lib = _lib.load()
+    h = C.c_void_p()
+    rc = lib.lcr_vcf_open(os.fsencode(path), 0, C.byref(h))
+    try:
+        if rc:
+            raise _lib.LcrError("lcr_vcf_open(%s): %s" % (path, lib.lcr_vcf_last_error(h).decode() if h else "out of memory"))
+        n, names = C.c_int32(), C.POINTER(C.c_char_p)()
+        if lib.lcr_vcf_contigs(h, C.byref(n), C.byref(names)):
+            raise _lib.LcrError(lib.lcr_vcf_last_error(h).decode())
+        out = {}
+        for name in [names[i] for i in range(n.value)]:
+            m, pos, gt, q = C.c_int32(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+            if lib.lcr_vcf_contig(h, name, C.byref(m), C.byref(pos), C.byref(gt), C.byref(q)):
+                raise _lib.LcrError(lib.lcr_vcf_last_error(h).decode())
+            k = m.value
+
+            def arr(ptr, dt):
+                if k == 0:
+                    return np.zeros(0, dt)
+                return np.frombuffer((C.c_char * (k * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).copy()
+            out[name.decode()] = (arr(pos, np.int64), arr(gt, np.uint8), arr(q, np.float32))
+        return out
+    finally:
+        if h:
+            lib.lcr_vcf_close(h)
+
+
+def _f2(x):  # Rust `{:.2}` of an f32: NaN prints as "NaN" (an imported site at a column without A/C/G/T counts)
+    return "NaN" if x != x else "%.2f" % x
 
 
 def _as_i32(x):  # Rust `f64 as i32`: saturating, NaN -> 0
@@ -52,8 +93,8 @@ def format_records(cands, chrom, min_phase_score):
                 continue
             gt = {1: "0/1", 2: "1/1", 3: "1/2"}[vt]
             filt, info, fmt = "dn", "RDS=dense_snp", "GT:GQ:DP:AF"
-            sample = ("%s:%d:%d:%.2f,%.2f" % (gt, gq, dp, af[0], af[1]) if vt == 3
-                      else "%s:%d:%d:%.2f" % (gt, gq, dp, af[0]))
+            sample = ("%s:%d:%d:%s,%s" % (gt, gq, dp, _f2(af[0]), _f2(af[1])) if vt == 3
+                      else "%s:%d:%d:%s" % (gt, gq, dp, _f2(af[0])))
         elif fl & _abi.F_NON_SELECTED:  # vcf.rs:80-174
             info, fmt = "RDS=noselect", "GT:GQ:DP:AF"
             if fl & _abi.F_RNA_EDIT:
@@ -62,15 +103,15 @@ def format_records(cands, chrom, min_phase_score):
                 one_alt()
                 filt = "RnaEdit"
                 gt = "0/1" if vt == 1 else "1/1"
-                sample = "%s:%d:%d:%.2f" % (gt, gq, dp, af[0])
+                sample = "%s:%d:%d:%s" % (gt, gq, dp, _f2(af[0]))
             else:
                 if vt in (0, 1, 2):
                     one_alt()
                     gt, filt = {0: ("0/0", "HomRef"), 1: ("0/1", "LowQual"), 2: ("1/1", "PASS")}[vt]
                 else:
                     by_genotype()
-                sample = ("%s:%d:%d:%.2f" % (gt, gq, dp, af[0]) if gt in ("0/0", "0/1", "1/1")
-                          else "%s:%d:%d:%.2f,%.2f" % (gt, gq, dp, af[0], af[1]))
+                sample = ("%s:%d:%d:%s" % (gt, gq, dp, _f2(af[0])) if gt in ("0/0", "0/1", "1/1")
+                          else "%s:%d:%d:%s,%s" % (gt, gq, dp, _f2(af[0]), _f2(af[1])))
         else:  # vcf.rs:175-303
             info, fmt = "RDS=select", "GT:GQ:PS:DP:AF:PQ"
             if float(s["phase_score"]) >= float(min_phase_score):
@@ -85,8 +126,8 @@ def format_records(cands, chrom, min_phase_score):
                     by_genotype()
             ps = str(int(s["phase_set"])) if int(s["phase_set"]) != 0 else "."
             pq = float(s["phase_score"])
-            sample = ("%s:%d:%s:%d:%.2f:%.2f" % (gt, gq, ps, dp, af[0], pq) if gt in ("0/0", "0/1", "1/1", "0|1", "1|0")
-                      else "%s:%d:%s:%d:%.2f,%.2f:%.2f" % (gt, gq, ps, dp, af[0], af[1], pq))
+            sample = ("%s:%d:%s:%d:%s:%.2f" % (gt, gq, ps, dp, _f2(af[0]), pq) if gt in ("0/0", "0/1", "1/1", "0|1", "1|0")
+                      else "%s:%d:%s:%d:%s,%s:%.2f" % (gt, gq, ps, dp, _f2(af[0]), _f2(af[1]), pq))
         if len(alt) not in (1, 2):
             continue
         out.append("%s\t%d\t.\t%s\t%s\t%d\t%s\t%s\t%s\t%s\n" % (

@@ -2,6 +2,7 @@
 """BAM + reference FASTA (+ .fai) -> phased VCF (and phased BAM) on one MI355X: longcallr_amd.pipeline.run.
 
   python tools/run_pipeline.py -b reads.bam -f ref.fa -o out.vcf [--out-bam phased.bam] [-p hifi-masseq] [-c chr20,chr21]
+                                 [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
 """
 import argparse
 import json
@@ -23,9 +24,10 @@ def main():
     ap.add_argument("-t", "--threads", type=int, default=0, help="host threads of the BAM decoder / writer (0 = all)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=2025)
+    ap.add_argument("-v", "--input-vcf", help="user-provided candidate sites (VCF / .vcf.gz with GT): phased instead of called")
     a = ap.parse_args()
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
-                      device=a.device, threads=a.threads, seed=a.seed)
+                      device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf)
     print(json.dumps(st))
 
 
