@@ -221,7 +221,12 @@ int lcr_host_unregister(void* p);
 int lcr_pileup(lcr_ctx*, const lcr_params*);
 int lcr_get_columns(lcr_ctx*, lcr_columns* out);
 
-/* replaces SNPFrag::get_candidate_snps (candidate.rs:54-528); thread.rs:118-133 */
+/* replaces SNPFrag::get_candidate_snps (candidate.rs:54-528); thread.rs:118-133.
+ * May be called again on the same pileup, also after lcr_import_candidates / lcr_fragments / lcr_phase: each call is a fresh candidate
+ * stage.  Its params may differ from lcr_pileup's in the fields the pileup does not read -- min_depth, max_depth, min_af,
+ * min_af_intron, low_cnt_cut, low_frac_cut, use_strand_bias, min_baseq, min_qual, dense_win, min_dense_cnt (and the fields of the
+ * later stages) --; platform and dist_to_end must be the pileup's (LCR_E_ARG otherwise, nothing changed), and so should polya_len
+ * (the HiFi presets' histograms apply the poly-A mask again). */
 int lcr_candidates(lcr_ctx*, const lcr_params*);
 int lcr_get_candidates(lcr_ctx*, lcr_candidate_list* out);
 /* The same records in device memory (HBM), current after lcr_candidates and after lcr_phase: for consumers that stay
@@ -251,13 +256,20 @@ int lcr_get_candidates_device(lcr_ctx*, const lcr_candidate** dev_cand, int32_t*
 int lcr_import_candidates(lcr_ctx*, const lcr_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* genotype,
                           const float* qual);
 
-/* replaces SNPFrag::get_fragments (fragment.rs:10-309); thread.rs:136-143 */
+/* replaces SNPFrag::get_fragments (fragment.rs:10-309); thread.rs:136-143.
+ * Reads the records of the last candidate stage (lcr_candidates or lcr_import_candidates); may be repeated until lcr_phase runs.
+ * lcr_phase rewrites those records (FOR_PHASING, variant type, genotype: the post-phase steps), so after it lcr_fragments returns
+ * LCR_E_STATE until a new candidate stage has run.  min_linkers = 0: LCR_E_ARG, nothing changed. */
 int lcr_fragments(lcr_ctx*, const lcr_params*);
 int lcr_get_fragmat(lcr_ctx*, lcr_fragmat* out);
 
 /* replaces init_haplotypes/init_assignment + SNPFrag::phase (phase.rs:1087-1296) and the
  * post-phase sequence thread.rs:162-201 (assign_reads_haplotype, assign_snp_haplotype_genotype,
- * eval_rna_edit_var_phase, eval_low_frac_var_phase, assign_phase_set). */
+ * eval_rna_edit_var_phase, eval_low_frac_var_phase, assign_phase_set).
+ * Once per candidate stage: it writes its results into the candidate records that K3 and the phase stage read, so a second lcr_phase
+ * (or lcr_fragments) returns LCR_E_STATE -- "run the candidate stage again" -- until lcr_candidates / lcr_import_candidates has run;
+ * the getters keep answering with this call's results.  ld_weight_threshold other than 1: LCR_E_ARG, nothing changed (a later
+ * lcr_phase with good params still runs). */
 int lcr_phase(lcr_ctx*, const lcr_params*);
 int lcr_get_phase_result(lcr_ctx*, lcr_phase_result* out);
 /* The per-row results once more as 12-byte records in device memory (HBM), current after lcr_phase: the second record type

@@ -466,7 +466,6 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
   // post-phase kernel; `side` runs the chain regions (S > max_enum_snps): LD blocks, LD-seeded start, block-flip pass
   // and perturbation rounds in ONE kernel per region class (k4_grid.hip: a workgroup per region, or all CUs on one
   // large region), then their post-phase kernel.  The host only sizes buffers and launches.
-  if (prm.ld_weight_threshold != 1) { if (err) *err = "ld_weight_threshold must be 1: SNPFrag::phase is only ever called with 1 (thread.rs:166)"; return LCR_E_ARG; }
   PhaseCall c(in, prm, user_stream, err, dbg.prof != 0);
   objective.assign(c.ng, 0.0);
   RCHK(open_queues(c));

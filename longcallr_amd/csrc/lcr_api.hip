@@ -44,6 +44,7 @@ struct lcr_ctx {
   bool have_planes = false;
   DevBuf planes;
   DevParams dp{};
+  int32_t pile_platform = -1; uint32_t pile_dist_to_end = 0;   // lcr_pileup's platform / dist_to_end: lcr_candidates must be called with the same
   float sor_thr = -1.f;
   HostBuf h_planes;
   HostBuf h_nnz;              // pinned: first entry of every region of the fragment matrix, [ng] = entry count (lcr_fragments -> frag_settle)
@@ -58,6 +59,8 @@ struct lcr_ctx {
 
   // K2
   bool have_cand = false;
+  bool cand_used = false;   // lcr_phase has rewritten the records' FOR_PHASING bit, variant type and genotype (k4_post.h), which K3 and k4_stage read:
+                            // lcr_fragments / lcr_phase need a fresh candidate stage
   DevBuf flags, tile_count, tile_off, total, survivors, sv_region_off, hist, cand_tmp, keep;
   DevBuf hit_cnt, hit_list, ovf_list;   // k2_hist's (read, survivor) hits for K3; the overflow counter sits behind the histograms
   bool hits_valid = false; int32_t hits_n_sv = 0;
@@ -431,7 +434,7 @@ int lcr_load_batch(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg) {
   // here or in lcr_pileup touches what that stage reads.  A host batch is copied into the context's staging buffers, which hold
   // the previous batch's region table: the stage has to be done first.
   if (rd->mem == LCR_MEM_HOST) { int rc = phase_settle(c); if (rc) return rc; }
-  c->loaded = c->have_planes = c->have_cand = c->have_frag = c->have_phase = false;
+  c->loaded = c->have_planes = c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
   c->bound_slot = -1;
   c->bound_host = rd->mem == LCR_MEM_HOST;
   const int nr = rd->n_reads, ng = rg->n_regions, mem = rd->mem;
@@ -575,7 +578,7 @@ int lcr_load_batch_async(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg,
   if (!u.ev) HIPCHK(c, hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
   if (c->bound_slot == slot) {   // the bound batch lives in this slot: its kernels must be done before it is overwritten
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->loaded = c->have_planes = c->have_cand = c->have_frag = c->have_phase = false;
+    c->loaded = c->have_planes = c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
     c->bound_slot = -1;
   }
   u.filled = false;
@@ -741,8 +744,9 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   c->pileup_bytes = c->n_bases + 8 * (int64_t)n_ops + (4 * LCR_NPLANES + 1) * c->n_cols;
   c->stage_bytes = c->n_bases + 4 * c->n_cigar + 37 * (int64_t)b.n_reads + (4 * LCR_NPLANES + 1) * c->n_cols;
   c->have_planes = true;
-  c->have_cand = c->have_frag = c->have_phase = false;
+  c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
   c->flt_fused = fuse; c->flt_dp = c->dp;
+  c->pile_platform = p->platform; c->pile_dist_to_end = p->dist_to_end;
   return LCR_OK;
 }
 
@@ -765,6 +769,11 @@ int lcr_candidates(lcr_ctx* c, const lcr_params* p) {
   HT("cand");
   if (!c || !p) return LCR_E_ARG;
   if (!c->have_planes) { c->err = "lcr_candidates before lcr_pileup"; return LCR_E_STATE; }
+  // (k2_hist trims the read ends by dist_to_end on records K0 cut with the pileup's value, and the ONT / HiFi planes differ)
+  if (p->platform != c->pile_platform || p->dist_to_end != c->pile_dist_to_end) {
+    c->err = "lcr_candidates: platform and dist_to_end must be those of lcr_pileup";
+    return LCR_E_ARG;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = phase_settle(c); if (rc) return rc; }   // (the previous batch's phase stage reads the candidate / fragment buffers rewritten from here on)
   HT("cand:settled");
@@ -781,9 +790,11 @@ int lcr_candidates(lcr_ctx* c, const lcr_params* p) {
   const bool have_flt = c->flt_fused && c->dbg_fuse_filter != 0 && fa.ont == fb.ont && fa.min_depth == fb.min_depth && fa.max_depth == fb.max_depth && fa.low_cnt_cut == fb.low_cnt_cut &&
                         fa.use_strand_bias == fb.use_strand_bias && fa.min_af_intron == fb.min_af_intron && fa.low_frac_cut == fb.low_frac_cut && fa.sor_threshold == fb.sor_threshold;
   { Timer t(c, LCR_K_CAND_FILTER);
-    if (!have_flt)
-    launch_k2_filter(c->bv, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols,
-                     c->planes.as<uint32_t>(), c->k0_tile_fill.as<int32_t>(), c->flags.as<uint8_t>(), c->tile_count.as<int32_t>(), c->stream);
+    if (!have_flt) {
+      c->flt_fused = false;   // (the pass below overwrites the flags and tile counts of lcr_pileup's epilogue)
+      launch_k2_filter(c->bv, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols,
+                       c->planes.as<uint32_t>(), c->k0_tile_fill.as<int32_t>(), c->flags.as<uint8_t>(), c->tile_count.as<int32_t>(), c->stream);
+    }
   }
   // survivors per region = tile offsets at the regions' first tiles (gathered on the device, pinned D2H)
   HIPCHK(c, c->sv_region_off.reserve((ng + 1) * 4));
@@ -886,7 +897,7 @@ int lcr_candidates(lcr_ctx* c, const lcr_params* p) {
   c->cand_pending = true;
   c->have_cand = true;
   HT("cand:ret");
-  c->have_frag = c->have_phase = false;
+  c->have_frag = c->have_phase = c->cand_used = false;
   return LCR_OK;
 }
 
@@ -961,7 +972,7 @@ int lcr_import_candidates(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t 
   HIPCHK(c, hipGetLastError());
   c->cand_pending = true;
   c->have_cand = true;
-  c->have_frag = c->have_phase = false;
+  c->have_frag = c->have_phase = c->cand_used = false;
   HT("import:ret");
   return LCR_OK;
 }
@@ -1003,6 +1014,7 @@ int lcr_fragments(lcr_ctx* c, const lcr_params* p) {
   HT("frag");
   if (!c || !p) return LCR_E_ARG;
   if (!c->have_cand) { c->err = "lcr_fragments before lcr_candidates"; return LCR_E_STATE; }
+  if (c->cand_used) { c->err = "lcr_fragments after lcr_phase: the phase stage has rewritten the candidate records; run the candidate stage again"; return LCR_E_STATE; }
   if (p->min_linkers == 0) { c->err = "min_linkers must be > 0 (fragment.rs:252)"; return LCR_E_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   const int ng = c->bv.n_regions;
@@ -1122,6 +1134,8 @@ int lcr_get_fragmat(lcr_ctx* c, lcr_fragmat* out) {
 int lcr_phase(lcr_ctx* c, const lcr_params* p) {
   if (!c || !p) return LCR_E_ARG;
   if (!c->have_frag) { c->err = "lcr_phase before lcr_fragments"; return LCR_E_STATE; }
+  if (c->cand_used) { c->err = "lcr_phase after lcr_phase: the phase stage has rewritten the candidate records; run the candidate stage again"; return LCR_E_STATE; }
+  if (p->ld_weight_threshold != 1) { c->err = "ld_weight_threshold must be 1: SNPFrag::phase is only ever called with 1 (thread.rs:166)"; return LCR_E_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = frag_settle(c); if (rc) return rc; }
   PhaseInputs in;
@@ -1135,6 +1149,7 @@ int lcr_phase(lcr_ctx* c, const lcr_params* p) {
   in.d_cand = c->d_cand.as<lcr_candidate>(); in.d_cand_off = c->d_cand_off.as<int32_t>();
   in.d_row_region_off = c->row_region_off.as<int32_t>(); in.d_start0 = c->bv.start0;
   Timer t(c, LCR_K_PHASE);
+  c->cand_used = true;   // (from here on the post-phase kernels may rewrite the records: an error part of the way through included)
   int rc = c->phase.run(in, *p, c->stream, &c->err);
   if (rc) {   // (an error part of the way through an asynchronous stage leaves kernels queued that read the candidate / fragment buffers)
     if (c->phase.q_first) (void)hipStreamSynchronize(c->phase.q_first);
