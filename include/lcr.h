@@ -109,7 +109,12 @@ int lcr_params_preset(int preset, lcr_params* out);
 
 /* Pileup columns (replaces Vec<BaseFreq>, util.rs:100-127) as u32 planes of n_cols each.
  * plane[k] = planes + k*n_cols.  Reverse-strand counts are cnt - fwd.  The never-read fields of
- * BaseFreq (forward_cnt, backward_cnt, distance_to_end, i) are not produced. */
+ * BaseFreq (forward_cnt, backward_cnt, distance_to_end, i) are not produced.
+ * Materialised on request: lcr_pileup stores the planes of the tiles that hold records; the columns no
+ * record touches (uncovered, or inside introns only: 0 everywhere, n = introns across them) are stored by
+ * lcr_get_columns itself, once per pileup, before it copies.  The getter returns every column, whenever it is
+ * called between lcr_pileup and the next lcr_load_batch / lcr_bind_batch / lcr_pileup; like the stage calls it
+ * reads the region arrays of a LCR_MEM_DEVICE batch.  No other call needs those columns. */
 enum {
   LCR_PL_A = 0, LCR_PL_C, LCR_PL_G, LCR_PL_T, /* a,c,g,t                                            */
   LCR_PL_N,                                    /* n  (intron)                                        */

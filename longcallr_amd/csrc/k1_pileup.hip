@@ -45,7 +45,7 @@
 #define K1_RPB 2                        // records per thread and batch
 #define K1_PMAP (8 * K1_THREADS)         // pieces per batch with a direct piece -> record map in LDS
 #ifndef K1_NT_STORES
-#define K1_NT_STORES 0                  // k1_empty_tiles: non-temporal plane stores (measurement builds: -DK1_NT_STORES=1; measured slower, HISTORY.md Appendix C)
+#define K1_NT_STORES 0                  // k1_empty_tiles: non-temporal plane stores (measurement builds: -DK1_NT_STORES=1; measured slower while the kernel ran in every step, HISTORY.md Appendix C)
 #endif
 #ifndef K1_PIF
 #define K1_PIF 4                        // 16-byte pieces in flight per thread (a batch of 1024 records has ~2500 pieces)
@@ -274,8 +274,10 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
   // tiles -- pure streams of plane stores, 75 % of the stage's HBM writes -- between the full ones so that the stores run
   // under the tally was measured: 0.74 instead of 0.43 ms, XCD-aware or not; the full tiles' dependent loads then queue
   // behind a saturated write stream)
-  // Record-free tiles -- uncovered, or inside introns only: most tiles of a spliced data set -- are written by
-  // k1_empty_tiles; `order` lists them behind the tiles with records, whose number the tile pass left in *n_full.
+  // Record-free tiles -- uncovered, or inside introns only: most tiles of a spliced data set -- are not written here, and not by
+  // lcr_pileup at all: their planes are constants (k1_empty_tiles, queued when somebody asks for the planes: lcr_get_columns) and
+  // k1_tiles_b has left their 0 in flt_count.  `order` lists them behind the tiles with records, whose number the tile pass left
+  // in *n_full.
   if ((int)blockIdx.x >= *n_full) return;
   const int tile = order[blockIdx.x];
   __shared__ uint32_t pl[P_NPL * TSTRIDE];
@@ -549,21 +551,21 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
 }
 
 // Record-free tiles (uncovered, or inside introns only): every plane is 0 except the intron plane, which is the number of
-// introns that cover the whole tile.  Three quarters of the tiles of a spliced data set and 75 % of the stage's HBM writes
-// are like this: a pure store stream, written by small workgroups without LDS (inside k1_pileup's 512-thread, 52 KB
-// workgroups -- three per CU -- the same stores ran at 3.7 TB/s; hipMemset reaches 6.8 on this part).
+// introns that cover the whole tile.  Three quarters of the tiles of a spliced data set and 75 % of the plane bytes
+// are like this: a pure store stream that no stage reads (lcr_api.hip, `planes_dense`), so lcr_pileup does not queue it; it runs
+// when the planes themselves are asked for (lcr_get_columns), once per pileup, over the tile order that pileup left.  Small workgroups
+// without LDS (inside k1_pileup's 512-thread, 52 KB workgroups -- three per CU -- the same stores ran at 3.7 TB/s; hipMemset reaches
+// 6.8 on this part).
 // One workgroup of 128 threads per tile (the bt-th behind the tiles with records in `order`): 16-byte stores, 4 consecutive
 // columns per thread and plane.
 __global__ void __launch_bounds__(128) k1_empty_tiles(BatchView b, const int32_t* __restrict__ tile_region, const int32_t* __restrict__ tile_col0,
                                                        int64_t n_cols, const int32_t* __restrict__ tile_nbase, uint32_t* __restrict__ planes,
-                                                       const int32_t* __restrict__ order, const int32_t* __restrict__ n_full, int n_tiles,
-                                                       int32_t* __restrict__ flt_count) {
+                                                       const int32_t* __restrict__ order, const int32_t* __restrict__ n_full, int n_tiles) {
   const int nf = *n_full;
   if (*b.error_flag != 0) return;
   const int bt = blockIdx.x, lt = threadIdx.x;
   if (bt + nf >= n_tiles) return;
   const int tile = order[nf + bt];
-  if (flt_count && lt == 0) flt_count[tile] = 0;   // (a record-free tile has no survivor of the count filters: k2_filter's verdict for it)
   const int g = tile_region[tile], tc0 = tile_col0[tile];
   const int tlen = min(LCR_TILE, b.len[g] - tc0);
   const int64_t gcol0 = b.col_off[g] + tc0;
@@ -573,8 +575,8 @@ __global__ void __launch_bounds__(128) k1_empty_tiles(BatchView b, const int32_t
     if (col + 4 <= tlen) {
 #pragma unroll
       for (int k = 0; k < LCR_NPLANES; k++) {
-        // (K1_NT_STORES: non-temporal stores -- 350 MB of zeros that nobody reads before the next batch would then not push the read bases k2_hist
-        // asks for next out of the Infinity Cache; measured: k2_hist 0.24 -> 0.20-0.23 ms, but this kernel 53 -> ~110 us: slower in sum)
+        // (K1_NT_STORES: non-temporal stores; measured while this kernel ran in every step: k2_hist 0.24 -> 0.20-0.23 ms, but this kernel
+        // 53 -> ~110 us: slower in sum)
         typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
         const u4_t v = k == LCR_PL_N ? (u4_t){nb, nb, nb, nb} : (u4_t){0u, 0u, 0u, 0u};
         if (K1_NT_STORES) __builtin_nontemporal_store(v, reinterpret_cast<u4_t*>(planes + (int64_t)k * n_cols + o));
@@ -597,20 +599,29 @@ __global__ void __launch_bounds__(128) k1_empty_tiles(BatchView b, const int32_t
 // last, both inside its region, so every region's entries sum to zero and no segment handling is needed), ent_off = the
 // tiles' offsets in the entry list (exclusive scan of their entry counts), and K0's accounting totals.
 // Two multi-block kernels (a single workgroup spent 60 us on load latency): pass A = class histogram + block sums,
-// pass B = offsets + scatter.  Class 32 = record-free tiles (three quarters of them), ranked by ballots.
+// pass B = offsets + scatter.  Class 32 = record-free tiles (three quarters of them), ranked by ballots.  Nothing behind
+// the tile passes writes a record-free tile's planes: pass A counts their columns for the stage's byte accounting (word 5
+// of the control block, with the words the host waits for anyway), pass B stores the 0 of their survivor count when the
+// tally's epilogue takes the filter pass (flt_count).
 #define TS_TILES 1024   // tiles per workgroup (256 threads x 4)
 struct TileScanTmp {    // scratch in HBM, cleared with K0's counters
   int cls_cnt[40];      // tiles per class
   int cls_cur[40];      // scatter cursors
-  int n_full, pad_[7];  // tiles with records (pass B, for K1's two kernels)
+  int n_full;           // tiles with records (pass B, for K1's two kernels)
+  int empty_cols;       // columns of the record-free tiles (pass A; its last block hands the sum to the host's control block).  32 bits hold it:
+                        // lcr_load_batch refuses a batch whose columns + regions reach 2^31 (tile origins and the intron array are int32 as well)
+  int done_a;           // blocks of pass A that have added theirs
+  int pad_[5];
 };
 __device__ __forceinline__ int tile_class(int fill) { return fill > 0 ? __clz(fill) : 32; }   // more records, lower class
 
 __global__ void __launch_bounds__(256) k1_tiles_a(const int32_t* __restrict__ tile_fill, const int32_t* __restrict__ tile_ndiff,
                                                    const int32_t* __restrict__ tile_nent, int32_t n_tiles, TileScanTmp* __restrict__ tmp,
                                                    int2* __restrict__ blk_sum, const unsigned int* __restrict__ acct, int32_t n_acct,
-                                                   unsigned int* __restrict__ ctl, unsigned int* __restrict__ host_ctl) {
-  __shared__ int hist[33], ws[4][2];
+                                                   unsigned int* __restrict__ ctl, unsigned int* __restrict__ host_ctl,
+                                                   const int32_t* __restrict__ tile_region, const int32_t* __restrict__ tile_col0,
+                                                   const int32_t* __restrict__ region_len) {
+  __shared__ int hist[33], ws[4][2], ecol_s;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (blockIdx.x == 0 && w == 0) {   // K0's accounting slots -> control block, fetched by the host behind this kernel
     int it = 0, rc = 0, pt = 0, dt = 0;   // items, records; fullest pool / descriptor shard
@@ -624,29 +635,40 @@ __global__ void __launch_bounds__(256) k1_tiles_a(const int32_t* __restrict__ ti
     }
   }
   if (tid < 33) hist[tid] = 0;
+  if (tid == 0) ecol_s = 0;
   __syncthreads();
   const int t0 = blockIdx.x * TS_TILES + tid * 4;
-  int sd = 0, sc = 0, n_empty = 0;
+  int sd = 0, sc = 0, n_empty = 0, e_cols = 0;
 #pragma unroll
   for (int x = 0; x < 4; x++) {
     const int t = t0 + x;
     if (t < n_tiles) {
       sd += tile_ndiff[t]; sc += tile_nent[t];
       const int c = tile_class(tile_fill[t]);
-      if (c == 32) n_empty++; else atomicAdd(&hist[c], 1);
+      if (c == 32) { n_empty++; e_cols += min(LCR_TILE, region_len[tile_region[t]] - tile_col0[t]); }
+      else atomicAdd(&hist[c], 1);
     }
   }
-  sd = wave_incl_scan(sd); sc = wave_incl_scan(sc); n_empty = wave_incl_scan(n_empty);
-  if (lane == 63) { ws[w][0] = sd; ws[w][1] = sc; atomicAdd(&hist[32], n_empty); }
+  sd = wave_incl_scan(sd); sc = wave_incl_scan(sc); n_empty = wave_incl_scan(n_empty); e_cols = wave_incl_scan(e_cols);
+  if (lane == 63) { ws[w][0] = sd; ws[w][1] = sc; atomicAdd(&hist[32], n_empty); if (e_cols) atomicAdd(&ecol_s, e_cols); }
   __syncthreads();
   if (tid == 0) blk_sum[blockIdx.x] = make_int2(ws[0][0] + ws[1][0] + ws[2][0] + ws[3][0], ws[0][1] + ws[1][1] + ws[2][1] + ws[3][1]);
   if (tid < 33 && hist[tid]) atomicAdd(&tmp->cls_cnt[tid], hist[tid]);
+  if (tid == 0) {   // columns of the record-free tiles: the block that adds its share last passes the total on
+    if (ecol_s) atomicAdd(&tmp->empty_cols, ecol_s);
+    __threadfence();
+    if (atomicAdd(&tmp->done_a, 1) == (int)gridDim.x - 1) {
+      const unsigned int total = (unsigned int)atomicAdd(&tmp->empty_cols, 0);
+      ctl[5] = total;
+      if (host_ctl) host_ctl[5] = total;
+    }
+  }
 }
 
 __global__ void __launch_bounds__(256) k1_tiles_b(const int32_t* __restrict__ tile_fill, const int32_t* __restrict__ tile_ndiff,
                                                    const int32_t* __restrict__ tile_nent, int32_t n_tiles, TileScanTmp* __restrict__ tmp,
                                                    const int2* __restrict__ blk_sum, int32_t* __restrict__ tile_nbase, int32_t* __restrict__ ent_off,
-                                                   int32_t* __restrict__ order) {
+                                                   int32_t* __restrict__ order, int32_t* __restrict__ flt_count) {
   __shared__ int hist[33], base[33], ws[4][2], pre[2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid < 33) hist[tid] = 0;
@@ -699,14 +721,16 @@ __global__ void __launch_bounds__(256) k1_tiles_b(const int32_t* __restrict__ ti
     if (t < n_tiles) {
       run_d += vd[x]; tile_nbase[t] = run_d;
       ent_off[t] = run_c; run_c += vc[x];
-      if (cls[x] == 32) order[base[32] + e_before++] = t;
-      else order[base[cls[x]] + atomicAdd(&hist[cls[x]], 1)] = t;
+      if (cls[x] == 32) {
+        order[base[32] + e_before++] = t;
+        if (flt_count) flt_count[t] = 0;   // (a record-free tile has no survivor of the count filters: k2_filter's verdict for it; the other tiles' counts: k1_pileup)
+      } else order[base[cls[x]] + atomicAdd(&hist[cls[x]], 1)] = t;
       if (t == n_tiles - 1) { ent_off[n_tiles] = run_c; tmp->n_full = n_tiles - tmp->cls_cnt[32]; }
     }
   }
 }
 
-// the tally, then the record-free tiles' stores behind it on the same queue
+// the tally (tiles with records only)
 void launch_k1_pileup(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,
                       int32_t n_tiles, int64_t n_cols, const int32_t* tile_fill, const int32_t* ent_off, const void* ents,
                       const unsigned long long* recs, const int32_t* tile_nbase, uint32_t* planes, const int32_t* order /* launch_k1_tiles_b */,
@@ -715,21 +739,28 @@ void launch_k1_pileup(const BatchView& b, const DevParams& p, const int32_t* til
   if (n_tiles == 0) return;
   hipLaunchKernelGGL(k1_pileup, dim3(n_tiles), dim3(K1_THREADS), 0, s, b, p, tile_region, tile_col0, n_cols, tile_fill, ent_off,
                      (const uint2*)ents, recs, tile_nbase, planes, order, tiles_tmp + 80 /* TileScanTmp::n_full */, bt, flt_flags, flt_count);
-  hipLaunchKernelGGL(k1_empty_tiles, dim3(n_tiles), dim3(128), 0, s, b, tile_region, tile_col0, n_cols, tile_nbase, planes, order, tiles_tmp + 80, n_tiles, flt_count);
+}
+// the record-free tiles' planes, over the tables the last launch_k1_tiles_b / launch_k1_pileup left (lcr_get_columns)
+void launch_k1_empty_tiles(const BatchView& b, const int32_t* tile_region, const int32_t* tile_col0, int32_t n_tiles, int64_t n_cols,
+                           const int32_t* tile_nbase, uint32_t* planes, const int32_t* order, const int32_t* tiles_tmp, hipStream_t s) {
+  if (n_tiles == 0) return;
+  hipLaunchKernelGGL(k1_empty_tiles, dim3(n_tiles), dim3(128), 0, s, b, tile_region, tile_col0, n_cols, tile_nbase, planes, order, tiles_tmp + 80, n_tiles);
 }
 // the tile-order / intron-base / accounting pass alone (the host fetches K0's control block behind it, before K1 is queued)
 // the tile passes alone (the host fetches K0's control block behind pass A, before the rest is queued)
 size_t launch_k1_tiles_tmp_words(int32_t n_tiles) { return 88 + 2 * (size_t)((n_tiles + TS_TILES - 1) / TS_TILES) + 8; }
 void launch_k1_tiles_a(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp /* zeroed */,
-                       const unsigned int* acct, int32_t n_acct, unsigned int* ctl, unsigned int* host_ctl, hipStream_t s) {
+                       const unsigned int* acct, int32_t n_acct, unsigned int* ctl, unsigned int* host_ctl, const int32_t* tile_region,
+                       const int32_t* tile_col0, const int32_t* region_len, hipStream_t s) {
   const int nb = (n_tiles + TS_TILES - 1) / TS_TILES;
-  hipLaunchKernelGGL(k1_tiles_a, dim3(nb), dim3(256), 0, s, tile_fill, tile_ndiff, tile_nent, n_tiles, (TileScanTmp*)tmp, (int2*)(tmp + 88), acct, n_acct, ctl, host_ctl);
+  hipLaunchKernelGGL(k1_tiles_a, dim3(nb), dim3(256), 0, s, tile_fill, tile_ndiff, tile_nent, n_tiles, (TileScanTmp*)tmp, (int2*)(tmp + 88), acct, n_acct, ctl, host_ctl,
+                     tile_region, tile_col0, region_len);
 }
 void launch_k1_tiles_b(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp,
-                       int32_t* tile_nbase, int32_t* ent_off, int32_t* order, hipStream_t s) {
+                       int32_t* tile_nbase, int32_t* ent_off, int32_t* order, int32_t* flt_count, hipStream_t s) {
   const int nb = (n_tiles + TS_TILES - 1) / TS_TILES;
   hipLaunchKernelGGL(k1_tiles_b, dim3(nb), dim3(256), 0, s, tile_fill, tile_ndiff, tile_nent, n_tiles, (TileScanTmp*)tmp, (const int2*)(tmp + 88),
-                     tile_nbase, ent_off, order);
+                     tile_nbase, ent_off, order, flt_count);
 }
 
 // ---------------------------------------------------------------------------------------------

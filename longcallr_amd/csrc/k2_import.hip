@@ -38,7 +38,8 @@ k2_import_count(const int64_t* __restrict__ start0, const int32_t* __restrict__ 
 // candidate.rs:545-600 for every kept site of region g, written at cand_off[g] + rank into the device records and the pinned host mirror
 __global__ void __launch_bounds__(LCR_BLOCK)
 k2_import_emit(const int64_t* __restrict__ start0, const int32_t* __restrict__ len, const int64_t* __restrict__ col_off,
-               const uint8_t* __restrict__ ref, int32_t n_regions, int64_t n_cols, const uint32_t* __restrict__ planes,
+               const uint8_t* __restrict__ ref, const int32_t* __restrict__ region_first_tile, const int32_t* __restrict__ tile_fill,
+               int32_t n_regions, int64_t n_cols, const uint32_t* __restrict__ planes,
                const int64_t* __restrict__ pos0, const uint8_t* __restrict__ gt, const float* __restrict__ qual, int32_t n_sites,
                const int32_t* __restrict__ cand_off, lcr_candidate* __restrict__ out, lcr_candidate* __restrict__ h_cand, int32_t* __restrict__ h_off) {
   const int g = (int)((blockIdx.x * (unsigned)LCR_BLOCK + threadIdx.x) / LCR_WAVE), lane = threadIdx.x & (LCR_WAVE - 1);
@@ -55,10 +56,12 @@ k2_import_emit(const int64_t* __restrict__ start0, const int32_t* __restrict__ l
     const bool keep = i < hi && site_kept(code, q);
     const unsigned long long m = __ballot(keep);
     if (keep) {
-      const int64_t gc = col_off[g] + (pos0[i] - s0);
+      const int64_t col = pos0[i] - s0, gc = col_off[g] + col;
+      // a tile without records has no counts, and lcr_pileup has not written its planes (what lies there is an earlier batch's)
+      const bool covered = tile_fill[region_first_tile[g] + (int32_t)(col / LCR_TILE)] != 0;
       uint32_t cnt[4];
 #pragma unroll
-      for (int k = 0; k < 4; k++) cnt[k] = planes[(size_t)k * n_cols + gc];
+      for (int k = 0; k < 4; k++) cnt[k] = covered ? planes[(size_t)k * n_cols + gc] : 0u;
       lcr_candidate r{};
       r.pos = pos0[i];
       r.region = g;
@@ -103,10 +106,10 @@ void launch_k2_import_count(const BatchView& b, const int64_t* pos0, const uint8
   if (ng > 0) hipLaunchKernelGGL(k2_import_count, dim3((ng + wpb - 1) / wpb), dim3(LCR_BLOCK), 0, s, b.start0, b.len, ng, pos0, gt, qual, n_sites, count);
 }
 
-void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int64_t* pos0, const uint8_t* gt, const float* qual,
+void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int32_t* tile_fill, const int64_t* pos0, const uint8_t* gt, const float* qual,
                            int32_t n_sites, const int32_t* cand_off, lcr_candidate* out, hipStream_t s, lcr_candidate* h_cand, int32_t* h_off) {
   const int ng = b.n_regions, wpb = LCR_BLOCK / LCR_WAVE;
-  if (ng > 0) hipLaunchKernelGGL(k2_import_emit, dim3((ng + wpb - 1) / wpb), dim3(LCR_BLOCK), 0, s, b.start0, b.len, b.col_off, b.ref, ng, n_cols, planes,
+  if (ng > 0) hipLaunchKernelGGL(k2_import_emit, dim3((ng + wpb - 1) / wpb), dim3(LCR_BLOCK), 0, s, b.start0, b.len, b.col_off, b.ref, b.region_first_tile, tile_fill, ng, n_cols, planes,
                                  pos0, gt, qual, n_sites, cand_off, out, h_cand, h_off);
 }
 

@@ -42,6 +42,26 @@ struct lcr_ctx {
 
   // K1
   bool have_planes = false;
+  // lcr_pileup writes the planes of the tiles that hold records (K0's fill counter > 0) and nothing else: a record-free tile's planes are
+  // constants -- 0, the intron plane tile_nbase[tile] -- and what lies at its columns after lcr_pileup is whatever an earlier batch left
+  // there.  planes_dense: the constants have been stored for the current pileup (planes_materialise: k1_empty_tiles over the tile order,
+  // tile_nbase and n_full of that pileup -- tile_order / tile_nbase / k0_tile_fill are rewritten by lcr_pileup only, tile_region / tile_col0
+  // by lcr_load_batch only, and both clear the flag).  Who reads c->planes, and why a tile that was never written is safe with each:
+  //   k1_pileup's fused filter epilogue   runs in the workgroups of tiles with records, on their LDS counters;
+  //   k1_zonefix / _ends / _slots         atomicSub at the column of an aligned base inside the region: that base's M record is in the tile;
+  //   k2_filter (eval_column)             leaves at tile_fill == 0 with tile_count = 0;
+  //   k2_compact (eval_column, ts planes) leaves at tile_count == 0 -- k2_filter's 0, or k1_tiles_b's on the fused path;
+  //   k2_hist / k2_hist_tiles / k2_gt, K3, K4   never touch the planes (k2_hist_tiles walks K0's records of tiles with tile_count > 0);
+  //   k2_import_emit                      takes the four counts of a site in a tile with tile_fill == 0 as 0 without loading them;
+  //   lcr_get_columns                     the one reader of every column: calls planes_materialise first.
+  // planes_materialise itself (k1_empty_tiles) reads, beside those tables, bv.error_flag (a word of k0_tile_fill, 0 after a pileup that returned
+  // LCR_OK) and the region arrays bv.len / bv.col_off: the context's copies of a host batch, the caller's arrays of a LCR_MEM_DEVICE batch, which
+  // therefore have to stay alive for lcr_get_columns as for every stage call (include/lcr.h).
+  // lcr_debug_set("poison_planes", 1) fills the whole buffer with 0xA5 in front of every pileup: a reader that looks at an unwritten tile
+  // then differs from a run without it, whatever the previous batch was (tests/test_sparse_planes.py).
+  bool planes_dense = false;
+  int dbg_poison_planes = 0;
+  size_t tiles_tmp_off = 0;   // words from k0_tile_fill to the tile passes' scratch (TileScanTmp: n_full) of the last lcr_pileup
   DevBuf planes;
   DevParams dp{};
   int32_t pile_platform = -1; uint32_t pile_dist_to_end = 0;   // lcr_pileup's platform / dist_to_end: lcr_candidates must be called with the same
@@ -434,7 +454,7 @@ int lcr_load_batch(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg) {
   // here or in lcr_pileup touches what that stage reads.  A host batch is copied into the context's staging buffers, which hold
   // the previous batch's region table: the stage has to be done first.
   if (rd->mem == LCR_MEM_HOST) { int rc = phase_settle(c); if (rc) return rc; }
-  c->loaded = c->have_planes = c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
+  c->loaded = c->have_planes = c->planes_dense = c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
   c->bound_slot = -1;
   c->bound_host = rd->mem == LCR_MEM_HOST;
   const int nr = rd->n_reads, ng = rg->n_regions, mem = rd->mem;
@@ -578,7 +598,7 @@ int lcr_load_batch_async(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg,
   if (!u.ev) HIPCHK(c, hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
   if (c->bound_slot == slot) {   // the bound batch lives in this slot: its kernels must be done before it is overwritten
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->loaded = c->have_planes = c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
+    c->loaded = c->have_planes = c->planes_dense = c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
     c->bound_slot = -1;
   }
   u.filled = false;
@@ -648,6 +668,8 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   c->dp = to_dev(p, c->sor_thr);
   c->dp.dbg = 0;
   HIPCHK(c, c->planes.reserve(std::max<size_t>((size_t)c->n_cols * LCR_NPLANES, 1) * 4));
+  c->have_planes = c->planes_dense = false;   // (from here on the buffer and the tile tables are rewritten)
+  if (c->dbg_poison_planes) HIPCHK(c, lcr_fill_async(c->planes.p, 0xA5, (size_t)c->n_cols * LCR_NPLANES * 4, c->stream));
   bool gated = false;   // (async_phase: K0 waits for the restarts of a phase stage still in flight -- below, behind the fill in front of it)
   BatchView& b = c->bv;
   const int nt = c->n_tiles;
@@ -674,6 +696,8 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   HIPCHK(c, c->read_scan.reserve(std::max<size_t>(b.n_reads, 1) * 8));
   HIPCHK(c, c->h_stage[0].reserve(64));
   int32_t n_recs = 0, bad = 0, n_ops = 0;
+  int64_t empty_cols = 0;   // columns of the record-free tiles
+  c->tiles_tmp_off = o_tmp;
   // pass 1 of the candidate filters inside the tally's epilogue (k2_eval.h): presets whose planes are final when K1 stores them (ONT: the
   // HiFi presets subtract the poly-A mask afterwards, k1_zonefix); lcr_candidates uses the flags if it is called with the same filters
   const bool fuse = c->dbg_fuse_filter != 0 && c->dp.ont && nt > 0;
@@ -709,16 +733,16 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
         unsigned int* d_ctl = nullptr;
         HIPCHK(c, hipHostGetDevicePointer((void**)&d_ctl, ctl, 0));
         launch_k1_tiles_a(nt, fill, fill + o_ndiff, fill + o_nch, fill + o_tmp, (unsigned int*)(fill + o_acct), launch_k0_acct_slots(),
-                          (unsigned int*)(fill + nt + 1), d_ctl, c->stream);
+                          (unsigned int*)(fill + nt + 1), d_ctl, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), b.len, c->stream);
       } else HIPCHK(c, hipMemcpyAsync(ctl, fill + nt + 1, 32, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipEventRecord(c->ev_ctl, c->stream));
       if (nt > 0) launch_k1_tiles_b(nt, fill, fill + o_ndiff, fill + o_nch, fill + o_tmp, c->tile_nbase.as<int32_t>(), c->chunk_off.as<int32_t>(),
-                                    c->tile_order.as<int32_t>(), c->stream);
+                                    c->tile_order.as<int32_t>(), fuse ? c->tile_count.as<int32_t>() : nullptr, c->stream);
       if (nt > 0 && c->n_ops > 0)
         launch_k0_desc_bin(fill + nt + 1, (const unsigned int*)(fill + o_acct), desc_sub, c->desc_tile.as<uint32_t>(), c->desc_val.p, c->chunk_off.as<int32_t>(), fill + o_cur,
                            c->chunks.p, n_blocks / 8 + 1, c->stream);
-      // ---- K1: per-tile tally from the records (leaves at once if K0 flagged an error), the record-free tiles; K1z: poly-A /
-      // homopolymer mask of the HiFi presets
+      // ---- K1: per-tile tally from the records (leaves at once if K0 flagged an error) -- the record-free tiles' planes stay
+      // unwritten (planes_dense) --; K1z: poly-A / homopolymer mask of the HiFi presets
       launch_k1_pileup(b, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols, fill, c->chunk_off.as<int32_t>(),
                        c->chunks.p, c->k0_items.as<unsigned long long>(), c->tile_nbase.as<int32_t>(), c->planes.as<uint32_t>(),
                        c->tile_order.as<int32_t>(), fill + o_tmp, c->stream, fuse ? c->flags.as<uint8_t>() : nullptr, fuse ? c->tile_count.as<int32_t>() : nullptr);
@@ -728,6 +752,7 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
     HIPCHK(c, hipEventSynchronize(c->ev_ctl));
   HT("pile:ctl");
     n_ops = ctl[1]; n_recs = ctl[2]; bad = ctl[3];
+    empty_cols = nt > 0 ? (int64_t)(uint32_t)ctl[5] : 0;   // (k1_tiles_a: with the words this wait is for anyway)
     if (*c->h_order.as<int32_t>() != 0) { c->err = "the reads of a region must be sorted by position (lcr_reads.pos)"; return LCR_E_ARG; }
     if (bad == 1) { c->err = "unknown CIGAR operation (reference panics: util.rs:944)"; return LCR_E_CIGAR; }
     if (bad == 2) { c->err = "CIGAR inconsistent with l_seq / soft clips"; return LCR_E_CIGAR; }
@@ -739,20 +764,33 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   }
   c->n_items = n_recs;
   // bytes K1 itself has to move: read bases once + 8-byte records + reference byte per column, 13 u32
-  // planes written per column
+  // planes written per column of a tile with records (the record-free tiles' planes are not written by this stage)
   // (8 bytes per M / D / I / N item: the extra records of items that cross a tile boundary are overhead, not algorithm)
-  c->pileup_bytes = c->n_bases + 8 * (int64_t)n_ops + (4 * LCR_NPLANES + 1) * c->n_cols;
-  c->stage_bytes = c->n_bases + 4 * c->n_cigar + 37 * (int64_t)b.n_reads + (4 * LCR_NPLANES + 1) * c->n_cols;
-  c->have_planes = true;
+  const int64_t plane_cols = c->n_cols - empty_cols;
+  c->pileup_bytes = c->n_bases + 8 * (int64_t)n_ops + c->n_cols + 4 * LCR_NPLANES * plane_cols;
+  c->stage_bytes = c->n_bases + 4 * c->n_cigar + 37 * (int64_t)b.n_reads + c->n_cols + 4 * LCR_NPLANES * plane_cols;
+  c->have_planes = true; c->planes_dense = false;
   c->have_cand = c->have_frag = c->have_phase = c->cand_used = false;
   c->flt_fused = fuse; c->flt_dp = c->dp;
   c->pile_platform = p->platform; c->pile_dist_to_end = p->dist_to_end;
   return LCR_OK;
 }
 
+// the record-free tiles' constant planes of the current pileup, stored once when somebody asks for every column (lcr_ctx::planes_dense)
+static int planes_materialise(lcr_ctx* c) {
+  if (c->planes_dense) return LCR_OK;
+  launch_k1_empty_tiles(c->bv, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), c->n_tiles, c->n_cols, c->tile_nbase.as<int32_t>(),
+                        c->planes.as<uint32_t>(), c->tile_order.as<int32_t>(), c->k0_tile_fill.as<int32_t>() + c->tiles_tmp_off, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->planes_dense = true;
+  return LCR_OK;
+}
+
 int lcr_get_columns(lcr_ctx* c, lcr_columns* out) {
   if (!c || !out) return LCR_E_ARG;
   if (!c->have_planes) { c->err = "lcr_get_columns before lcr_pileup"; return LCR_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = planes_materialise(c); if (rc) return rc; }
   const size_t bytes = (size_t)c->n_cols * LCR_NPLANES * 4;
   HIPCHK(c, c->h_planes.reserve(std::max<size_t>(bytes, 1)));
   if (bytes) HIPCHK(c, hipMemcpyAsync(c->h_planes.p, c->planes.p, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -957,7 +995,7 @@ int lcr_import_candidates(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t 
     Timer t(c, LCR_K_CAND_IMPORT);
     launch_k2_import_count(c->bv, d_pos, d_gt, d_q, n_sites, c->imp_cnt.as<int32_t>(), c->stream);
     launch_scan_i32(c->scan_tmp, c->imp_cnt.as<int32_t>(), c->d_cand_off.as<int32_t>(), ng, c->d_cand_off.as<int32_t>() + ng, c->stream);
-    launch_k2_import_emit(c->bv, c->n_cols, c->planes.as<uint32_t>(), d_pos, d_gt, d_q, n_sites, c->d_cand_off.as<int32_t>(),
+    launch_k2_import_emit(c->bv, c->n_cols, c->planes.as<uint32_t>(), c->k0_tile_fill.as<int32_t>(), d_pos, d_gt, d_q, n_sites, c->d_cand_off.as<int32_t>(),
                           c->d_cand.as<lcr_candidate>(), c->stream, hp, ho); }
   c->cand_dl_other = false;
   // rows of the fragment matrix per region, as lcr_candidates leaves them
@@ -1356,6 +1394,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "k3_hits") c->dbg_k3_hits = value != 0;
   else if (k == "fuse_filter") c->dbg_fuse_filter = value != 0;
   else if (k == "spec_compact") c->dbg_spec_compact = value != 0;
+  else if (k == "poison_planes") c->dbg_poison_planes = value != 0;
   else if (k == "grid_spec_batch") d.spec_batch = (int)value;
   else if (k == "grid_spec_lanes") d.spec_lanes = (int)std::max<int64_t>(1, std::min<int64_t>(value, 16));
   else { c->err = "lcr_debug_set: unknown key " + k; return LCR_E_ARG; }

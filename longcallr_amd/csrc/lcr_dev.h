@@ -193,14 +193,17 @@ void launch_k0_desc_bin(const void* ctl, const unsigned int* acct, unsigned int 
                         hipStream_t s);
 size_t launch_k1_tiles_tmp_words(int32_t n_tiles);
 void launch_k1_tiles_a(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp /* zeroed */,
-                       const unsigned int* acct, int32_t n_acct, unsigned int* ctl, unsigned int* host_ctl /* pinned host block as the device sees it, or nullptr */, hipStream_t s);
+                       const unsigned int* acct, int32_t n_acct, unsigned int* ctl, unsigned int* host_ctl /* pinned host block as the device sees it, or nullptr */,
+                       const int32_t* tile_region, const int32_t* tile_col0, const int32_t* region_len /* -> ctl[5] / host_ctl[5]: columns of the record-free tiles */, hipStream_t s);
 void launch_k1_tiles_b(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp,
-                       int32_t* tile_nbase, int32_t* ent_off, int32_t* order, hipStream_t s);
+                       int32_t* tile_nbase, int32_t* ent_off, int32_t* order, int32_t* flt_count /* != nullptr: 0 for every record-free tile */, hipStream_t s);
 void launch_k1_pileup(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,
                       int32_t n_tiles, int64_t n_cols, const int32_t* tile_fill, const int32_t* chunk_off, const void* chunks,
                       const unsigned long long* recs, const int32_t* tile_nbase, uint32_t* planes, const int32_t* order,
                       const int32_t* tiles_tmp /* scratch of launch_k1_tiles_a / _b */, hipStream_t s,
                       uint8_t* flt_flags /* n_cols: != nullptr = pass 1 of the candidate filters in the tally's epilogue (k2_filter's flags) */, int32_t* flt_count /* n_tiles: survivors per tile */);
+void launch_k1_empty_tiles(const BatchView& b, const int32_t* tile_region, const int32_t* tile_col0, int32_t n_tiles, int64_t n_cols,
+                           const int32_t* tile_nbase, uint32_t* planes, const int32_t* order, const int32_t* tiles_tmp, hipStream_t s);
 void launch_k1_zonefix(const BatchView& b, const ReadBin* rbin, int D, int L, int64_t n_cols, uint32_t* planes, hipStream_t s);
 void launch_k2_filter(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,
                       int32_t n_tiles, int64_t n_cols, const uint32_t* planes, const int32_t* tile_fill, uint8_t* flags,
@@ -227,7 +230,7 @@ void launch_k2_finish(DevBuf& scan_tmp, const lcr_candidate* tmp, const int32_t*
                       uint32_t min_dense_cnt, hipStream_t s, lcr_candidate* h_cand = nullptr, int32_t* h_off = nullptr);
 // k2_import.hip: the candidate stage of caller-provided sites (lcr_import_candidates, candidate.rs:530-613)
 void launch_k2_import_count(const BatchView& b, const int64_t* pos0, const uint8_t* gt, const float* qual, int32_t n_sites, int32_t* count /* n_regions */, hipStream_t s);
-void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int64_t* pos0, const uint8_t* gt, const float* qual,
+void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int32_t* tile_fill /* K0's record counters of the last lcr_pileup */, const int64_t* pos0, const uint8_t* gt, const float* qual,
                            int32_t n_sites, const int32_t* cand_off /* n_regions + 1 */, lcr_candidate* out, hipStream_t s,
                            lcr_candidate* h_cand /* pinned (device pointer): the records and ... */, int32_t* h_off /* ... their offsets, or nullptr */);
 void launch_k2_import_check(const int64_t* pos0, const uint8_t* gt, int32_t n_sites, int32_t* bad /* zeroed */, hipStream_t s);
