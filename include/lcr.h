@@ -311,6 +311,40 @@ typedef struct {
 } lcr_phase_collected;
 int lcr_collect_phase(lcr_ctx*, lcr_phase_collected* out);
 
+/* Down-sampling: phase deep regions on a read sample (longcallR --downsample / --downsample-depth: thread.rs:144-151, phase.rs:693-701).
+ * A region with at least `depth` fragment rows (all rows of lcr_get_fragmat, empty ones included) is down-sampled: the optimiser
+ * (cross_optimize and its checks, cal_overall_probability, cross_optimize_by_block), the first two post-phase rounds
+ * (assign_reads_haplotype / assign_snp_haplotype_genotype, thread.rs:168-172) and the evidence of the two rescue evaluations see `depth`
+ * sampled rows only; LD blocks and LD seeding, every random draw (init_assignment, the perturbation rounds, the rescue commit), the
+ * THIRD post-phase round -- which assigns every read against the final haplotypes -- and assign_phase_set see all rows, as in the
+ * reference.  The sample replaces StdRng + shuffle (which cannot be restated here) by the rule of the project's other draws: the
+ * `depth` rows with the smallest keys  mix64(region_seed(seed, start0) + (r + 1) * 0x9E3779B97F4A7C15), r = the row's index inside
+ * its region -- a uniform depth-subset, a pure function of (seed, region start, row).  The reference calls with seed 2025.
+ *   lcr_set_downsample       sticky on the context; depth = 0 (the default) turns it off: lcr_phase is then exactly what it was.
+ *   lcr_set_downsample_rows  the caller's own sample (e.g. the reference's StdRng shuffle over row_region_off) for the NEXT lcr_phase
+ *       only, overriding lcr_set_downsample for it: one byte per fragment row of lcr_get_fragmat, non-zero = sampled (mem =
+ *       LCR_MEM_HOST or LCR_MEM_DEVICE; copied before the call returns).  A region is down-sampled iff one of its rows is unsampled.
+ *       Call it between lcr_fragments and lcr_phase (LCR_E_STATE otherwise; a new lcr_fragments drops it); n_rows other than the
+ *       fragment stage's: LCR_E_ARG.
+ *   lcr_get_downsample       what the last lcr_phase did: per region whether it was down-sampled (the reference prints this,
+ *       thread.rs:153-157), per fragment row the sampled byte (0 / 1) in pinned host memory and in HBM -- both NULL when no region was
+ *       down-sampled (every row counts as sampled); n_regions / n_rows are those of that lcr_phase.  Like lcr_collect_phase it outlives
+ *       lcr_load_batch / lcr_bind_batch / lcr_pileup of the next batch and waits for an asynchronous phase stage: call it before the
+ *       next candidate stage (LCR_E_STATE after it, and before the first lcr_phase).
+ * While down-sampling is on (depth > 0, or a sample was given), lcr_phase answers LCR_E_ARG, nothing changed, to
+ * read_assign_cutoff <= 0 (an unsampled row's haplotag carries no sign: the last round gives the same assignment for either sign only
+ * because |q - qn| = 0 is below every positive cutoff) and to the "post_host" debug cross-check (the host epilogue does not know the
+ * sample).  The asynchronous phase stage and lcr_collect_phase work as without it. */
+typedef struct {
+  int32_t n_regions, n_rows;
+  const uint8_t* region_applied; /* n_regions: 1 = the region was down-sampled                        */
+  const uint8_t* sampled;        /* n_rows (pinned host memory), or NULL                              */
+  const uint8_t* dev_sampled;    /* the same bytes in HBM, or NULL                                    */
+} lcr_downsample_info;
+int lcr_set_downsample(lcr_ctx*, uint32_t depth, uint64_t seed);
+int lcr_set_downsample_rows(lcr_ctx*, int32_t mem, int32_t n_rows, const uint8_t* sampled);
+int lcr_get_downsample(lcr_ctx*, lcr_downsample_info* out);
+
 /* LD blocks of one region of the last lcr_phase (SNPFrag.ld_blocks, snpfrags.rs:29; built by divide_snps_into_blocks,
  * candidate.rs:615-747): block b = snp_idx[block_off[b] .. block_off[b + 1]) (candidate indices inside the region), in
  * the reference's block and node order.  Only regions with more than max_enum_snps candidates build blocks (the

@@ -98,6 +98,11 @@ class LcrPhaseCollected(C.Structure):   # include/lcr.h: lcr_phase_collected
                 ("dev_cand", C.c_void_p), ("dev_read_rec", C.c_void_p)]
 
 
+class LcrDownsampleInfo(C.Structure):   # include/lcr.h: lcr_downsample_info
+    _fields_ = [("n_regions", C.c_int32), ("n_rows", C.c_int32), ("region_applied", C.c_void_p), ("sampled", C.c_void_p),
+                ("dev_sampled", C.c_void_p)]
+
+
 # presets: the code values of main.rs:272-396 (not the help text)
 PRESETS = {
     "hifi-isoseq": dict(platform=LCR_PLATFORM_HIFI, min_depth=6, min_phase_score=11.0, min_af=0.15,

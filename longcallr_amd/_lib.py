@@ -15,6 +15,7 @@ SYMBOLS = [
     "lcr_get_candidates", "lcr_get_candidates_device", "lcr_fragments", "lcr_get_fragmat", "lcr_phase", "lcr_get_phase_result", "lcr_get_read_records_device", "lcr_collect_phase", "lcr_get_ld_blocks", "lcr_get_tie_census",
     "lcr_enable_timing", "lcr_kernel_ms", "lcr_pileup_bytes", "lcr_pileup_stage_bytes", "lcr_discover_regions", "lcr_version", "lcr_release_cached_memory", "lcr_set_cache_limits",
     "lcr_bam_open", "lcr_bam_open_keep", "lcr_bam_close", "lcr_bam_last_error", "lcr_bam_refs", "lcr_bam_n_records", "lcr_bam_resident", "lcr_bam_spans", "lcr_bam_batch", "lcr_bam_write_phased", "lcr_bam_write_reads",
+    "lcr_set_downsample", "lcr_set_downsample_rows", "lcr_get_downsample",
     "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
 ]
 
@@ -96,6 +97,9 @@ def load():
     l.lcr_bam_write_phased.argtypes = [vp, C.c_char_p, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_char_p, vp, vp, C.c_int32, C.c_int32]
     l.lcr_bam_write_reads.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(_abi.LcrReads), C.c_int32, C.c_int32]
     l.lcr_import_candidates.argtypes = [vp, C.POINTER(_abi.LcrParams), C.c_int32, C.c_int32, vp, vp, vp]
+    l.lcr_set_downsample.argtypes = [vp, C.c_uint32, C.c_uint64]
+    l.lcr_set_downsample_rows.argtypes = [vp, C.c_int32, C.c_int32, vp]
+    l.lcr_get_downsample.argtypes = [vp, C.POINTER(_abi.LcrDownsampleInfo)]
     l.lcr_vcf_open.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vp)]
     l.lcr_vcf_close.argtypes = [vp]
     l.lcr_vcf_close.restype = None

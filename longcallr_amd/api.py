@@ -189,6 +189,27 @@ class Engine:
         self._chk(self.lib.lcr_phase(self.h, C.byref(self.params)), "lcr_phase")
         return self
 
+    def set_downsample(self, depth, seed=2025):
+        """lcr_set_downsample: regions with at least `depth` fragment rows are phased on a sample of `depth` rows (longcallR --downsample /
+        --downsample-depth; thread.rs:149 passes seed 2025).  Sticky; depth = 0 turns it off."""
+        self._chk(self.lib.lcr_set_downsample(self.h, int(depth), int(seed)), "lcr_set_downsample")
+        return self
+
+    def set_downsample_rows(self, sampled):
+        """lcr_set_downsample_rows: the caller's own sample for the next phase() only -- one byte per fragment row of fragmat(), non-zero =
+        sampled; call it between get_fragments() and phase()."""
+        m = np.ascontiguousarray(sampled, dtype=np.uint8)
+        self._chk(self.lib.lcr_set_downsample_rows(self.h, _abi.LCR_MEM_HOST, int(m.size), m.ctypes.data), "lcr_set_downsample_rows")
+        return self
+
+    def downsample_info(self):
+        """lcr_get_downsample after phase(): dict(applied = per region whether it was down-sampled, sampled = byte per fragment row -- None
+        when no region was down-sampled --, dev_sampled = the bytes' address in HBM or 0)"""
+        o = _abi.LcrDownsampleInfo()
+        self._chk(self.lib.lcr_get_downsample(self.h, C.byref(o)), "lcr_get_downsample")
+        return dict(applied=_view(o.region_applied, np.uint8, o.n_regions),
+                    sampled=_view(o.sampled, np.uint8, o.n_rows) if o.sampled else None, dev_sampled=int(o.dev_sampled or 0))
+
     def run_all(self):
         return self.fill_data_into_freq_vec().get_candidate_snps().get_fragments().phase()
 

@@ -644,10 +644,12 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
     uint32_t dneg = e & smask;            // bit i: delta_i == -1 (doubling order of phase.rs:1099-1106)
     uint32_t eta0 = e0_init, etap = ep_init;   // eta_i == 0 / eta_i == +1
     // init_assignment (phase.rs:673-680): u01() < 0.5  <=>  top bit of the draw clear  -> sigma = -1
-    const uint64_t ctr0 = (uint64_t)S + (uint64_t)R + (uint64_t)e * (uint64_t)R;
+    // (a down-sampled region draws for all F_all rows with enough links; phasing row `row` holds draw draw_row(dord, row))
+    const uint64_t ctr0 = (uint64_t)S + (uint64_t)rd.F_all + (uint64_t)e * (uint64_t)rd.F_all;
+    const int32_t* const dord = P.draw_ord ? P.draw_ord + rd.sig_off : nullptr;
     for (int k = 0; k <= nk; k++) {
       const int row = lane + 64 * k;
-      const bool neg = row < R && (mix64(rd.seed + (ctr0 + row + 1) * 0x9E3779B97F4A7C15ULL) >> 63) == 0;
+      const bool neg = row < R && (mix64(rd.seed + (ctr0 + draw_row(dord, row) + 1) * 0x9E3779B97F4A7C15ULL) >> 63) == 0;
       const unsigned long long b = __ballot(neg);
       if (lane == 0) sgb[k] = b;
     }
@@ -1059,12 +1061,15 @@ k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, ui
       // (e_base + s) R + row + 1) G): the argument advances by R G per restart and by 64 G per 64 rows (adds instead of 64-bit multiplies), and only the top
       // bit of the second multiply of mix64 is formed (three 32-bit multiplies instead of the full product: the last xor-shift cannot reach bit 63).
       constexpr uint64_t G = 0x9E3779B97F4A7C15ULL;
-      const uint64_t RG = (uint64_t)R * G;
-      uint64_t a_row = rd.seed + ((uint64_t)S + (uint64_t)R + (uint64_t)e_base * (uint64_t)R + (uint64_t)lane + 1ull) * G;
+      // (a down-sampled region: F_all rows draw per restart, and this row's draw is its ordinal's -- read from the table instead of stepped)
+      const uint64_t FA = (uint64_t)rd.F_all, RG = FA * G;
+      const uint64_t a_0 = rd.seed + ((uint64_t)S + FA + (uint64_t)e_base * FA + 1ull) * G;
+      const int32_t* const dord = P.draw_ord ? P.draw_ord + rd.sig_off : nullptr;
+      uint64_t a_row = a_0 + (uint64_t)lane * G;
       for (int k = 0; k < nk; k++) {
         const int row = lane + 64 * k;
         uint32_t b = 0;
-        uint64_t a = a_row;
+        uint64_t a = dord ? a_0 + (uint64_t)(row < R ? dord[row] : 0) * G : a_row;
 #pragma unroll
         for (int s = 0; s < 8; s++) {
           uint64_t z = (a ^ (a >> 30)) * 0xBF58476D1CE4E5B9ULL;
@@ -1419,8 +1424,9 @@ __device__ __forceinline__ void enum_big_restart(const PhaseDev& P, const Region
   const uint32_t nk = (uint32_t)(rd.R + 63) / 64, sw = enum_state_words((uint32_t)rd.R);
   const bool keep = !winner && st_words && st_base[slot] >= 0;
   for (int i = threadIdx.x; i < rd.S; i += blockDim.x) { dl[i] = ((e >> i) & 1u) ? -1 : 1; et[i] = init_genotype(vt[i]); }
-  const uint64_t ctr0 = (uint64_t)rd.S + (uint64_t)rd.R + (uint64_t)e * (uint64_t)rd.R;
-  for (int row = threadIdx.x; row < rd.R; row += blockDim.x) sg[row] = u01(rd.seed, ctr0 + row) < 0.5 ? -1 : 1;
+  const uint64_t ctr0 = (uint64_t)rd.S + (uint64_t)rd.F_all + (uint64_t)e * (uint64_t)rd.F_all;   // (F_all rows draw per restart: = R unless down-sampled)
+  const int32_t* const dord = P.draw_ord ? P.draw_ord + rd.sig_off : nullptr;
+  for (int row = threadIdx.x; row < rd.R; row += blockDim.x) sg[row] = u01(rd.seed, ctr0 + draw_row(dord, row)) < 0.5 ? -1 : 1;
   __syncthreads();
   const long long obj = cross_optimize(P, rd, mv, sg, dl, et, false, true, red, wl, macc, 32, nullptr, 0, nullptr, nullptr, nullptr, nullptr, qrow);
   if (winner) {

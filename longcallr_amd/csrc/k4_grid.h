@@ -15,7 +15,7 @@ constexpr int K4_GRID_BATCH_CTL_BYTES = 128 + 2048 + 128 + K4_GRID_BATCH_MAX_WG 
 inline size_t k4_grid_batch_lds(int64_t S) { return (size_t)(12 * (S + 2) + 24 * 1024); }
 // workgroups of a grid launch (co-resident by construction); 0 = no device
 int k4_grid_blocks();
-// k4_stage for one large region with all CUs; blk_tot: 2 * k4_grid_blocks() + 1 int32 of scratch
+// k4_stage for one large region with all CUs; blk_tot: 3 * k4_grid_blocks() + 1 int32 of scratch
 hipError_t k4_stage_launch_grid(const StageIn& in, const StageOut& out, const PhaseLutDev& lut, int g, GridCtl* ctl, int32_t* blk_tot, hipStream_t s);
 // post-phase steps for one large region with all CUs
 hipError_t k4_post_launch_grid(const PostIn& post_in, const PostScratch& ps, int g, const PostLut& lut, hipStream_t s);

@@ -582,9 +582,11 @@ __device__ __forceinline__ void chain_run(SC& sc, const ChainDev& C, const Regio
   ld_graph(sc, v, sm);
   mark();
   // start state (phase.rs:1124-1131): random delta (draws S+F ..), genotype from the variant type, random sigma
-  const uint64_t SF = (uint64_t)S + (uint64_t)R;
+  // (a down-sampled region draws for every row with enough links, sampled or not: F_all of them, this row's being draw_row())
+  const uint64_t SF = (uint64_t)S + (uint64_t)rd.F_all;
+  const int32_t* const dord = C.P.draw_ord ? C.P.draw_ord + rd.sig_off : nullptr;
   for (int i = sc.tid(); i < S; i += sc.nt()) { v.dl[i] = u01(rd.seed, SF + i) < 0.5 ? 1 : -1; v.et[i] = init_genotype(v.vt[i]); }
-  for (int row = sc.tid(); row < R; row += sc.nt()) v.sg[row] = u01(rd.seed, SF + S + row) < 0.5 ? -1 : 1;
+  for (int row = sc.tid(); row < R; row += sc.nt()) v.sg[row] = u01(rd.seed, SF + S + draw_row(dord, row)) < 0.5 ? -1 : 1;
   sc.sync();
   if (sc.blk() == 0 && (threadIdx.x >> 6) == 0) { ld_components_wave(v); ld_seed_wave(v); }
   sc.sync();
@@ -624,7 +626,7 @@ __device__ __forceinline__ void chain_run(SC& sc, const ChainDev& C, const Regio
     sc.sync();
     settle(cross(false, false));
     for (int row = sc.tid(); row < R; row += sc.nt())
-      if (u01(rd.seed, ctr_t + S + row) < 0.1) v.sg[row] = (int8_t)(-v.sg[row]);
+      if (u01(rd.seed, ctr_t + S + draw_row(dord, row)) < 0.1) v.sg[row] = (int8_t)(-v.sg[row]);
     sc.sync();
     settle(cross(false, false));
   }
@@ -914,7 +916,8 @@ __device__ __forceinline__ bool chain_rounds_fast(GridScope& sc, const ChainDev&
     if (C.dbg && sub.tid() == 0) C.dbg[15] += iters;
     return obj;   // = f_total + sum of w over the hits: every phase entry lies in exactly one column
   };
-  const uint64_t SF = (uint64_t)S + (uint64_t)R;
+  const uint64_t SF = (uint64_t)S + (uint64_t)rd.F_all;
+  const int32_t* const dord = C.P.draw_ord ? C.P.draw_ord + rd.sig_off : nullptr;
   // the state of half-round h (0 .. 2 T - 1: even = delta perturbation, odd = sigma flips of round h / 2) applied to the working
   // copy of this scope, which holds the best state; owner-local, no barrier inside
   auto perturb = [&](int h) {
@@ -932,7 +935,7 @@ __device__ __forceinline__ bool chain_rounds_fast(GridScope& sc, const ChainDev&
       for (int j = wj0; j < ng; j += nw) {
         const int row = 64 * j + lane;
         const unsigned long long word = cload(&wsw[j]);
-        const unsigned long long fm = __ballot(row < R && u01(rd.seed, ctr_t + S + row) < 0.1);
+        const unsigned long long fm = __ballot(row < R && u01(rd.seed, ctr_t + S + draw_row(dord, row)) < 0.1);
         if (lane == 0 && fm) cstore(&wsw[j], word ^ fm);
       }
     }
@@ -1222,7 +1225,7 @@ __global__ void __launch_bounds__(CH_THREADS) k4_stage_grid(StageIn in, StageOut
   __shared__ long long red[CH_WAVES];
   __shared__ unsigned long long bc[2];
   __shared__ int sm[2][16];
-  __shared__ int s_sum[5];
+  __shared__ int s_sum[7];   // [5], [6]: rows with enough links (the rows that draw) in front of this slab / in the region
   __shared__ long long s_fe[32], s_f1e[32];
   GridScope sc{ctl, red, bc, 0u};
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x, nb = gridDim.x;
@@ -1235,6 +1238,7 @@ __global__ void __launch_bounds__(CH_THREADS) k4_stage_grid(StageIn in, StageOut
   rd.seed = region_seed(in.seed, in.start0[g]);
   if (tid < 32) { s_fe[tid] = tid < 31 ? lut.fe[tid] : 0; s_f1e[tid] = tid < 31 ? lut.f1e[tid] : 0; }
   int32_t* wmax = blk_tot + 2 * nb;
+  int32_t* blk_lnk = blk_tot + 2 * nb + 1;   // per slab: rows with enough links (down-sampling: the draw ordinals count them)
   for (int i = sc.tid(); i < S; i += sc.nt()) {
     const lcr_candidate& c = in.cand[c0 + i];
     out.snp_fp[c0 + i] = (c.flags & LCR_F_FOR_PHASING) ? 1 : 0;
@@ -1247,8 +1251,9 @@ __global__ void __launch_bounds__(CH_THREADS) k4_stage_grid(StageIn in, StageOut
   const uint8_t* fp = out.snp_fp + c0;
   const int rs = (((nrow + nb - 1) / nb) + 63) & ~63;         // rows per slab
   const int s0 = min(nrow, b * rs), s1 = min(nrow, s0 + rs);
-  auto row_info = [&](int r, int& isp, int& cnt, int& span) {
-    isp = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
+  auto row_info = [&](int r, int& isp, int& cnt, int& span, int& isl) {
+    isl = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
+    isp = isl && (!in.sampled || in.sampled[r0 + r]) ? 1 : 0;
     cnt = 0; span = 0;
     int first = -1, last = -1;
     for (int64_t e = in.row_ptr[r0 + r]; e < in.row_ptr[r0 + r + 1]; e++) { const int ci = in.col[e] - c0; if (fp[ci]) { cnt++; if (first < 0) first = ci; last = ci; } }
@@ -1256,36 +1261,42 @@ __global__ void __launch_bounds__(CH_THREADS) k4_stage_grid(StageIn in, StageOut
     if (!isp) cnt = 0;
   };
   // ---- slab totals
-  if (tid < 5) s_sum[tid] = 0;
+  if (tid < 7) s_sum[tid] = 0;
   __syncthreads();
   {
-    int rows = 0, ents = 0, w = 0;
-    for (int r = s0 + tid; r < s1; r += CH_THREADS) { int isp, cnt, span; row_info(r, isp, cnt, span); rows += isp; ents += cnt; w = max(w, span); }
-    atomicAdd(&s_sum[0], rows); atomicAdd(&s_sum[1], ents); atomicMax(&s_sum[2], w);
+    int rows = 0, ents = 0, w = 0, lnk = 0;
+    for (int r = s0 + tid; r < s1; r += CH_THREADS) { int isp, cnt, span, isl; row_info(r, isp, cnt, span, isl); rows += isp; ents += cnt; w = max(w, span); lnk += isl; }
+    atomicAdd(&s_sum[0], rows); atomicAdd(&s_sum[1], ents); atomicMax(&s_sum[2], w); atomicAdd(&s_sum[5], lnk);
   }
   __syncthreads();
-  if (tid == 0) { blk_tot[2 * b] = s_sum[0]; blk_tot[2 * b + 1] = s_sum[1]; if (s_sum[2]) atomicMax(wmax, s_sum[2]); }
+  if (tid == 0) { blk_tot[2 * b] = s_sum[0]; blk_tot[2 * b + 1] = s_sum[1]; blk_lnk[b] = s_sum[5]; if (s_sum[2]) atomicMax(wmax, s_sum[2]); }
   sc.sync();
   // ---- offsets of this slab, totals of the region
-  if (tid < 5) s_sum[tid] = 0;
+  if (tid < 7) s_sum[tid] = 0;
   __syncthreads();
   for (int k = tid; k < nb; k += CH_THREADS) {
-    const int rr = blk_tot[2 * k], ee = blk_tot[2 * k + 1];
-    if (k < b) { atomicAdd(&s_sum[0], rr); atomicAdd(&s_sum[1], ee); }
-    atomicAdd(&s_sum[3], rr); atomicAdd(&s_sum[4], ee);
+    const int rr = blk_tot[2 * k], ee = blk_tot[2 * k + 1], ll = blk_lnk[k];
+    if (k < b) { atomicAdd(&s_sum[0], rr); atomicAdd(&s_sum[1], ee); atomicAdd(&s_sum[5], ll); }
+    atomicAdd(&s_sum[3], rr); atomicAdd(&s_sum[4], ee); atomicAdd(&s_sum[6], ll);
   }
   __syncthreads();
-  int R = s_sum[0], E = s_sum[1];
-  const int R_tot = s_sum[3], E_tot = s_sum[4];
+  int R = s_sum[0], E = s_sum[1], Fa = s_sum[5];
+  const int R_tot = s_sum[3], E_tot = s_sum[4], F_tot = s_sum[6];
   int32_t* prp = out.prow_ptr + rd.rp_off;
   int32_t* pcp = out.ccol_ptr + rd.cp_off;
   // ---- CSR of the slab (row order), column counts
   for (int base = s0; base < s1; base += CH_THREADS) {
     const int r = base + tid;
-    int isp = 0, cnt = 0, span = 0;
-    if (r < s1) row_info(r, isp, cnt, span);
+    int isp = 0, cnt = 0, span = 0, isl = 0;
+    if (r < s1) row_info(r, isp, cnt, span, isl);
     int k, eo, tk, te;
     block_scan2n<CH_WAVES, 16>(isp, cnt, k, eo, tk, te, sm);
+    if (in.sampled) {   // (uniform) draw ordinals: the rank among the rows with enough links
+      int ord, d0, tl, d1;
+      block_scan2n<CH_WAVES, 16>(isl, 0, ord, d0, tl, d1, sm);
+      if (isp) out.prow_ord[r0 + R + k] = Fa + ord;
+      Fa += tl;
+    }
     if (isp) {
       k += R; eo += E;
       prp[k] = eo;
@@ -1338,7 +1349,7 @@ __global__ void __launch_bounds__(CH_THREADS) k4_stage_grid(StageIn in, StageOut
   }
   const long long ftot = sc.sync_sum(ft);
   if (sc.tid() == 0) {
-    rd.R = R_tot; rd.f_total = ftot;
+    rd.R = R_tot; rd.f_total = ftot; rd.F_all = in.sampled ? F_tot : R_tot;
     out.reg[g] = rd;
     out.stat[g] = StageStat{R_tot, E_tot, INT_MAX, INT_MAX, (int)std::min<int64_t>(E_all, INT_MAX), *wmax};
   }
@@ -1359,7 +1370,8 @@ __global__ void __launch_bounds__(CH_THREADS) k4_gpost(PostIn in, PostScratch ps
   const int64_t e_base = in.row_ptr[r0];
   const int E = (int)(in.row_ptr[r0 + nrow] - e_base);
   PostView<int32_t> v;
-  v.g = g; v.S = S; v.nrow = nrow; v.E = E; v.F = in.reg[g].R; v.r0 = r0; v.c0 = c0;
+  v.g = g; v.S = S; v.nrow = nrow; v.E = E; v.F = in.reg[g].R; v.FA = in.reg[g].F_all; v.r0 = r0; v.c0 = c0;
+  v.smp = in.sampled ? in.sampled + r0 : nullptr;
   v.le = s_lut; v.l1e = s_lut + 32;
   v.sps = ps.sps; v.rpa = ps.rpa; v.rpb = ps.rpb; v.sflags = ps.sflags; v.soflags = ps.soflags; v.parent = ps.parent;
   v.rptr = ps.rptr; v.ecol = ps.ecol; v.erow = ps.erow; v.cent = ps.cent; v.ccptr = ps.ccptr; v.ev = ps.ev;
@@ -1381,7 +1393,7 @@ __global__ void __launch_bounds__(CH_THREADS) k4_gpost(PostIn in, PostScratch ps
   for (int r = sc.tid(); r < nrow; r += sc.nt()) {
     const int isp = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
     v.rptr[r] = (int32_t)(in.row_ptr[r0 + r] - e_base);
-    v.lok[r] = (uint8_t)isp; v.fp[r] = (uint8_t)isp; v.asg[r] = 0; v.tag[r] = 0;
+    v.lok[r] = (uint8_t)isp; v.fp[r] = (uint8_t)isp; v.asg[r] = 0; v.tag[r] = (int8_t)(isp && v.smp && !v.smp[r] ? 1 : 0);   // (an unsampled row's init_assignment tag: its sign is never read)
   }
   if (sc.tid() == 0) v.rptr[nrow] = E;
   for (int e = sc.tid(); e < E; e += sc.nt()) { v.ecol[e] = in.col[e_base + e] - c0; v.ev[e] = in.val[e_base + e]; }

@@ -286,7 +286,8 @@ __device__ __forceinline__ bool chain_rounds_batch(GridScope& sc, const ChainDev
     s_col[t] = c;
   }
   __syncthreads();
-  const uint64_t SF = (uint64_t)S + (uint64_t)R;
+  const uint64_t SF = (uint64_t)S + (uint64_t)rd.F_all;
+  const int32_t* const dord = C.P.draw_ord ? C.P.draw_ord + rd.sig_off : nullptr;
   const int H = 2 * (S / 4 + 1);
   unsigned bstamp = 0;   // barriers passed (the words are zero at the launch)
   // light barrier (see BatchCtl); `flags` are ORed over the grid.  need(changed) = mask of the states whose sums the caller wants (<- s_out)
@@ -365,7 +366,7 @@ __device__ __forceinline__ bool chain_rounds_batch(GridScope& sc, const ChainDev
 #pragma unroll
         for (int s = 0; s < 8; s++) {   // (the sigma half-rounds are the odd ones)
           const int hh = h + s;
-          if (hh < H && (hh & 1) && u01(rd.seed, 2 * SF + (uint64_t)(hh >> 1) * SF + (uint64_t)S + (uint64_t)row) < 0.1) x ^= 1u << s;
+          if (hh < H && (hh & 1) && u01(rd.seed, 2 * SF + (uint64_t)(hh >> 1) * SF + (uint64_t)S + draw_row(dord, row)) < 0.1) x ^= 1u << s;
         }
         cstore(&sig8[p], (uint8_t)x);
       }

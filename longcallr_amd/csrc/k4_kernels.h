@@ -103,6 +103,10 @@ void launch_k4_enum_resolve_big(int32_t n, hipStream_t s, const PhaseDev& P, con
 constexpr int STAGE_THREADS = 256;    // (1024 threads per region were measured: more barrier cost than latency saved)
 constexpr int STG_E = 8192, STG_R = 4096, STG_S = 512;   // k4_stage: a region's slice of the fragment matrix that is staged in LDS
 void launch_k4_stage(int32_t n_regions, hipStream_t s, const StageIn& in, const StageOut& out, const PhaseLutDev& lut);
+// ---- down-sampling (k4_sample.hip): the byte per fragment row of the regions listed in d_slots (each with >= depth >= 1 rows)
+constexpr int SAMPLE_THREADS = 1024;
+void launch_k4_sample(int32_t n_slots, const int32_t* d_slots, const int32_t* d_row_region_off, const int64_t* d_start0, uint32_t depth, uint64_t seed,
+                      uint8_t* d_sampled, hipStream_t s);
 
 // ---- post-phase steps, one workgroup per region (k4_post.hip) ----
 constexpr int CHAIN_THREADS = 1024;   // k4_post of the chain regions: 16 waves

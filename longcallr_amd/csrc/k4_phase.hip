@@ -470,6 +470,7 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
   objective.assign(c.ng, 0.0);
   RCHK(open_queues(c));
   RCHK(size_buffers(c));
+  RCHK(sample(c));
   RCHK(stage(c));
   RCHK(classify(c));
   RCHK(wait_sizes(c));
@@ -581,6 +582,44 @@ int PhaseHost::size_buffers(PhaseCall& c) {
   return LCR_OK;
 }
 
+// Down-sampling (thread.rs:144-151): a region applies when it has at least ds_depth fragment rows (all rows of lcr_get_fragmat, empty
+// ones included) -- or, with the caller's own bytes, when one of its rows is unsampled (a region whose rows are all sampled behaves as
+// with the feature off).  k4_sample writes the bytes of the regions that apply, the others' are 1.  No region applies: nothing is
+// launched and every kernel gets null pointers -- exactly the call with the feature off.
+int PhaseHost::sample(PhaseCall& c) {
+  const PhaseInputs& in = c.in;
+  ds_applied.assign((size_t)std::max(c.ng, 1), 0); ds_any = false;
+  ds_ng = (int32_t)c.ng; ds_nrow = (int32_t)c.nrow;
+  if (!in.ds_rows && in.ds_depth == 0) return LCR_OK;
+  PCHK(h_smp_slots.reserve((size_t)std::max(c.ng, 1) * 4));
+  int32_t* const slots = h_smp_slots.as<int32_t>();
+  int n = 0;
+  for (int g = 0; g < c.ng; g++) {
+    const int r0 = in.row_region_off[g], F = in.row_region_off[g + 1] - r0;
+    bool app = false;
+    if (in.ds_rows) app = F > 0 && memchr(in.ds_rows + r0, 0, (size_t)F) != nullptr;
+    else app = F > 0 && (uint32_t)F >= in.ds_depth;
+    if (app) { ds_applied[g] = 1; slots[n++] = g; }
+  }
+  if (!n) return LCR_OK;
+  ds_any = true;
+  PCHK(d_sampled.reserve(c.nr1)); PCHK(h_sampled.reserve(c.nr1)); PCHK(d_prow_ord.reserve(c.nr1 * 4));
+  if (in.ds_rows) {
+    memcpy(h_sampled.p, in.ds_rows, (size_t)c.nrow);
+    PCHK(hipMemcpyAsync(d_sampled.p, h_sampled.p, (size_t)c.nrow, hipMemcpyHostToDevice, c.sq));
+  } else {
+    int32_t* d_slots = nullptr;
+    PCHK(hipHostGetDevicePointer((void**)&d_slots, slots, 0));
+    PCHK(lcr_fill_async(d_sampled.p, 1, (size_t)c.nrow, c.sq));
+    launch_k4_sample(n, d_slots, in.d_row_region_off, in.d_start0, in.ds_depth, in.ds_seed, d_sampled.as<uint8_t>(), c.sq);
+    PCHK(hipGetLastError());
+    PCHK(hipMemcpyAsync(h_sampled.p, d_sampled.p, (size_t)c.nrow, hipMemcpyDeviceToHost, c.sq));   // (complete when the host has the staging kernel's sizes)
+  }
+  c.P.draw_ord = c.Pc.draw_ord = d_prow_ord.as<int32_t>();
+  c.pin.sampled = c.pinc.sampled = d_sampled.as<uint8_t>();
+  return LCR_OK;
+}
+
 // k4_stage on the caller's queue -- launched before the host sorts the regions into their kernel classes (the device would idle for
 // that long); the per-region sizes arrive in pinned host memory
 int PhaseHost::stage(PhaseCall& c) {
@@ -588,13 +627,14 @@ int PhaseHost::stage(PhaseCall& c) {
   c.grid_min = dbg.grid_min >= 0 ? dbg.grid_min : (1 << 17);   // chain regions with at least this many phase entries get all CUs (tests: 0 = every region)
   c.stat = h_stat.as<StageStat>();
   c.si = StageIn{in.d_row_ptr, in.d_col, in.d_val, in.d_row_links, in.d_cand, in.d_cand_off, in.d_row_region_off, in.d_start0,
-                 c.prm.min_linkers, c.prm.max_enum_snps, c.prm.seed, std::max<int64_t>(c.grid_min, 1)};
+                 c.prm.min_linkers, c.prm.max_enum_snps, c.prm.seed, std::max<int64_t>(c.grid_min, 1), ds_any ? d_sampled.as<uint8_t>() : nullptr};
   if (!c.ng) return LCR_OK;
   StageStat* d_stat = nullptr;   // the per-region sizes go straight into pinned host memory (no copy behind the staging kernels)
   PCHK(hipHostGetDevicePointer((void**)&d_stat, c.stat, 0));
   c.so = StageOut{d_reg.as<RegionDev>(), d_stat, d_prow_ptr.as<int32_t>(), d_pcol.as<int32_t>(), d_pval.as<uint8_t>(),
                   d_ccol_ptr.as<int32_t>(), d_crow.as<int32_t>(), d_cval.as<uint8_t>(), d_snp.as<uint8_t>(), d_snp.as<int8_t>() + c.nc1,
-                  d_snp.as<uint8_t>() + 2 * c.nc1, d_snp_const.as<long long>(), d_cur.as<int32_t>(), d_prow_src.as<int32_t>()};
+                  d_snp.as<uint8_t>() + 2 * c.nc1, d_snp_const.as<long long>(), d_cur.as<int32_t>(), d_prow_src.as<int32_t>(),
+                  ds_any ? d_prow_ord.as<int32_t>() : nullptr};
   launch_k4_stage((int32_t)c.ng, c.sq, c.si, c.so, hlut().dev);
   PCHK(hipGetLastError());
   HT("  ph:stage_q");
@@ -651,7 +691,7 @@ int PhaseHost::wait_sizes(PhaseCall& c) {
   if (c.ng) {
     if (!c.gstage_slots.empty()) {   // large regions: all CUs on one region at a time (every persistent launch goes to `side`)
       RCHK(c.lock_grid(*this));
-      PCHK(d_grid_ctl.reserve((4 + 16) * sizeof(GridCtl))); PCHK(d_grid_tot.reserve((size_t)(2 * std::max(1, k4_grid_blocks()) + 1) * 4 + 64));
+      PCHK(d_grid_ctl.reserve((4 + 16) * sizeof(GridCtl))); PCHK(d_grid_tot.reserve((size_t)(3 * std::max(1, k4_grid_blocks()) + 1) * 4 + 64));
       for (int g : c.gstage_slots) PCHK(k4_stage_launch_grid(c.si, c.so, hlut().dev, g, d_grid_ctl.as<GridCtl>(), d_grid_tot.as<int32_t>(), side));
       PCHK(hipEventRecord(ev_join, side));
       PCHK(hipStreamWaitEvent(sq, ev_join, 0));

@@ -18,6 +18,8 @@ namespace {
 template <class IDX>
 struct PostView {
   int g, S, nrow, E, F;          // region, candidates, fragment rows, entries, phasing rows
+  int FA;                        // rows with enough links (RegionDev::F_all): the rows the optimiser drew for
+  const uint8_t* smp = nullptr;  // down-sampling: the sampled byte of the region's fragment rows (global memory); nullptr = off
   int r0, c0;
   double *le, *l1e;              // LDS in both scopes
   double *sps, *rpa, *rpb;
@@ -55,6 +57,10 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
   // exact identity here: the sums start at +0.0 and every term is a finite log) in LDS; then lane a adds the
   // 64 staged terms of accumulator a in entry order.  The additions are the host's, in the host's order;
   // only the loads and the filter run in parallel.  Results are returned wave-uniform.
+  // Down-sampling (thread.rs:168-182): the first two rounds and the rescue lists' evidence see the sampled rows only, the last round every
+  // row.  An unsampled row with enough links keeps fp = 1, assignment 0 and a non-zero tag until then, so the rescue commit draws for it.
+  const uint8_t* const smp = v.smp;
+  bool gate = smp != nullptr;
   double* stg = v.stage + (threadIdx.x >> 6) * (4 * POST_SSTR);
   auto col_sums = [&](int ti, bool skip_unassigned, auto term, double* acc, int nacc, int& hap1, int& hap2, int& nobs) {
     hap1 = hap2 = nobs = 0;
@@ -63,7 +69,7 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
     for (int k0 = kb; k0 < ke; k0 += 64) {
       const int k = k0 + lane;
       bool keep = false; int r = 0, e = 0;
-      if (k < ke) { e = cent[k]; r = erow[e]; keep = fp[r] && lok[r] && !(skip_unassigned && asg[r] == 0); }
+      if (k < ke) { e = cent[k]; r = erow[e]; keep = fp[r] && lok[r] && !(skip_unassigned && asg[r] == 0) && !(gate && !smp[r]); }
       double t[4] = {0.0, 0.0, 0.0, 0.0};
       if (keep) term((int)tag[r], ev[e], t);
       for (int a = 0; a < nacc; a++) stg[a * POST_SSTR + lane] = t[a];
@@ -100,7 +106,7 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
   // snpfrags.rs:548-625
   auto reads_hap = [&]() {
     for (int r = sc.tid(); r < nrow; r += sc.nt()) {
-      if (!fp[r]) continue;
+      if (!fp[r] || (gate && !smp[r])) continue;
       const int sigma_k = tag[r];
       double q1 = 0, q2 = 0, q3 = 0, n1 = 0;
       int n = 0;
@@ -185,7 +191,7 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
   // round, the first member that does see a changed row starts the next round.
   unsigned long long ctr = 0;   // first wave: draws so far (thread.rs call order, see PhaseHost::run)
   {
-    const unsigned long long Su = (unsigned long long)S, Fu = (unsigned long long)v.F;
+    const unsigned long long Su = (unsigned long long)S, Fu = (unsigned long long)v.FA;
     ctr = (uint32_t)S <= in.max_enum_snps ? Su + Fu + (1ull << S) * Fu : 2 * (Su + Fu) + (Su / 4 + 1) * (Su + Fu);
   }
   auto rescue = [&](uint32_t list_flag, float min_ps, bool low_frac, uint64_t rseed) -> bool {   // true: some SNP state changed
@@ -510,7 +516,8 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
   const bool c1 = rescue(LCR_F_RNA_EDIT, relaxed, false, rseed);
   const bool c2 = rescue(LCR_F_CAND_SOMATIC, relaxed, true, rseed);
   mark();
-  if (redo || c1 || c2) { reads_hap(); snp_hap(); }
+  gate = false;   // (the third round is not idempotent under a sample: it is the first to see every row)
+  if (redo || c1 || c2 || smp) { reads_hap(); snp_hap(); }
   mark();
   phase_set();
   mark();

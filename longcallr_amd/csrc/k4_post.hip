@@ -30,7 +30,8 @@ __global__ void __launch_bounds__(NT) k4_post(PostIn in, const int32_t* __restri
   const int E = (int)(in.row_ptr[r0 + nrow] - e_base);
   const PostLayout L = post_layout(nrow, E, S);
   PostView<uint16_t> v;
-  v.g = g; v.S = S; v.nrow = nrow; v.E = E; v.F = in.reg[g].R; v.r0 = r0; v.c0 = c0;
+  v.g = g; v.S = S; v.nrow = nrow; v.E = E; v.F = in.reg[g].R; v.FA = in.reg[g].F_all; v.r0 = r0; v.c0 = c0;
+  v.smp = in.sampled ? in.sampled + r0 : nullptr;
   v.le = (double*)lds; v.l1e = v.le + 32;
   v.sps = (double*)(lds + L.sps); v.rpa = (double*)(lds + L.rpa); v.rpb = (double*)(lds + L.rpb);
   v.sflags = (uint32_t*)(lds + L.sflags); v.soflags = (uint32_t*)(lds + L.soflags);
@@ -61,7 +62,7 @@ __global__ void __launch_bounds__(NT) k4_post(PostIn in, const int32_t* __restri
   for (int r = tid; r < nrow; r += NT) {
     const int isp = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
     rptr[r] = (uint16_t)(in.row_ptr[r0 + r] - e_base);
-    v.lok[r] = (uint8_t)isp; v.fp[r] = (uint8_t)isp; v.asg[r] = 0; v.tag[r] = 0;
+    v.lok[r] = (uint8_t)isp; v.fp[r] = (uint8_t)isp; v.asg[r] = 0; v.tag[r] = (int8_t)(isp && v.smp && !v.smp[r] ? 1 : 0);   // (an unsampled row's init_assignment tag: its sign is never read)
   }
   if (tid == 0) rptr[nrow] = (uint16_t)E;
   __syncthreads();

@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(STAGE_THREADS) k4_stage(StageIn in, StageOut o
   rd.S = S; rd.rp_off = r0 + g; rd.cp_off = c0 + g; rd.e_off = e_base; rd.sig_off = r0; rd.snp_off = c0;
   rd.seed = region_seed(in.seed, in.start0[g]);
   if (S == 0) {
-    if (tid == 0) { out.reg[g] = rd; out.stat[g] = StageStat{0, 0, 0, 0, 0, 0}; out.prow_ptr[rd.rp_off] = 0; out.ccol_ptr[rd.cp_off] = 0; }
+    if (tid == 0) { rd.F_all = 0; out.reg[g] = rd; out.stat[g] = StageStat{0, 0, 0, 0, 0, 0}; out.prow_ptr[rd.rp_off] = 0; out.ccol_ptr[rd.cp_off] = 0; }
     return;
   }
   if (tid < 32) { s_fe[tid] = tid < 31 ? lut.fe[tid] : 0; s_f1e[tid] = tid < 31 ? lut.f1e[tid] : 0; }
@@ -57,15 +57,20 @@ __global__ void __launch_bounds__(STAGE_THREADS) k4_stage(StageIn in, StageOut o
   if (staged) {
     for (int e = tid; e < (int)E_all; e += STAGE_THREADS) { s_col[e] = (uint16_t)(in.col[e_base + e] - c0); s_val[e] = in.val[e_base + e]; }
     for (int r = tid; r <= nrow; r += STAGE_THREADS) s_rp[r] = (uint16_t)(in.row_ptr[r0 + r] - e_base);
-    for (int r = tid; r < nrow; r += STAGE_THREADS) s_isp[r] = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
+    // bit 0: phasing row (enough links, and sampled when the region is down-sampled), bit 1: enough links (the rows that draw)
+    for (int r = tid; r < nrow; r += STAGE_THREADS) {
+      const int isl = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
+      s_isp[r] = (uint8_t)((isl && (!in.sampled || in.sampled[r0 + r]) ? 1 : 0) | (isl << 1));
+    }
   }
   __syncthreads();
   int32_t* prp = out.prow_ptr + rd.rp_off;
   int32_t* pcp = out.ccol_ptr + rd.cp_off;
-  int R = 0, E = 0;
+  int R = 0, E = 0, Fa = 0;
   auto build = [&](auto staged_tag) {
     constexpr bool ST = decltype(staged_tag)::value;
-    auto isp_of = [&](int r) -> int { if constexpr (ST) return s_isp[r]; else return in.links[r0 + r] >= in.min_linkers ? 1 : 0; };
+    auto isl_of = [&](int r) -> int { if constexpr (ST) return s_isp[r] >> 1; else return in.links[r0 + r] >= in.min_linkers ? 1 : 0; };
+    auto isp_of = [&](int r) -> int { if constexpr (ST) return s_isp[r] & 1; else return in.links[r0 + r] >= in.min_linkers && (!in.sampled || in.sampled[r0 + r]) ? 1 : 0; };
     auto rp_of = [&](int r) -> int { if constexpr (ST) return s_rp[r]; else return (int)(in.row_ptr[r0 + r] - e_base); };   // region relative
     auto col_of = [&](int e) -> int { if constexpr (ST) return s_col[e]; else return in.col[e_base + e] - c0; };              // region relative
     auto val_of = [&](int e) -> uint8_t { if constexpr (ST) return s_val[e]; else return in.val[e_base + e]; };
@@ -85,6 +90,12 @@ __global__ void __launch_bounds__(STAGE_THREADS) k4_stage(StageIn in, StageOut o
       }
       int k, eo, tk, te;
       block_scan2n<NW, 16>(isp, cnt, k, eo, tk, te, sm);
+      if (in.sampled) {   // (uniform) draw ordinals: the rank among the rows with enough links
+        int ord, d0, tl, d1;
+        block_scan2n<NW, 16>(r < nrow ? isl_of(r) : 0, 0, ord, d0, tl, d1, sm);
+        if (isp) out.prow_ord[r0 + R + k] = Fa + ord;
+        Fa += tl;
+      }
       if (isp) {
         k += R; eo += E;
         prp[k] = eo;
@@ -167,7 +178,7 @@ __global__ void __launch_bounds__(STAGE_THREADS) k4_stage(StageIn in, StageOut o
   if (tid == 0) {
     long long ftot = 0;
     for (int w = 0; w < NW; w++) ftot += s_ft[w];
-    rd.R = R; rd.f_total = ftot;
+    rd.R = R; rd.f_total = ftot; rd.F_all = in.sampled ? Fa : R;
     out.reg[g] = rd;
     out.stat[g] = StageStat{R, E, max(s_max[0], (int)enum_chunk((uint32_t)E)), s_max[1], (int)E_all, s_max[2]};
   }

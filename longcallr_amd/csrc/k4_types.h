@@ -11,6 +11,8 @@ struct RegionDev {
   int32_t snp_off;       // offset into per-SNP arrays
   uint64_t seed;
   long long f_total;     // sum of fe[q] over all phase entries (the sigma/delta independent part of the objective)
+  int32_t F_all;         // rows with >= min_linkers links: the rows that DRAW (= R unless the region is down-sampled, k4_sample.hip)
+  int32_t pad_;
 };
 
 struct PhaseDev {
@@ -32,7 +34,13 @@ struct PhaseDev {
   int32_t tie_arith;   // 0: fixed point only (ties change nothing), 1: + configurations of equal objective by their f64 sums, 2: + sigma ties by the f64 scores,
                        // 3: + (enumeration kernels) delta / eta ties at the maximum and the verdict of tie-only steps
   int32_t pad_;
+  // down-sampling (k4_sample.hip): per phasing row (at sig_off + k) its DRAW ORDINAL, the rank among all rows with >= min_linkers links -- the
+  // reference draws for every such row, sampled or not (phase.rs:673-680, 1218-1225), so counters are formed from the ordinal and
+  // RegionDev::F_all.  nullptr (the feature is off, or no region of the call applies): the ordinal is the row index itself, no table load
+  const int32_t* draw_ord;
 };
+// draw index of phasing row `row` of a region (ord = draw_ord + sig_off, or nullptr)
+__device__ __forceinline__ uint64_t draw_row(const int32_t* ord, int row) { return ord ? (uint64_t)ord[row] : (uint64_t)row; }
 // census of exact fixed-point ties of one lcr_phase call (lcr_get_tie_census): the RESOLVED classes follow the reference's f64
 // arithmetic; an UNRESOLVED count other than zero means a decision fell to "a tie changes nothing" where the reference's f64
 // rounding noise might have decided otherwise
@@ -116,12 +124,14 @@ struct StageIn {
   const lcr_candidate* cand; const int32_t* cand_off; const int32_t* row_region_off; const int64_t* start0;
   uint32_t min_linkers, max_enum_snps; uint64_t seed;
   int64_t grid_min;    // regions with at least this many fragment entries are staged by k4_stage_grid
+  const uint8_t* sampled;   // down-sampling: one byte per fragment row (batch-wide), 0 = the optimiser does not see the row; nullptr = every row
 };
 struct StageOut {
   RegionDev* reg; StageStat* stat;
   int32_t* prow_ptr; int32_t* pcol; uint8_t* pval; int32_t* ccol_ptr; int32_t* crow; uint8_t* cval;
   uint8_t* snp_fp; int8_t* snp_vt; uint8_t* snp_cons; long long* snp_const; int32_t* cursor;
   int32_t* prow_src;   // per phasing row (at r0 + k): its fragment row, region relative
+  int32_t* prow_ord;   // per phasing row (at r0 + k): its draw ordinal (PhaseDev::draw_ord); written only when StageIn::sampled is set
 };
 // HBM image of ONE region for k4_gpost (post-phase steps with all CUs on the region)
 struct PostScratch {
@@ -143,4 +153,5 @@ struct PostIn {
   uint32_t min_linkers, max_enum_snps; uint64_t seed; double cutoff; float min_phase_score;
   long long* dbg_clk;   // LCR_PHASE_PROF: 100 MHz timestamps of every workgroup's steps, 16 per region (nullptr otherwise)
   const RegionDev* reg; const int32_t* prow_src;   // phasing rows of the region (k4_stage): count, and their fragment rows
+  const uint8_t* sampled;   // down-sampling: the byte per fragment row k4_stage saw (gates rounds 1 / 2 and the rescue evidence); nullptr = off
 };

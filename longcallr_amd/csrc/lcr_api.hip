@@ -113,6 +113,9 @@ struct lcr_ctx {
   int phase_slot = -1;      // staging slot of the batch whose (asynchronous) phase stage may be in flight: -1 = the caller's own device arrays, -2 = in_[] (a host batch)
   PhaseHost phase;
   std::vector<int32_t> ld_off, ld_snps;   // lcr_get_ld_blocks
+  // down-sampling: the sticky setting (lcr_set_downsample; 0 = off) and the caller's own sample for the next lcr_phase (lcr_set_downsample_rows)
+  uint32_t ds_depth = 0; uint64_t ds_seed = 0;
+  std::vector<uint8_t> ds_rows; bool ds_rows_set = false;
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
@@ -1122,6 +1125,7 @@ int lcr_fragments(lcr_ctx* c, const lcr_params* p) {
                    c->col.as<int32_t>(), c->val.as<uint8_t>(), hits, c->stream); }
   HIPCHK(c, hipGetLastError());
   c->have_frag = true;
+  c->ds_rows_set = false;   // (a sample names the rows of ONE fragment stage)
   HT("frag:ret");
   c->have_phase = false;
   return LCR_OK;
@@ -1174,9 +1178,14 @@ int lcr_phase(lcr_ctx* c, const lcr_params* p) {
   if (!c->have_frag) { c->err = "lcr_phase before lcr_fragments"; return LCR_E_STATE; }
   if (c->cand_used) { c->err = "lcr_phase after lcr_phase: the phase stage has rewritten the candidate records; run the candidate stage again"; return LCR_E_STATE; }
   if (p->ld_weight_threshold != 1) { c->err = "ld_weight_threshold must be 1: SNPFrag::phase is only ever called with 1 (thread.rs:166)"; return LCR_E_ARG; }
+  const bool ds_on = c->ds_rows_set || c->ds_depth > 0;
+  if (ds_on && !(p->read_assign_cutoff > 0.0)) { c->err = "down-sampling needs read_assign_cutoff > 0: the last read assignment must not depend on the sign of an unsampled row's haplotag"; return LCR_E_ARG; }
+  if (ds_on && c->phase.dbg.post_host) { c->err = "the post_host cross-check does not know the sample: switch it off while down-sampling is on"; return LCR_E_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = frag_settle(c); if (rc) return rc; }
   PhaseInputs in;
+  in.ds_depth = c->ds_depth; in.ds_seed = c->ds_seed; in.ds_rows = c->ds_rows_set ? c->ds_rows.data() : nullptr;
+  c->ds_rows_set = false;   // (for this lcr_phase only)
   in.n_regions = c->bv.n_regions; in.n_rows = c->n_rows; in.nnz = c->nnz;
   in.row_region_off = c->h_row_region_off.data(); in.cand_region_off = c->h_cand_off.data();
   in.region_start0 = c->h_start0.data();
@@ -1198,6 +1207,38 @@ int lcr_phase(lcr_ctx* c, const lcr_params* p) {
   c->have_phase = true;
   c->res_valid = true; c->res_ng = c->bv.n_regions;
   c->phase_slot = c->bound_slot >= 0 ? c->bound_slot : (c->bound_host ? -2 : -1);
+  return LCR_OK;
+}
+
+int lcr_set_downsample(lcr_ctx* c, uint32_t depth, uint64_t seed) {
+  if (!c) return LCR_E_ARG;
+  c->ds_depth = depth; c->ds_seed = seed;
+  return LCR_OK;
+}
+
+int lcr_set_downsample_rows(lcr_ctx* c, int32_t mem, int32_t n_rows, const uint8_t* sampled) {
+  if (!c || (mem != LCR_MEM_HOST && mem != LCR_MEM_DEVICE)) return LCR_E_ARG;
+  if (!c->have_frag || c->cand_used) { c->err = "lcr_set_downsample_rows names the rows of a fragment stage: call it between lcr_fragments and lcr_phase"; return LCR_E_STATE; }
+  if (n_rows != c->n_rows || (n_rows > 0 && !sampled)) { c->err = "lcr_set_downsample_rows: one byte per fragment row of lcr_get_fragmat"; return LCR_E_ARG; }
+  c->ds_rows.resize((size_t)n_rows);
+  if (n_rows > 0) {
+    if (mem == LCR_MEM_HOST) memcpy(c->ds_rows.data(), sampled, (size_t)n_rows);
+    else { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipMemcpy(c->ds_rows.data(), sampled, (size_t)n_rows, hipMemcpyDeviceToHost)); }
+  }
+  for (uint8_t& b : c->ds_rows) b = b ? 1 : 0;
+  c->ds_rows_set = true;
+  return LCR_OK;
+}
+
+int lcr_get_downsample(lcr_ctx* c, lcr_downsample_info* out) {
+  if (!c || !out) return LCR_E_ARG;
+  if (!c->res_valid) { c->err = "lcr_get_downsample: no phase results (call it after lcr_phase and before the next candidate stage)"; return LCR_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = phase_settle(c); if (rc) return rc; }   // (the asynchronous stage: the bytes' copy is queued with it)
+  out->n_regions = c->phase.ds_ng; out->n_rows = c->phase.ds_nrow;   // (of that lcr_phase, not of a later fragment stage)
+  out->region_applied = c->phase.ds_applied.data();
+  out->sampled = c->phase.ds_any ? c->phase.h_sampled.as<uint8_t>() : nullptr;
+  out->dev_sampled = c->phase.ds_any ? c->phase.d_sampled.as<uint8_t>() : nullptr;
   return LCR_OK;
 }
 

@@ -26,6 +26,9 @@ struct PhaseInputs {
   const int32_t* d_cand_off = nullptr;       // device, n_regions+1
   const int32_t* d_row_region_off = nullptr; // device, n_regions+1
   const int64_t* d_start0 = nullptr;         // device, region start columns
+  // down-sampling (lcr_set_downsample / lcr_set_downsample_rows): regions with at least ds_depth > 0 fragment rows are phased on the ds_depth
+  // rows k4_sample picks; ds_rows (host, n_rows bytes of 0 / 1; overrides the depth): the caller's own sample
+  uint32_t ds_depth = 0; uint64_t ds_seed = 0; const uint8_t* ds_rows = nullptr;
   int snps(int g) const { return cand_region_off[g + 1] - cand_region_off[g]; }   // SNPs (candidates) of region g
 };
 
@@ -117,6 +120,11 @@ struct PhaseHost {
   // ---- buffers, by the step that uses them (each grows to the largest batch seen; freed with the context)
   // staging matrices (k4_stage): region table, row / column-major phase matrices, per-SNP bytes and constants, cursors, source rows
   DevBuf d_reg, d_prow_ptr, d_pcol, d_pval, d_ccol_ptr, d_crow, d_cval, d_snp, d_snp_const, d_cur, d_prow_src;
+  // down-sampling (k4_sample): byte per fragment row, draw ordinal per phasing row; pinned: the bytes again | the launch's regions
+  DevBuf d_sampled, d_prow_ord; HostBuf h_sampled, h_smp_slots;
+  std::vector<uint8_t> ds_applied;   // per region of the last run: down-sampled (lcr_get_downsample)
+  bool ds_any = false;               // ... some region was: d_sampled / h_sampled hold the last run's bytes
+  int32_t ds_ng = 0, ds_nrow = 0;    // ... its region and fragment-row counts (the fragment stage may have moved on since)
   DevBuf d_grid_ctl, d_grid_tot;   // grid-scope launches: barrier blocks, k4_stage's per-workgroup totals
   // result state: sigma | delta | eta | objective of the enumeration and of the chain regions, per-row records in HBM (k4_post),
   // f64 table of the tie paths (PostLut), tie census counters; k4_post's step clocks (phase_prof)
@@ -175,7 +183,7 @@ struct PhaseHost {
   void free_work();
   int run(const PhaseInputs& in, const lcr_params& p, hipStream_t s, std::string* err);
   // the steps of run(), in order (k4_phase.hip); PhaseCall holds the values of one call
-  int open_queues(PhaseCall& c), size_buffers(PhaseCall& c), stage(PhaseCall& c), classify(PhaseCall& c), wait_sizes(PhaseCall& c);
+  int open_queues(PhaseCall& c), size_buffers(PhaseCall& c), sample(PhaseCall& c), stage(PhaseCall& c), classify(PhaseCall& c), wait_sizes(PhaseCall& c);
   int launch_enum(PhaseCall& c), launch_chain(PhaseCall& c), launch_gpost(PhaseCall& c), report_prof(PhaseCall& c), host_epilogue(PhaseCall& c);
   bool mark_pending(PhaseCall& c);
   // queues, events, host pool and host work (the buffers free themselves; the owner has drained the queues: lcr_ctx_destroy)

@@ -13,7 +13,7 @@ the five hot-path calls, with one context per GPU instead of one rayon task per 
 
   thread.rs:70-74,107-116 user-provided candidates (-v)   -> vcf.read_sites once + lcr_import_candidates per chunk
 
-Not here (out of scope): gene annotation / exon filter, down-sampling, region truncation, the somatic model.  Records are written in contig order of the .fai and position order inside
+Not here (out of scope): gene annotation / exon filter, region truncation, the somatic model.  Records are written in contig order of the .fai and position order inside
 a contig (the reference writes them in region-completion order, thread.rs:216-221: compare as a set)."""
 import os
 
@@ -106,7 +106,8 @@ def _gather_names(name_off, blob, rows):
 
 
 def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs=None, device=0, threads=0, seed=2025,
-        read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None, **param_overrides):
+        read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None,
+        downsample=False, downsample_depth=10000, downsample_seed=2025, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -117,9 +118,18 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     chunk_cost or async_phase.
     input_vcf: phase the sites of this VCF / .vcf.gz instead of calling candidates (longcallR -v, thread.rs:107-116): the file is read
     once (vcf.read_sites), every chunk takes its contig's sites inside its span (none when the contig is not in the file) through
-    lcr_import_candidates.  Adds the stats input_sites (sites read) and imported_sites (sites handed to the candidate stage)."""
+    lcr_import_candidates.  Adds the stats input_sites (sites read) and imported_sites (sites handed to the candidate stage).
+    downsample / downsample_depth: longcallR --downsample / --downsample-depth (thread.rs:144-151): a region with at least
+    downsample_depth fragments is phased on a sample of that many (lcr_set_downsample, include/lcr.h; the sample is the project's
+    counter-based one, not StdRng's); the last post-phase round still assigns every read.  Off by default.  It needs a positive
+    read_assign_cutoff (the presets' is 0.0: pass e.g. read_assign_cutoff=1e-6), ValueError otherwise."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
+    params = _abi.make_params(preset, seed=seed, **param_overrides)
+    downsample = bool(downsample) and downsample_depth > 0
+    if downsample and not params.read_assign_cutoff > 0:    # (lcr_phase would answer LCR_E_ARG in the first chunk: include/lcr.h)
+        raise ValueError("downsample=True needs read_assign_cutoff > 0 (preset %r has %r): an unsampled read's haplotag carries no sign, "
+                         "pass e.g. read_assign_cutoff=1e-6" % (preset, float(params.read_assign_cutoff)))
     fai = ref_path + ".fai"
     if not os.path.exists(fai):
         raise FileNotFoundError("Reference index file .fai does not exist.")   # util.rs:575-577
@@ -127,11 +137,13 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     refs = load_reference(ref_path)
     flt = dict(_abi.READ_FILTER)
     flt.update(read_filter or {})
-    params = _abi.make_params(preset, seed=seed, **param_overrides)
     nb = bamio.NativeBam(bam_path, threads)
     bam_ids = {n: i for i, (n, _) in enumerate(nb.refs)}
     devices = list(devices) if devices else [device]
     engines = [api.Engine(d, params) for d in devices]
+    if downsample:
+        for e in engines:
+            e.set_downsample(downsample_depth, downsample_seed)
     # a ctx is single-threaded (include/lcr.h): the producer thread below never touches a working engine -- region
     # discovery has a context of its own (its kernels share scratch buffers and a stream with nothing else)
     scout = api.Engine(devices[0], params)

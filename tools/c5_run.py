@@ -21,13 +21,16 @@ def main():
     ap.add_argument("--depth", type=float, default=500.0)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--downsample-depth", type=int, default=0, help="> 0: phase the island on a sample of this many fragments (lcr_set_downsample)")
     a = ap.parse_args()
     from longcallr_amd import _abi, api, synth
     t0 = time.perf_counter()
     b = synth.make_island("ont-drna-c5", n_loci=a.loci, locus_len=a.locus_len, depth=a.depth, seed=a.seed)
     gen_s = time.perf_counter() - t0
-    params = _abi.make_params("ont-drna", seed=a.seed)
+    params = _abi.make_params("ont-drna", seed=a.seed, **(dict(read_assign_cutoff=1e-6) if a.downsample_depth > 0 else {}))
     E = api.Engine(0, params)
+    if a.downsample_depth > 0:
+        E.set_downsample(a.downsample_depth, 2025)
     out = dict(workload="C5: %d loci x %d bp as one island, %.0fx" % (a.loci, a.locus_len, a.depth), generate_s=gen_s,
                columns=int(b.len[0]), reads=b.n_reads, aligned_bases=int(b.bases.size), runs=[])
     digest = None
