@@ -374,12 +374,25 @@ int lcr_get_ld_blocks(lcr_ctx*, int32_t region, int32_t* n_blocks, const int32_t
  * All UNRESOLVED counts zero = every decision of the call was the reference arithmetic's decision. */
 int lcr_get_tie_census(lcr_ctx*, uint64_t out[8]);
 
-/* Region discovery: replaces find_isolated_regions_with_depth (util.rs:236-332, truncation
- * off) for one contig.  ref_start / ref_end are record.reference_start() / reference_end() of the reads that
- * pass the filters of util.rs:264-279 (mem = LCR_MEM_HOST or LCR_MEM_DEVICE).  Region i covers 0-based columns
- * [start0[i], start0[i] + len[i]) — the reference's 1-based [start, end) = [start0+1, start0+len+1).  As in the
- * reference, cursors and max_coverage are reset only when a region is emitted (`region_end > region_start`,
- * util.rs:297-310): a single-column island stays pending and starts the region that ends with the next island. */
+/* Region discovery: replaces find_isolated_regions_with_depth (util.rs:236-332, with and
+ * without --truncation) for one contig.  ref_start / ref_end are record.reference_start() / reference_end() of
+ * the reads that pass the filters of util.rs:264-279 (mem = LCR_MEM_HOST or LCR_MEM_DEVICE).  Region i covers
+ * 0-based columns [start0[i], start0[i] + len[i]) — the reference's 1-based [start, end) = [start0+1, start0+len+1).
+ *
+ * The rule (util.rs:287-330).  A column is a BREAK when its depth is 0 or, with truncation on, above
+ * truncation_coverage (a depth equal to it is kept); islands are the maximal runs of the other columns.  At a
+ * break a pending region with region_end > region_start is emitted, and only then are the cursors and
+ * max_coverage reset; after the last column a pending region is emitted the same way.  So a single-column island
+ * stays pending and starts the region that ends with the next island, the breaks between them included, and the
+ * columns above the cap are in no region unless they lie between such a pair: the flanks of an over-deep stretch
+ * become regions of their own (a read that spans the stretch is listed in both by lcr_bam_batch).
+ *
+ * max_cov is NOT the maximum over the region's columns: the reference takes it from every column before the
+ * break test and resets it at an emission.  Region k gets the maximum depth over (p_{k-1}, p_k], p_k the column
+ * at which it is emitted (the first break behind its last island, or the contig's last column; p_{-1} = -1): the
+ * over-deep column that closes a region counts for that region, the rest of the stretch for the NEXT region, a
+ * stretch in front of the first island for the first region, and columns behind the last emission for nothing.
+ * With truncation a region's max_cov can therefore exceed the cap although none of its columns does. */
 typedef struct {
   int32_t n_regions;
   const int64_t* start0;
@@ -388,6 +401,13 @@ typedef struct {
 } lcr_region_list;
 int lcr_discover_regions(lcr_ctx*, int32_t mem, int32_t n_reads, const int32_t* ref_start, const int32_t* ref_end,
                          int64_t contig_len, lcr_region_list* out);
+/* The same with longcallR's --truncation / --truncation-coverage (default 200000).  truncation == 0 ignores the cap
+ * and is exactly lcr_discover_regions (which is this call with 0, 0, NULL).  *n_truncated (may be NULL): the
+ * columns whose depth exceeds the cap, 0 when truncation is off.  The depth vector stays on the device; the host
+ * receives per-island arrays only. */
+int lcr_discover_regions_truncated(lcr_ctx*, int32_t mem, int32_t n_reads, const int32_t* ref_start, const int32_t* ref_end,
+                                   int64_t contig_len, int32_t truncation, uint32_t truncation_coverage, lcr_region_list* out,
+                                   int64_t* n_truncated);
 
 /* ---- BGZF / BAM decode -> lcr_reads on the host -------------------------------------------
  * Replaces the rust-htslib IndexedReader calls of util.rs:636-691 and fragment.rs:19-59 (and the read pass of

@@ -50,6 +50,7 @@ class Engine:
         self.params = params if params is not None else _abi.make_params()
         self._sites = None   # device tensors of the last import_external_candidates: its kernels read them after the call returns
         self._keep = None
+        self.last_truncated_columns = 0   # columns above the cap of the last discover_regions(truncation=True)
         if timing:
             self.lib.lcr_enable_timing(self.h, 1)
             if timing is not True:   # an iterable of _abi.K_* : only these kernel groups get their two event records per call
@@ -119,13 +120,21 @@ class Engine:
         self._chk(self.lib.lcr_bind_batch(self.h, int(slot)), "lcr_bind_batch")
         return self
 
-    def discover_regions(self, ref_start, ref_end, contig_len):
-        """find_isolated_regions_with_depth (util.rs:236-332) for one contig -> [(start0, len, max_cov)]."""
+    def discover_regions(self, ref_start, ref_end, contig_len, truncation=False, truncation_coverage=200000):
+        """find_isolated_regions_with_depth (util.rs:236-332) for one contig -> [(start0, len, max_cov)].
+        truncation / truncation_coverage: longcallR --truncation / --truncation-coverage -- a column deeper than the cap ends a
+        region like an uncovered one (include/lcr.h).  last_truncated_columns holds the number of such columns of the last call
+        (0 with truncation off)."""
+        if not 0 <= int(truncation_coverage) < 1 << 32:
+            raise ValueError("truncation_coverage must be in [0, 2^32), got %r" % (truncation_coverage,))
         rs = np.ascontiguousarray(ref_start, dtype=np.int32)
         re_ = np.ascontiguousarray(ref_end, dtype=np.int32)
         o = _abi.LcrRegionList()
-        self._chk(self.lib.lcr_discover_regions(self.h, _abi.LCR_MEM_HOST, int(rs.size), rs.ctypes.data, re_.ctypes.data,
-                                                int(contig_len), C.byref(o)), "lcr_discover_regions")
+        nt = C.c_int64(0)
+        self._chk(self.lib.lcr_discover_regions_truncated(self.h, _abi.LCR_MEM_HOST, int(rs.size), rs.ctypes.data, re_.ctypes.data,
+                                                          int(contig_len), 1 if truncation else 0, int(truncation_coverage), C.byref(o),
+                                                          C.byref(nt)), "lcr_discover_regions_truncated")
+        self.last_truncated_columns = int(nt.value)
         return list(zip(_view(o.start0, np.int64, o.n_regions).tolist(), _view(o.len, np.int32, o.n_regions).tolist(),
                         _view(o.max_cov, np.uint32, o.n_regions).tolist()))
 

@@ -153,14 +153,16 @@ def passes_filter(r, min_mapq=20, min_read_length=500, divergence=0.5):
     return True
 
 
-def discover_regions(recs, ref_id, ref_len):
-    """util.rs:236-332 (no truncation) on the host: coverage islands as (start0, len, max_cov).
+def discover_regions(recs, ref_id, ref_len, truncation=False, truncation_coverage=200000):
+    """util.rs:236-332 on the host: coverage islands as (start0, len, max_cov).
 
     The reference emits 1-based [start, end) = [first0+1, last0+2); we return the 0-based column
-    window (start0=first0, len=last0-first0+1).  As in the reference, a single-column island is not
-    emitted on its own: it stays pending and starts the region that ends with the next island
-    (cursors and max_coverage are only reset when a region is emitted).  `lcr_discover_regions` is the
-    GPU version of the same function.
+    window (start0=first0, len=last0-first0+1).  A column breaks a region when its depth is 0 or, with
+    `truncation`, above `truncation_coverage` (longcallR --truncation / --truncation-coverage).  As in the
+    reference, a single-column island is not emitted on its own: it stays pending and starts the region that
+    ends with the next island (cursors and max_coverage are only reset when a region is emitted), and
+    max_coverage is taken from every column since the last emission, breaks included -- up to and with the
+    break at which the region is emitted.  `lcr_discover_regions_truncated` is the GPU version of the same function.
     """
     diff = np.zeros(ref_len + 1, dtype=np.int64)
     for r in recs:
@@ -171,10 +173,13 @@ def discover_regions(recs, ref_id, ref_len):
         diff[min(e, ref_len)] -= 1
     depth = np.cumsum(diff[:-1])
     cov = depth > 0
+    if truncation:
+        cov &= depth <= truncation_coverage
     edges = np.flatnonzero(np.diff(np.concatenate(([0], cov.view(np.int8), [0]))))
-    out, pend, running = [], -1, 0
-    for s, e in zip(edges[0::2], edges[1::2]):  # island [s, e)
-        running = max(running, int(depth[s:e].max()))
+    out, pend, running, seen = [], -1, 0, 0     # seen: the columns max_coverage has taken so far
+    for s, e in zip(edges[0::2], edges[1::2]):  # island [s, e); column e (if any) is the break that closes it
+        running = max(running, int(depth[seen:e + 1].max()))
+        seen = int(e) + 1
         if pend < 0:
             pend = int(s)
         if e - 1 > pend:

@@ -1244,7 +1244,14 @@ int lcr_get_downsample(lcr_ctx* c, lcr_downsample_info* out) {
 
 int lcr_discover_regions(lcr_ctx* c, int32_t mem, int32_t n_reads, const int32_t* ref_start, const int32_t* ref_end,
                          int64_t contig_len, lcr_region_list* out) {
+  return lcr_discover_regions_truncated(c, mem, n_reads, ref_start, ref_end, contig_len, 0, 0, out, nullptr);
+}
+
+int lcr_discover_regions_truncated(lcr_ctx* c, int32_t mem, int32_t n_reads, const int32_t* ref_start, const int32_t* ref_end,
+                                   int64_t contig_len, int32_t truncation, uint32_t truncation_coverage, lcr_region_list* out, int64_t* n_truncated) {
   if (!c || !out || n_reads < 0 || contig_len < 0 || contig_len > 0x7FFFFFF0ll) return LCR_E_ARG;
+  if (n_truncated) *n_truncated = 0;
+  const uint32_t cap = truncation ? truncation_coverage : UINT32_MAX;   // util.rs:294-296: depth > cap breaks a region like depth == 0
   HIPCHK(c, hipSetDevice(c->device));
   c->rl_start0.clear(); c->rl_len.clear(); c->rl_max.clear();
   out->n_regions = 0; out->start0 = nullptr; out->len = nullptr; out->max_cov = nullptr;
@@ -1281,31 +1288,40 @@ int lcr_discover_regions(lcr_ctx* c, int32_t mem, int32_t n_reads, const int32_t
   launch_scan_i32(c->scan_tmp, (const int32_t*)c->rd_diff.p, c->rd_ex.as<int32_t>(), (int32_t)nd, nullptr, c->stream);
   const int32_t nb = (int32_t)((contig_len + 1023) / 1024);
   HIPCHK(c, c->rd_cnt.reserve(((size_t)nb + 1) * 4)); HIPCHK(c, c->rd_off.reserve(((size_t)nb + 2) * 4));
-  launch_k5_bounds(false, c->rd_ex.as<int32_t>(), contig_len, nb, c->rd_cnt.as<int32_t>(), nullptr, nullptr, nullptr, c->stream);
+  // rd_off: nb offsets, [nb] the number of islands, [nb + 1] the columns above the cap (counted only while truncation is on)
+  uint32_t* d_trunc = truncation ? c->rd_off.as<uint32_t>() + nb + 1 : nullptr;
+  if (d_trunc) HIPCHK(c, hipMemsetAsync(d_trunc, 0, 4, c->stream));
+  launch_k5_bounds(false, c->rd_ex.as<int32_t>(), contig_len, cap, nb, c->rd_cnt.as<int32_t>(), nullptr, nullptr, nullptr, nullptr, 0, d_trunc, c->stream);
   launch_scan_i32(c->scan_tmp, c->rd_cnt.as<int32_t>(), c->rd_off.as<int32_t>(), nb, c->rd_off.as<int32_t>() + nb, c->stream);
-  int32_t n_isl = 0;
-  HIPCHK(c, hipMemcpyAsync(&n_isl, c->rd_off.as<int32_t>() + nb, 4, hipMemcpyDeviceToHost, c->stream));
+  int32_t tot[2] = {0, 0};      // islands, columns above the cap
+  HIPCHK(c, hipMemcpyAsync(tot, c->rd_off.as<int32_t>() + nb, d_trunc ? 8 : 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
+  const int32_t n_isl = tot[0];
+  if (n_truncated) *n_truncated = (int64_t)(uint32_t)tot[1];
   if (n_isl == 0) return LCR_OK;
-  HIPCHK(c, c->rd_s.reserve((size_t)n_isl * 4)); HIPCHK(c, c->rd_e.reserve((size_t)n_isl * 4)); HIPCHK(c, c->rd_max.reserve((size_t)n_isl * 4));
-  launch_k5_bounds(true, c->rd_ex.as<int32_t>(), contig_len, nb, nullptr, c->rd_off.as<int32_t>(), c->rd_s.as<int32_t>(), c->rd_e.as<int32_t>(), c->stream);
-  launch_k5_island_max(c->rd_ex.as<int32_t>(), c->rd_s.as<int32_t>(), c->rd_e.as<int32_t>(), n_isl, c->rd_max.as<uint32_t>(), c->stream);
+  const int32_t n_keys = 2 * n_isl + 1;     // (n_isl <= window / 2 + 1 < 2^30)
+  HIPCHK(c, c->rd_s.reserve((size_t)n_isl * 4)); HIPCHK(c, c->rd_e.reserve((size_t)n_isl * 4)); HIPCHK(c, c->rd_max.reserve((size_t)n_keys * 4));
+  HIPCHK(c, hipMemsetAsync(c->rd_max.p, 0, (size_t)n_keys * 4, c->stream));
+  launch_k5_bounds(true, c->rd_ex.as<int32_t>(), contig_len, cap, nb, nullptr, c->rd_off.as<int32_t>(), c->rd_s.as<int32_t>(), c->rd_e.as<int32_t>(),
+                   c->rd_max.as<uint32_t>(), n_keys, nullptr, c->stream);
   std::vector<int32_t> hs(n_isl), he(n_isl);
-  std::vector<uint32_t> hm(n_isl);
+  std::vector<uint32_t> hm(n_keys);
   HIPCHK(c, hipMemcpyAsync(hs.data(), c->rd_s.p, (size_t)n_isl * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(he.data(), c->rd_e.p, (size_t)n_isl * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hm.data(), c->rd_max.p, (size_t)n_isl * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hm.data(), c->rd_max.p, (size_t)n_keys * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
   // util.rs:287-330: cursors and max_coverage are reset only when a region is emitted, and a region is
   // emitted only if region_end > region_start: a single-column island stays pending and becomes the
-  // start of the region that ends with the next island (the gap between them included).
+  // start of the region that ends with the next island (the gap between them included).  max_coverage runs over
+  // every column since the last emission, breaks included: the breaks in front of the island (hm[2 i]), then the
+  // island and the break that closes it (hm[2 i + 1]) -- the column at which the reference emits.
   uint32_t running = 0;
   int64_t pend = -1;
   for (int i = 0; i < n_isl; i++) {
     hs[i] += (int32_t)w_lo; he[i] += (int32_t)w_lo;   // back to contig positions
-    running = std::max(running, hm[i]);
+    running = std::max(running, std::max(hm[2 * i], hm[2 * i + 1]));
     if (pend < 0) pend = hs[i];
     if ((int64_t)he[i] > pend) {
       c->rl_start0.push_back(pend); c->rl_len.push_back((int32_t)(he[i] - pend + 1)); c->rl_max.push_back(running);

@@ -255,9 +255,11 @@ void launch_scan_i32_to_i64(DevBuf& tmp, const int32_t* in, int64_t* out_excl, i
 
 void launch_k5_span_window(const int32_t* ref_start, const int32_t* ref_end, int32_t n, int64_t contig_len, int32_t* out /* {INT_MAX, 0} */, hipStream_t s);
 void launch_k5_span_diff(const int32_t* ref_start, const int32_t* ref_end, int32_t n, int64_t contig_len, int64_t lo /* first position of diff */, uint32_t* diff, hipStream_t s);
-void launch_k5_bounds(bool write, const int32_t* ex, int64_t contig_len, int32_t n_blocks, int32_t* blk_cnt, const int32_t* blk_off,
-                      int32_t* starts, int32_t* ends, hipStream_t s);
-void launch_k5_island_max(const int32_t* ex, const int32_t* starts, const int32_t* ends, int32_t n_islands, uint32_t* maxcov, hipStream_t s);
+// cap: columns deeper than it break a region like uncovered ones (UINT32_MAX: none).  Count pass (write = false): blk_cnt, and *n_trunc (zeroed, or
+// nullptr) += columns above the cap.  Write pass: starts / ends and imax (n_keys = 2 n_islands + 1, zeroed): [2 j + 1] island j and its closing column,
+// [2 j] the breaks in front of island j from behind the previous closing column on.
+void launch_k5_bounds(bool write, const int32_t* ex, int64_t contig_len, uint32_t cap, int32_t n_blocks, int32_t* blk_cnt, const int32_t* blk_off,
+                      int32_t* starts, int32_t* ends, uint32_t* imax, int32_t n_keys, uint32_t* n_trunc, hipStream_t s);
 
 // device helpers shared by kernels -------------------------------------------------------------
 #ifdef __HIPCC__

@@ -5,7 +5,8 @@ Host orchestration only; the work is done behind the C ABI (include/lcr.h).  It 
 the five hot-path calls, with one context per GPU instead of one rayon task per region:
 
   util.rs:214-234 load_reference / parse_fai                 -> load_reference / parse_fai below
-  util.rs:558-600 extract_isolated_regions_parallel          -> lcr_bam_spans + lcr_discover_regions per contig
+  util.rs:558-600 extract_isolated_regions_parallel          -> lcr_bam_spans + lcr_discover_regions_truncated per contig
+                                                                (--truncation / --truncation-coverage included)
   thread.rs:77-221 the per-region closure                    -> one lcr_load_batch + pileup / candidates /
                                                                 fragments / phase per contig (all its regions)
   thread.rs:223-305 VCF header + records                     -> write_vcf (records from vcf.format_records)
@@ -13,7 +14,7 @@ the five hot-path calls, with one context per GPU instead of one rayon task per 
 
   thread.rs:70-74,107-116 user-provided candidates (-v)   -> vcf.read_sites once + lcr_import_candidates per chunk
 
-Not here (out of scope): gene annotation / exon filter, region truncation, the somatic model.  Records are written in contig order of the .fai and position order inside
+Not here (out of scope): gene annotation / exon filter, the somatic model.  Records are written in contig order of the .fai and position order inside
 a contig (the reference writes them in region-completion order, thread.rs:216-221: compare as a set)."""
 import os
 
@@ -107,7 +108,7 @@ def _gather_names(name_off, blob, rows):
 
 def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs=None, device=0, threads=0, seed=2025,
         read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None,
-        downsample=False, downsample_depth=10000, downsample_seed=2025, **param_overrides):
+        downsample=False, downsample_depth=10000, downsample_seed=2025, truncation=False, truncation_coverage=200000, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -122,9 +123,18 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     downsample / downsample_depth: longcallR --downsample / --downsample-depth (thread.rs:144-151): a region with at least
     downsample_depth fragments is phased on a sample of that many (lcr_set_downsample, include/lcr.h; the sample is the project's
     counter-based one, not StdRng's); the last post-phase round still assigns every read.  Off by default.  It needs a positive
-    read_assign_cutoff (the presets' is 0.0: pass e.g. read_assign_cutoff=1e-6), ValueError otherwise."""
+    read_assign_cutoff (the presets' is 0.0: pass e.g. read_assign_cutoff=1e-6), ValueError otherwise.
+    truncation / truncation_coverage: longcallR --truncation / --truncation-coverage (util.rs:294-296): a column deeper than
+    truncation_coverage ends a region like an uncovered one, so an over-deep stretch is neither piled up nor phased and its flanks
+    become regions of their own (a read that spans it is listed in both; the phased BAM keeps the reads contained in a region).
+    Adds the stat truncated_columns (columns above the cap, summed over contigs).  Off by default; truncation_coverage outside
+    [0, 2^32) is a ValueError."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
+    truncation = bool(truncation)
+    if isinstance(truncation_coverage, bool) or int(truncation_coverage) != truncation_coverage or not 0 <= int(truncation_coverage) < 1 << 32:
+        raise ValueError("truncation_coverage must be an integer in [0, 2^32) (the reference's u32), got %r" % (truncation_coverage,))
+    truncation_coverage = int(truncation_coverage)
     params = _abi.make_params(preset, seed=seed, **param_overrides)
     downsample = bool(downsample) and downsample_depth > 0
     if downsample and not params.read_assign_cutoff > 0:    # (lcr_phase would answer LCR_E_ARG in the first chunk: include/lcr.h)
@@ -155,6 +165,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         sites = vcf.read_sites(input_vcf)      # vcf.rs:400-462, once for the whole run (thread.rs:70-74)
         stats["input_sites"] = sum(int(v[0].size) for v in sites.values())
         stats["imported_sites"] = 0
+    if truncation:
+        stats["truncated_columns"] = 0
     no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
     # Every engine is a long-lived worker with the ASYNCHRONOUS phase stage (lcr_ctx_set_async_phase, include/lcr.h): a chunk is uploaded
@@ -225,7 +237,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             rs, re_ = nb.spans(rid, **flt)
             if rs.size == 0:
                 continue
-            regions = scout.discover_regions(rs, re_, length)     # util.rs:236-332
+            regions = scout.discover_regions(rs, re_, length, truncation, truncation_coverage)     # util.rs:236-332
+            if truncation:
+                stats["truncated_columns"] += scout.last_truncated_columns
             if not regions:
                 continue
             ref = refs[name]

@@ -3,6 +3,7 @@
 
   python tools/run_pipeline.py -b reads.bam -f ref.fa -o out.vcf [--out-bam phased.bam] [-p hifi-masseq] [-c chr20,chr21]
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
+                                 [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
 """
 import argparse
 import json
@@ -27,12 +28,15 @@ def main():
     ap.add_argument("-v", "--input-vcf", help="user-provided candidate sites (VCF / .vcf.gz with GT): phased instead of called")
     ap.add_argument("--downsample", action="store_true", help="phase regions of at least --downsample-depth fragments on a sample of that many (needs --read-assign-cutoff > 0)")
     ap.add_argument("--downsample-depth", type=int, default=10000)
+    ap.add_argument("--truncation", action="store_true", help="end a region at columns deeper than --truncation-coverage, as at uncovered ones")
+    ap.add_argument("--truncation-coverage", type=int, default=200000)
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     extra = {} if a.read_assign_cutoff is None else dict(read_assign_cutoff=a.read_assign_cutoff)
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
                       device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf,
-                      downsample=a.downsample, downsample_depth=a.downsample_depth, **extra)
+                      downsample=a.downsample, downsample_depth=a.downsample_depth,
+                      truncation=a.truncation, truncation_coverage=a.truncation_coverage, **extra)
     print(json.dumps(st))
 
 
