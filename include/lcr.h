@@ -220,7 +220,12 @@ int lcr_host_unregister(void* p);
 
 /* The four stage calls below queue their kernels on the context's stream and return as soon as the host has what it
  * needs to go on (error verdicts, sizes); the last kernels of a stage may still be running.  Later stage calls queue
- * behind them; the lcr_get_* calls and lcr_ctx_sync wait.  An error a stage can raise is always raised by that call. */
+ * behind them; the lcr_get_* calls and lcr_ctx_sync wait.  An error a stage can raise is always raised by that call.
+ * A call refused on its arguments or on the call order (LCR_E_ARG / LCR_E_STATE in front of any work) changes nothing.  A call that
+ * fails after it has begun to rewrite what the later stages read (lcr_pileup: LCR_E_CIGAR, unsorted reads, LCR_E_DEVICE; any stage:
+ * a HIP or allocation error) leaves the context at the stage in front of it: a failed lcr_pileup at the bound batch, a failed
+ * candidate stage at the pileup, a failed lcr_fragments at the candidate stage.  The stage calls and getters behind that point return
+ * LCR_E_STATE ("... before lcr_...") until the failed stage has been run again with success; they never answer from an earlier pass. */
 /* replaces Profile::fill_data_into_freq_vec (util.rs:621-949); thread.rs:93-103.
  * Returns LCR_E_CIGAR for an unknown CIGAR op or a CIGAR inconsistent with l_seq / soft clips. */
 int lcr_pileup(lcr_ctx*, const lcr_params*);

@@ -128,12 +128,6 @@ struct K0Hdr {           // what an op needs to know about its read (48 bytes, L
   int32_t reb, rel_pos;  // seq_len - trailing soft clip (CIGAR vs l_seq check); pos - region start
 };
 
-struct K0Ctl {           // control block in HBM behind the tile counters (cleared with them, fetched with one copy)
-  unsigned int pool_top, n_items, n_recs;
-  int32_t error;
-  unsigned int desc_top, pad_[3];
-};
-
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -504,20 +498,20 @@ __global__ void __launch_bounds__(LCR_BLOCK) k0_desc_bin(const K0Ctl* __restrict
     for (int e = 0; e < ne; e++) dst[e] = make_uint2(d.x + 16u * (unsigned int)e, min(16u, d.y - 16u * (unsigned int)e));
   }
 }
-void launch_k0_desc_bin(const void* ctl, const unsigned int* acct, unsigned int desc_sub, const uint32_t* desc_tile, const void* desc_val,
+void launch_k0_desc_bin(const K0Ctl* ctl, const unsigned int* acct, unsigned int desc_sub, const uint32_t* desc_tile, const void* desc_val,
                         const int32_t* chunk_off, int32_t* cursor, void* sorted, int32_t n_blocks_hint, hipStream_t s) {
   const int per = std::max(1, std::min((n_blocks_hint + K0_ACC - 1) / K0_ACC, 32));
-  hipLaunchKernelGGL(k0_desc_bin, dim3(per * K0_ACC), dim3(LCR_BLOCK), 0, s, (const K0Ctl*)ctl, acct, desc_sub, desc_tile, (const uint2*)desc_val,
+  hipLaunchKernelGGL(k0_desc_bin, dim3(per * K0_ACC), dim3(LCR_BLOCK), 0, s, ctl, acct, desc_sub, desc_tile, (const uint2*)desc_val,
                      chunk_off, cursor, (uint2*)sorted);
 }
 
 void launch_k0_ops(const BatchView& b, const ReadBin* rb, const int32_t* blk_first_read, uint64_t cig0, uint32_t n_ops, int ont, int D,
-                   int32_t n_tiles, int32_t* tile_fill, int32_t* tile_nchunks, int32_t* tile_ndiff, void* ctl, unsigned int* acct,
+                   int32_t n_tiles, int32_t* tile_fill, int32_t* tile_nchunks, int32_t* tile_ndiff, K0Ctl* ctl, unsigned int* acct,
                    unsigned int pool_sub, unsigned long long* recs, unsigned int desc_sub, uint32_t* desc_tile, void* desc_val, void* read_scan,
                    hipStream_t s) {
   if (b.n_reads == 0) return;
-  if (n_ops == 0) { hipLaunchKernelGGL(k0_empty_reads, dim3((b.n_reads + LCR_BLOCK - 1) / LCR_BLOCK), dim3(LCR_BLOCK), 0, s, b, rb, (K0Ctl*)ctl); return; }
+  if (n_ops == 0) { hipLaunchKernelGGL(k0_empty_reads, dim3((b.n_reads + LCR_BLOCK - 1) / LCR_BLOCK), dim3(LCR_BLOCK), 0, s, b, rb, ctl); return; }
   const int opb = launch_k0_opb();
   hipLaunchKernelGGL(k0_ops<K0_OPT>, dim3((n_ops + opb - 1) / opb), dim3(K0_THREADS), 0, s, b, rb, blk_first_read, cig0, n_ops, ont, D, n_tiles,
-                     tile_fill, tile_nchunks, tile_ndiff, (K0Ctl*)ctl, acct, pool_sub, recs, desc_sub, desc_tile, (uint2*)desc_val, (int2*)read_scan);
+                     tile_fill, tile_nchunks, tile_ndiff, ctl, acct, pool_sub, recs, desc_sub, desc_tile, (uint2*)desc_val, (int2*)read_scan);
 }

@@ -552,7 +552,7 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
 
 // Record-free tiles (uncovered, or inside introns only): every plane is 0 except the intron plane, which is the number of
 // introns that cover the whole tile.  Three quarters of the tiles of a spliced data set and 75 % of the plane bytes
-// are like this: a pure store stream that no stage reads (lcr_api.hip, `planes_dense`), so lcr_pileup does not queue it; it runs
+// are like this: a pure store stream that no stage reads (lcr_ctx.h, `planes_dense`), so lcr_pileup does not queue it; it runs
 // when the planes themselves are asked for (lcr_get_columns), once per pileup, over the tile order that pileup left.  Small workgroups
 // without LDS (inside k1_pileup's 512-thread, 52 KB workgroups -- three per CU -- the same stores ran at 3.7 TB/s; hipMemset reaches
 // 6.8 on this part).
@@ -600,7 +600,7 @@ __global__ void __launch_bounds__(128) k1_empty_tiles(BatchView b, const int32_t
 // tiles' offsets in the entry list (exclusive scan of their entry counts), and K0's accounting totals.
 // Two multi-block kernels (a single workgroup spent 60 us on load latency): pass A = class histogram + block sums,
 // pass B = offsets + scatter.  Class 32 = record-free tiles (three quarters of them), ranked by ballots.  Nothing behind
-// the tile passes writes a record-free tile's planes: pass A counts their columns for the stage's byte accounting (word 5
+// the tile passes writes a record-free tile's planes: pass A counts their columns for the stage's byte accounting (empty_cols
 // of the control block, with the words the host waits for anyway), pass B stores the 0 of their survivor count when the
 // tally's epilogue takes the filter pass (flt_count).
 #define TS_TILES 1024   // tiles per workgroup (256 threads x 4)
@@ -618,7 +618,7 @@ __device__ __forceinline__ int tile_class(int fill) { return fill > 0 ? __clz(fi
 __global__ void __launch_bounds__(256) k1_tiles_a(const int32_t* __restrict__ tile_fill, const int32_t* __restrict__ tile_ndiff,
                                                    const int32_t* __restrict__ tile_nent, int32_t n_tiles, TileScanTmp* __restrict__ tmp,
                                                    int2* __restrict__ blk_sum, const unsigned int* __restrict__ acct, int32_t n_acct,
-                                                   unsigned int* __restrict__ ctl, unsigned int* __restrict__ host_ctl,
+                                                   K0Ctl* __restrict__ ctl, K0Ctl* __restrict__ host_ctl,
                                                    const int32_t* __restrict__ tile_region, const int32_t* __restrict__ tile_col0,
                                                    const int32_t* __restrict__ region_len) {
   __shared__ int hist[33], ws[4][2], ecol_s;
@@ -629,9 +629,9 @@ __global__ void __launch_bounds__(256) k1_tiles_a(const int32_t* __restrict__ ti
     it = wave_incl_scan(it); rc = wave_incl_scan(rc);
     for (int o = 32; o > 0; o >>= 1) { pt = max(pt, __shfl_xor(pt, o, 64)); dt = max(dt, __shfl_xor(dt, o, 64)); }
     if (lane == 63) {
-      ctl[0] = (unsigned int)pt; ctl[1] = (unsigned int)it; ctl[2] = (unsigned int)rc; ctl[4] = (unsigned int)dt;
-      // the same five words straight into the host's pinned block (ctl[3] = K0's verdict): no copy in the queue in front of k1_tiles_b
-      if (host_ctl) { host_ctl[0] = (unsigned int)pt; host_ctl[1] = (unsigned int)it; host_ctl[2] = (unsigned int)rc; host_ctl[3] = ctl[3]; host_ctl[4] = (unsigned int)dt; }
+      ctl->pool_top = (unsigned int)pt; ctl->n_items = (unsigned int)it; ctl->n_recs = (unsigned int)rc; ctl->desc_top = (unsigned int)dt;
+      // the same five words straight into the host's pinned block (error = K0's verdict): no copy in the queue in front of k1_tiles_b
+      if (host_ctl) { host_ctl->pool_top = (unsigned int)pt; host_ctl->n_items = (unsigned int)it; host_ctl->n_recs = (unsigned int)rc; host_ctl->error = ctl->error; host_ctl->desc_top = (unsigned int)dt; }
     }
   }
   if (tid < 33) hist[tid] = 0;
@@ -659,8 +659,8 @@ __global__ void __launch_bounds__(256) k1_tiles_a(const int32_t* __restrict__ ti
     __threadfence();
     if (atomicAdd(&tmp->done_a, 1) == (int)gridDim.x - 1) {
       const unsigned int total = (unsigned int)atomicAdd(&tmp->empty_cols, 0);
-      ctl[5] = total;
-      if (host_ctl) host_ctl[5] = total;
+      ctl->empty_cols = total;
+      if (host_ctl) host_ctl->empty_cols = total;
     }
   }
 }
@@ -750,7 +750,7 @@ void launch_k1_empty_tiles(const BatchView& b, const int32_t* tile_region, const
 // the tile passes alone (the host fetches K0's control block behind pass A, before the rest is queued)
 size_t launch_k1_tiles_tmp_words(int32_t n_tiles) { return 88 + 2 * (size_t)((n_tiles + TS_TILES - 1) / TS_TILES) + 8; }
 void launch_k1_tiles_a(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp /* zeroed */,
-                       const unsigned int* acct, int32_t n_acct, unsigned int* ctl, unsigned int* host_ctl, const int32_t* tile_region,
+                       const unsigned int* acct, int32_t n_acct, K0Ctl* ctl, K0Ctl* host_ctl, const int32_t* tile_region,
                        const int32_t* tile_col0, const int32_t* region_len, hipStream_t s) {
   const int nb = (n_tiles + TS_TILES - 1) / TS_TILES;
   hipLaunchKernelGGL(k1_tiles_a, dim3(nb), dim3(256), 0, s, tile_fill, tile_ndiff, tile_nent, n_tiles, (TileScanTmp*)tmp, (int2*)(tmp + 88), acct, n_acct, ctl, host_ctl,

@@ -1,0 +1,183 @@
+// lcr_ctx.h — the context behind the C ABI (include/lcr.h) and what its host units share: the stage state, timers, uploads, the settle
+// functions.  Private to lcr_api.hip (lifecycle, cache, fills, debug switches, phase entry, region discovery), lcr_batch.hip (binding and
+// upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns) and lcr_calls.hip (candidate, import and fragment stages with their getters).
+#pragma once
+#include <algorithm>
+#include <cstring>
+
+#include "lcr_dev.h"
+#include "lcr_phase_host.h"
+
+// How far the bound batch has come.  Every driver asks for the stage it reads (stage >= X) and moves the value with rewind_to() /
+// by assignment at its successful end: nothing else says which buffers hold what.
+enum Stage { ST_NONE, ST_LOADED, ST_PILED, ST_CALLED, ST_FRAGGED, ST_PHASED };
+
+struct lcr_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  std::string err;
+  Stage stage = ST_NONE;
+
+  // bound batch
+  BatchView bv{};
+  int64_t n_cols = 0, n_bases = 0, n_cigar = 0;
+  int32_t n_tiles = 0;
+  std::vector<int64_t> h_start0, h_col_off;
+  std::vector<int32_t> h_len, h_read_begin, h_region_first_tile;
+  DevBuf in_[16];  // device copies of host inputs (LCR_MEM_HOST)
+  // asynchronous input path (lcr_load_batch_async / lcr_bind_batch): two staging slots, filled on an upload stream
+  struct UploadSlot { DevBuf buf[16]; hipEvent_t ev = nullptr; bool filled = false; lcr_reads rd{}; lcr_regions rg{}; } up[2];
+  hipStream_t up_stream = nullptr;
+  int bound_slot = -1;
+  bool bound_host = false;   // the bound batch was copied into in_[] (LCR_MEM_HOST)
+  DevBuf scan_tmp, read_region, read_bin, read_rend, tile_region, tile_col0, first_tile, k0_tile_fill, k0_items, tile_nbase, tile_order;
+  DevBuf desc_tile, desc_val, chunks, chunk_off;   // K0's chunk descriptors, the same sorted by tile, their per-tile offsets
+  DevBuf blk_first_read, read_scan, cig_compact, cig_off_new, cig_new_off32;   // K0 op blocks (k0_ops.hip)
+  uint64_t cig0 = 0;      // index of the batch's first op in bv.cigar
+  uint32_t n_ops = 0;     // ops of the batch (one flat op space)
+  int64_t n_items = 0;
+
+  // K1
+  // lcr_pileup writes the planes of the tiles that hold records (K0's fill counter > 0) and nothing else: a record-free tile's planes are
+  // constants -- 0, the intron plane tile_nbase[tile] -- and what lies at its columns after lcr_pileup is whatever an earlier batch left
+  // there.  planes_dense: the constants have been stored for the current pileup (planes_materialise: k1_empty_tiles over the tile order,
+  // tile_nbase and n_full of that pileup -- tile_order / tile_nbase / k0_tile_fill are rewritten by lcr_pileup only, tile_region / tile_col0
+  // by lcr_load_batch only, and both clear the flag: rewind_to).  Who reads c->planes, and why a tile that was never written is safe with each:
+  //   k1_pileup's fused filter epilogue   runs in the workgroups of tiles with records, on their LDS counters;
+  //   k1_zonefix / _ends / _slots         atomicSub at the column of an aligned base inside the region: that base's M record is in the tile;
+  //   k2_filter (eval_column)             leaves at tile_fill == 0 with tile_count = 0;
+  //   k2_compact (eval_column, ts planes) leaves at tile_count == 0 -- k2_filter's 0, or k1_tiles_b's on the fused path;
+  //   k2_hist / k2_hist_tiles / k2_gt, K3, K4   never touch the planes (k2_hist_tiles walks K0's records of tiles with tile_count > 0);
+  //   k2_import_emit                      takes the four counts of a site in a tile with tile_fill == 0 as 0 without loading them;
+  //   lcr_get_columns                     the one reader of every column: calls planes_materialise first.
+  // planes_materialise itself (k1_empty_tiles) reads, beside those tables, bv.error_flag (K0Ctl::error in k0_tile_fill, 0 after a pileup that returned
+  // LCR_OK) and the region arrays bv.len / bv.col_off: the context's copies of a host batch, the caller's arrays of a LCR_MEM_DEVICE batch, which
+  // therefore have to stay alive for lcr_get_columns as for every stage call (include/lcr.h).
+  // lcr_debug_set("poison_planes", 1) fills the whole buffer with 0xA5 in front of every pileup: a reader that looks at an unwritten tile
+  // then differs from a run without it, whatever the previous batch was (tests/test_sparse_planes.py).
+  bool planes_dense = false;
+  int dbg_poison_planes = 0;
+  DevBuf planes;
+  DevParams dp{};
+  int32_t pile_platform = -1; uint32_t pile_dist_to_end = 0;   // lcr_pileup's platform / dist_to_end: lcr_candidates must be called with the same
+  float sor_thr = -1.f;
+  HostBuf h_planes;
+  HostBuf h_nnz;              // pinned: first entry of every region of the fragment matrix, [ng] = entry count (lcr_fragments -> frag_settle)
+  DevBuf region_e_off, frag_tmp_col, frag_tmp_val;
+  // one of each per context (lcr_ctx_create): K0's verdict, the survivors' number, the candidate stage's host copies, the entry counts,
+  // the verdict on device-resident import sites
+  hipEvent_t ev_ctl = nullptr, ev_sv = nullptr, ev_cand = nullptr, ev_nnz = nullptr, ev_imp = nullptr;
+  int32_t sv_cap_guess = 0;   // lcr_candidates: survivors the buffers are sized for before their number is known (the last call's + a quarter; 0: wait first)
+  bool nnz_pending = false, cand_pending = false;
+  HostBuf h_order;      // pinned: k0_pack raises it when a region's reads are not sorted by position
+  static constexpr int UP_LANES = 4;   // staging lanes of pageable host uploads (upload_bytes): two page-locked 8 MB buffers + events each
+  HostBuf h_up[2 * UP_LANES]; hipEvent_t ev_up[2 * UP_LANES] = {}; bool up_busy[2 * UP_LANES] = {};
+  HostBuf h_stage[4];   // pinned staging of lcr_candidates / lcr_fragments: survivor offsets, candidate records, keep flags, region rows
+
+  // K2
+  bool cand_used = false;   // lcr_phase has rewritten the records' FOR_PHASING bit, variant type and genotype (k4_post.h), which K3 and k4_stage read:
+                            // lcr_fragments / lcr_phase need a fresh candidate stage
+  DevBuf flags, tile_count, tile_off, total, survivors, sv_region_off, hist, cand_tmp, keep;
+  DevBuf hit_cnt, hit_list, ovf_list;   // k2_hist's (read, survivor) hits for K3; the overflow counter sits behind the histograms
+  bool hits_valid = false; int32_t hits_n_sv = 0;
+  int dbg_hist_tiles = 0;   // lcr_debug_set("hist_tiles"): 0 = by survivor density, 1 = the tile form whenever it applies, -1 = never
+  int dbg_spec_compact = 1; // lcr_debug_set("spec_compact"): 0 = lcr_candidates waits for the survivors' number before it queues their compaction
+  int dbg_fuse_filter = 1;  // lcr_debug_set("fuse_filter"): 0 = pass 1 of the candidate filters always by k2_filter (its own pass over the planes)
+  bool flt_fused = false;   // the last lcr_pileup left k2_filter's flags and per-tile counts (ONT presets: no poly-A pass behind the tally)
+  DevParams flt_dp{};       // ... computed with these parameters
+  int dbg_k3_hits = 1;      // lcr_debug_set("k3_hits"): 0 = K3's count pass walks every read's CIGAR itself (the path of batches without hit lists)
+  std::vector<lcr_candidate> h_cand;
+  std::vector<int32_t> h_cand_off;
+  DevBuf d_cand, d_cand_off;
+  DevBuf imp_pos, imp_gt, imp_q, imp_cnt;   // lcr_import_candidates: host sites copied to HBM, sites kept per region
+  HostBuf h_imp_bad;                         // ... verdict of the check of device-resident sites
+
+  // K3
+  uint32_t min_linkers = 1;
+  int32_t n_rows = 0;
+  int64_t nnz = 0;
+  std::vector<int32_t> h_row_region_off;
+  DevBuf region_rows, row_region_off, row_cnt, row_links, row_ptr, col, val;
+  HostBuf h_row_ptr, h_row_read, h_col, h_val, h_row_fp, h_row_links;
+
+  // K4 + post-phase
+  bool res_valid = false;   // lcr_collect_phase: the last lcr_phase's results (host + HBM) are intact -- they outlive lcr_load_batch / lcr_pileup of the next batch
+  int32_t res_ng = 0;
+  int phase_slot = -1;      // staging slot of the batch whose (asynchronous) phase stage may be in flight: -1 = the caller's own device arrays, -2 = in_[] (a host batch)
+  PhaseHost phase;
+  std::vector<int32_t> ld_off, ld_snps;   // lcr_get_ld_blocks
+  // down-sampling: the sticky setting (lcr_set_downsample; 0 = off) and the caller's own sample for the next lcr_phase (lcr_set_downsample_rows)
+  uint32_t ds_depth = 0; uint64_t ds_seed = 0;
+  std::vector<uint8_t> ds_rows; bool ds_rows_set = false;
+
+  // region discovery (N3)
+  DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
+  std::vector<int64_t> rl_start0;
+  std::vector<int32_t> rl_len;
+  std::vector<uint32_t> rl_max;
+
+  // timing
+  bool timing = false;
+  uint32_t timing_mask = 0;   // lcr_debug_set("timing_mask"): bit k = LCR_K_* k is timed; 0 = all of them (every timer is two event records on the stream)
+  hipEvent_t ev[LCR_NKERNELS][2] = {};
+  bool ev_valid[LCR_NKERNELS] = {};
+  int64_t pileup_bytes = 0, stage_bytes = 0;
+};
+
+// Back to stage `to` (no-op above it): a driver calls this at the point where it begins to overwrite what the stages behind `to` read --
+// not at its successful end, so a call that fails part of the way leaves nothing downstream looking valid -- and sets its own stage
+// when it has queued everything.  What belongs to the stages that are dropped goes with them, each rule once:
+inline void rewind_to(lcr_ctx* c, Stage to) {
+  if (c->stage > to) c->stage = to;
+  if (to < ST_PILED) {
+    c->planes_dense = false;   // tile order / tile_nbase / tile tables are rewritten: the stored constants are another pileup's (or batch's)
+    c->flt_fused = false;      // the tally's epilogue has not left this pileup's pass-1 flags yet
+  }
+  if (to < ST_CALLED) {
+    c->hits_valid = false;     // k2_hist's hit lists name the survivors of the candidate stage that is going away
+    c->cand_used = false;      // the records lcr_phase rewrote are replaced by the next candidate stage
+  }
+  if (to < ST_FRAGGED) c->ds_rows_set = false;   // a sample names the rows of ONE fragment stage
+  // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
+  // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
+  // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and
+  // flt_fused across a candidate stage that does not overwrite the flags (lcr_import_candidates: to == ST_PILED).
+}
+
+struct Timer {  // records HIP events on the ctx stream around one kernel
+  lcr_ctx* c; int k;
+  bool on() const { return c->timing && (c->timing_mask == 0 || ((c->timing_mask >> k) & 1u)); }
+  Timer(lcr_ctx* c_, int k_) : c(c_), k(k_) { if (on()) { (void)hipEventRecord(c->ev[k][0], c->stream); } }
+  ~Timer() { if (on()) { (void)hipEventRecord(c->ev[k][1], c->stream); c->ev_valid[k] = true; } }
+};
+
+inline DevParams to_dev(const lcr_params* p, float sor_thr) {
+  DevParams d{};
+  d.ont = p->platform == LCR_PLATFORM_ONT;
+  d.dist_to_end = (int32_t)p->dist_to_end;
+  d.polya_len = (int32_t)p->polya_len;
+  d.min_baseq = p->min_baseq; d.min_depth = p->min_depth; d.max_depth = p->max_depth; d.min_qual = p->min_qual;
+  d.low_cnt_cut = p->low_cnt_cut; d.min_linkers = p->min_linkers; d.use_strand_bias = p->use_strand_bias;
+  d.min_af = p->min_af; d.min_af_intron = p->min_af_intron; d.low_frac_cut = p->low_frac_cut;
+  d.sor_threshold = sor_thr;
+  return d;
+}
+
+// Host -> device copy of a caller's array on a queue of the context (nullptr: its stream); lcr_batch.hip
+int upload_bytes(lcr_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t q = nullptr);
+
+template <class T>
+int upload(lcr_ctx* c, DevBuf& buf, const T* src, size_t n, const T** dst, int mem) {
+  if (mem == LCR_MEM_DEVICE) { *dst = src; return LCR_OK; }
+  HIPCHK(c, buf.reserve(std::max<size_t>(n, 1) * sizeof(T)));
+  if (n) { const int rc = upload_bytes(c, buf.p, src, n * sizeof(T)); if (rc) return rc; }
+  *dst = buf.as<T>();
+  return LCR_OK;
+}
+
+// lcr_phase leaves its kernels in flight on the phase stage's own queues (lcr_phase_host.h): whoever needs its results, or is about
+// to overwrite what it reads / writes, collects them first
+inline int phase_settle(lcr_ctx* c) { return c->phase.settle(&c->err); }
+int cand_settle(lcr_ctx* c);   // the candidate stage's host copies (lcr_calls.hip)
+int frag_settle(lcr_ctx* c);   // lcr_fragments' entry count (lcr_calls.hip)

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <climits>
+#include <cstddef>
 #include <stdint.h>
 
 #include <string>
@@ -155,6 +156,8 @@ struct HostBuf {  // pinned
     return e;
   }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+  // the block as the device sees it: kernels write small results straight into it, no copy in the queue
+  template <class T> hipError_t dev(T** out) const { return hipHostGetDevicePointer((void**)out, p, 0); }
 };
 
 // ---- phasing LUT (fixed point, scale 2^40; DESIGN.md "Decision arithmetic") ----
@@ -162,6 +165,19 @@ struct PhaseLutDev {
   int64_t fe[31], f1e[31];           // log10(eps), log10(1-eps), eps = 10^(-q/10) (q=0 -> q=1)
   int64_t f_homref, f_homvar, f_het0, f_log2;
 };
+
+// K0's control block: in HBM inside lcr_pileup's cleared scratch (PileScratch), and once more in pinned host memory, where k1_tiles_a
+// leaves the host its copy.  k0_ops raises `error` (1 unknown CIGAR op, 2 CIGAR inconsistent with l_seq / soft clips, 3 pool overflow) and
+// every kernel behind it leaves early while it is set; k1_tiles_a fills the other words from K0's accounting slots.
+struct K0Ctl {
+  unsigned int pool_top, n_items, n_recs;   // slots the fullest pool shard asked for; M / D / I / N items; records
+  int32_t error;
+  unsigned int desc_top;                    // descriptors the fullest shard asked for
+  unsigned int empty_cols;                  // columns of the record-free tiles
+  unsigned int pad_[2];
+};
+static_assert(sizeof(K0Ctl) == 32, "K0Ctl is eight words: the host fetches it with one 32-byte copy");
+static_assert(offsetof(K0Ctl, error) == 12, "BatchView::error_flag is word 3 of K0Ctl");
 
 // ---- kernel launchers (defined in the .hip files) ----
 void launch_k0_region_setup(const int64_t* start0, const int32_t* len, const int64_t* col_off, const int32_t* read_begin, int32_t ng,
@@ -183,18 +199,37 @@ void launch_k0_cig_compact(const uint32_t* cigar, const uint64_t* cig_off, const
 int launch_k0_opb();   // ops per K0 workgroup
 void launch_k0_block_reads(const ReadBin* rbin, int32_t nr, uint64_t cig0, int32_t opb, int32_t n_blocks, int32_t* blk_first_read, hipStream_t s);
 void launch_k0_ops(const BatchView& b, const ReadBin* rb, const int32_t* blk_first_read, uint64_t cig0, uint32_t n_ops, int ont, int D,
-                   int32_t n_tiles, int32_t* tile_fill, int32_t* tile_nchunks, int32_t* tile_ndiff, void* ctl, unsigned int* acct /* launch_k0_acct_words() zeroed words */,
+                   int32_t n_tiles, int32_t* tile_fill, int32_t* tile_nchunks, int32_t* tile_ndiff, K0Ctl* ctl, unsigned int* acct /* launch_k0_acct_words() zeroed words */,
                    unsigned int pool_sub /* slots per shard */, unsigned long long* recs, unsigned int desc_sub, uint32_t* desc_tile, void* desc_val /* uint2 */,
                    void* read_scan /* n_reads x int2 scratch */, hipStream_t s);
 int launch_k0_acct_words();
 int launch_k0_acct_slots();
-void launch_k0_desc_bin(const void* ctl, const unsigned int* acct, unsigned int desc_sub, const uint32_t* desc_tile, const void* desc_val,
+void launch_k0_desc_bin(const K0Ctl* ctl, const unsigned int* acct, unsigned int desc_sub, const uint32_t* desc_tile, const void* desc_val,
                         const int32_t* chunk_off, int32_t* cursor /* n_tiles zeroed ints */, void* sorted /* uint2, all shards */, int32_t n_blocks_hint,
                         hipStream_t s);
 size_t launch_k1_tiles_tmp_words(int32_t n_tiles);
+// lcr_pileup's one cleared buffer (lcr_ctx::k0_tile_fill), in 32-bit words from its start: what K0 and the tile passes count into.  The fill
+// counters stay at the start: k2_filter and k2_import_emit take the buffer as their tile_fill.
+struct PileScratch {
+  size_t ctl;     // K0Ctl (behind the n_tiles fill counters and one spare word)
+  size_t ndiff;   // tile-level intron difference array
+  size_t nch;     // chunks per tile
+  size_t cur;     // bin cursors of k0_desc_bin
+  size_t acct;    // K0's accounting slots (launch_k0_acct_words())
+  size_t tmp;     // scratch of the tile passes (TileScanTmp: class counts, cursors, n_full; block sums)
+  size_t words;   // all of it, a multiple of 256 bytes: one fill kernel, not a body and a tail
+};
+inline PileScratch pile_scratch(int32_t n_tiles) {
+  const size_t nt = (size_t)n_tiles;
+  PileScratch L{};
+  L.ctl = nt + 1; L.ndiff = nt + 16; L.nch = L.ndiff + nt + 8; L.cur = L.nch + nt + 8; L.acct = L.cur + nt + 8;
+  L.tmp = L.acct + launch_k0_acct_words();
+  L.words = (L.tmp + launch_k1_tiles_tmp_words(n_tiles) + 63) & ~(size_t)63;
+  return L;
+}
 void launch_k1_tiles_a(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp /* zeroed */,
-                       const unsigned int* acct, int32_t n_acct, unsigned int* ctl, unsigned int* host_ctl /* pinned host block as the device sees it, or nullptr */,
-                       const int32_t* tile_region, const int32_t* tile_col0, const int32_t* region_len /* -> ctl[5] / host_ctl[5]: columns of the record-free tiles */, hipStream_t s);
+                       const unsigned int* acct, int32_t n_acct, K0Ctl* ctl, K0Ctl* host_ctl /* pinned host block as the device sees it, or nullptr */,
+                       const int32_t* tile_region, const int32_t* tile_col0, const int32_t* region_len /* -> empty_cols of both blocks: columns of the record-free tiles */, hipStream_t s);
 void launch_k1_tiles_b(int32_t n_tiles, const int32_t* tile_fill, const int32_t* tile_ndiff, const int32_t* tile_nent, int32_t* tmp,
                        int32_t* tile_nbase, int32_t* ent_off, int32_t* order, int32_t* flt_count /* != nullptr: 0 for every record-free tile */, hipStream_t s);
 void launch_k1_pileup(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,

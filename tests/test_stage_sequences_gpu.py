@@ -291,8 +291,8 @@ def seq_async_reentry(engine_cls, orc, key, capfd):
 
 
 def seq_errors_midway(engine_cls, orc, key, capfd):
-    """frag with min_linkers = 0 (ARG); frag; phase with ld_weight_threshold = 2 (ARG); phase; a batch with an unknown CIGAR op
-    (CIGAR at lcr_pileup); the good batch again.  A refused call changes nothing: the good steps == oracle."""
+    """frag with min_linkers = 0 (ARG); frag; phase with ld_weight_threshold = 2 (ARG); cand with another dist_to_end (ARG); phase;
+    a batch with an unknown CIGAR op (CIGAR at lcr_pileup); the good batch again.  A refused call changes nothing: the good steps == oracle."""
     regs = oracle(orc, key)
     E = _engine(engine_cls, key)
     E.fill_data_into_freq_vec().get_candidate_snps()
@@ -307,6 +307,10 @@ def seq_errors_midway(engine_cls, orc, key, capfd):
     E.params = params(key, ld_weight_threshold=2)
     with pytest.raises(LcrError, match=r"lcr_phase failed \(-1\).*ld_weight_threshold"):
         E.phase()
+    assert E.candidates()[0].tobytes() == called and fm_bytes(E.fragmat()) == fm_bytes(fm)
+    E.params = params(key, dist_to_end=int(params(key).dist_to_end) + 1)   # (refused in front of the point where lcr_candidates rewinds)
+    with pytest.raises(LcrError, match=r"lcr_candidates failed \(-1\).*dist_to_end"):
+        E.get_candidate_snps()
     assert E.candidates()[0].tobytes() == called and fm_bytes(E.fragmat()) == fm_bytes(fm)
     E.params = params(key)
     E.phase()
@@ -355,6 +359,43 @@ def seq_platform_mismatch(engine_cls, orc, key, capfd):
     E.close()
 
 
+def seq_failed_pileup_rewinds(engine_cls, orc, key, capfd):
+    """device-resident batch: pileup; cand; frag; one CIGAR word of the caller's tensor gets an unknown op code; pileup fails (CIGAR)
+    part of the way through its rewrite of the tile tables and the record pool: the context is back at the loaded batch, and the
+    stage calls and getters behind it are refused -- not answered from the previous pass; the word restored: pileup; cand; frag;
+    phase == a fresh context's."""
+    import torch
+    import bench
+    regs = oracle(orc, key)
+    reads, regions, t = bench.to_device(batch(key), torch, torch.device("cuda", 0))
+    E = engine_cls(0, params(key))
+    E.load_batch((reads, regions, t))
+    E.fill_data_into_freq_vec()
+    par.check_pileup(E, regs, batch(key))
+    E.get_candidate_snps()
+    check_called(E, regs)
+    E.get_fragments()
+    par.check_fragmat(E, regs)
+    E.sync()
+    k = int(t["cigar"].numel()) // 2
+    good = int(t["cigar"][k])
+    t["cigar"][k] = (good & ~15) | 15
+    torch.cuda.synchronize()
+    with pytest.raises(LcrError, match=r"lcr_pileup failed \(-2\).*CIGAR"):
+        E.fill_data_into_freq_vec()
+    for call, text in ((E.get_fragments, "lcr_fragments before lcr_candidates"), (E.candidates, "lcr_get_candidates before lcr_candidates"),
+                       (E.fragmat, "lcr_get_fragmat before lcr_fragments"), (E.columns, "lcr_get_columns before lcr_pileup")):
+        with pytest.raises(LcrError, match=text):
+            call()
+    t["cigar"][k] = good
+    torch.cuda.synchronize()
+    E.fill_data_into_freq_vec()
+    par.check_pileup(E, regs, batch(key))
+    E.get_candidate_snps()
+    assert phase_round(E, regs) == _fresh(engine_cls, key, "P0")
+    E.close()
+
+
 SEQUENCES = [
     ("cand_p_p2_p", "cdna21"), ("cand_p_p2_p", "drna22"), ("cand_p_p2_p", "masseq13"),
     ("fuse_switch", "cdna21"), ("fuse_switch", "drna22"),
@@ -366,6 +407,7 @@ SEQUENCES = [
     ("errors_midway", "masseq13"),
     ("pileup_twice", "cdna21"), ("pileup_twice", "masseq13"),
     ("platform_mismatch", "cdna21"),
+    ("failed_pileup_rewinds", "cdna21"),
 ]
 
 
