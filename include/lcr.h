@@ -316,6 +316,46 @@ typedef struct {
 } lcr_phase_collected;
 int lcr_collect_phase(lcr_ctx*, lcr_phase_collected* out);
 
+/* Allele-specific junctions (K6): the haplotype x junction table of the allele-specific analysis that consumes the phased reads
+ * (allele_specific/longcallR-asj.py: get_exon_intron_regions' N arm, process_chunk :229-236, analyze_gene :671-676 / :734,
+ * check_absent_present, haplotype_event_test), counted on the GPU from what lcr_phase left there.  Defined per region -- a region
+ * stands where the script has a gene.  Row r of region g is a row of lcr_get_fragmat: its read is row_read[r], its haplotype
+ * assignment[r], its phase set phase_set[r] (0 = none, the script's PS ".").
+ *   junctions of a read   every N op of length >= 1 gives (s, l): s = 0-based contig column of the first skipped base = pos + the
+ *       lengths of the earlier M, D, N, = and X ops (I, S, H, P consume nothing); the script's 1-based inclusive junction is
+ *       (s + 1, s + l).  rend = pos + all reference-consuming lengths (exclusive).
+ *   participating rows    assignment 1 or 2 (the rule by which an HP tag is written) and more than min_junctions junctions.  Every
+ *       other read takes no part, neither as present nor as absent: assignment 0, reads that are no row, too few junctions.
+ *   kept junctions        n_reads(g, s, l) = participating rows of g that have the junction; kept iff n_reads >= min_count.
+ *   overlap               a participating row overlaps a kept junction iff pos < s + l && rend > s; it is PRESENT if one of its
+ *       junctions has the same s and l, ABSENT otherwise.
+ *   phase set             among the overlapping rows, count per value of ps; the junction's phase_set is the value with the most rows,
+ *       ties to the smallest value, 0 a value like any other; n_phase_sets = distinct values seen; h1_absent, h1_present, h2_absent,
+ *       h2_present count the rows of that phase set only.
+ *   motif                 the reference bytes at s, s+1 and s+l-2, s+l-1 of the region's window, upper-cased: 1 = GT..AG, 2 = CT..AC,
+ *       0 otherwise, for l < 2, or when either pair lies outside the window.
+ *   order                 by region, then s, then l, ascending; independent of the batch's composition and bit-reproducible (integer adds).
+ * Not the script's: no annotation (no gene assignment of reads, no exon-overlap filter, no Novel / Strand / Gene_name); the tie between
+ * equally large phase sets goes to the smallest value (the script: a Python set's iteration order); zero-length N ops are ignored;
+ * rows are not restricted to reads contained in the region (with --truncation a read that spans a cut is a row of both flanks).
+ * lcr_junctions needs the bound batch after lcr_phase (LCR_E_STATE otherwise, nothing changed; params == NULL: LCR_E_ARG), collects an
+ * asynchronous phase stage in flight first, queues on the context's stream, writes no buffer another stage or getter reads, and may be
+ * repeated with other parameters.  Its results die with the phase stage's: at the next candidate stage and at lcr_load_batch /
+ * lcr_bind_batch; lcr_get_junctions answers LCR_E_STATE then.  junc / junc_region_off: pinned host memory the stage's last kernels
+ * wrote, valid until the next lcr_junctions; dev_junc: the same records in HBM. */
+typedef struct { uint32_t min_count, min_junctions; } lcr_junction_params;   /* script defaults: 10, 2 */
+typedef struct {
+  int32_t region; uint8_t motif; uint8_t pad_[3];
+  int64_t start0;            /* contig coordinate of the first skipped base */
+  int32_t len; uint32_t n_reads;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1_absent, h1_present, h2_absent, h2_present;
+} lcr_junction;              /* 48 bytes */
+typedef struct { int32_t n_regions, n_junctions; const lcr_junction* junc; const int32_t* junc_region_off;
+                 const lcr_junction* dev_junc; } lcr_junction_list;
+int lcr_junctions(lcr_ctx*, const lcr_junction_params*);
+int lcr_get_junctions(lcr_ctx*, lcr_junction_list* out);
+
 /* Down-sampling: phase deep regions on a read sample (longcallR --downsample / --downsample-depth: thread.rs:144-151, phase.rs:693-701).
  * A region with at least `depth` fragment rows (all rows of lcr_get_fragmat, empty ones included) is down-sampled: the optimiser
  * (cross_optimize and its checks, cal_overall_probability, cross_optimize_by_block), the first two post-phase rounds
@@ -536,7 +576,7 @@ enum { LCR_K_SPANS = 0 /* K0: CIGAR decode + binning */, LCR_K_PILEUP, LCR_K_CAN
        LCR_K_FRAG_COUNT, LCR_K_FRAG_FILL, LCR_K_PHASE,
        LCR_K_BIND /* lcr_load_batch: read headers, read / tile -> region tables, op blocks' first reads (part of the pileup stage) */,
        LCR_K_BIND_TABLE /* lcr_load_batch of a device batch: region table + CIGAR layout check, before its one host wait */,
-       LCR_K_CAND_IMPORT /* lcr_import_candidates: count, scan, emit */, LCR_NKERNELS };
+       LCR_K_CAND_IMPORT /* lcr_import_candidates: count, scan, emit */, LCR_K_JUNCTIONS /* lcr_junctions, first kernel to last */, LCR_NKERNELS };
 int lcr_enable_timing(lcr_ctx*, int on);
 int lcr_kernel_ms(lcr_ctx*, int kernel, float* ms);
 /* Bytes the pileup tally kernel (K1) of the last lcr_pileup has to move: read bases once (B) + 8-byte

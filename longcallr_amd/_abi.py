@@ -18,7 +18,7 @@ F_RNA_EDIT, F_DENSE, F_HET, F_FOR_PHASING, F_HOM, F_SINGLE, F_NON_SELECTED, F_CA
     1, 2, 4, 8, 16, 32, 64, 128)
 
 (K_SPANS, K_PILEUP, K_CAND_FILTER, K_CAND_HIST, K_CAND_GT, K_FRAG_COUNT, K_FRAG_FILL, K_PHASE, K_BIND, K_BIND_TABLE,
- K_CAND_IMPORT, NKERNELS) = range(12)
+ K_CAND_IMPORT, K_JUNCTIONS, NKERNELS) = range(13)
 
 
 class LcrReads(C.Structure):
@@ -101,6 +101,22 @@ class LcrPhaseCollected(C.Structure):   # include/lcr.h: lcr_phase_collected
 class LcrDownsampleInfo(C.Structure):   # include/lcr.h: lcr_downsample_info
     _fields_ = [("n_regions", C.c_int32), ("n_rows", C.c_int32), ("region_applied", C.c_void_p), ("sampled", C.c_void_p),
                 ("dev_sampled", C.c_void_p)]
+
+
+class LcrJunctionParams(C.Structure):   # include/lcr.h: lcr_junction_params (longcallR-asj.py defaults: 10, 2)
+    _fields_ = [("min_count", C.c_uint32), ("min_junctions", C.c_uint32)]
+
+
+# lcr_junction (include/lcr.h): one kept junction of a region with its haplotype x presence table
+JUNC_DTYPE = np.dtype([("region", "<i4"), ("motif", "u1"), ("pad_", "u1", 3), ("start0", "<i8"), ("len", "<i4"), ("n_reads", "<u4"),
+                       ("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("h1_absent", "<u4"), ("h1_present", "<u4"),
+                       ("h2_absent", "<u4"), ("h2_present", "<u4")], align=True)
+assert JUNC_DTYPE.itemsize == 48, JUNC_DTYPE.itemsize
+
+
+class LcrJunctionList(C.Structure):   # include/lcr.h: lcr_junction_list
+    _fields_ = [("n_regions", C.c_int32), ("n_junctions", C.c_int32), ("junc", C.c_void_p), ("junc_region_off", C.c_void_p),
+                ("dev_junc", C.c_void_p)]
 
 
 # presets: the code values of main.rs:272-396 (not the help text)

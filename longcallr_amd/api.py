@@ -198,6 +198,16 @@ class Engine:
         self._chk(self.lib.lcr_phase(self.h, C.byref(self.params)), "lcr_phase")
         return self
 
+    def junctions(self, min_count=10, min_junctions=2):
+        """lcr_junctions + lcr_get_junctions after phase(): the kept junctions of every region with their haplotype x presence tables
+        (include/lcr.h; the table longcallR-asj.py builds per gene) -> (records as a structured array of _abi.JUNC_DTYPE, copied;
+        junc_region_off, n_regions + 1).  Waits for an asynchronous phase stage in flight; may be repeated with other parameters."""
+        p = _abi.LcrJunctionParams(int(min_count), int(min_junctions))
+        self._chk(self.lib.lcr_junctions(self.h, C.byref(p)), "lcr_junctions")
+        o = _abi.LcrJunctionList()
+        self._chk(self.lib.lcr_get_junctions(self.h, C.byref(o)), "lcr_get_junctions")
+        return _view(o.junc, _abi.JUNC_DTYPE, o.n_junctions), _view(o.junc_region_off, np.int32, o.n_regions + 1)
+
     def set_downsample(self, depth, seed=2025):
         """lcr_set_downsample: regions with at least `depth` fragment rows are phased on a sample of `depth` rows (longcallR --downsample /
         --downsample-depth; thread.rs:149 passes seed 2025).  Sticky; depth = 0 turns it off."""

@@ -1,0 +1,131 @@
+"""Allele-specific junctions: the junction-scale host arithmetic behind Engine.junctions() (include/lcr.h: lcr_junctions).
+
+The read-scale work -- junction walk, dedupe and count, overlap and presence per haplotype -- is K6 on the GPU; what is left per
+kept junction is small and plain: the clusters, the two tests, the Benjamini-Hochberg adjustment and the TSV text of
+allele_specific/longcallR-asj.py (cluster_junctions_connected_components, haplotype_event_test, calc_sor, g_test_2x2, the
+multipletests(method="fdr_bh") call and AseEvent).  Standard library + NumPy only: fisher_exact, chi2 and multipletests are
+restated below.  Not the script's: there is no annotation, so Strand and Novel are "." and Gene_name is the region."""
+import math
+
+import numpy as np
+
+HEADER = ("#Junction\tStrand\tJunction_set\tPhase_set\tHap1_absent\tHap1_present\tHap2_absent\tHap2_present\t"
+          "P_value\tSOR\tNovel\tGT_AG\tGene_name")
+
+
+def cluster(junc):
+    """Connected components of the kept junctions (records of Engine.junctions(), any number of regions) where two junctions of a
+    region are joined when they share s or share s + l (donor or acceptor).  Returns an int array: for every junction the index
+    of its component's first junction in output order."""
+    n = len(junc)
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    seen = {}
+    for i in range(n):
+        g, s, l = int(junc["region"][i]), int(junc["start0"][i]), int(junc["len"][i])
+        for key in ((g, 0, s), (g, 1, s + l)):
+            j = seen.setdefault(key, i)
+            a, b = find(i), find(j)
+            if a != b:
+                parent[max(a, b)] = min(a, b)    # the root is the component's first junction
+    return np.array([find(i) for i in range(n)], dtype=np.int64)
+
+
+def _log_hyper(x, r1, c1, n):
+    """log P(X = x) of the hypergeometric distribution: x of the r1 first-row items among the c1 first-column ones, n in all"""
+    lg = math.lgamma
+    return (lg(r1 + 1) - lg(x + 1) - lg(r1 - x + 1) + lg(n - r1 + 1) - lg(c1 - x + 1) - lg(n - r1 - c1 + x + 1)
+            - (lg(n + 1) - lg(c1 + 1) - lg(n - c1 + 1)))
+
+
+def fisher_two_sided(table):
+    """Two-sided Fisher exact test of a 2x2 table (scipy.stats.fisher_exact's p-value): the sum of the hypergeometric
+    probabilities that are <= the observed one, with scipy's relative slack of 1e-7."""
+    (a, b), (c, d) = [[int(v) for v in row] for row in table]
+    r1, c1, n = a + b, a + c, a + b + c + d
+    if n == 0:
+        return 1.0
+    p_obs = math.exp(_log_hyper(a, r1, c1, n))
+    total = 0.0
+    for x in range(max(0, r1 + c1 - n), min(r1, c1) + 1):
+        p = math.exp(_log_hyper(x, r1, c1, n))
+        if p <= p_obs * (1.0 + 1e-7):
+            total += p
+    return min(total, 1.0)
+
+
+def g_test(table, pseudocount=1e-10):
+    """g_test_2x2 of the script: (G, p) of the log-likelihood-ratio test, the pseudocount on observed and expected alike;
+    p = 1 - chi2.cdf(G, 1) = 1 - erf(sqrt(G / 2)) for G > 0 and 1.0 otherwise."""
+    t = [[float(v) for v in row] for row in table]
+    rows = [t[0][0] + t[0][1], t[1][0] + t[1][1]]
+    cols = [t[0][0] + t[1][0], t[0][1] + t[1][1]]
+    n = rows[0] + rows[1]
+    if n <= 0:
+        return 0.0, 1.0
+    g = 0.0
+    for i in range(2):
+        for j in range(2):
+            obs = t[i][j] + pseudocount
+            exp = rows[i] * cols[j] / n + pseudocount
+            g += obs * math.log(obs / exp)
+    g *= 2.0
+    return g, (1.0 - math.erf(math.sqrt(g / 2.0)) if g > 0 else 1.0)
+
+
+def sor(h1_absent, h1_present, h2_absent, h2_present):
+    """calc_sor of the script (GATK's AS_StrandOddsRatio form): ln(R + 1 / R), R the odds ratio of the table with 1 added to every cell"""
+    r = ((h1_absent + 1) * (h2_present + 1)) / ((h1_present + 1) * (h2_absent + 1))
+    return math.log(r + 1.0 / r)
+
+
+def bh_adjust(p):
+    """Benjamini-Hochberg adjusted p-values (multipletests(p, method="fdr_bh")[1]), in the order given"""
+    p = np.asarray(p, dtype=np.float64)
+    n = p.size
+    if n == 0:
+        return p.copy()
+    order = np.argsort(p, kind="stable")
+    adj = p[order] * n / np.arange(1, n + 1)
+    adj = np.minimum(np.minimum.accumulate(adj[::-1])[::-1], 1.0)
+    out = np.empty(n, dtype=np.float64)
+    out[order] = adj
+    return out
+
+
+def junction_p(rec):
+    """max(Fisher, G-test) of one record's table [[h1_absent, h2_absent], [h1_present, h2_present]] (haplotype_event_test)"""
+    t = [[int(rec["h1_absent"]), int(rec["h2_absent"])], [int(rec["h1_present"]), int(rec["h2_present"])]]
+    return max(fisher_two_sided(t), g_test(t)[1])
+
+
+def format_tsv(tables, min_count=10):
+    """The script's .asj.tsv text.  tables: [(chrom, junc, region_start0, region_len)] -- per batch the contig's name, the records of
+    Engine.junctions() and the batch's region arrays (junc["region"] indexes them).  Written are the junctions whose table sums to
+    >= min_count, in the order given; P_value is max(Fisher, G-test), Benjamini-Hochberg adjusted over all written junctions.
+    Coordinates are the script's 1-based inclusive ones: junction (s + 1, s + l), region (start0 + 1, start0 + len).  Strand and
+    Novel are "." (no annotation), Gene_name is the region, GT_AG is True iff the motif is GT..AG or CT..AC."""
+    rows, pvals = [], []
+    for chrom, junc, start0, length in tables:
+        comp = cluster(junc)
+        for i in range(len(junc)):
+            r = junc[i]
+            cells = [int(r["h1_absent"]), int(r["h1_present"]), int(r["h2_absent"]), int(r["h2_present"])]
+            if sum(cells) < min_count:
+                continue
+            s, l, g, f = int(r["start0"]), int(r["len"]), int(r["region"]), int(comp[i])
+            fs, fl = int(junc["start0"][f]), int(junc["len"][f])
+            ps = int(r["phase_set"])
+            rows.append(("%s:%d-%d\t.\t%s:%d-%d\t%s\t%d\t%d\t%d\t%d" % ((chrom, s + 1, s + l, chrom, fs + 1, fs + fl, ps if ps else ".") + tuple(cells)),
+                         sor(*cells), "%s\t%s:%d-%d" % (int(r["motif"]) != 0, chrom, int(start0[g]) + 1, int(start0[g]) + int(length[g]))))
+            pvals.append(junction_p(r))
+    adj = bh_adjust(pvals)
+    lines = [HEADER + "\n"]
+    for (head, s_or, tail), p in zip(rows, adj):
+        lines.append("%s\t%s\t%s\t.\t%s\n" % (head, float(p), s_or, tail))
+    return "".join(lines)

@@ -172,7 +172,7 @@ int lcr_ctx_create(int device, lcr_ctx** out) {
   for (int k = 0; k < LCR_NKERNELS; k++)
     for (int j = 0; j < 2; j++)
       if (hipEventCreate(&c->ev[k][j]) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
-  for (hipEvent_t* e : {&c->ev_ctl, &c->ev_sv, &c->ev_cand, &c->ev_nnz, &c->ev_imp})
+  for (hipEvent_t* e : {&c->ev_ctl, &c->ev_sv, &c->ev_cand, &c->ev_nnz, &c->ev_imp, &c->ev_junc})
     if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
   *out = c;
   return LCR_OK;
@@ -187,7 +187,7 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
   for (auto& u : c->up) if (u.ev) (void)hipEventDestroy(u.ev);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  for (hipEvent_t e : {c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp, c->ev_junc}) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2 * lcr_ctx::UP_LANES; k++) if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
   c->phase.release();
   for (int k = 0; k < LCR_NKERNELS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);
@@ -236,8 +236,6 @@ int lcr_pileup_stage_bytes(lcr_ctx* c, int64_t* bytes) {
   *bytes = c->stage_bytes;
   return LCR_OK;
 }
-
-static int read_records_fresh(lcr_ctx* c);
 
 int lcr_phase(lcr_ctx* c, const lcr_params* p) {
   if (!c || !p) return LCR_E_ARG;
@@ -418,15 +416,6 @@ int lcr_get_read_records_device(lcr_ctx* c, const lcr_read_record** dev_rec, int
   { int rc = read_records_fresh(c); if (rc) return rc; }
   *dev_rec = c->phase.d_read_rec.as<lcr_read_record>();
   *n_rows = c->n_rows;
-  return LCR_OK;
-}
-
-static int read_records_fresh(lcr_ctx* c) {   // regions that took the host epilogue (debug hook / fallback): the HBM records are rebuilt from the host arrays
-  if (!c->phase.read_rec_stale) return LCR_OK;
-  std::vector<lcr_read_record> h((size_t)std::max(c->n_rows, 0));
-  for (int r = 0; r < c->n_rows; r++) h[r] = lcr_read_record{r, c->phase.r_haplotag[r], c->phase.r_assignment[r], 0, c->phase.r_phase_set[r]};
-  if (c->n_rows) { const int rc2 = upload_bytes(c, c->phase.d_read_rec.p, h.data(), h.size() * sizeof(lcr_read_record)); if (rc2) return rc2; HIPCHK(c, hipStreamSynchronize(c->stream)); }
-  c->phase.read_rec_stale = false;
   return LCR_OK;
 }
 

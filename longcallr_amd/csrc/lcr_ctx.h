@@ -1,6 +1,7 @@
 // lcr_ctx.h — the context behind the C ABI (include/lcr.h) and what its host units share: the stage state, timers, uploads, the settle
 // functions.  Private to lcr_api.hip (lifecycle, cache, fills, debug switches, phase entry, region discovery), lcr_batch.hip (binding and
-// upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns) and lcr_calls.hip (candidate, import and fragment stages with their getters).
+// upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns), lcr_calls.hip (candidate, import and fragment stages with their getters) and
+// lcr_junctions.hip (lcr_junctions, lcr_get_junctions).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -111,6 +112,13 @@ struct lcr_ctx {
   uint32_t ds_depth = 0; uint64_t ds_seed = 0;
   std::vector<uint8_t> ds_rows; bool ds_rows_set = false;
 
+  // K6 (lcr_junctions): scratch and results of its own -- no other stage or getter reads them
+  bool junc_valid = false;   // lcr_get_junctions: the last lcr_junctions' table belongs to the phase results of the bound batch (rewind_to)
+  int32_t junc_n = 0, junc_ng = 0;
+  DevBuf j_part, j_npair, j_part_off, j_pair_off, j_tsz, j_tbl_off, j_rows, j_keys, j_tbl_key, j_tbl_cnt, j_flag, j_koff, j_ck, j_cc, j_cg, j_off, d_junc;
+  HostBuf h_junc_ctl, h_junc, h_junc_off;   // pinned: {participating rows, pairs, kept junctions}; the records; their offsets per region
+  hipEvent_t ev_junc = nullptr;             // behind the stage's last kernel
+
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
   std::vector<int64_t> rl_start0;
@@ -139,6 +147,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
     c->cand_used = false;      // the records lcr_phase rewrote are replaced by the next candidate stage
   }
   if (to < ST_FRAGGED) c->ds_rows_set = false;   // a sample names the rows of ONE fragment stage
+  if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and
@@ -179,5 +188,14 @@ int upload(lcr_ctx* c, DevBuf& buf, const T* src, size_t n, const T** dst, int m
 // lcr_phase leaves its kernels in flight on the phase stage's own queues (lcr_phase_host.h): whoever needs its results, or is about
 // to overwrite what it reads / writes, collects them first
 inline int phase_settle(lcr_ctx* c) { return c->phase.settle(&c->err); }
+// regions that took the host epilogue (debug hook / fallback): the HBM records of lcr_get_read_records_device are rebuilt from the host arrays
+inline int read_records_fresh(lcr_ctx* c) {
+  if (!c->phase.read_rec_stale) return LCR_OK;
+  std::vector<lcr_read_record> h((size_t)std::max(c->n_rows, 0));
+  for (int r = 0; r < c->n_rows; r++) h[r] = lcr_read_record{r, c->phase.r_haplotag[r], c->phase.r_assignment[r], 0, c->phase.r_phase_set[r]};
+  if (c->n_rows) { const int rc2 = upload_bytes(c, c->phase.d_read_rec.p, h.data(), h.size() * sizeof(lcr_read_record)); if (rc2) return rc2; HIPCHK(c, hipStreamSynchronize(c->stream)); }
+  c->phase.read_rec_stale = false;
+  return LCR_OK;
+}
 int cand_settle(lcr_ctx* c);   // the candidate stage's host copies (lcr_calls.hip)
 int frag_settle(lcr_ctx* c);   // lcr_fragments' entry count (lcr_calls.hip)

@@ -296,6 +296,24 @@ void launch_k5_span_diff(const int32_t* ref_start, const int32_t* ref_end, int32
 void launch_k5_bounds(bool write, const int32_t* ex, int64_t contig_len, uint32_t cap, int32_t n_blocks, int32_t* blk_cnt, const int32_t* blk_off,
                       int32_t* starts, int32_t* ends, uint32_t* imax, int32_t n_keys, uint32_t* n_trunc, hipStream_t s);
 
+// k6_junctions.hip: haplotype x junction counts over the phased rows (lcr_junctions)
+void launch_k6_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, uint32_t min_junctions,
+                     int32_t* part_flag, int32_t* npair, hipStream_t s);
+void launch_k6_sizes(const BatchView& b, const int32_t* part_off /* n_reads + 1 */, const int32_t* pair_off /* n_reads + 1 */, int32_t* tsz /* n_regions */,
+                     int32_t* host_ctl /* pinned (device pointer): [0] participating rows, [1] pairs */, hipStream_t s);
+size_t launch_k6_row_bytes();   // bytes of a participating row's record
+void launch_k6_emit(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* part_flag,
+                    const int32_t* part_off, const int32_t* pair_off, const int32_t* tbl_off /* n_regions + 1 */, void* rows, uint64_t* keys,
+                    uint64_t* tbl_key /* 0xff-filled */, uint32_t* tbl_cnt /* zeroed */, hipStream_t s);
+void launch_k6_flag(const uint64_t* tbl_key, const uint32_t* tbl_cnt, int32_t n_slots, uint32_t min_count, int32_t* flag, hipStream_t s);
+void launch_k6_offsets(const int32_t* tbl_off, const int32_t* koff /* n_slots + 1 */, int32_t ng, int32_t n_slots, int32_t* joff, int32_t* host_joff,
+                       int32_t* host_ctl /* [2] kept junctions */, hipStream_t s);
+void launch_k6_place(const BatchView& b, const uint64_t* tbl_key, const uint32_t* tbl_cnt, const int32_t* flag, const int32_t* koff,
+                     const int32_t* tbl_off, int32_t n_slots, const int32_t* joff, int32_t n_kept, uint64_t* ck, uint32_t* cc, int32_t* cgr,
+                     lcr_junction* junc, hipStream_t s);
+void launch_k6_tables(const BatchView& b, const int32_t* part_off, const void* rows, const uint64_t* keys, int32_t n_kept, lcr_junction* junc,
+                      lcr_junction* host_junc /* pinned (device pointer) */, hipStream_t s);
+
 // device helpers shared by kernels -------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ int base_code(uint8_t b) {

@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import _abi, api, bamio, vcf
+from . import _abi, api, asj, bamio, vcf
 
 VCF_HEADER_TAIL = (   # thread.rs:232-262, verbatim
     '##FILTER=<ID=PASS,Description="All filters passed">\n'
@@ -108,7 +108,8 @@ def _gather_names(name_off, blob, rows):
 
 def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs=None, device=0, threads=0, seed=2025,
         read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None,
-        downsample=False, downsample_depth=10000, downsample_seed=2025, truncation=False, truncation_coverage=200000, **param_overrides):
+        downsample=False, downsample_depth=10000, downsample_seed=2025, truncation=False, truncation_coverage=200000,
+        asj_out=None, asj_min_count=10, asj_min_junctions=2, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -128,7 +129,12 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     truncation_coverage ends a region like an uncovered one, so an over-deep stretch is neither piled up nor phased and its flanks
     become regions of their own (a read that spans it is listed in both; the phased BAM keeps the reads contained in a region).
     Adds the stat truncated_columns (columns above the cap, summed over contigs).  Off by default; truncation_coverage outside
-    [0, 2^32) is a ValueError."""
+    [0, 2^32) is a ValueError.
+    asj_out / asj_min_count / asj_min_junctions: the allele-specific junction table of longcallR-asj.py (--min_count / --min_junctions;
+    a region stands where the script has a gene, there is no annotation: include/lcr.h, lcr_junctions) as that script's .asj.tsv, written
+    to asj_out.  Every chunk calls Engine.junctions right behind phase(); that call waits for the phase stage, so the chunk's overlap with
+    the next chunk's upload and pileup (async_phase) is given up.  Adds the stat junctions (kept junctions, summed over chunks).  VCF and
+    phased BAM do not depend on it; without asj_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -174,14 +180,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm = in_flight[k]
+        idx, name, batch, want_reads, fm, junc = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -193,6 +199,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["hp"] = np.where((fm["row_for_phasing"] != 0) | (asg != 0), asg, -1)
             out["ps"] = res["phase_set"].copy()
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
+        if junc is not None:
+            out["junc"] = (name, junc, batch.start0, batch.len)
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates)
@@ -218,7 +226,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 f = E.fragmat()
                 fm = dict(row_for_phasing=f["row_for_phasing"], row_read=f["row_read"])
             E.phase()
-            in_flight[k] = (idx, name, batch, want_reads, fm)
+            junc = E.junctions(asj_min_count, asj_min_junctions)[0] if asj_out is not None else None   # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc)
         finally:
             with free_lock:
                 free.append(k)
@@ -272,6 +281,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     stats["candidates"] = sum(r["n_cand"] for r in results)
     stats["vcf_records"] = text.count("\n")
     write_vcf(out_vcf, contig_lengths, [text])
+    if asj_out is not None:
+        stats["junctions"] = sum(int(r["junc"][1].size) for r in results)
+        with open(asj_out, "w") as f:
+            f.write(asj.format_tsv([r["junc"] for r in results], asj_min_count))
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

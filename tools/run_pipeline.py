@@ -4,6 +4,7 @@
   python tools/run_pipeline.py -b reads.bam -f ref.fa -o out.vcf [--out-bam phased.bam] [-p hifi-masseq] [-c chr20,chr21]
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
+                                 [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]]   (allele-specific junction table)
 """
 import argparse
 import json
@@ -30,13 +31,17 @@ def main():
     ap.add_argument("--downsample-depth", type=int, default=10000)
     ap.add_argument("--truncation", action="store_true", help="end a region at columns deeper than --truncation-coverage, as at uncovered ones")
     ap.add_argument("--truncation-coverage", type=int, default=200000)
+    ap.add_argument("--asj-out", help="write the allele-specific junction table (longcallR-asj.py's .asj.tsv; regions in place of genes)")
+    ap.add_argument("--asj-min-count", type=int, default=10, help="reads a junction needs to be kept, and a table needs to be written")
+    ap.add_argument("--asj-min-junctions", type=int, default=2, help="a read takes part with MORE junctions than this")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     extra = {} if a.read_assign_cutoff is None else dict(read_assign_cutoff=a.read_assign_cutoff)
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
                       device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf,
                       downsample=a.downsample, downsample_depth=a.downsample_depth,
-                      truncation=a.truncation, truncation_coverage=a.truncation_coverage, **extra)
+                      truncation=a.truncation, truncation_coverage=a.truncation_coverage,
+                      asj_out=a.asj_out, asj_min_count=a.asj_min_count, asj_min_junctions=a.asj_min_junctions, **extra)
     print(json.dumps(st))
 
 
