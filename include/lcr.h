@@ -378,8 +378,7 @@ int lcr_get_junctions(lcr_ctx*, lcr_junction_list* out);
  *       next candidate stage (LCR_E_STATE after it, and before the first lcr_phase).
  * While down-sampling is on (depth > 0, or a sample was given), lcr_phase answers LCR_E_ARG, nothing changed, to
  * read_assign_cutoff <= 0 (an unsampled row's haplotag carries no sign: the last round gives the same assignment for either sign only
- * because |q - qn| = 0 is below every positive cutoff) and to the "post_host" debug cross-check (the host epilogue does not know the
- * sample).  The asynchronous phase stage and lcr_collect_phase work as without it. */
+ * because |q - qn| = 0 is below every positive cutoff).  The asynchronous phase stage and lcr_collect_phase work as without it. */
 typedef struct {
   int32_t n_regions, n_rows;
   const uint8_t* region_applied; /* n_regions: 1 = the region was down-sampled                        */
@@ -538,8 +537,8 @@ int lcr_bam_write_reads(const char* out_path, const char* contig, int64_t contig
  * -- the enumeration restarts -- is done, and run beside its resolve / post-phase tails, which leave most CUs idle.
  * CONTRACT CHANGE while it is on: the input arrays of a device-resident batch must stay unchanged until that batch's results have
  * been collected (a getter or lcr_ctx_sync) -- with the synchronous stage they are free when lcr_phase returns.  A host batch
- * (lcr_load_batch with LCR_MEM_HOST, lcr_load_batch_async) waits for the stage in flight by itself.  Persistent all-CU launches,
- * the host epilogue and phase_prof make lcr_phase wait as before.  The stage then uses four queues: the process should run with
+ * (lcr_load_batch with LCR_MEM_HOST, lcr_load_batch_async) waits for the stage in flight by itself.  Persistent all-CU launches
+ * and phase_prof make lcr_phase wait as before.  The stage then uses four queues: the process should run with
  * GPU_MAX_HW_QUEUES >= 8 in its environment (ROCm's default of 4 maps two of them onto one hardware queue: correct, but measured
  * without gain).  The HIP runtime reads that variable when it starts, so the library cannot set it: lcr_ctx_set_async_phase(ctx, 1)
  * returns LCR_W_HW_QUEUES (> 0: the mode IS on) when the variable is unset or below 8, and lcr_last_error says what to export. */
@@ -555,9 +554,9 @@ int lcr_ctx_set_async_phase(lcr_ctx*, int on);
  * be taken makes lcr_phase fail with LCR_E_DEVICE -- it is never skipped. */
 int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
 
-/* Debug / test switches (the library reads no environment variable): key = "phase_prof", "post_host", "grid_min_entries",
+/* Debug / test switches (the library reads no environment variable): key = "phase_prof", "grid_min_entries",
  * "grid_generic", "grid_spec_lanes", "post_half", "enum_force_big", "enum_force_stream" (1: every LDS-resident enumeration region by the
- * streaming kernel, one restart per wave), "host_threads", "tie_arith", "timing_mask",
+ * streaming kernel, one restart per wave), "tie_arith", "timing_mask",
  * "k3_hits" (0: the fragment stage walks the CIGARs itself), "async_phase" (1: lcr_phase returns with its kernels in flight),
  * "grid_spec_batch" (0: the all-CU chain kernel's speculative half-rounds side by side on sub-grids; default 1: as eight bits of one state)
  * (bit k: only the kernel groups LCR_K_* k are timed when timing is enabled; 0 = all) (see PhaseDebug in

@@ -501,7 +501,7 @@ __device__ void block_flip(SC& sc, const ChainDev& C, const ChainView& v, const 
     v.flipcol[k] = last;
   }
   sc.sync();
-  // per block SNP: the two ratio scores (ColScores of the host path = cal_delta_eta_sigma_log, phase.rs:128-176)
+  // per block SNP: the two ratio scores (cal_delta_eta_sigma_log, phase.rs:128-176)
   double* stg = stage + (threadIdx.x >> 6) * (4 * SSTR);
   const int n_nodes = v.blk_ptr[nb];
   for (int t = sc.wave(); t < n_nodes; t += sc.nwaves()) {

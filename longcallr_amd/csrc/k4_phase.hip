@@ -1,4 +1,4 @@
-// k4_phase.hip — K4: haplotype phasing on gfx950, HOST CONTROL (buffer sizing, launches, the LD-block flip pass, host epilogue).
+// k4_phase.hip — K4: haplotype phasing on gfx950, HOST CONTROL (buffer sizing, launches, collecting the results).
 //
 // Replaces SNPFrag::phase (reference src/phase.rs:1087-1296) with its kernel cross_optimize
 // (phase.rs:810-976) and the probability functions phase.rs:32-49,77-96,128-176,257-276, plus the
@@ -35,7 +35,6 @@
 #include <cstring>
 #include <climits>
 #include <map>
-#include <thread>
 #include <mutex>
 #include <fcntl.h>
 #include <sys/file.h>
@@ -70,222 +69,6 @@ struct HostLut {
   }
 };
 const HostLut& hlut() { static HostLut l; return l; }
-
-struct Obs { int sigma; uint8_t v; };  // one (read haplotag, entry value) observation of a SNP column
-
-inline double lg(int sigma, int delta, int eta, uint8_t v) {  // log10(aki(...)), phase.rs:32-49
-  const int p = (v & 32) ? 1 : -1, x = eta == 0 ? sigma * delta : eta;
-  return p == x ? hlut().l1e[v & 31] : hlut().le[v & 31];
-}
-// phase.rs:128-176.  The five log sums of one call are running sums over the same observation order;
-// the sum for eta != 0 does not depend on delta, and log_q1 repeats one of the other four, so the four
-// distinct sums are computed once (identical addition sequences => identical doubles) and each of
-// the reference's calls is assembled from them.
-struct ColScores {
-  double het_d = 0, het_nd = 0, homref = 0, homvar = 0;  // sum log10 aki for (delta,0), (-delta,0), (.,+1), (.,-1)
-  double p_het = 0;
-  ColScores(int delta_i, const std::vector<Obs>& o) {
-    p_het = o.empty() ? hlut().log_theta : hlut().log_theta - (double)(uint32_t)o.size() * hlut().log2;
-    for (const Obs& x : o) {
-      het_d += lg(x.sigma, delta_i, 0, x.v); het_nd += lg(x.sigma, -delta_i, 0, x.v);
-      homref += lg(x.sigma, delta_i, 1, x.v); homvar += lg(x.sigma, delta_i, -1, x.v);
-    }
-  }
-  // cal_delta_eta_sigma_log(sign * delta_i, eta_i, ...), sign = +1 / -1
-  double score(int sign, int eta_i) const {
-    const double hd = sign > 0 ? het_d : het_nd, hn = sign > 0 ? het_nd : het_d;
-    double q1 = eta_i == 0 ? hd : (eta_i == 1 ? homref : homvar);
-    q1 += eta_i == 0 ? p_het : (eta_i == 1 ? hlut().p_homref : hlut().p_homvar);
-    const double q2 = homvar + hlut().p_homvar, q3 = hd + p_het, q4 = homref + hlut().p_homref, q5 = hn + p_het;
-    return 1.0 - q1 / (q2 + q3 + q4 + q5);
-  }
-};
-double delta_eta_sigma_log(int delta_i, int eta_i, const std::vector<Obs>& o) { return ColScores(delta_i, o).score(1, eta_i); }
-// phase.rs:238-255
-double phase_score_log(int delta_i, int eta_i, const std::vector<Obs>& o) {
-  double q1 = 0, q2 = 0, q3 = 0;
-  for (const Obs& x : o) q1 += lg(x.sigma, delta_i, eta_i, x.v);
-  for (const Obs& x : o) { q2 += lg(x.sigma, 1, eta_i, x.v); q3 += lg(x.sigma, -1, eta_i, x.v); }
-  return 1.0 - q1 / (q2 + q3);
-}
-
-// host view of one region: full fragment rows (all entries) + mutable phasing state
-struct RegionHost {
-  int g = 0, S = 0, nrow = 0;
-  int c0 = 0;                      // first candidate (global index)
-  int r0 = 0;                      // first row (global index)
-  const int64_t* row_ptr = nullptr;  // global CSR (host copy)
-  const int32_t* col = nullptr;
-  const uint8_t* val = nullptr;
-  const uint32_t* links = nullptr;
-  lcr_candidate* cand = nullptr;   // cand[0..S)
-  std::vector<uint8_t> phase_site; // per entry of this region (index e - row_ptr[r0])
-  std::vector<int8_t> tag;         // haplotag per row
-  std::vector<uint8_t> asg, fp;    // assignment, for_phasing per row
-  std::vector<std::vector<int>> cover;  // per SNP: rows (local) in push order (fragment.rs:293-306)
-  std::vector<int> fp_rows;        // local rows with for_phasing at K3 time (the phase matrix rows)
-  uint64_t seed = 0, ctr = 0;
-  uint32_t min_linkers = 1;
-  int64_t e0 = 0;
-  double rnd() { return u01(seed, ctr++); }
-  int64_t eb(int r) const { return row_ptr[r0 + r]; }
-  int64_t ee(int r) const { return row_ptr[r0 + r + 1]; }
-  int lc(int64_t e) const { return col[e] - c0; }
-  bool fphase(int i) const { return (cand[i].flags & LCR_F_FOR_PHASING) != 0; }
-
-  // snpfrags.rs:548-625
-  void assign_reads_haplotype(double cutoff) {
-    for (int r = 0; r < nrow; r++) {
-      if (!fp[r]) continue;
-      const int sigma_k = tag[r];
-      double q1 = 0, q2 = 0, q3 = 0, n1 = 0;
-      int n = 0;
-      for (int64_t e = eb(r); e < ee(r); e++) {
-        const int i = lc(e);
-        if (!phase_site[e - e0] && fphase(i)) phase_site[e - e0] = 1;
-        if (!fphase(i) || cand[i].haplotype == 0 || cand[i].genotype != 0) continue;
-        // cal_sigma_delta_eta_log (phase.rs:77-96) for sigma_k and -sigma_k share log_q2/log_q3
-        q1 += lg(sigma_k, cand[i].haplotype, 0, val[e]);
-        n1 += lg(-sigma_k, cand[i].haplotype, 0, val[e]);
-        n++;
-      }
-      if (sigma_k == 0 || n == 0) { asg[r] = 0; tag[r] = 0; continue; }
-      for (int64_t e = eb(r); e < ee(r); e++) {
-        const int i = lc(e);
-        if (!fphase(i) || cand[i].haplotype == 0 || cand[i].genotype != 0) continue;
-        q2 += lg(1, cand[i].haplotype, 0, val[e]); q3 += lg(-1, cand[i].haplotype, 0, val[e]);
-      }
-      const double q = 1.0 - q1 / (q2 + q3), qn = 1.0 - n1 / (q2 + q3);
-      if (std::fabs(q - qn) >= cutoff) {
-        if (q >= qn) asg[r] = sigma_k == 1 ? 1 : 2;
-        else if (sigma_k == 1) { asg[r] = 2; tag[r] = -1; }
-        else { asg[r] = 1; tag[r] = 1; }
-      } else { asg[r] = 0; tag[r] = 0; }
-    }
-  }
-
-  void gather(int ti, bool need_assigned, bool het_skip_unassigned, std::vector<Obs>& o, int& hap1, int& hap2) const {
-    o.clear(); hap1 = hap2 = 0;
-    for (int r : cover[ti]) {
-      if (!fp[r] || links[r0 + r] < min_linkers) continue;
-      if (need_assigned && asg[r] == 0) continue;
-      if (het_skip_unassigned && asg[r] == 0) continue;
-      for (int64_t e = eb(r); e < ee(r); e++)
-        if (lc(e) == ti) {
-          if (asg[r] == 1) hap1++; else if (asg[r] == 2) hap2++;
-          o.push_back({tag[r], val[e]});
-        }
-    }
-  }
-
-  // snpfrags.rs:378-546
-  void assign_snp_haplotype_genotype() {
-    std::vector<Obs> o;
-    for (int ti = 0; ti < S; ti++) {
-      lcr_candidate& snp = cand[ti];
-      if (!fphase(ti)) { snp.flags |= LCR_F_NON_SELECTED; continue; }
-      if (cover[ti].empty()) { snp.flags |= LCR_F_SINGLE; continue; }
-      const int delta_i = snp.haplotype;
-      int hap1, hap2;
-      gather(ti, false, snp.variant_type == 1, o, hap1, hap2);
-      if (o.empty()) { snp.flags |= LCR_F_NON_SELECTED; continue; }
-      const ColScores cs(delta_i, o);
-      const double q1 = cs.score(1, 0), q2 = cs.score(-1, 0), q3 = cs.score(1, 1), q4 = cs.score(1, -1);
-      const double mx = std::fmax(q1, std::fmax(q2, std::fmax(q3, q4)));
-      if (q1 == mx) { snp.haplotype = delta_i; snp.genotype = 0; snp.variant_type = 1; }
-      else if (q2 == mx) { snp.haplotype = -delta_i; snp.genotype = 0; snp.variant_type = 1; }
-      else if (q3 == mx) { snp.haplotype = delta_i; snp.genotype = 1; snp.variant_type = 0; }
-      else if (q4 == mx) { snp.haplotype = delta_i; snp.genotype = -1; if (snp.variant_type != 2 && snp.variant_type != 3) snp.variant_type = 2; }
-      else continue;  // NaN scores: the reference panics here
-      if (snp.genotype != 0) { snp.flags |= LCR_F_NON_SELECTED; continue; }
-      if (hap1 >= 1 && hap2 >= 1) snp.phase_score = -10.0 * std::log10(1.0 - phase_score_log(snp.haplotype, snp.genotype, o));
-      else snp.phase_score = 0.19940219;
-    }
-  }
-
-  // snpfrags.rs:191-376 (eval_rna_edit_var_phase / eval_low_frac_var_phase)
-  void eval_rescue(uint32_t list_flag, float min_phase_score, bool low_frac) {
-    std::vector<int> list;  // edit_snps / somatic_snps are fixed at candidate time (snpfrags.rs:20-26)
-    for (int i = 0; i < S; i++) if (orig_flags[i] & list_flag) list.push_back(i);
-    std::vector<Obs> o;
-    for (int ti : list) {
-      lcr_candidate& snp = cand[ti];
-      if (cover[ti].empty()) { snp.flags |= LCR_F_SINGLE; continue; }
-      if (snp.variant_type != 1) { snp.flags |= LCR_F_NON_SELECTED; continue; }
-      int hap1, hap2;
-      gather(ti, true, false, o, hap1, hap2);
-      if (o.empty() || hap1 < 2 || hap2 < 2) { snp.flags |= LCR_F_SINGLE; continue; }
-      const double ps1 = -10.0 * std::log10(1.0 - phase_score_log(1, 0, o));
-      const double ps2 = -10.0 * std::log10(1.0 - phase_score_log(-1, 0, o));
-      snp.flags &= ~(uint32_t)LCR_F_SINGLE;
-      if (std::fmax(ps1, ps2) >= (double)min_phase_score) {
-        snp.flags &= ~(uint32_t)(LCR_F_NON_SELECTED | LCR_F_RNA_EDIT);
-        if (low_frac) snp.flags &= ~(uint32_t)LCR_F_CAND_SOMATIC;
-        snp.flags |= LCR_F_FOR_PHASING;
-        for (int r : cover[ti]) {
-          fp[r] = 1;
-          if (tag[r] == 0 || asg[r] == 0) tag[r] = rnd() < 0.5 ? -1 : 1;
-        }
-        snp.haplotype = ps1 >= ps2 ? 1 : -1;
-        snp.genotype = 0; snp.variant_type = 1; snp.phase_score = std::fmax(ps1, ps2);
-      } else {
-        snp.flags |= LCR_F_NON_SELECTED;
-        if (low_frac) { snp.flags |= LCR_F_CAND_SOMATIC; snp.flags &= ~(uint32_t)LCR_F_FOR_PHASING; }
-        else snp.flags |= LCR_F_RNA_EDIT;
-      }
-    }
-  }
-  std::vector<uint32_t> orig_flags;
-
-  // snpfrags.rs:628-733
-  // snpfrags.rs:628-733.  The reference builds a petgraph GraphMap whose nodes are the PASS het SNPs
-  // (added in index order), adds an edge per read and allele-consistent SNP pair, and walks
-  // kosaraju_scc: components come out in descending order of their first-inserted (= smallest-index)
-  // node, a component's phase set is pos+1 of that node, and a read takes the phase set of the first
-  // component in that order that owns one of its edges.  Union-find gives exactly that.
-  void assign_phase_set(float min_phase_score, uint32_t* row_ps /* global rows */) {
-    std::vector<int> parent(S, -1);  // -1: not a node
-    for (int i = 0; i < S; i++) {
-      const lcr_candidate& s = cand[i];
-      if (s.genotype != 0 || s.variant_type != 1) continue;
-      if (s.flags & (LCR_F_DENSE | LCR_F_RNA_EDIT)) continue;
-      if (s.phase_score < (double)min_phase_score) continue;
-      parent[i] = i;
-    }
-    auto find = [&](int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
-    auto unite = [&](int x, int y) { x = find(x); y = find(y); if (x != y) { if (x < y) parent[y] = x; else parent[x] = y; } };  // root = min index
-    int ns[64], np[64];
-    auto row_nodes = [&](int r) {
-      int n = 0;
-      for (int64_t e = eb(r); e < ee(r) && n < 64; e++)
-        if (parent[lc(e)] >= 0) { ns[n] = lc(e); np[n] = (val[e] & 32) ? 1 : -1; n++; }
-      return n;
-    };
-    for (int r = 0; r < nrow; r++) {
-      if (!fp[r] || asg[r] == 0) continue;
-      const int n = row_nodes(r);
-      for (int x = 0; x < n; x++)
-        for (int y = x + 1; y < n; y++)
-          if (cand[ns[x]].haplotype * cand[ns[y]].haplotype == np[x] * np[y]) unite(ns[x], ns[y]);
-    }
-    for (int i = 0; i < S; i++) if (parent[i] >= 0) cand[i].phase_set = (uint32_t)(cand[find(i)].pos + 1);
-    for (int r = 0; r < nrow; r++) {
-      if (!fp[r] || asg[r] == 0) continue;
-      const int n = row_nodes(r);
-      int best = -1;  // largest component root among the components that own an edge of this read
-      if (n == 1) best = find(ns[0]);  // self loop (snpfrags.rs:659-665)
-      for (int x = 0; x < n; x++)
-        for (int y = x + 1; y < n; y++)
-          if (cand[ns[x]].haplotype * cand[ns[y]].haplotype == np[x] * np[y]) best = std::max(best, find(ns[x]));
-      if (best >= 0) row_ps[r0 + r] = (uint32_t)(cand[best].pos + 1);
-    }
-  }
-
-};
-
-struct PhaseWork {   // host epilogue structures, reused across calls
-  std::vector<RegionHost> R;
-};
 
 }  // namespace
 
@@ -372,8 +155,6 @@ struct GridLock {
   }
 };
 
-void PhaseHost::free_work() { delete static_cast<PhaseWork*>(work); work = nullptr; }
-
 int PhaseHost::ld_blocks(const PhaseInputs& in, int region, std::vector<int32_t>* off, std::vector<int32_t>* snps, hipStream_t s, std::string* err) {
   off->assign(1, 0); snps->clear();
   for (const ChainDesc& d : chain_desc) {
@@ -415,12 +196,11 @@ int PhaseHost::settle(std::string* err) {
   std::vector<lcr_candidate>& cand = *pend.cand;
   for (int g = 0; g < pend.ng; g++) {
     const int c0 = pend.cand_off[g], S = pend.cand_off[g + 1] - c0;
-    if (S == 0 || pend.host_post[g]) continue;
+    if (S == 0) continue;
     memcpy(cand.data() + c0, h_cand_obj.as<lcr_candidate>() + c0, (size_t)S * sizeof(lcr_candidate));
     objective[g] = (double)h_obj[g] / FX_SCALE;
   }
   r_haplotag = (int8_t*)(h_r + pend.res_tag); r_assignment = h_r + pend.res_asg; r_phase_set = (uint32_t*)(h_r + pend.res_ps);
-  read_rec_stale = pend.any_host_post;   // (rows of regions that took the host epilogue: records rebuilt on demand)
   return LCR_OK;
 }
 
@@ -444,8 +224,8 @@ struct PhaseCall {
   StageIn si{}; StageOut so{};
   int64_t grid_min = 0; StageStat* stat = nullptr;   // per-region sizes, written by k4_stage into pinned host memory
   std::vector<int32_t> enum_slots, chain_slots, gpost_slots, gstage_slots;
-  std::vector<uint8_t> host_post, grid_post;   // per region: the host epilogue / k4_gpost
-  bool any_host_post = false; uint32_t post_lds = 0;
+  std::vector<uint8_t> grid_post;   // per region: k4_gpost
+  uint32_t post_lds = 0;
   size_t gp_S = 1, gp_rows = 1, gp_E = 1;   // largest region image of k4_gpost
   GridLock grid_lock;   // held from the first persistent launch until run() returns (all queues are drained by then)
   PhaseCall(const PhaseInputs& in_, const lcr_params& prm_, hipStream_t user_stream, std::string* err_, bool prof_)
@@ -490,8 +270,8 @@ int PhaseHost::run(const PhaseInputs& in, const lcr_params& prm, hipStream_t use
   RCHK(settle(err));
   c.lap("enumeration kernels");
   if (c.prof) RCHK(report_prof(c));
-  if (!c.any_host_post) { c.lap("results"); return LCR_OK; }
-  return host_epilogue(c);
+  c.lap("results");
+  return LCR_OK;
 }
 
 // async_phase (opt-in): everything is queued on the stage's OWN first queue, behind what the caller's stream holds now (the
@@ -642,8 +422,8 @@ int PhaseHost::stage(PhaseCall& c) {
 }
 
 // enumeration (S <= max_enum_snps) and chain regions; the post-phase epilogue of every region: k4_post (a workgroup per region, the
-// region in LDS) where it fits its LDS image, else k4_gpost (all CUs on the region); the host epilogue (RegionHost) for all regions
-// under post_host, as a cross-check.  The regions' sizes are on the host already (lcr_fragments), so this is known before anything is queued.
+// region in LDS) where it fits its LDS image, else k4_gpost (all CUs on the region).  The regions' sizes are on the host already
+// (lcr_fragments), so this is known before anything is queued.
 int PhaseHost::classify(PhaseCall& c) {
   const PhaseInputs& in = c.in;
   for (int g = 0; g < c.ng; g++) {
@@ -651,8 +431,7 @@ int PhaseHost::classify(PhaseCall& c) {
     if (S == 0) continue;
     if ((uint32_t)S <= c.prm.max_enum_snps) c.enum_slots.push_back(g); else c.chain_slots.push_back(g);
   }
-  const bool force_host_post = dbg.post_host != 0;
-  c.host_post.assign(c.ng, 0); c.grid_post.assign(c.ng, 0);
+  c.grid_post.assign(c.ng, 0);
   for (int g = 0; g < c.ng; g++) {
     const int S = in.snps(g);
     if (S == 0) continue;
@@ -663,8 +442,7 @@ int PhaseHost::classify(PhaseCall& c) {
     bool fits = !(nr_g > POST_MAX_ROWS || E_all > POST_MAX_ENTRIES || S > POST_MAX_SNPS);
     uint32_t need = 0;
     if (fits) { need = post_layout(nr_g, (uint32_t)E_all, S).total; if (need > 64 * 1024) fits = false; }
-    if (force_host_post) { c.host_post[g] = 1; c.any_host_post = true; }
-    else if (!fits || (c.grid_min == 0 && (uint32_t)S > c.prm.max_enum_snps)) {
+    if (!fits || (c.grid_min == 0 && (uint32_t)S > c.prm.max_enum_snps)) {
       c.grid_post[g] = 1; c.gpost_slots.push_back(g);
       c.gp_S = std::max(c.gp_S, (size_t)S); c.gp_rows = std::max(c.gp_rows, (size_t)nr_g); c.gp_E = std::max(c.gp_E, (size_t)E_all);
     } else c.post_lds = std::max(c.post_lds, need);
@@ -672,22 +450,11 @@ int PhaseHost::classify(PhaseCall& c) {
   return LCR_OK;
 }
 
-// queue `side`: the fragment matrix goes to the host (pinned) only when a region takes the host epilogue; the large regions' staging
-// with all CUs; then the host waits for the per-region sizes
+// queue `side`: the large regions' staging with all CUs; then the host waits for the per-region sizes
 int PhaseHost::wait_sizes(PhaseCall& c) {
-  const PhaseInputs& in = c.in; hipStream_t const sq = c.sq;
+  hipStream_t const sq = c.sq;
   PCHK(hipEventRecord(ev_in, sq));
   PCHK(hipStreamWaitEvent(side, ev_in, 0));
-  if (c.any_host_post) {
-    PCHK(h_row_ptr.reserve((c.nr1 + 1) * 8)); PCHK(h_col.reserve(c.nnz1 * 4));
-    PCHK(h_val.reserve(c.nnz1)); PCHK(h_links.reserve(c.nr1 * 4));
-    PCHK(hipMemcpyAsync(h_row_ptr.p, in.d_row_ptr, (size_t)(c.nrow + 1) * 8, hipMemcpyDeviceToHost, side));
-    if (c.nnz) {
-      PCHK(hipMemcpyAsync(h_col.p, in.d_col, (size_t)c.nnz * 4, hipMemcpyDeviceToHost, side));
-      PCHK(hipMemcpyAsync(h_val.p, in.d_val, (size_t)c.nnz, hipMemcpyDeviceToHost, side));
-    }
-    if (c.nrow) PCHK(hipMemcpyAsync(h_links.p, in.d_row_links, (size_t)c.nrow * 4, hipMemcpyDeviceToHost, side));
-  }
   if (c.ng) {
     if (!c.gstage_slots.empty()) {   // large regions: all CUs on one region at a time (every persistent launch goes to `side`)
       RCHK(c.lock_grid(*this));
@@ -700,15 +467,6 @@ int PhaseHost::wait_sizes(PhaseCall& c) {
   }
   if (c.async_mode) { PCHK(hipEventRecord(ev_user, sq)); PCHK(hipStreamWaitEvent(c.stream, ev_user, 0)); }
   HT("ph:presync");
-  if (!pool) {
-    // one ctx per GPU: share the host's hardware threads between the GPUs of the node
-    int ndev = 1;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) ndev = 1;
-    int nthreads = (int)std::thread::hardware_concurrency() / ndev;
-    if (dbg.host_threads > 0) nthreads = dbg.host_threads;
-    nthreads = std::max(1, std::min(nthreads, dbg.host_threads > 0 ? 256 : 48));
-    pool = new HostPool(nthreads > 1 ? nthreads : 0);
-  }
   if (c.ng) PCHK(hipStreamSynchronize(sq));
   HT("ph:synced");
   c.lap("stage + sizes");
@@ -786,7 +544,7 @@ int PhaseHost::launch_enum(PhaseCall& c) {
     spans[cls].push_back({g, (uint32_t)n_t[cls]});
     n_t[cls] += (size_t)((n + per_of[cls] - 1) / per_of[cls]);
     nj += (int64_t)n;
-    if (!c.host_post[g] && !c.grid_post[g]) (cls == CL_BITS ? post_slots_b : (cls == CL_BIG ? post_slots_c : post_slots)).push_back(g);
+    if (!c.grid_post[g]) (cls == CL_BITS ? post_slots_b : (cls == CL_BIG ? post_slots_c : post_slots)).push_back(g);
     if (c.prof && cls == CL_BIG) fprintf(stderr, "[phase]   global-memory enumeration region %d: R %d E %d S %d max_rows %d max_n %d, LDS image %u B\n", g, st.R, st.E, S, st.max_rows, st.max_n, EL.total);
   }
   if (c.prof) fprintf(stderr, "[phase]   enumeration classes: bit states %zu regions / %zu tiles, streaming %zu / %zu, global %zu / %zu\n",
@@ -937,7 +695,7 @@ int PhaseHost::launch_chain(PhaseCall& c) {
   }
   // post-phase: device epilogue for the chain regions that fit it
   std::vector<int32_t> post_slots;
-  for (int k = 0; k < nc; k++) if (!c.host_post[desc[k].slot] && !c.grid_post[desc[k].slot]) post_slots.push_back(desc[k].slot);
+  for (int k = 0; k < nc; k++) if (!c.grid_post[desc[k].slot]) post_slots.push_back(desc[k].slot);
   const size_t nps = post_slots.size();
   const size_t desc_bytes = ((size_t)nc * sizeof(ChainDesc) + 15) & ~(size_t)15;
   PCHK(h_ch_up.reserve(desc_bytes + nps * 4 + 64));
@@ -1074,16 +832,16 @@ int PhaseHost::launch_gpost(PhaseCall& c) {
 }
 
 // Everything is queued: the results become pending.  Returns false when run() returns now -- settle() collects them when somebody
-// asks --, true when it has to wait for them (synchronous mode, persistent launches, the host epilogue or phase_prof).
+// asks --, true when it has to wait for them (synchronous mode, persistent launches or phase_prof).
 bool PhaseHost::mark_pending(PhaseCall& c) {
   const PhaseInputs& in = c.in;
-  pend.ng = c.ng; pend.any_host_post = c.any_host_post;
-  pend.cand_off.assign(in.cand_region_off, in.cand_region_off + c.ng + 1); pend.host_post = c.host_post;
+  pend.ng = c.ng;
+  pend.cand_off.assign(in.cand_region_off, in.cand_region_off + c.ng + 1);
   pend.res_ps = c.res_ps; pend.res_tag = c.res_tag; pend.res_asg = c.res_asg; pend.hc_obj = c.hc_obj; pend.cand = in.cand;
   pending = true;
   HT("ph:ret");
   if (g_lcr_host_trace) lcr_host_trace_flush();
-  return !(c.async_mode && !c.prof && !c.any_host_post && !c.grid_lock.held);
+  return !(c.async_mode && !c.prof && !c.grid_lock.held);
 }
 
 // phase_prof: the enumeration regions' sizes, the steps of the last chain launch and of k4_post / k4_gpost (every queue is drained)
@@ -1148,7 +906,7 @@ int PhaseHost::report_prof(PhaseCall& c) {
     std::vector<std::pair<long long, int>> tot;
     for (int g = 0; g < ng; g++) {
       const int S = in.snps(g);
-      if (S == 0 || c.host_post[g] || c.grid_post[g] || ((uint32_t)S > c.prm.max_enum_snps) != (chain == 1)) continue;
+      if (S == 0 || c.grid_post[g] || ((uint32_t)S > c.prm.max_enum_snps) != (chain == 1)) continue;
       tot.push_back({clk[(size_t)g * 16 + 9] - clk[(size_t)g * 16], g});
     }
     if (tot.empty()) continue;
@@ -1170,82 +928,6 @@ int PhaseHost::report_prof(PhaseCall& c) {
   return LCR_OK;
 }
 
-// ---- host epilogue (thread.rs:168-201) for the regions that did not take k4_post.  Regions are independent (the
-// reference runs them as rayon tasks, thread.rs:77): a small host thread pool walks them; results do not depend
-// on the thread count (per-region RNG stream, disjoint output rows).
-int PhaseHost::host_epilogue(PhaseCall& c) {
-  const PhaseInputs& in = c.in; const lcr_params& prm = c.prm; const int ng = c.ng; hipStream_t const stream = c.stream;
-  std::vector<lcr_candidate>& cand = *in.cand;
-  uint8_t* const h_r = h_res.as<uint8_t>();   // (the host epilogue writes its regions' rows into the pinned block of k4_post's results)
-  int8_t* const h_tag = (int8_t*)(h_r + c.res_tag); uint8_t* const h_asg = h_r + c.res_asg; uint32_t* const h_ps = (uint32_t*)(h_r + c.res_ps);
-  PCHK(h_st_enum.reserve(c.st_bytes + 16)); PCHK(h_st_chain.reserve(c.st_bytes + 16));
-  int8_t* const st1 = h_st_enum.as<int8_t>(), * const st2 = h_st_chain.as<int8_t>();   // enumeration / chain results
-  PCHK(hipMemcpyAsync(st1, d_st_enum.p, c.st_bytes, hipMemcpyDeviceToHost, stream));
-  PCHK(hipMemcpyAsync(st2, d_st_chain.p, c.st_bytes, hipMemcpyDeviceToHost, stream));
-  PCHK(hipStreamSynchronize(stream));
-  if (!work) work = new PhaseWork();
-  PhaseWork& W = *static_cast<PhaseWork*>(work);
-  if ((int)W.R.size() < ng) W.R.resize(ng);
-  std::vector<RegionHost>& R = W.R;
-  auto epilogue = [&](int g) {
-    if (!c.host_post[g]) return;
-    RegionHost& rh = R[g];
-    rh.g = g; rh.c0 = in.cand_region_off[g]; rh.S = in.snps(g);
-    rh.r0 = in.row_region_off[g]; rh.nrow = in.row_region_off[g + 1] - rh.r0;
-    rh.row_ptr = h_row_ptr.as<int64_t>(); rh.col = h_col.as<int32_t>(); rh.val = h_val.as<uint8_t>(); rh.links = h_links.as<uint32_t>();
-    rh.cand = cand.data() + rh.c0;
-    rh.seed = region_seed(prm.seed, in.region_start0[g]);
-    rh.min_linkers = prm.min_linkers;
-    rh.e0 = rh.row_ptr[rh.r0];
-    const bool chain = (uint32_t)rh.S > prm.max_enum_snps;
-    const int64_t e1 = rh.row_ptr[rh.r0 + rh.nrow];
-    rh.phase_site.assign((size_t)(e1 - rh.e0), 0);
-    rh.tag.assign(rh.nrow, 0); rh.asg.assign(rh.nrow, 0); rh.fp.assign(rh.nrow, 0);
-    if ((int)rh.cover.size() < rh.S) rh.cover.resize(rh.S);
-    for (int i = 0; i < rh.S; i++) rh.cover[i].clear();
-    rh.fp_rows.clear();
-    rh.orig_flags.resize(rh.S);
-    for (int i = 0; i < rh.S; i++) rh.orig_flags[i] = rh.cand[i].flags;
-    for (int r = 0; r < rh.nrow; r++) {
-      for (int64_t e = rh.eb(r); e < rh.ee(r); e++) {
-        const int i = rh.lc(e);
-        rh.cover[i].push_back(r);
-        if (rh.fphase(i)) rh.phase_site[e - rh.e0] = 1;  // fragment.rs:144-146 snapshot
-      }
-      if (rh.links[rh.r0 + r] >= prm.min_linkers) { rh.fp[r] = 1; rh.fp_rows.push_back(r); }   // fragment.rs:253-255
-    }
-    // the optimiser's result
-    const int8_t* st = chain ? st2 : st1;
-    const int8_t* sg = st + c.st_sig + rh.r0; const int8_t* dl = st + c.st_del + rh.c0; const int8_t* et = st + c.st_eta + rh.c0;
-    for (size_t k = 0; k < rh.fp_rows.size(); k++) rh.tag[rh.fp_rows[k]] = sg[k];
-    for (int i = 0; i < rh.S; i++) { rh.cand[i].haplotype = dl[i]; rh.cand[i].genotype = et[i]; }
-    objective[g] = (double)(*((const long long*)(st + c.st_obj) + g)) / FX_SCALE;
-    // draws so far: thread.rs:162-163 (S + F, overwritten), then the optimiser's (see k4_post)
-    const uint64_t S = rh.S, F = rh.fp_rows.size();
-    rh.ctr = !chain ? S + F + ((uint64_t)1 << S) * F : 2 * (S + F) + (S / 4 + 1) * (S + F);
-    rh.assign_reads_haplotype(prm.read_assign_cutoff);
-    rh.assign_snp_haplotype_genotype();
-    rh.assign_reads_haplotype(prm.read_assign_cutoff);
-    rh.assign_snp_haplotype_genotype();
-    const float relaxed = prm.min_phase_score - 3.0f;
-    rh.eval_rescue(LCR_F_RNA_EDIT, relaxed, false);
-    rh.eval_rescue(LCR_F_CAND_SOMATIC, relaxed, true);
-    rh.assign_reads_haplotype(prm.read_assign_cutoff);
-    rh.assign_snp_haplotype_genotype();
-    for (int r = 0; r < rh.nrow; r++) h_ps[rh.r0 + r] = 0;
-    rh.assign_phase_set(prm.min_phase_score, h_ps);
-    for (int r = 0; r < rh.nrow; r++) { h_tag[rh.r0 + r] = rh.tag[r]; h_asg[rh.r0 + r] = rh.asg[r]; }
-  };
-  pool->parallel_for(ng, epilogue);
-  c.lap("host post-phase epilogue");
-  // keep the device copy of the candidates current (lcr_get_candidates_device)
-  for (int g = 0; g < ng; g++) {
-    const int c0 = in.cand_region_off[g], S = in.snps(g);
-    if (S && c.host_post[g]) PCHK(hipMemcpyAsync(const_cast<lcr_candidate*>(in.d_cand) + c0, cand.data() + c0, (size_t)S * sizeof(lcr_candidate), hipMemcpyHostToDevice, stream));
-  }
-  PCHK(hipStreamSynchronize(stream));
-  return LCR_OK;
-}
 #undef RCHK
 #undef PCHK
 #undef PCHK_TO

@@ -435,9 +435,12 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
     return sc.sync_or(chg) != 0;
   };
 
-  // snpfrags.rs:628-733: connected components of the PASS het SNPs (edges = allele-consistent SNP pairs of
-  // a read); component label = smallest SNP index (see RegionHost::assign_phase_set), by min-label
-  // propagation over the reads + pointer jumping until no edge joins two labels
+  // snpfrags.rs:628-733.  The reference builds a petgraph GraphMap whose nodes are the PASS het SNPs (added in index
+  // order), adds an edge per read and allele-consistent SNP pair, and walks kosaraju_scc: components come out in
+  // descending order of their first-inserted (= smallest-index) node, a component's phase set is pos+1 of that node,
+  // and a read takes the phase set of the first component in that order that owns one of its edges.  Here: connected
+  // components with component label = smallest SNP index, by min-label propagation over the reads + pointer jumping
+  // until no edge joins two labels; a read takes the largest label among the components that own one of its edges.
   auto phase_set = [&]() {
     for (int i = sc.tid(); i < S; i += sc.nt()) {
       const bool node = sgt[i] == 0 && svt[i] == 1 && !(sflags[i] & (LCR_F_DENSE | LCR_F_RNA_EDIT)) &&

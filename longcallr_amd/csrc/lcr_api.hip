@@ -244,7 +244,6 @@ int lcr_phase(lcr_ctx* c, const lcr_params* p) {
   if (p->ld_weight_threshold != 1) { c->err = "ld_weight_threshold must be 1: SNPFrag::phase is only ever called with 1 (thread.rs:166)"; return LCR_E_ARG; }
   const bool ds_on = c->ds_rows_set || c->ds_depth > 0;
   if (ds_on && !(p->read_assign_cutoff > 0.0)) { c->err = "down-sampling needs read_assign_cutoff > 0: the last read assignment must not depend on the sign of an unsampled row's haplotag"; return LCR_E_ARG; }
-  if (ds_on && c->phase.dbg.post_host) { c->err = "the post_host cross-check does not know the sample: switch it off while down-sampling is on"; return LCR_E_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = frag_settle(c); if (rc) return rc; }
   PhaseInputs in;
@@ -413,7 +412,6 @@ int lcr_get_read_records_device(lcr_ctx* c, const lcr_read_record** dev_rec, int
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = phase_settle(c); if (rc) return rc; }
   static_assert(sizeof(lcr_read_record) == 12, "lcr_read_record is 12 bytes");
-  { int rc = read_records_fresh(c); if (rc) return rc; }
   *dev_rec = c->phase.d_read_rec.as<lcr_read_record>();
   *n_rows = c->n_rows;
   return LCR_OK;
@@ -426,7 +424,6 @@ int lcr_collect_phase(lcr_ctx* c, lcr_phase_collected* out) {
   if (!c->res_valid) { c->err = "lcr_collect_phase: no phase results (call it after lcr_phase and before the next lcr_candidates)"; return LCR_E_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = phase_settle(c); if (rc) return rc; }
-  { int rc = read_records_fresh(c); if (rc) return rc; }
   out->n_regions = c->res_ng; out->n_rows = c->n_rows; out->n_cand = (int32_t)c->h_cand.size(); out->pad_ = 0;
   out->cand = c->h_cand.data(); out->cand_region_off = c->h_cand_off.data(); out->row_region_off = c->h_row_region_off.data();
   out->haplotag = c->phase.r_haplotag; out->assignment = c->phase.r_assignment; out->phase_set = c->phase.r_phase_set;
@@ -462,13 +459,11 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   PhaseDebug& d = c->phase.dbg;
   const std::string k(key);
   if (k == "phase_prof") d.prof = (int)value;
-  else if (k == "post_host") d.post_host = (int)value;
   else if (k == "grid_min_entries") d.grid_min = value;
   else if (k == "grid_generic") d.grid_generic = (int)value;
   else if (k == "post_half") d.post_half = (int)value;
   else if (k == "enum_force_big") d.enum_force_big = (int)value;
   else if (k == "enum_force_stream") d.enum_force_stream = (int)value;
-  else if (k == "host_threads") d.host_threads = (int)value;
   else if (k == "async_phase") d.async_phase = value != 0;
   else if (k == "host_trace") g_lcr_host_trace = value != 0;
   else if (k == "own_fill") g_lcr_own_fill = value != 0;

@@ -188,14 +188,5 @@ int upload(lcr_ctx* c, DevBuf& buf, const T* src, size_t n, const T** dst, int m
 // lcr_phase leaves its kernels in flight on the phase stage's own queues (lcr_phase_host.h): whoever needs its results, or is about
 // to overwrite what it reads / writes, collects them first
 inline int phase_settle(lcr_ctx* c) { return c->phase.settle(&c->err); }
-// regions that took the host epilogue (debug hook / fallback): the HBM records of lcr_get_read_records_device are rebuilt from the host arrays
-inline int read_records_fresh(lcr_ctx* c) {
-  if (!c->phase.read_rec_stale) return LCR_OK;
-  std::vector<lcr_read_record> h((size_t)std::max(c->n_rows, 0));
-  for (int r = 0; r < c->n_rows; r++) h[r] = lcr_read_record{r, c->phase.r_haplotag[r], c->phase.r_assignment[r], 0, c->phase.r_phase_set[r]};
-  if (c->n_rows) { const int rc2 = upload_bytes(c, c->phase.d_read_rec.p, h.data(), h.size() * sizeof(lcr_read_record)); if (rc2) return rc2; HIPCHK(c, hipStreamSynchronize(c->stream)); }
-  c->phase.read_rec_stale = false;
-  return LCR_OK;
-}
 int cand_settle(lcr_ctx* c);   // the candidate stage's host copies (lcr_calls.hip)
 int frag_settle(lcr_ctx* c);   // lcr_fragments' entry count (lcr_calls.hip)

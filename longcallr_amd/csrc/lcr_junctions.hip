@@ -10,7 +10,6 @@ int lcr_junctions(lcr_ctx* c, const lcr_junction_params* p) {
   if (c->stage < ST_PHASED) { c->err = "lcr_junctions before lcr_phase"; return LCR_E_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = phase_settle(c); if (rc) return rc; }       // an asynchronous phase stage in flight writes the read records
-  { int rc = read_records_fresh(c); if (rc) return rc; }
   static_assert(sizeof(lcr_junction) == 48, "lcr_junction is 48 bytes");
   c->junc_valid = false;   // (from here on the last call's table is overwritten)
   const BatchView& b = c->bv;

@@ -1,11 +1,6 @@
 // lcr_phase_host.h — host driver of the phasing stage (K4 kernels + sequential control).
 #pragma once
 #include <string>
-#include <atomic>
-#include <functional>
-#include <memory>
-#include <semaphore.h>
-#include <thread>
 
 #include "lcr_dev.h"
 #include "k4_types.h"
@@ -32,65 +27,10 @@ struct PhaseInputs {
   int snps(int g) const { return cand_region_off[g + 1] - cand_region_off[g]; }   // SNPs (candidates) of region g
 };
 
-// Persistent host worker pool: regions are independent units of host-side work (the reference runs
-// them as rayon tasks, thread.rs:77); parallel_for hands out region indices through an atomic counter.
-// Only as many workers as there are items are woken (one semaphore each: a broadcast on a condition variable
-// made every worker take the mutex in turn, ~3 us apiece, whatever the number of items), the caller takes a
-// share of the items itself, and the last worker to finish posts the completion semaphore.
-class HostPool {
- public:
-  explicit HostPool(int n) {
-    sem_init(&done_, 0, 0);
-    for (int i = 0; i < n; i++) {
-      w_.emplace_back(new Worker());
-      sem_init(&w_.back()->go, 0, 0);
-    }
-    for (int i = 0; i < n; i++) w_[i]->t = std::thread([this, i]() { loop(i); });
-  }
-  ~HostPool() {
-    stop_.store(true);
-    for (auto& w : w_) sem_post(&w->go);
-    for (auto& w : w_) { w->t.join(); sem_destroy(&w->go); }
-    sem_destroy(&done_);
-  }
-  int size() const { return (int)w_.size(); }
-  void parallel_for(int n, const std::function<void(int)>& fn) {
-    if (n <= 0) return;
-    if (w_.empty() || n == 1) { for (int i = 0; i < n; i++) fn(i); return; }
-    const int k = std::min(n - 1, (int)w_.size());
-    fn_ = &fn; n_ = n;
-    next_.store(0, std::memory_order_relaxed);
-    pending_.store(k, std::memory_order_release);
-    for (int i = 0; i < k; i++) sem_post(&w_[i]->go);
-    for (int i = next_.fetch_add(1); i < n; i = next_.fetch_add(1)) fn(i);
-    while (sem_wait(&done_) != 0) {}   // (EINTR)
-    fn_ = nullptr;
-  }
- private:
-  struct Worker { std::thread t; sem_t go; };
-  void loop(int w) {
-    for (;;) {
-      while (sem_wait(&w_[w]->go) != 0) {}
-      if (stop_.load()) return;
-      const std::function<void(int)>* fn = fn_;
-      const int n = n_;
-      for (int i = next_.fetch_add(1); i < n; i = next_.fetch_add(1)) (*fn)(i);
-      if (pending_.fetch_sub(1, std::memory_order_acq_rel) == 1) sem_post(&done_);
-    }
-  }
-  std::vector<std::unique_ptr<Worker>> w_;
-  sem_t done_;
-  const std::function<void(int)>* fn_ = nullptr;
-  int n_ = 0;
-  std::atomic<int> next_{0}, pending_{0};
-  std::atomic<bool> stop_{false};
-};
-
 // Debug / test switches of the phase stage (lcr_debug_set, include/lcr.h): none of them is read from the environment inside
 // the library; the defaults are the product behaviour.
 struct PhaseDebug {
   int prof = 0;                 // "phase_prof": per-step timers to stderr (2: also the per-workgroup histogram)
-  int post_host = 0;            // "post_host": every region through the host epilogue (cross-check of k4_post)
   long long grid_min = -1;      // "grid_min_entries": chain regions with at least this many phase entries get all CUs (-1: 2^17)
   int grid_generic = 0;         // "grid_generic": fenced grid barriers only
   int post_half = 0;            // "post_half": the eight-wave epilogue of the chain regions
@@ -101,7 +41,6 @@ struct PhaseDebug {
   int redo_lds = 64 * 1024;     // "redo_lds": bytes of dynamic LDS of the enumeration branch's repair pass (k4_enum_redo: state + matrix of a restart's region where they fit; 0: global memory)
   int chain_ties = 1;           // "chain_ties": chain regions of workgroup scope that meet a class-2 / class-4 tie run again under the complete tie contract (0: counted as unresolved)
   int tie_arith = 3;            // "tie_arith": which exact fixed-point ties the reference-order f64 arithmetic decides (PhaseDev::tie_arith; 3 = all that liblcr resolves)
-  int host_threads = 0;         // "host_threads": size of the host pool of the host epilogue (0: hardware threads / devices, <= 48)
   int async_phase = 0;          // "async_phase": lcr_phase returns when its kernels are queued (on a queue of its own); settle() collects the results
 };
 
@@ -110,11 +49,8 @@ struct PhaseCall;   // k4_phase.hip
 struct PhaseHost {
   PhaseDebug dbg;
   std::string lock_dir;          // directory of the per-GPU lock file of persistent launches ("" = /tmp/liblcr-<uid>)
-  std::vector<int8_t> haplotag;
-  std::vector<uint8_t> assignment;
-  std::vector<uint32_t> phase_set;
   std::vector<double> objective;
-  const int8_t* r_haplotag = nullptr;      // results of the last run (host vectors above or pinned buffers)
+  const int8_t* r_haplotag = nullptr;      // results of the last run: per row, in the pinned block k4_post / k4_gpost wrote (h_res)
   const uint8_t* r_assignment = nullptr;
   const uint32_t* r_phase_set = nullptr;
   // ---- buffers, by the step that uses them (each grows to the largest batch seen; freed with the context)
@@ -141,16 +77,14 @@ struct PhaseHost {
   DevBuf d_gp_snp, d_gp_ent, d_gp_part;   // k4_gpost scratch: per SNP and row, per entry, partial counts
   // pinned: region sizes (k4_stage), k4_post's results and candidate mirror | objectives, tie census, the two upload tables
   HostBuf h_stat, h_res, h_cand_obj, h_census, h_en_up, h_ch_up;
-  HostBuf h_row_ptr, h_col, h_val, h_links, h_st_enum, h_st_chain;   // host-epilogue copies: fragment matrix, both states
   unsigned long long tie_census[TIE_NCTR] = {0, 0, 0, 0, 0, 0, 0, 0};   // of the last run (lcr_get_tie_census)
-  bool read_rec_stale = false;   // some regions took the host epilogue: the records are rebuilt from the host arrays on demand
-  hipStream_t side = nullptr;   // second queue: fragment matrix download + chain regions
+  hipStream_t side = nullptr;   // second queue: chain regions, every persistent launch
   hipEvent_t ev_in = nullptr, ev_csr = nullptr, ev_fork = nullptr, ev_join = nullptr;
   hipStream_t aux = nullptr;   // the bit-state and global-memory enumeration classes beside the streaming class
   // lcr_debug_set("async_phase", 1) (round 5, opt-in): the stage's FIRST queue is its own too, lcr_phase returns when everything is
   // queued, the caller's stream is free for the next batch's lcr_load_batch / lcr_pileup, and the results are collected by
   // settle(): every getter, lcr_ctx_sync, the next lcr_candidates / lcr_phase call it.  Persistent all-CU launches (device
-  // lock), the host epilogue and phase_prof settle before run() returns.  Default: the caller's stream, settle() inside run().
+  // lock) and phase_prof settle before run() returns.  Default: the caller's stream, settle() inside run().
   hipStream_t main_q = nullptr, q_first = nullptr;   // q_first: the queue the last run() used as its first
   // async_phase: the next batch's pileup is gated on these -- recorded behind the enumeration restarts on the stage's first queue and
   // on `aux`: the dense part of the stage.  What follows them (repair pass, resolve, post-phase: a few hundred workgroups) leaves
@@ -166,33 +100,28 @@ struct PhaseHost {
   hipEvent_t ev_user = nullptr;
   bool pending = false;
   struct Pending {
-    int ng = 0; bool any_host_post = false;
-    std::vector<int32_t> cand_off; std::vector<uint8_t> host_post;
+    int ng = 0;
+    std::vector<int32_t> cand_off;
     size_t res_ps = 0, res_tag = 0, res_asg = 0, hc_obj = 0;
     std::vector<lcr_candidate>* cand = nullptr;
   } pend;
   int settle(std::string* err);
-  HostPool* pool = nullptr;
-  void* work = nullptr;   // PhaseWork (k4_phase.hip): per-region host state reused across calls
   ChainDev chain_dev{};                // chain-region buffers of the last run (LD blocks are read back from them)
   std::vector<ChainDesc> chain_desc;
   std::vector<uint64_t> enum_keys;                   // scratch of the enumeration launch preparation, kept across calls
   std::vector<int64_t> enum_job_base, enum_st_base;
   // LD blocks of one region of the last run in the reference's order (candidate.rs:733-745): off[n_blocks + 1], SNP indices
   int ld_blocks(const PhaseInputs& in, int region, std::vector<int32_t>* off, std::vector<int32_t>* snps, hipStream_t s, std::string* err);
-  void free_work();
   int run(const PhaseInputs& in, const lcr_params& p, hipStream_t s, std::string* err);
   // the steps of run(), in order (k4_phase.hip); PhaseCall holds the values of one call
   int open_queues(PhaseCall& c), size_buffers(PhaseCall& c), sample(PhaseCall& c), stage(PhaseCall& c), classify(PhaseCall& c), wait_sizes(PhaseCall& c);
-  int launch_enum(PhaseCall& c), launch_chain(PhaseCall& c), launch_gpost(PhaseCall& c), report_prof(PhaseCall& c), host_epilogue(PhaseCall& c);
+  int launch_enum(PhaseCall& c), launch_chain(PhaseCall& c), launch_gpost(PhaseCall& c), report_prof(PhaseCall& c);
   bool mark_pending(PhaseCall& c);
-  // queues, events, host pool and host work (the buffers free themselves; the owner has drained the queues: lcr_ctx_destroy)
+  // queues and events (the buffers free themselves; the owner has drained the queues: lcr_ctx_destroy)
   void release() {
     for (hipStream_t* q : {&side, &aux, &main_q}) { if (*q) (void)hipStreamDestroy(*q); *q = nullptr; }
     for (hipEvent_t* e : {&ev_in, &ev_csr, &ev_fork, &ev_join, &ev_user, &ev_gate[0], &ev_gate[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     gate_set[0] = gate_set[1] = false;
     pending = false;
-    delete pool; pool = nullptr;
-    free_work();
   }
 };

@@ -317,17 +317,17 @@ def test_contract_and_reentry(engine_cls):
     assert snap(E) == on
     stage(E); E.get_fragments().phase()
     assert snap(E) == base
-    # read_assign_cutoff <= 0 and the post_host cross-check are refused while down-sampling is on, and nothing has changed
+    # read_assign_cutoff <= 0 is refused while down-sampling is on, and nothing has changed; the keys of the host epilogue are unknown
     E.set_downsample(64)
     stage(E); E.get_fragments()
     E.params = prm0
     with pytest.raises(LcrError, match=r"\(-1\)"):
         E.phase()
     E.params = prm
-    E.debug_set("post_host", 1)
     with pytest.raises(LcrError, match=r"\(-1\)"):
-        E.phase()
-    E.debug_set("post_host", 0)
+        E.debug_set("post_host", 1)
+    with pytest.raises(LcrError, match=r"\(-1\)"):
+        E.debug_set("host_threads", 4)
     E.phase()
     assert snap(E) == on
     E.close()
