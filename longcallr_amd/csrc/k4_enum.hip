@@ -74,7 +74,18 @@ __device__ __forceinline__ EnumTile enum_tile_of(const PhaseDev& P, const EnumSp
 //      the winner's state goes to the region's result slots (no re-run of the winning restart).
 // ---------------------------------------------------------------------------------------------
 // measurement build (-DENUM_PROF): the slowest workgroup's time (10 ns units) up to a point of k4_enum_resolve -> tie census slot i
-#ifdef ENUM_PROF
+// (-DENUM_PROF=2: the slots carry the restart kernels' step counts instead -- ENUM_STEP(k), k = 0: sigma steps executed, 1: skipped, 2: delta
+// steps executed, 3: skipped, each weighted by the region's phase entries; k4_enum_bits: slots 0 - 3, k4_enum_reg: 4 - 7; tools/prof_decode.py)
+#if defined(ENUM_PROF) && ENUM_PROF == 2
+#define ENUM_PROF_STEPS 1
+#define ENUM_STEP(k) do { prof_steps[k] += (unsigned long long)E; } while (0)
+#define ENUM_STEP_FLUSH(base) do { if (lane == 0) for (int k = 0; k < 4; k++) atomicAdd(&P.tie_ctr[(base) + k], prof_steps[k]); } while (0)
+#else
+#define ENUM_STEP(k) do { } while (0)
+#define ENUM_STEP_FLUSH(base) do { } while (0)
+#endif
+#if defined(ENUM_PROF) && !defined(ENUM_PROF_STEPS)
+#define ENUM_PROF_TIMES 1
 #define ENUM_PT(i) do { if (threadIdx.x == 0) atomicMax(&P.tie_ctr[i], (unsigned long long)((long long)wall_clock64() - prof_t0)); } while (0)
 #else
 #define ENUM_PT(i) do { } while (0)
@@ -180,7 +191,7 @@ k4_enum_resolve(PhaseDev P, const EnumSpan* __restrict__ spans, const int64_t* _
   dif = 0;
 #endif
   if (dif && P.tie_arith < 1) { if (tid == 0) TIE_COUNT(P.tie_ctr, TIE_BEST_UNRES, 1ull); dif = 0; }
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
   long long prof_t5 = 0;
   __shared__ uint32_t s_tloc[ENUM_WAVES], s_tfull[ENUM_WAVES];
   if (tid < ENUM_WAVES) { s_tloc[tid] = 0; s_tfull[tid] = 0; }
@@ -351,7 +362,7 @@ k4_enum_resolve(PhaseDev P, const EnumSpan* __restrict__ spans, const int64_t* _
 #endif
     const uint32_t n_ev = min(s_nev, EVCAP);
     ENUM_PT(5);
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
     prof_t5 = (long long)wall_clock64();
 #endif
     // ---- chunks of the restarts of maximal objective, in ascending order
@@ -360,7 +371,7 @@ k4_enum_resolve(PhaseDev P, const EnumSpan* __restrict__ spans, const int64_t* _
       const uint32_t n = min(ENUM_TCAP, n_tied - cur);
       if ((uint32_t)tid < n) t_e[tid] = tl[cur + tid];
       __syncthreads();
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
       const long long pf0 = (long long)wall_clock64();
 #endif
       // ---- a lane per configuration: rows that differ from the reference's, each re-added from the reference's running sum
@@ -446,12 +457,12 @@ k4_enum_resolve(PhaseDev P, const EnumSpan* __restrict__ spans, const int64_t* _
           if (!fallback) t_sum[tid] = finish();
         }
       }
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
       const long long pf1 = (long long)wall_clock64();
       if (lane == 0) atomicAdd(&s_tloc[wave], (uint32_t)(pf1 - pf0));
 #endif
       if (__ballot(fallback)) { if (fallback) t_sum[tid] = full_sum(my_e, dneg, eta0, etap); }
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
       if (lane == 0) atomicAdd(&s_tfull[wave], (uint32_t)((long long)wall_clock64() - pf1));
 #endif
 #ifdef ENUM_VERIFY   // (measurement build: every sum that left the reference's chain, once more by adding all terms)
@@ -479,7 +490,7 @@ k4_enum_resolve(PhaseDev P, const EnumSpan* __restrict__ spans, const int64_t* _
     }
   }
   if (dif) ENUM_PT(6);
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
   __shared__ unsigned long long s_prof;
   if (tid == 0) s_prof = 0;
   __syncthreads();
@@ -495,7 +506,7 @@ k4_enum_resolve(PhaseDev P, const EnumSpan* __restrict__ spans, const int64_t* _
   }
   for (int row = tid; row < R; row += nt) P.st_sigma[rd.sig_off + row] = (int8_t)(((ld_st(we, (uint32_t)row >> 6) >> (row & 63)) & 1ull) ? -1 : 1);
   if (tid == 0) P.st_obj[slot] = best;
-#ifdef ENUM_PROF
+#ifdef ENUM_PROF_TIMES
   __syncthreads();
   if (tid == 0) atomicMax(&P.tie_ctr[7], ((unsigned long long)(((long long)wall_clock64() - prof_t0) & 0xfffff) << 44) | s_prof);
 #endif
@@ -635,6 +646,9 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
   unsigned long long* const st_reg = st_words + st_base[t.slot];
   const uint32_t stw = enum_state_words((uint32_t)R);
   uint32_t n_tie_f64 = 0, n_tie_flip = 0, n_dtie = 0, n_step = 0, n_tie_unres = 0;   // census of this wave's restarts (lane 0 adds them up at the end)
+#ifdef ENUM_PROF_STEPS
+  unsigned long long prof_steps[4] = {0, 0, 0, 0};
+#endif
   // my rows of more than two entries (a bit per row of the lane) (the rows whose tie needs the f64 scores, see the sigma step)
   unsigned long long bigm = 0;
   for (int row = r_a; row < (int)first_row[lane + 1]; row++) if (rp[row + 1] - rp[row] > 2) bigm |= 1ull << (row - r_a);
@@ -659,9 +673,13 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
     int iters = 0;
     long long obj_i = 0;
     const uint32_t ev0 = n_dtie + n_step, n_step0 = n_step, n_dtie0 = n_dtie;   // (wave-uniform) this restart's ties at a delta / eta maximum + tie-only steps
+    // step elision (P.enum_elide; see k4_enum_bits): a step whose inputs have not changed since it last ran is not executed -- it would change
+    // nothing and meet the ties of that run again, which are counted
+    bool need_sigma = true, need_delta = true;   // (wave-uniform) (delta, eta) / sigma changed since the last sigma / delta step
+    uint32_t last_tie = 0, last_dtie = 0;        // the lane's tied rows in the last executed sigma step; (wave-uniform) ties at a maximum in the last delta step
     while (hg_inc | h_inc) {
       // ---- sigma step (phase.rs:824-862)
-      {
+      if (!P.enum_elide || need_sigma) {
         const unsigned long long w0 = sgb[r_a >> 6], w1 = sgb[(r_a >> 6) + 1];
         const unsigned long long win = (wsh ? (w0 >> wsh) | (w1 << (64 - wsh)) : w0);
         int alo = 0, ahi = 0;
@@ -697,6 +715,8 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
 #ifdef ENUM_ABL_NOTIE
         tm = 0;
 #endif
+        last_tie = (uint32_t)__popcll(tm);
+        bool tflip = false;   // (wave-uniform) a tied row flipped
         if (P.tie_arith < 2) { if (tm) n_tie_unres += (uint32_t)__popcll(tm); }
         else if (__ballot(tm != 0)) {
           n_tie_f64 += (uint32_t)__popcll(tm);
@@ -726,7 +746,8 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
             if (enum_tie_row_flips(r_a + roff, (uint32_t)(win >> roff) & 1u, dneg, eta0, etap, rp, ent16, lut)) { fm |= 1ull << roff; nfl++; }
           }
           n_tie_flip += nfl;
-          if (!any && __ballot(nfl != 0)) n_step++;   // only tie flips: "no improvement" (check_new_haplotag's sums are not formed)
+          tflip = __ballot(nfl != 0) != 0;
+          if (!any && tflip) n_step++;   // only tie flips: "no improvement" (check_new_haplotag's sums are not formed)
         }
         if (fm) {
           atomicXor(&sgb[r_a >> 6], fm << wsh);
@@ -734,67 +755,82 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
         }
         wave_lds_sync();
         if (!any) h_inc = false; else { h_inc = true; hg_inc = true; }
+        need_delta = any || tflip || iters == 0;   // (the first delta step always runs: its masks are the start masks, not a step's)
+        ENUM_STEP(0);
+      } else {   // the same rows tie again, none flips
+        if (P.tie_arith < 2) n_tie_unres += last_tie; else n_tie_f64 += last_tie;
+        h_inc = false; need_delta = false;
+        ENUM_STEP(1);
       }
-      // ---- delta / eta step (phase.rs:872-959): a lane's chunk is CSC-ordered (SNP index non-decreasing)
-      {
-        constexpr int HB = 8;   // look-ups of one batch in flight, then its run-length flush
-        int cur = -1; int alo = 0, ahi = 0;
-        auto del_batch = [&](const uint32_t* v8) {
-          uint32_t sw[HB]; uint2 wq[HB];
+      if (!P.enum_elide || need_delta) {
+        // ---- delta / eta step (phase.rs:872-959): a lane's chunk is CSC-ordered (SNP index non-decreasing)
+        {
+          constexpr int HB = 8;   // look-ups of one batch in flight, then its run-length flush
+          int cur = -1; int alo = 0, ahi = 0;
+          auto del_batch = [&](const uint32_t* v8) {
+            uint32_t sw[HB]; uint2 wq[HB];
 #pragma unroll
-          for (int x = 0; x < HB; x++) {
-            const uint32_t row = v8[x] & 0xffffu;
-            sw[x] = ((const uint32_t*)sgb)[row >> 5];
-            wq[x] = wl2[(v8[x] >> 22) & 31u];
-          }
-#pragma unroll
-          for (int x = 0; x < HB; x++) {
-            const uint32_t v = v8[x];
-            const int i = (v >> 16) & 31;
-            const uint32_t hit = ((v >> 21) ^ (sw[x] >> (v & 31u)) ^ (dneg >> i)) & (v >> 31);
-            if ((v >> 31) && i != cur) {
-              if (alo | ahi) atomicAdd(&Macc[cur], (unsigned long long)(((long long)ahi << 23) + alo));
-              cur = i; alo = 0; ahi = 0;
+            for (int x = 0; x < HB; x++) {
+              const uint32_t row = v8[x] & 0xffffu;
+              sw[x] = ((const uint32_t*)sgb)[row >> 5];
+              wq[x] = wl2[(v8[x] >> 22) & 31u];
             }
-            alo += __mul24((int)hit, (int)wq[x].x);
-            ahi += __mul24((int)hit, (int)wq[x].y);   // sign-extends the 24-bit hi limb
-          }
-        };
-        for (int h = 0; h < n_del; h += HB) {
-          uint32_t v8[HB];
 #pragma unroll
-          for (int x = 0; x < HB; x++) v8[x] = c0 + h + x < c1 ? csc[c0 + h + x] : 0;
-          del_batch(v8);
+            for (int x = 0; x < HB; x++) {
+              const uint32_t v = v8[x];
+              const int i = (v >> 16) & 31;
+              const uint32_t hit = ((v >> 21) ^ (sw[x] >> (v & 31u)) ^ (dneg >> i)) & (v >> 31);
+              if ((v >> 31) && i != cur) {
+                if (alo | ahi) atomicAdd(&Macc[cur], (unsigned long long)(((long long)ahi << 23) + alo));
+                cur = i; alo = 0; ahi = 0;
+              }
+              alo += __mul24((int)hit, (int)wq[x].x);
+              ahi += __mul24((int)hit, (int)wq[x].y);   // sign-extends the 24-bit hi limb
+            }
+          };
+          for (int h = 0; h < n_del; h += HB) {
+            uint32_t v8[HB];
+#pragma unroll
+            for (int x = 0; x < HB; x++) v8[x] = c0 + h + x < c1 ? csc[c0 + h + x] : 0;
+            del_batch(v8);
+          }
+          if (alo | ahi) atomicAdd(&Macc[cur], (unsigned long long)(((long long)ahi << 23) + alo));
         }
-        if (alo | ahi) atomicAdd(&Macc[cur], (unsigned long long)(((long long)ahi << 23) + alo));
+        wave_lds_sync();
+        bool changed = false, dtie = false;
+        int d_new = (dneg >> lane) & 1u, h_new = ((eta0 >> lane) & 1u) ? 0 : (((etap >> lane) & 1u) ? 1 : -1);
+        if (live) {
+          const long long M = (long long)Macc[lane];
+          Macc[lane] = 0;
+          const long long N0 = cF + M + het, N1 = cF + cW - M + het;
+          int ch = 0; long long nb = N0;                       // first maximum (phase.rs:908-921)
+          if (N1 > nb) { ch = 1; nb = N1; }
+          if (cRef > nb) { ch = 2; nb = cRef; }
+          if (cVar > nb) { ch = 3; nb = cVar; }
+          dtie = (int)(N0 == nb) + (int)(N1 == nb) + (int)(cRef == nb) + (int)(cVar == nb) > 1;   // a tie at the maximum: the first one is kept
+          const long long ncur = h_new == 0 ? N0 : (h_new == 1 ? cRef : cVar);
+          changed = nb > ncur;
+          if (ch == 1) d_new ^= 1;
+          h_new = ch <= 1 ? 0 : (ch == 2 ? 1 : -1);
+          obj_i = ch <= 1 ? nb - het : (ch == 2 ? cRef - P.lut.f_homref : cVar - P.lut.f_homvar);
+        }
+        const uint32_t dneg_n = (uint32_t)__ballot(lane < S && d_new);
+        const uint32_t eta0_n = (uint32_t)__ballot(lane < S && h_new == 0);
+        const uint32_t etap_n = (uint32_t)__ballot(lane < S && h_new == 1);
+        const bool any2 = __ballot(changed) != 0;
+        last_dtie = (uint32_t)__popcll(__ballot(dtie));
+        n_dtie += last_dtie;
+        need_sigma = dneg_n != dneg || eta0_n != eta0 || etap_n != etap;
+        if (!any2 && need_sigma) n_step++;   // only tie changes in this step
+        dneg = dneg_n; eta0 = eta0_n; etap = etap_n;
+        wave_lds_sync();
+        if (!any2) hg_inc = false; else { hg_inc = true; h_inc = true; }
+        ENUM_STEP(2);
+      } else {   // the same SNPs tie at their maximum again: first maximum, the masks stay
+        n_dtie += last_dtie;
+        hg_inc = false; need_sigma = false;
+        ENUM_STEP(3);
       }
-      wave_lds_sync();
-      bool changed = false, dtie = false;
-      int d_new = (dneg >> lane) & 1u, h_new = ((eta0 >> lane) & 1u) ? 0 : (((etap >> lane) & 1u) ? 1 : -1);
-      if (live) {
-        const long long M = (long long)Macc[lane];
-        Macc[lane] = 0;
-        const long long N0 = cF + M + het, N1 = cF + cW - M + het;
-        int ch = 0; long long nb = N0;                       // first maximum (phase.rs:908-921)
-        if (N1 > nb) { ch = 1; nb = N1; }
-        if (cRef > nb) { ch = 2; nb = cRef; }
-        if (cVar > nb) { ch = 3; nb = cVar; }
-        dtie = (int)(N0 == nb) + (int)(N1 == nb) + (int)(cRef == nb) + (int)(cVar == nb) > 1;   // a tie at the maximum: the first one is kept
-        const long long ncur = h_new == 0 ? N0 : (h_new == 1 ? cRef : cVar);
-        changed = nb > ncur;
-        if (ch == 1) d_new ^= 1;
-        h_new = ch <= 1 ? 0 : (ch == 2 ? 1 : -1);
-        obj_i = ch <= 1 ? nb - het : (ch == 2 ? cRef - P.lut.f_homref : cVar - P.lut.f_homvar);
-      }
-      const uint32_t dneg_n = (uint32_t)__ballot(lane < S && d_new);
-      const uint32_t eta0_n = (uint32_t)__ballot(lane < S && h_new == 0);
-      const uint32_t etap_n = (uint32_t)__ballot(lane < S && h_new == 1);
-      const bool any2 = __ballot(changed) != 0;
-      n_dtie += (uint32_t)__popcll(__ballot(dtie));
-      if (!any2 && (dneg_n != dneg || eta0_n != eta0 || etap_n != etap)) n_step++;   // only tie changes in this step
-      dneg = dneg_n; eta0 = eta0_n; etap = etap_n;
-      wave_lds_sync();
-      if (!any2) hg_inc = false; else { hg_inc = true; h_inc = true; }
       if (++iters > 20) break;  // phase.rs:967-972
     }
     // A restart that met such a tie took "first maximum" / "no improvement" there.  With the complete tie contract (tie_arith >= 3) it
@@ -867,6 +903,7 @@ k4_enum_reg(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uin
     if (n_dtie) TIE_COUNT(P.tie_ctr, TIE_DELTA_UNRES, (unsigned long long)n_dtie);
     if (n_step) TIE_COUNT(P.tie_ctr, TIE_STEP_UNRES, (unsigned long long)n_step);
   }
+  ENUM_STEP_FLUSH(4);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -888,6 +925,9 @@ __device__ __forceinline__ int enum_mad24(int a, int b, int c) { int d; asm("v_m
 
 #ifndef ENUM_BITS_OCC
 #define ENUM_BITS_OCC 2
+#endif
+#ifndef ENUM_ITER_CAP
+#define ENUM_ITER_CAP 20   // phase.rs:967-972 (-DENUM_ITER_CAP=0 / 1: measurement builds -- k4_enum_bits with one / two iterations per restart, for the share of the sigma / delta steps in its time)
 #endif
 __global__ void __launch_bounds__(64 * ENUM_WAVES, ENUM_BITS_OCC)   // (waves per SIMD the register allocation aims at; -DENUM_BITS_OCC: measurement builds)
 k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, uint32_t per, const int64_t* __restrict__ job_base,
@@ -1040,6 +1080,8 @@ k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, ui
   uint32_t* const ms = (uint32_t*)(mt + 32);                                    // [3][8]: dneg, eta0, etap of every restart
   uint32_t* const tq = ms + 24;                                            // queue of tied rows: row | tie8 << 16 | sneg8 << 24
   uint32_t* const tq_n = tq + ENUM_TQ;
+  __shared__ uint32_t s_tcnt[ENUM_WAVES][8];
+  uint32_t* const tcnt = s_tcnt[wave];   // sigma ties of every restart in the wave's last executed sigma step (a skipped step meets them again)
   const int c0 = min((int)E, lane * (int)c), c1 = min((int)E, (lane + 1) * (int)c);
   const int n_del = (int)min(c, E);
   const uint32_t smask = S >= 32 ? 0xffffffffu : ((1u << S) - 1u);
@@ -1049,6 +1091,9 @@ k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, ui
   const uint32_t stw = enum_state_words((uint32_t)R);
   uint32_t n_tie_f64 = 0, n_tie_flip = 0, n_tie_unres = 0;   // per lane
   uint32_t n_dtie = 0, n_step = 0;                          // wave-uniform
+#ifdef ENUM_PROF_STEPS
+  unsigned long long prof_steps[4] = {0, 0, 0, 0};
+#endif
   const int n_pass = (S + 7) >> 3;
   for (uint32_t g0 = 8u * wave; g0 < t.ne; g0 += 8u * ENUM_WAVES) {
     const uint32_t e_base = t.e0 + g0;                      // (a multiple of 8: restart s of the group is e_base + s)
@@ -1092,77 +1137,90 @@ k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, ui
 #pragma unroll
     for (int s = 0; s < 8; s++) { ev_d[s] = 0; ev_s[s] = 0; }
     long long objl[4] = {0, 0, 0, 0};   // lane (state, SNP of pass p): the chosen branch's data term of the restart's last iteration
+    // Step elision (P.enum_elide): a sigma step is a function of (sigma, delta, eta) and a second one behind unchanged (delta, eta) flips no row (a
+    // flipped row has its two scores swapped; a tied row was decided by q < qn, false after the flip); a delta / eta step is the first maximum
+    // per SNP and a second one behind an unchanged sigma changes no mask.  So a step runs only if some active restart of the group had the
+    // other half of its state changed since its last step of that kind (tie flips count), and then for all eight as before.  A skipped step leaves
+    // what the executed one would: no change (loop control below), the same ties met once more (census), objl[] of the last executed step.
+    uint32_t need_sigma8 = 0xFFu, need_delta8 = 0xFFu;   // (wave-uniform) restarts whose (delta, eta) / sigma changed since their last sigma / delta step
+    uint32_t ld_dt[8];   // ties at a maximum each restart met in its last executed delta step
+#pragma unroll
+    for (int s = 0; s < 8; s++) ld_dt[s] = 0;
     while (act) {
-      // ---- the SNPs' masks of this iteration from the restarts' masks
-      if (lane < 32) {
-        uint32_t dn = 0, h8 = 0, ep = 0;
-#pragma unroll
-        for (int s = 0; s < 8; s++) { dn |= ((ms[s] >> lane) & 1u) << s; h8 |= ((ms[8 + s] >> lane) & 1u) << s; ep |= ((ms[16 + s] >> lane) & 1u) << s; }
-        mt[lane] = make_uint2(enum_spread8(h8) | (enum_spread8(dn) << 16), dn | (h8 << 8) | (ep << 16));
-      }
-      wave_lds_sync();
-      // ---- sigma step (phase.rs:824-862)
       uint32_t any8 = 0, tflip8 = 0;
-      {
-        int alo[8], ahi[8];
+      if (!P.enum_elide || (need_sigma8 & act)) {
+        // ---- the SNPs' masks of this iteration from the restarts' masks
+        if (lane < 32) {
+          uint32_t dn = 0, h8 = 0, ep = 0;
 #pragma unroll
-        for (int s = 0; s < 8; s++) { alo[s] = 0; ahi[s] = 0; }
-        for (int g = 0; g < nG; g++) {   // 64 rows of (nearly) one length, a lane per row
-          const int gb = __builtin_amdgcn_readfirstlane((int)gof[g]), Lg = __builtin_amdgcn_readfirstlane((int)gof[g + 1]) - gb;
-          const int kq = 64 * g + lane;
-          const int row = kq < nM ? (int)perm[kq] : 0;
-          const uint32_t sgb = kq < nM ? (uint32_t)sg8[row] : 0u;
-          const uint32_t sg16 = enum_spread8(sgb);
-          const uint2* const pe = csr + 64 * gb + lane;
-          uint32_t uacc = 0;
-          for (int x0 = 0; x0 < Lg; x0 += 2) {   // (two entries per step: most groups are two to four long, and Lg is the wave's)
-            const bool two = x0 + 1 < Lg;
-            uint2 v[2]; uint32_t mmv[2];
-            v[0] = pe[64 * x0]; v[1] = two ? pe[64 * (x0 + 1)] : make_uint2(0, 0);
-            mmv[0] = mt[(v[0].x >> 24) & 31u].x; mmv[1] = mt[(v[1].x >> 24) & 31u].x;
+          for (int s = 0; s < 8; s++) { dn |= ((ms[s] >> lane) & 1u) << s; h8 |= ((ms[8 + s] >> lane) & 1u) << s; ep |= ((ms[16 + s] >> lane) & 1u) << s; }
+          mt[lane] = make_uint2(enum_spread8(h8) | (enum_spread8(dn) << 16), dn | (h8 << 8) | (ep << 16));
+          if (lane < 8) tcnt[lane] = 0;
+        }
+        wave_lds_sync();
+        // ---- sigma step (phase.rs:824-862)
+        {
+          int alo[8], ahi[8];
 #pragma unroll
-            for (int u = 0; u < 2; u++) {
-              if (u == 1 && !two) break;
-              const uint32_t v0 = v[u].x, v1 = v[u].y;
-              const uint32_t m = v0 >> 24;
-              const uint32_t mm = mmv[u];
-              const uint32_t use16 = (m & 128u) ? (mm & 0xFFFFu) : 0u;                          // het sites only (a zero word: behind the row's last entry)
-              const uint32_t hit16 = (((m & 32u) ? 0x5555u : 0u) ^ sg16 ^ (mm >> 16)) & use16;   // p == sigma * delta
-              const uint32_t code = use16 | ((hit16 ^ use16) << 1);                              // 01: +w (A), 11: -w (B)
-              uacc |= use16;
+          for (int s = 0; s < 8; s++) { alo[s] = 0; ahi[s] = 0; }
+          for (int g = 0; g < nG; g++) {   // 64 rows of (nearly) one length, a lane per row
+            const int gb = __builtin_amdgcn_readfirstlane((int)gof[g]), Lg = __builtin_amdgcn_readfirstlane((int)gof[g + 1]) - gb;
+            const int kq = 64 * g + lane;
+            const int row = kq < nM ? (int)perm[kq] : 0;
+            const uint32_t sgb = kq < nM ? (uint32_t)sg8[row] : 0u;
+            const uint32_t sg16 = enum_spread8(sgb);
+            const uint2* const pe = csr + 64 * gb + lane;
+            uint32_t uacc = 0;
+            for (int x0 = 0; x0 < Lg; x0 += 2) {   // (two entries per step: most groups are two to four long, and Lg is the wave's)
+              const bool two = x0 + 1 < Lg;
+              uint2 v[2]; uint32_t mmv[2];
+              v[0] = pe[64 * x0]; v[1] = two ? pe[64 * (x0 + 1)] : make_uint2(0, 0);
+              mmv[0] = mt[(v[0].x >> 24) & 31u].x; mmv[1] = mt[(v[1].x >> 24) & 31u].x;
 #pragma unroll
-              for (int s = 0; s < 8; s++) {
-                const int sgn = __builtin_amdgcn_sbfe((int)code, 2 * s, 2);
-                alo[s] = enum_mad24(sgn, (int)v0, alo[s]); ahi[s] = enum_mad24(sgn, (int)v1, ahi[s]);
+              for (int u = 0; u < 2; u++) {
+                if (u == 1 && !two) break;
+                const uint32_t v0 = v[u].x, v1 = v[u].y;
+                const uint32_t m = v0 >> 24;
+                const uint32_t mm = mmv[u];
+                const uint32_t use16 = (m & 128u) ? (mm & 0xFFFFu) : 0u;                          // het sites only (a zero word: behind the row's last entry)
+                const uint32_t hit16 = (((m & 32u) ? 0x5555u : 0u) ^ sg16 ^ (mm >> 16)) & use16;   // p == sigma * delta
+                const uint32_t code = use16 | ((hit16 ^ use16) << 1);                              // 01: +w (A), 11: -w (B)
+                uacc |= use16;
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                  const int sgn = __builtin_amdgcn_sbfe((int)code, 2 * s, 2);
+                  alo[s] = enum_mad24(sgn, (int)v0, alo[s]); ahi[s] = enum_mad24(sgn, (int)v1, ahi[s]);
+                }
               }
             }
-          }
-          {   // the rows' eight decisions
-            uint32_t fl = 0, tie = 0;
+            {   // the rows' eight decisions
+              uint32_t fl = 0, tie = 0;
 #pragma unroll
-            for (int s = 0; s < 8; s++) {
-              const int top = ahi[s] + (alo[s] >> 23);   // sign of ahi * 2^23 + alo
-              fl |= (uint32_t)(top < 0) << s;
-              tie |= (uint32_t)(top == 0 && (alo[s] & 0x7fffff) == 0 && ((uacc >> (2 * s)) & 1u)) << s;
-              alo[s] = 0; ahi[s] = 0;
-            }
-            fl &= act; tie &= act;
-            any8 |= fl;
-            if (fl) sg8[row] = (uint8_t)(sgb ^ fl);
-            if (tie) {
-              // A == B at a row with a het entry: the f64 scores decide (a row without one scores the same for both signs, term by term)
-              if (P.tie_arith < 2) n_tie_unres += (uint32_t)__popc(tie);
-              else {
-                n_tie_f64 += (uint32_t)__popc(tie);
-                if (rp[row + 1] - rp[row] > 2) {   // (two entries: log_q2 = a + b, log_q3 = b + a -- the same double)
-                  const uint32_t at = atomicAdd(tq_n, 1u);
-                  if (at < ENUM_TQ) tq[at] = (uint32_t)row | (tie << 16) | (sgb << 24);
-                  else {
-                    for (uint32_t tt = tie; tt; tt &= tt - 1u) {
-                      const int s = __ffs((int)tt) - 1;
-                      if (enum_tie_row_flips(row, (sgb >> s) & 1u, ms[s], ms[8 + s], ms[16 + s], rp, ent16, lut)) {
-                        atomicXor((uint32_t*)(sg8 + (row & ~3)), 1u << (8 * (row & 3) + s));
-                        n_tie_flip++; tflip8 |= 1u << s;
+              for (int s = 0; s < 8; s++) {
+                const int top = ahi[s] + (alo[s] >> 23);   // sign of ahi * 2^23 + alo
+                fl |= (uint32_t)(top < 0) << s;
+                tie |= (uint32_t)(top == 0 && (alo[s] & 0x7fffff) == 0 && ((uacc >> (2 * s)) & 1u)) << s;
+                alo[s] = 0; ahi[s] = 0;
+              }
+              fl &= act; tie &= act;
+              any8 |= fl;
+              if (fl) sg8[row] = (uint8_t)(sgb ^ fl);
+              if (tie) {
+                for (uint32_t tt = tie; tt; tt &= tt - 1u) atomicAdd(&tcnt[__ffs((int)tt) - 1], 1u);
+                // A == B at a row with a het entry: the f64 scores decide (a row without one scores the same for both signs, term by term)
+                if (P.tie_arith < 2) n_tie_unres += (uint32_t)__popc(tie);
+                else {
+                  n_tie_f64 += (uint32_t)__popc(tie);
+                  if (rp[row + 1] - rp[row] > 2) {   // (two entries: log_q2 = a + b, log_q3 = b + a -- the same double)
+                    const uint32_t at = atomicAdd(tq_n, 1u);
+                    if (at < ENUM_TQ) tq[at] = (uint32_t)row | (tie << 16) | (sgb << 24);
+                    else {
+                      for (uint32_t tt = tie; tt; tt &= tt - 1u) {
+                        const int s = __ffs((int)tt) - 1;
+                        if (enum_tie_row_flips(row, (sgb >> s) & 1u, ms[s], ms[8 + s], ms[16 + s], rp, ent16, lut)) {
+                          atomicXor((uint32_t*)(sg8 + (row & ~3)), 1u << (8 * (row & 3) + s));
+                          n_tie_flip++; tflip8 |= 1u << s;
+                        }
                       }
                     }
                   }
@@ -1170,153 +1228,173 @@ k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, ui
               }
             }
           }
-        }
-        // ---- the rows of one entry, a lane per row: the sum is +-w, the row flips where it is negative (w < 0 for q <= 3) -- no tie (w != 0)
-        for (int x0 = lane; x0 < nS; x0 += 4 * 64) {
-          uint2 v[4]; int rw[4];
+          // ---- the rows of one entry, a lane per row: the sum is +-w, the row flips where it is negative (w < 0 for q <= 3) -- no tie (w != 0)
+          for (int x0 = lane; x0 < nS; x0 += 4 * 64) {
+            uint2 v[4]; int rw[4];
 #pragma unroll
-          for (int u = 0; u < 4; u++) { const int x = x0 + 64 * u; v[u] = x < nS ? csr[eM + x] : make_uint2(0, 0); rw[u] = x < nS ? (int)perm[nM + x] : 0; }
+            for (int u = 0; u < 4; u++) { const int x = x0 + 64 * u; v[u] = x < nS ? csr[eM + x] : make_uint2(0, 0); rw[u] = x < nS ? (int)perm[nM + x] : 0; }
 #pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const uint32_t v0 = v[u].x, v1 = v[u].y;
-            const uint32_t m = v0 >> 24, i = m & 31u;
-            if (!(m & 128u)) continue;
-            const int row = rw[u];
-            const uint32_t sb = sg8[row], s16 = enum_spread8(sb);
-            const uint32_t mm = mt[i].x;
-            const uint32_t use16 = mm & 0xFFFFu;                                              // het sites only
-            const uint32_t hit16 = (((m & 32u) ? 0x5555u : 0u) ^ s16 ^ (mm >> 16)) & use16;   // p == sigma * delta: the term is + w
-            const bool wneg = ((v1 >> 23) & 1u) != 0;                                         // (sign of the signed 24-bit limb = sign of w)
-            uint32_t f = wneg ? hit16 : (use16 & ~hit16);                                     // states whose sum is negative, at bit 2 s
-            f &= 0x5555u; f = (f | (f >> 1)) & 0x3333u; f = (f | (f >> 2)) & 0x0F0Fu; f = (f | (f >> 4)) & 0xFFu;
-            f &= act;
-            any8 |= f;
-            if (f) sg8[row] = (uint8_t)(sb ^ f);
+            for (int u = 0; u < 4; u++) {
+              const uint32_t v0 = v[u].x, v1 = v[u].y;
+              const uint32_t m = v0 >> 24, i = m & 31u;
+              if (!(m & 128u)) continue;
+              const int row = rw[u];
+              const uint32_t sb = sg8[row], s16 = enum_spread8(sb);
+              const uint32_t mm = mt[i].x;
+              const uint32_t use16 = mm & 0xFFFFu;                                              // het sites only
+              const uint32_t hit16 = (((m & 32u) ? 0x5555u : 0u) ^ s16 ^ (mm >> 16)) & use16;   // p == sigma * delta: the term is + w
+              const bool wneg = ((v1 >> 23) & 1u) != 0;                                         // (sign of the signed 24-bit limb = sign of w)
+              uint32_t f = wneg ? hit16 : (use16 & ~hit16);                                     // states whose sum is negative, at bit 2 s
+              f &= 0x5555u; f = (f | (f >> 1)) & 0x3333u; f = (f | (f >> 2)) & 0x0F0Fu; f = (f | (f >> 4)) & 0xFFu;
+              f &= act;
+              any8 |= f;
+              if (f) sg8[row] = (uint8_t)(sb ^ f);
+            }
           }
         }
-      }
-      wave_lds_sync();
-      {   // the queue: a lane per (row, state)
-        const uint32_t nq = min(tq_n[0], ENUM_TQ);
-        for (uint32_t b0 = 0; b0 < nq; b0 += 8) {
-          const uint32_t j = b0 + (uint32_t)(lane >> 3);
-          const int s = lane & 7;
-          if (j < nq) {
-            const uint32_t ent = tq[j], row = ent & 0xffffu;
-            if ((ent >> (16 + s)) & 1u) {
-              if (enum_tie_row_flips((int)row, (ent >> (24 + s)) & 1u, ms[s], ms[8 + s], ms[16 + s], rp, ent16, lut)) {
-                atomicXor((uint32_t*)(sg8 + (row & ~3u)), 1u << (8 * (row & 3u) + s));
-                n_tie_flip++; tflip8 |= 1u << s;
+        wave_lds_sync();
+        {   // the queue: a lane per (row, state)
+          const uint32_t nq = min(tq_n[0], ENUM_TQ);
+          for (uint32_t b0 = 0; b0 < nq; b0 += 8) {
+            const uint32_t j = b0 + (uint32_t)(lane >> 3);
+            const int s = lane & 7;
+            if (j < nq) {
+              const uint32_t ent = tq[j], row = ent & 0xffffu;
+              if ((ent >> (16 + s)) & 1u) {
+                if (enum_tie_row_flips((int)row, (ent >> (24 + s)) & 1u, ms[s], ms[8 + s], ms[16 + s], rp, ent16, lut)) {
+                  atomicXor((uint32_t*)(sg8 + (row & ~3u)), 1u << (8 * (row & 3u) + s));
+                  n_tie_flip++; tflip8 |= 1u << s;
+                }
               }
             }
           }
+          if (lane == 0) tq_n[0] = 0;
         }
-        if (lane == 0) tq_n[0] = 0;
-      }
-      {   // OR over the wave
+        {   // OR over the wave
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { any8 |= (uint32_t)__shfl_xor((int)any8, d, 64); tflip8 |= (uint32_t)__shfl_xor((int)tflip8, d, 64); }
-      }
+          for (int d = 32; d >= 1; d >>= 1) { any8 |= (uint32_t)__shfl_xor((int)any8, d, 64); tflip8 |= (uint32_t)__shfl_xor((int)tflip8, d, 64); }
+        }
 #pragma unroll
-      for (int s = 0; s < 8; s++) if (((tflip8 & ~any8) >> s) & 1u) { n_step++; ev_s[s]++; }   // only tie flips: "no improvement"
+        for (int s = 0; s < 8; s++) if (((tflip8 & ~any8) >> s) & 1u) { n_step++; ev_s[s]++; }   // only tie flips: "no improvement"
+        need_delta8 = iters == 0 ? 0xFFu : (any8 | tflip8);   // (the first delta step always runs: its masks are the start masks, not a step's)
+        ENUM_STEP(0);
+        wave_lds_sync();
+      } else {   // the active restarts meet the tied rows of their last sigma step again, and none flips
+        uint32_t again = 0;
+#pragma unroll
+        for (int s = 0; s < 8; s++) if ((act >> s) & 1u) again += tcnt[s];
+        if (lane == 0) { if (P.tie_arith < 2) n_tie_unres += again; else n_tie_f64 += again; }
+        need_delta8 = 0;
+        ENUM_STEP(1);
+      }
       // (!any: h_inc = false; else both true)
       hinc = (hinc & ~act) | (any8 & act); hginc |= any8 & act;
-      wave_lds_sync();
-      // ---- delta / eta step (phase.rs:872-959): a lane's chunk is CSC-ordered (SNP index non-decreasing)
-      {
-        int cur = -1;
-        uint32_t alo[8]; int ahi[8];
+      uint32_t any2 = 0, chg8 = 0;   // per state: an improvement / a mask changed
+      if (!P.enum_elide || (need_delta8 & act)) {
+        // ---- delta / eta step (phase.rs:872-959): a lane's chunk is CSC-ordered (SNP index non-decreasing)
 #pragma unroll
-        for (int s = 0; s < 8; s++) { alo[s] = 0; ahi[s] = 0; }
-        auto flush = [&]() {
+        for (int q = 0; q < 8; q++) ld_dt[q] = 0;
+        {
+          int cur = -1;
+          uint32_t alo[8]; int ahi[8];
 #pragma unroll
-          for (int s = 0; s < 8; s++) {
-            if (alo[s] | (uint32_t)ahi[s]) atomicAdd(&Macc[s * Sp + cur], (unsigned long long)((long long)alo[s] + (long long)ahi[s] * (1ll << 23)));
-            alo[s] = 0; ahi[s] = 0;
-          }
-        };
-        for (int h = 0; h < n_del; h += 4) {
-          uint32_t v4[4], sw[4], dn[4]; uint2 wq[4];
-#pragma unroll
-          for (int x = 0; x < 4; x++) v4[x] = c0 + h + x < c1 ? csc[c0 + h + x] : 0u;
-#pragma unroll
-          for (int x = 0; x < 4; x++) { sw[x] = sg8[v4[x] & 0xffffu]; wq[x] = wl2[(v4[x] >> 22) & 31u]; dn[x] = mt[(v4[x] >> 16) & 31u].y & 0xFFu; }
-#pragma unroll
-          for (int x = 0; x < 4; x++) {
-            const uint32_t v = v4[x];
-            const int i = (v >> 16) & 31;
-            if ((v >> 31) && i != cur) { if (cur >= 0) flush(); cur = i; }
-            const uint32_t hit = (v >> 31) ? ((((v >> 21) & 1u) ? 0xFFu : 0u) ^ sw[x] ^ dn[x]) & 0xFFu : 0u;
-            const int whi = ((int)(wq[x].y << 8)) >> 8;   // the signed 24-bit limb
+          for (int s = 0; s < 8; s++) { alo[s] = 0; ahi[s] = 0; }
+          auto flush = [&]() {
 #pragma unroll
             for (int s = 0; s < 8; s++) {
-              const uint32_t b = (hit >> s) & 1u;
-              alo[s] += __umul24(b, wq[x].x); ahi[s] += __mul24((int)b, whi);
+              if (alo[s] | (uint32_t)ahi[s]) atomicAdd(&Macc[s * Sp + cur], (unsigned long long)((long long)alo[s] + (long long)ahi[s] * (1ll << 23)));
+              alo[s] = 0; ahi[s] = 0;
+            }
+          };
+          for (int h = 0; h < n_del; h += 4) {
+            uint32_t v4[4], sw[4], dn[4]; uint2 wq[4];
+#pragma unroll
+            for (int x = 0; x < 4; x++) v4[x] = c0 + h + x < c1 ? csc[c0 + h + x] : 0u;
+#pragma unroll
+            for (int x = 0; x < 4; x++) { sw[x] = sg8[v4[x] & 0xffffu]; wq[x] = wl2[(v4[x] >> 22) & 31u]; dn[x] = mt[(v4[x] >> 16) & 31u].y & 0xFFu; }
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+              const uint32_t v = v4[x];
+              const int i = (v >> 16) & 31;
+              if ((v >> 31) && i != cur) { if (cur >= 0) flush(); cur = i; }
+              const uint32_t hit = (v >> 31) ? ((((v >> 21) & 1u) ? 0xFFu : 0u) ^ sw[x] ^ dn[x]) & 0xFFu : 0u;
+              const int whi = ((int)(wq[x].y << 8)) >> 8;   // the signed 24-bit limb
+#pragma unroll
+              for (int s = 0; s < 8; s++) {
+                const uint32_t b = (hit >> s) & 1u;
+                alo[s] += __umul24(b, wq[x].x); ahi[s] += __mul24((int)b, whi);
+              }
             }
           }
+          if (cur >= 0) flush();
         }
-        if (cur >= 0) flush();
-      }
-      wave_lds_sync();
-      // a lane per (state, SNP), eight SNPs per pass: the four-way decision (first maximum, phase.rs:908-921)
-      uint32_t any2 = 0, chg8 = 0;   // per state: an improvement / a mask changed
-      {
-        const int s = lane >> 3;
-        const uint32_t od = ms[s], oe0 = ms[8 + s], oep = ms[16 + s];
-        uint32_t nd = od, ne0 = oe0, nep = oep;
-        for (int p = 0; p < n_pass; p++) {
-          const int i = 8 * p + (lane & 7);
-          const bool in = i < S;
-          const bool live = in && s_live[i & 31] != 0;
-          int d_new = (int)((od >> i) & 1u), h_new = ((oe0 >> i) & 1u) ? 0 : (((oep >> i) & 1u) ? 1 : -1);
-          bool changed = false, dtie = false;
-          if (live && ((act >> s) & 1u)) {
-            const long long M = (long long)Macc[s * Sp + i];
-            const long long cF = s_cF[i], cW = s_cW[i], cRef = s_cRef[i], cVar = s_cVar[i], het = s_het[i];
-            const long long N0 = cF + M + het, N1 = cF + cW - M + het;
-            int ch = 0; long long nb = N0;
-            if (N1 > nb) { ch = 1; nb = N1; }
-            if (cRef > nb) { ch = 2; nb = cRef; }
-            if (cVar > nb) { ch = 3; nb = cVar; }
-            dtie = (int)(N0 == nb) + (int)(N1 == nb) + (int)(cRef == nb) + (int)(cVar == nb) > 1;   // a tie at the maximum: the first one is kept
-            const long long ncur = h_new == 0 ? N0 : (h_new == 1 ? cRef : cVar);
-            changed = nb > ncur;
-            if (ch == 1) d_new ^= 1;
-            h_new = ch <= 1 ? 0 : (ch == 2 ? 1 : -1);
-            objl[p] = ch <= 1 ? nb - het : (ch == 2 ? cRef - P.lut.f_homref : cVar - P.lut.f_homvar);
-          }
-          if (in) Macc[s * Sp + i] = 0;
-          const unsigned long long bd = __ballot(in && d_new), b0 = __ballot(in && h_new == 0), bp = __ballot(in && h_new == 1);
-          const unsigned long long bc = __ballot(changed), bt = __ballot(dtie);
-          const uint32_t sh = 8u * (uint32_t)s, keep = ~(0xFFu << (8 * p));
-          nd = (nd & keep) | ((uint32_t)((bd >> sh) & 0xFFull) << (8 * p));
-          ne0 = (ne0 & keep) | ((uint32_t)((b0 >> sh) & 0xFFull) << (8 * p));
-          nep = (nep & keep) | ((uint32_t)((bp >> sh) & 0xFFull) << (8 * p));
-#pragma unroll
-          for (int q = 0; q < 8; q++) {
-            if ((bc >> (8 * q)) & 0xFFull) any2 |= 1u << q;
-            const uint32_t nt8 = (uint32_t)__popcll((bt >> (8 * q)) & 0xFFull);
-            n_dtie += nt8; ev_d[q] += nt8;
-          }
-        }
-        nd &= smask; ne0 &= smask; nep &= smask;
-        const bool frozen = !((act >> s) & 1u);
-        if (frozen) { nd = od; ne0 = oe0; nep = oep; }
-        const unsigned long long bm = __ballot(nd != od || ne0 != oe0 || nep != oep);
-#pragma unroll
-        for (int q = 0; q < 8; q++) if ((bm >> (8 * q)) & 0xFFull) chg8 |= 1u << q;
         wave_lds_sync();
-        if ((lane & 7) == 0) { ms[s] = nd; ms[8 + s] = ne0; ms[16 + s] = nep; }
-      }
-      any2 &= act;
+        // a lane per (state, SNP), eight SNPs per pass: the four-way decision (first maximum, phase.rs:908-921)
+        {
+          const int s = lane >> 3;
+          const uint32_t od = ms[s], oe0 = ms[8 + s], oep = ms[16 + s];
+          uint32_t nd = od, ne0 = oe0, nep = oep;
+          for (int p = 0; p < n_pass; p++) {
+            const int i = 8 * p + (lane & 7);
+            const bool in = i < S;
+            const bool live = in && s_live[i & 31] != 0;
+            int d_new = (int)((od >> i) & 1u), h_new = ((oe0 >> i) & 1u) ? 0 : (((oep >> i) & 1u) ? 1 : -1);
+            bool changed = false, dtie = false;
+            if (live && ((act >> s) & 1u)) {
+              const long long M = (long long)Macc[s * Sp + i];
+              const long long cF = s_cF[i], cW = s_cW[i], cRef = s_cRef[i], cVar = s_cVar[i], het = s_het[i];
+              const long long N0 = cF + M + het, N1 = cF + cW - M + het;
+              int ch = 0; long long nb = N0;
+              if (N1 > nb) { ch = 1; nb = N1; }
+              if (cRef > nb) { ch = 2; nb = cRef; }
+              if (cVar > nb) { ch = 3; nb = cVar; }
+              dtie = (int)(N0 == nb) + (int)(N1 == nb) + (int)(cRef == nb) + (int)(cVar == nb) > 1;   // a tie at the maximum: the first one is kept
+              const long long ncur = h_new == 0 ? N0 : (h_new == 1 ? cRef : cVar);
+              changed = nb > ncur;
+              if (ch == 1) d_new ^= 1;
+              h_new = ch <= 1 ? 0 : (ch == 2 ? 1 : -1);
+              objl[p] = ch <= 1 ? nb - het : (ch == 2 ? cRef - P.lut.f_homref : cVar - P.lut.f_homvar);
+            }
+            if (in) Macc[s * Sp + i] = 0;
+            const unsigned long long bd = __ballot(in && d_new), b0 = __ballot(in && h_new == 0), bp = __ballot(in && h_new == 1);
+            const unsigned long long bc = __ballot(changed), bt = __ballot(dtie);
+            const uint32_t sh = 8u * (uint32_t)s, keep = ~(0xFFu << (8 * p));
+            nd = (nd & keep) | ((uint32_t)((bd >> sh) & 0xFFull) << (8 * p));
+            ne0 = (ne0 & keep) | ((uint32_t)((b0 >> sh) & 0xFFull) << (8 * p));
+            nep = (nep & keep) | ((uint32_t)((bp >> sh) & 0xFFull) << (8 * p));
 #pragma unroll
-      for (int q = 0; q < 8; q++) if (((chg8 & ~any2 & act) >> q) & 1u) { n_step++; ev_s[q]++; }   // only tie changes in this step
+            for (int q = 0; q < 8; q++) {
+              if ((bc >> (8 * q)) & 0xFFull) any2 |= 1u << q;
+              const uint32_t nt8 = (uint32_t)__popcll((bt >> (8 * q)) & 0xFFull);
+              n_dtie += nt8; ev_d[q] += nt8; ld_dt[q] += nt8;
+            }
+          }
+          nd &= smask; ne0 &= smask; nep &= smask;
+          const bool frozen = !((act >> s) & 1u);
+          if (frozen) { nd = od; ne0 = oe0; nep = oep; }
+          const unsigned long long bm = __ballot(nd != od || ne0 != oe0 || nep != oep);
+#pragma unroll
+          for (int q = 0; q < 8; q++) if ((bm >> (8 * q)) & 0xFFull) chg8 |= 1u << q;
+          wave_lds_sync();
+          if ((lane & 7) == 0) { ms[s] = nd; ms[8 + s] = ne0; ms[16 + s] = nep; }
+        }
+        any2 &= act;
+#pragma unroll
+        for (int q = 0; q < 8; q++) if (((chg8 & ~any2 & act) >> q) & 1u) { n_step++; ev_s[q]++; }   // only tie changes in this step
+        need_sigma8 = chg8;
+        ENUM_STEP(2);
+        wave_lds_sync();
+      } else {   // the same SNPs tie at their maximum again: first maximum, the masks stay
+#pragma unroll
+        for (int q = 0; q < 8; q++) if ((act >> q) & 1u) { n_dtie += ld_dt[q]; ev_d[q] += ld_dt[q]; }
+        need_sigma8 = 0;
+        ENUM_STEP(3);
+      }
       // (!any2: hg_inc = false; else both true)
       hginc = (hginc & ~act) | (any2 & act); hinc |= any2 & act;
-      wave_lds_sync();
       iters++;
       act &= hinc | hginc;
-      if (iters > 20) act = 0;  // phase.rs:967-972
+      if (iters > ENUM_ITER_CAP) act = 0;  // phase.rs:967-972
     }
     // ---- what the restarts leave
     long long tot = objl[0] + objl[1] + objl[2] + objl[3];
@@ -1406,6 +1484,7 @@ k4_enum_bits(PhaseDev P, const EnumSpan* __restrict__ spans, int32_t n_spans, ui
     if (n_dtie) TIE_COUNT(P.tie_ctr, TIE_DELTA_UNRES, (unsigned long long)n_dtie);
     if (n_step) TIE_COUNT(P.tie_ctr, TIE_STEP_UNRES, (unsigned long long)n_step);
   }
+  ENUM_STEP_FLUSH(0);
 }
 
 // the same tiles for regions whose matrix does not fit the LDS budget: one restart at a time per workgroup.  Every restart leaves

@@ -347,7 +347,7 @@ int PhaseHost::size_buffers(PhaseCall& c) {
     const int fv[4] = {0, 0, 0x80, 0};
     const size_t fs[4] = {TIE_NCTR * 8, ng ? c.st_bytes : 0, (size_t)ng * 8, dbg.tie_arith >= 3 ? 2 * (16 + 8 * (size_t)REDO_CAP) : 0};
     PCHK(lcr_fill_multi_async(4, fp, fv, fs, c.sq)); }
-  P.lut64 = d_lut64.as<PostLut>(); P.tie_ctr = d_tie.as<unsigned long long>(); P.tie_arith = dbg.tie_arith;
+  P.lut64 = d_lut64.as<PostLut>(); P.tie_ctr = d_tie.as<unsigned long long>(); P.tie_arith = dbg.tie_arith; P.enum_elide = dbg.enum_elide;
 
   c.Pc = P;
   c.Pc.st_sigma = d_st_chain.as<int8_t>() + c.st_sig; c.Pc.st_delta = d_st_chain.as<int8_t>() + c.st_del; c.Pc.st_eta = d_st_chain.as<int8_t>() + c.st_eta;

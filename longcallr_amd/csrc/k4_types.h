@@ -33,7 +33,7 @@ struct PhaseDev {
   unsigned long long* tie_ctr;
   int32_t tie_arith;   // 0: fixed point only (ties change nothing), 1: + configurations of equal objective by their f64 sums, 2: + sigma ties by the f64 scores,
                        // 3: + (enumeration kernels) delta / eta ties at the maximum and the verdict of tie-only steps
-  int32_t pad_;
+  int32_t enum_elide;  // k4_enum_bits / k4_enum_reg: 1 = a sigma / delta step whose inputs have not changed since its last run is not executed ("enum_elide")
   // down-sampling (k4_sample.hip): per phasing row (at sig_off + k) its DRAW ORDINAL, the rank among all rows with >= min_linkers links -- the
   // reference draws for every such row, sampled or not (phase.rs:673-680, 1218-1225), so counters are formed from the ordinal and
   // RegionDev::F_all.  nullptr (the feature is off, or no region of the call applies): the ordinal is the row index itself, no table load
@@ -53,7 +53,8 @@ enum { TIE_SIGMA_F64 = 0,      // sigma decisions with A == B at a row with an e
        TIE_SIGMA_UNRES = 6,    // sigma ties in kernels without the f64 path
        TIE_STEP_F64 = 7,       // delta / eta ties at the maximum + tie-only steps decided by the f64 scores (enumeration kernels, round 5; k4_chain_wg<COMPLETE>, round 6)
        TIE_NCTR = 8 };
-// (-DENUM_PROF, a measurement build: the census slots carry k4_enum_resolve's times instead)
+// (-DENUM_PROF, a measurement build: the census slots carry k4_enum_resolve's times instead; -DENUM_PROF=2: the executed and skipped
+// sigma / delta steps of k4_enum_bits (slots 0 - 3) and k4_enum_reg (slots 4 - 7), each step weighted by its region's phase entries)
 #ifdef ENUM_PROF
 #define TIE_COUNT(ctr, which, n) do { } while (0)
 #else

@@ -464,6 +464,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "post_half") d.post_half = (int)value;
   else if (k == "enum_force_big") d.enum_force_big = (int)value;
   else if (k == "enum_force_stream") d.enum_force_stream = (int)value;
+  else if (k == "enum_elide") d.enum_elide = value != 0;
   else if (k == "async_phase") d.async_phase = value != 0;
   else if (k == "host_trace") g_lcr_host_trace = value != 0;
   else if (k == "own_fill") g_lcr_own_fill = value != 0;

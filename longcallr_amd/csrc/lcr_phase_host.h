@@ -36,6 +36,7 @@ struct PhaseDebug {
   int post_half = 0;            // "post_half": the eight-wave epilogue of the chain regions
   int enum_force_big = 0;       // "enum_force_big" / "enum_force_stream": the fallback enumeration kernels
   int enum_force_stream = 0;    // (every LDS-resident region by the streaming kernel, k4_enum_reg)
+  int enum_elide = 1;           // "enum_elide": k4_enum_bits / k4_enum_reg skip the sigma / delta steps whose inputs have not changed since they last ran (0: every step is executed)
   int spec_batch = 1;           // "grid_spec_batch": eight speculative half-rounds per pass over the matrix (k4_grid_batch.h); 0: the side-by-side lanes below
   int spec_lanes = 8;           // "grid_spec_lanes": half-rounds of the perturbation loop run at once at grid scope (1: one after the other; C5 with packed entries: 454 / 370 / 348 / 366 ms with 2 / 4 / 8 / 16 -- eight lanes = one XCD each)
   int redo_lds = 64 * 1024;     // "redo_lds": bytes of dynamic LDS of the enumeration branch's repair pass (k4_enum_redo: state + matrix of a restart's region where they fit; 0: global memory)
