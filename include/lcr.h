@@ -356,6 +356,49 @@ typedef struct { int32_t n_regions, n_junctions; const lcr_junction* junc; const
 int lcr_junctions(lcr_ctx*, const lcr_junction_params*);
 int lcr_get_junctions(lcr_ctx*, lcr_junction_list* out);
 
+/* Allele-specific expression (K7): the haplotype counts and the parent-of-origin votes of the analysis that consumes the phased reads
+ * (allele_specific/longcallR-ase.py: calculate_ase_pvalue, the vote loops of calculate_ase_pvalue_pat_mat), counted on the GPU from what
+ * lcr_phase left there.  Defined per region -- a region stands where the script has a gene, as for lcr_junctions.  Row r of region g is a
+ * row of lcr_get_fragmat: its haplotype a = assignment[r], its phase set ps = phase_set[r].
+ *   counting rows      a is 1 or 2 and ps != 0 (the script's `if ps and hp`); every other row takes no part.
+ *   phase set          count the counting rows per value of ps; the region's phase_set is the value with the most rows, ties to the
+ *       smallest value; n_phase_sets = distinct values seen; h1 / h2 = counting rows of that phase set with a = 1 / 2.  Without a
+ *       counting row: phase_set 0, every count 0.
+ *   parental sites     (optional) pos0 0-based, ascending and unique; pat / mat ASCII A / C / G / T, pat != mat.  They carry no contig:
+ *       the call is defined for a batch on ONE contig with that contig's sites, the rule of lcr_import_candidates.
+ *   eligible site      a candidate of region g that (1) the VCF writer would print as PASS with a phased het GT -- LCR_F_DENSE and
+ *       LCR_F_NON_SELECTED not set, variant_type == 1, phase_score >= min_phase_score, allele1 or allele2 differs from ref_base --,
+ *       (2) has a phase_set != 0 that (3) equals the region's, and (4) whose pos is one of the parental pos0.  n_sites counts them.
+ *   votes              every counting row of the region's phase set; every CSR entry of that row at an eligible site whose q field (the
+ *       fragment matrix clamps it to 30) is >= min_baseq counts as pat if its base code equals the site's pat, else as mat if it equals
+ *       mat, else as nothing.  The row votes paternal if pat > mat, maternal if pat < mat, not at all if they are equal (a row without
+ *       an eligible entry among them).  h1_pat, h1_mat, h2_pat, h2_mat count the votes by the row's haplotype.
+ *   order              one record per region, in region order; integer adds only: bit-reproducible, independent of the batch's composition.
+ * Not the script's: no annotation (no gene assignment of reads, no exon filter); the tie between equally large phase sets goes to the
+ * smallest value (the script: a dict's order); a read's base is seen only where the fragment matrix has an entry -- the base is the
+ * site's reference or one of its two major alleles (fragment.rs:134-152) --, so a parental allele that is neither is never counted; only
+ * single-base REF / ALT parental records are used; rows are not restricted to reads contained in the region.
+ * lcr_ase needs the bound batch after lcr_phase (LCR_E_STATE otherwise, nothing changed; params == NULL or min_baseq > 30: LCR_E_ARG),
+ * collects an asynchronous phase stage in flight first, queues on the context's stream, writes no buffer another stage or getter reads,
+ * and may be repeated with other parameters or sites.  n_sites == 0 (NULL arrays) is the plain mode: phase_set, n_phase_sets, h1, h2 are
+ * filled, the site and vote fields are 0.  mem as in lcr_import_candidates: LCR_MEM_HOST arrays are copied before the call returns,
+ * LCR_MEM_DEVICE arrays are read in place on the context's stream and stay valid until lcr_get_ase / lcr_ctx_sync.  Unsorted or duplicate
+ * positions, a pat / mat byte outside ACGT and pat == mat are LCR_E_ARG, found by a kernel whose verdict the call waits for (its one host
+ * wait; the last call's records stay valid).  The records die with the phase stage's results: at the next candidate stage and at
+ * lcr_load_batch / lcr_bind_batch; lcr_get_ase answers LCR_E_STATE then.  rec: pinned host memory the call's last kernel wrote, valid
+ * until the next lcr_ase; dev_rec: the same records in HBM. */
+typedef struct { uint32_t min_baseq; float min_phase_score; } lcr_ase_params;   /* 13 (pysam's pileup default), the VCF writer's value */
+typedef struct {
+  int32_t region;
+  uint32_t phase_set, n_phase_sets;   /* the phase set with the most counting rows (0 = none), distinct sets seen */
+  uint32_t h1, h2;                    /* counting rows of that phase set per haplotype                             */
+  uint32_t n_sites;                   /* eligible sites                                                            */
+  uint32_t h1_pat, h1_mat, h2_pat, h2_mat;
+} lcr_ase_region;            /* 40 bytes */
+typedef struct { int32_t n_regions; const lcr_ase_region* rec; const lcr_ase_region* dev_rec; } lcr_ase_list;
+int lcr_ase(lcr_ctx*, const lcr_ase_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* pat, const uint8_t* mat);
+int lcr_get_ase(lcr_ctx*, lcr_ase_list* out);
+
 /* Down-sampling: phase deep regions on a read sample (longcallR --downsample / --downsample-depth: thread.rs:144-151, phase.rs:693-701).
  * A region with at least `depth` fragment rows (all rows of lcr_get_fragmat, empty ones included) is down-sampled: the optimiser
  * (cross_optimize and its checks, cal_overall_probability, cross_optimize_by_block), the first two post-phase rounds
@@ -509,6 +552,10 @@ const char* lcr_vcf_last_error(const lcr_vcf*);
 int lcr_vcf_contigs(lcr_vcf*, int32_t* n, const char* const** names);
 /* the sites of one contig sorted by position (n = 0 for a contig without sites); pointers valid until lcr_vcf_close */
 int lcr_vcf_contig(lcr_vcf*, const char* name, int32_t* n, const int64_t** pos0, const uint8_t** genotype, const float** qual);
+/* REF, ALT and the phase bit of the same sites: arrays parallel to lcr_vcf_contig's (same n, same order, the same winning record and
+ * sample).  ref = REF's byte when REF is one base, else 0; alt = the first ALT's byte when EVERY ALT allele is one base, else 0 (the
+ * indel test of longcallR-ase.py's VCF loaders); phase: 0 = the GT is unphased, 1 = `0|1`, 2 = `1|0`, 3 = phased, any other alleles. */
+int lcr_vcf_contig_alleles(lcr_vcf*, const char* name, int32_t* n, const uint8_t** ref, const uint8_t** alt, const uint8_t** phase);
 
 /* ---- phased BAM, replaces thread.rs:307-361 ------------------------------------------------
  * Writes to out_path the header of the opened file and, region by region in the order given (region i = columns
@@ -576,7 +623,8 @@ enum { LCR_K_SPANS = 0 /* K0: CIGAR decode + binning */, LCR_K_PILEUP, LCR_K_CAN
        LCR_K_FRAG_COUNT, LCR_K_FRAG_FILL, LCR_K_PHASE,
        LCR_K_BIND /* lcr_load_batch: read headers, read / tile -> region tables, op blocks' first reads (part of the pileup stage) */,
        LCR_K_BIND_TABLE /* lcr_load_batch of a device batch: region table + CIGAR layout check, before its one host wait */,
-       LCR_K_CAND_IMPORT /* lcr_import_candidates: count, scan, emit */, LCR_K_JUNCTIONS /* lcr_junctions, first kernel to last */, LCR_NKERNELS };
+       LCR_K_CAND_IMPORT /* lcr_import_candidates: count, scan, emit */, LCR_K_JUNCTIONS /* lcr_junctions, first kernel to last */,
+       LCR_K_ASE /* lcr_ase, first kernel to last behind the check of the parental sites */, LCR_NKERNELS };
 int lcr_enable_timing(lcr_ctx*, int on);
 int lcr_kernel_ms(lcr_ctx*, int kernel, float* ms);
 /* Bytes the pileup tally kernel (K1) of the last lcr_pileup has to move: read bases once (B) + 8-byte

@@ -18,7 +18,7 @@ F_RNA_EDIT, F_DENSE, F_HET, F_FOR_PHASING, F_HOM, F_SINGLE, F_NON_SELECTED, F_CA
     1, 2, 4, 8, 16, 32, 64, 128)
 
 (K_SPANS, K_PILEUP, K_CAND_FILTER, K_CAND_HIST, K_CAND_GT, K_FRAG_COUNT, K_FRAG_FILL, K_PHASE, K_BIND, K_BIND_TABLE,
- K_CAND_IMPORT, K_JUNCTIONS, NKERNELS) = range(13)
+ K_CAND_IMPORT, K_JUNCTIONS, K_ASE, NKERNELS) = range(14)
 
 
 class LcrReads(C.Structure):
@@ -117,6 +117,20 @@ assert JUNC_DTYPE.itemsize == 48, JUNC_DTYPE.itemsize
 class LcrJunctionList(C.Structure):   # include/lcr.h: lcr_junction_list
     _fields_ = [("n_regions", C.c_int32), ("n_junctions", C.c_int32), ("junc", C.c_void_p), ("junc_region_off", C.c_void_p),
                 ("dev_junc", C.c_void_p)]
+
+
+class LcrAseParams(C.Structure):   # include/lcr.h: lcr_ase_params (13 = pysam's pileup default; the VCF writer's min_phase_score)
+    _fields_ = [("min_baseq", C.c_uint32), ("min_phase_score", C.c_float)]
+
+
+# lcr_ase_region (include/lcr.h): one region's haplotype counts and parent-of-origin votes
+ASE_DTYPE = np.dtype([("region", "<i4"), ("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("h1", "<u4"), ("h2", "<u4"), ("n_sites", "<u4"),
+                      ("h1_pat", "<u4"), ("h1_mat", "<u4"), ("h2_pat", "<u4"), ("h2_mat", "<u4")], align=True)
+assert ASE_DTYPE.itemsize == 40, ASE_DTYPE.itemsize
+
+
+class LcrAseList(C.Structure):   # include/lcr.h: lcr_ase_list
+    _fields_ = [("n_regions", C.c_int32), ("rec", C.c_void_p), ("dev_rec", C.c_void_p)]
 
 
 # presets: the code values of main.rs:272-396 (not the help text)

@@ -16,7 +16,7 @@ SYMBOLS = [
     "lcr_enable_timing", "lcr_kernel_ms", "lcr_pileup_bytes", "lcr_pileup_stage_bytes", "lcr_discover_regions", "lcr_discover_regions_truncated", "lcr_version", "lcr_release_cached_memory", "lcr_set_cache_limits",
     "lcr_bam_open", "lcr_bam_open_keep", "lcr_bam_close", "lcr_bam_last_error", "lcr_bam_refs", "lcr_bam_n_records", "lcr_bam_resident", "lcr_bam_spans", "lcr_bam_batch", "lcr_bam_write_phased", "lcr_bam_write_reads",
     "lcr_set_downsample", "lcr_set_downsample_rows", "lcr_get_downsample",
-    "lcr_junctions", "lcr_get_junctions",
+    "lcr_junctions", "lcr_get_junctions", "lcr_ase", "lcr_get_ase", "lcr_vcf_contig_alleles",
     "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
 ]
 
@@ -112,5 +112,8 @@ def load():
     l.lcr_vcf_last_error.restype = C.c_char_p
     l.lcr_vcf_contigs.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_char_p))]
     l.lcr_vcf_contig.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    l.lcr_ase.argtypes = [vp, C.POINTER(_abi.LcrAseParams), C.c_int32, C.c_int32, vp, vp, vp]
+    l.lcr_get_ase.argtypes = [vp, C.POINTER(_abi.LcrAseList)]
+    l.lcr_vcf_contig_alleles.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     _lib = l
     return l

@@ -208,6 +208,38 @@ class Engine:
         self._chk(self.lib.lcr_get_junctions(self.h, C.byref(o)), "lcr_get_junctions")
         return _view(o.junc, _abi.JUNC_DTYPE, o.n_junctions), _view(o.junc_region_off, np.int32, o.n_regions + 1)
 
+    def ase(self, sites=None, min_baseq=13, min_phase_score=None):
+        """lcr_ase + lcr_get_ase after phase(): per region the phase set with the most assigned rows, its haplotype counts and -- with
+        parental sites -- the parent-of-origin votes of those rows (include/lcr.h; what longcallR-ase.py computes per gene) -> a
+        structured array of _abi.ASE_DTYPE, one record per region, copied.  sites: None (plain mode: the site and vote fields stay 0) or
+        (pos0, pat, mat) of the batch's contig -- numpy arrays (converted), or contiguous int64 / uint8 / uint8 tensors on this engine's
+        device, read in place.  min_phase_score: the VCF writer's (default: the engine's params).  Waits for an asynchronous phase stage
+        in flight; may be repeated with other parameters or sites."""
+        p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))
+        if sites is None:
+            rc = self.lib.lcr_ase(self.h, C.byref(p), _abi.LCR_MEM_HOST, 0, None, None, None)
+        elif any(getattr(t, "is_cuda", False) for t in sites):
+            import torch
+            ts = tuple(sites)
+            for name, t, dt in zip(("pos0", "pat", "mat"), ts, (torch.int64, torch.uint8, torch.uint8)):
+                if not getattr(t, "is_cuda", False) or t.dtype != dt or t.device.index != self.device or t.dim() != 1 or not t.is_contiguous():
+                    raise ValueError("device sites: %s must be a contiguous 1-d %s tensor on device %d" % (name, dt, self.device))
+            if len({t.numel() for t in ts}) != 1:
+                raise ValueError("pos0, pat and mat must have the same length")
+            torch.cuda.current_stream(self.device).synchronize()   # (the tensors may still be being written on torch's stream)
+            rc = self.lib.lcr_ase(self.h, C.byref(p), _abi.LCR_MEM_DEVICE, int(ts[0].numel()), *[C.c_void_p(t.data_ptr()) for t in ts])
+        else:
+            pos = np.ascontiguousarray(sites[0], dtype=np.int64)
+            pat = np.ascontiguousarray(sites[1], dtype=np.uint8)
+            mat = np.ascontiguousarray(sites[2], dtype=np.uint8)
+            if not (pos.size == pat.size == mat.size):
+                raise ValueError("pos0, pat and mat must have the same length")
+            rc = self.lib.lcr_ase(self.h, C.byref(p), _abi.LCR_MEM_HOST, int(pos.size), pos.ctypes.data, pat.ctypes.data, mat.ctypes.data)
+        self._chk(rc, "lcr_ase")
+        o = _abi.LcrAseList()
+        self._chk(self.lib.lcr_get_ase(self.h, C.byref(o)), "lcr_get_ase")   # (waits for the call's kernels: device sites are read by then)
+        return _view(o.rec, _abi.ASE_DTYPE, o.n_regions)
+
     def set_downsample(self, depth, seed=2025):
         """lcr_set_downsample: regions with at least `depth` fragment rows are phased on a sample of `depth` rows (longcallR --downsample /
         --downsample-depth; thread.rs:149 passes seed 2025).  Sticky; depth = 0 turns it off."""

@@ -1,0 +1,131 @@
+"""Allele-specific expression: the region-scale host arithmetic behind Engine.ase() (include/lcr.h: lcr_ase).
+
+The read-scale work -- the phase set with the most assigned reads, its haplotype counts, the parent-of-origin vote of every read over
+the phased heterozygous sites -- is K7 on the GPU; what is left per region is small and plain: the beta-binomial test, the
+Benjamini-Hochberg adjustment, the VCF loaders and the three TSV texts of allele_specific/longcallR-ase.py (beta_binomial_p_value,
+load_whole_genome_phased_vcf, load_dna_vcf, calculate_ase_pvalue_filtering, the analyze_ase_genes* writers).  Standard library + NumPy
+only: scipy.stats.betabinom and multipletests are restated (the latter in asj.bh_adjust).  Not the script's: there is no annotation, so
+Gene_name is the region."""
+import math
+
+import numpy as np
+
+from . import _abi, asj, vcf
+
+HEADER = "#Gene_name\tChr\tPS\tH1\tH2\tP_value"
+HEADER_PATMAT = HEADER + "\tH1_Paternal\tH1_Maternal\tH2_Paternal\tH2_Maternal"
+
+
+def convert_mu_rho_to_alpha_beta(mu, rho):
+    """the script's function of that name, as written"""
+    phi = (1 - rho) / rho - 1
+    alpha = mu * phi
+    beta = (1 - mu) * phi
+    return alpha, beta
+
+
+def betabinom_two_sided(k, n, mu=0.5, rho=0.001):
+    """beta_binomial_p_value(k, n, mu, rho, "two-sided") of the script: the sum of the beta-binomial probabilities that are <= the
+    observed one (with asj.fisher_two_sided's relative slack of 1e-7, so that the mirror image of k counts whatever the rounding), capped at 1."""
+    k, n = int(k), int(n)
+    if n == 0:
+        return 1.0
+    a, b = convert_mu_rho_to_alpha_beta(mu, rho)
+    lg = math.lgamma
+    const = lg(n + 1) + lg(a + b) - lg(a) - lg(b) - lg(n + a + b)
+    pmf = [math.exp(const - lg(x + 1) - lg(n - x + 1) + lg(x + a) + lg(n - x + b)) for x in range(n + 1)]
+    lim = pmf[k] * (1.0 + 1e-7)
+    return min(sum(p for p in pmf if p <= lim), 1.0)
+
+
+def _acgt(x):
+    return (x == 65) | (x == 67) | (x == 71) | (x == 84)
+
+
+def _pick(vcf_path, contig, f):
+    """f(pos0, genotype, ref, alt, phase) of one contig of the VCF, or of every contig (contig None: a dict)"""
+    sites = {c: (v[0], v[1]) + v[3:] for c, v in vcf.read_sites(vcf_path, alleles=True).items()}
+    if contig is None:
+        return {c: f(*v) for c, v in sites.items()}
+    z = np.zeros(0, np.uint8)
+    return f(*sites.get(contig, (np.zeros(0, np.int64), z, z, z, z)))
+
+
+def parental_sites(vcf_path, contig=None):
+    """load_whole_genome_phased_vcf of the script for one contig (None: a dict of all contigs) -> (pos0, pat, mat), the arrays
+    Engine.ase takes: records with genotype 0|1 or 1|0 (phased) and single-base REF and ALT in ACGT; 0|1 gives pat = ALT, mat = REF,
+    1|0 gives pat = REF, mat = ALT."""
+    def f(pos, gt, ref, alt, ph):
+        keep = (gt == 1) & ((ph == 1) | (ph == 2)) & _acgt(ref) & _acgt(alt) & (ref != alt)
+        pos, ref, alt, ph = pos[keep], ref[keep], alt[keep], ph[keep]
+        return pos, np.where(ph == 1, alt, ref).astype(np.uint8), np.where(ph == 1, ref, alt).astype(np.uint8)
+    return _pick(vcf_path, contig, f)
+
+
+def dna_het_sites(vcf_path, contig=None):
+    """load_dna_vcf of the script for one contig (None: a dict of all contigs) -> pos0 of the records with a heterozygous 0/1 genotype,
+    phased or not, and single-base alleles"""
+    def f(pos, gt, ref, alt, ph):
+        return pos[(gt == 1) & (ref != 0) & (alt != 0)]
+    return _pick(vcf_path, contig, f)
+
+
+def eligible_candidates(cands, rec, min_phase_score):
+    """Mask over the candidate records: what the VCF writer prints as PASS with a phased het GT (vcf.format_records), with a phase set,
+    and that phase set the one chosen for the candidate's region in `rec` (Engine.ase's records): lcr_ase's eligibility without the join."""
+    fl = cands["flags"]
+    ok = ((fl & (_abi.F_DENSE | _abi.F_NON_SELECTED)) == 0) & (cands["variant_type"] == 1)
+    ok &= cands["phase_score"] >= float(min_phase_score)
+    ok &= (cands["allele1"] != cands["ref_base"]) | (cands["allele2"] != cands["ref_base"])
+    ok &= cands["phase_set"] != 0
+    if len(cands):
+        ok &= cands["phase_set"] == rec["phase_set"][cands["region"]]
+    return ok
+
+
+def filter_regions(rec, cands, dna_pos0, min_phase_score, min_support=10, overdispersion=0.001):
+    """calculate_ase_pvalue_filtering's drop rule, from the candidate records: a region is kept when one of its PASS phased-het sites of
+    the chosen phase set lies in the DNA set, has dp >= min_support and a beta-binomial p < 0.05 for alt_cnt = int(dp * af) of dp -- dp
+    and af as the VCF prints them (af to two decimals), sites with dp == 0 or a NaN af skipped.  -> bool per region."""
+    keep = np.zeros(len(rec), dtype=bool)
+    dna = np.asarray(dna_pos0, dtype=np.int64)
+    ok = eligible_candidates(cands, rec, min_phase_score) & np.isin(cands["pos"], dna)
+    for i in np.flatnonzero(ok):
+        s = cands[i]
+        g = int(s["region"])
+        if keep[g]:
+            continue
+        dp = int(s["depth"])
+        af = float(vcf._f2(float(s["af1"] if s["allele1"] != s["ref_base"] else s["af2"])))
+        if dp == 0 or af != af:
+            continue
+        if dp >= min_support and betabinom_two_sided(int(dp * af), dp, 0.5, overdispersion) < 0.05:
+            keep[g] = True
+    return keep
+
+
+def format_tsv(tables, min_support=10, overdispersion=0.001, patmat=False):
+    """The script's table text: .ase.tsv / .filter_ase.tsv (patmat=False) or .patmat_ase.tsv (patmat=True).  tables: [(chrom, rec,
+    region_start0, region_len[, keep])] -- per batch the contig's name, the records of Engine.ase(), the batch's region arrays and, for
+    the filter mode, filter_regions' mask (a region it drops is not written).  Written are the regions with h1 + h2 >= min_support, in the
+    order given; P_value is the two-sided beta-binomial test of h1 among h1 + h2, Benjamini-Hochberg adjusted over all written regions.
+    Gene_name is the region in the script's 1-based inclusive coordinates (as asj.format_tsv names it), PS is "." for 0."""
+    rows, pvals = [], []
+    for t in tables:
+        chrom, rec, start0, length = t[:4]
+        keep = t[4] if len(t) > 4 else None
+        for i in range(len(rec)):
+            r = rec[i]
+            h1, h2 = int(r["h1"]), int(r["h2"])
+            if h1 + h2 < min_support or (keep is not None and not keep[i]):
+                continue
+            g, ps = int(r["region"]), int(r["phase_set"])
+            head = "%s:%d-%d\t%s\t%s\t%d\t%d" % (chrom, int(start0[g]) + 1, int(start0[g]) + int(length[g]), chrom, ps if ps else ".", h1, h2)
+            tail = "\t%d\t%d\t%d\t%d" % (int(r["h1_pat"]), int(r["h1_mat"]), int(r["h2_pat"]), int(r["h2_mat"])) if patmat else ""
+            rows.append((head, tail))
+            pvals.append(betabinom_two_sided(h1, h1 + h2, 0.5, overdispersion))
+    adj = asj.bh_adjust(pvals)
+    lines = [(HEADER_PATMAT if patmat else HEADER) + "\n"]
+    for (head, tail), p in zip(rows, adj):
+        lines.append("%s\t%s%s\n" % (head, float(p), tail))
+    return "".join(lines)

@@ -1,7 +1,7 @@
 // lcr_ctx.h — the context behind the C ABI (include/lcr.h) and what its host units share: the stage state, timers, uploads, the settle
 // functions.  Private to lcr_api.hip (lifecycle, cache, fills, debug switches, phase entry, region discovery), lcr_batch.hip (binding and
 // upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns), lcr_calls.hip (candidate, import and fragment stages with their getters) and
-// lcr_junctions.hip (lcr_junctions, lcr_get_junctions).
+// lcr_junctions.hip (lcr_junctions, lcr_get_junctions) and lcr_ase.hip (lcr_ase, lcr_get_ase).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -119,6 +119,13 @@ struct lcr_ctx {
   HostBuf h_junc_ctl, h_junc, h_junc_off;   // pinned: {participating rows, pairs, kept junctions}; the records; their offsets per region
   hipEvent_t ev_junc = nullptr;             // behind the stage's last kernel
 
+  // K7 (lcr_ase): scratch and results of its own -- no other stage or getter reads them
+  bool ase_valid = false;    // lcr_get_ase: the last lcr_ase's records belong to the phase results of the bound batch (rewind_to)
+  int32_t ase_ng = 0;
+  DevBuf a_pos, a_pat, a_mat, a_tag, a_site, d_ase;   // host sites copied to HBM; a word per row, a byte per candidate; the records
+  HostBuf h_ase, h_ase_bad;                            // pinned: the records; the verdict on the parental sites
+  hipEvent_t ev_ase = nullptr;                         // behind the sites' check, then behind the call's last kernel
+
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
   std::vector<int64_t> rl_start0;
@@ -148,6 +155,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   }
   if (to < ST_FRAGGED) c->ds_rows_set = false;   // a sample names the rows of ONE fragment stage
   if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
+  if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and

@@ -314,6 +314,16 @@ void launch_k6_place(const BatchView& b, const uint64_t* tbl_key, const uint32_t
 void launch_k6_tables(const BatchView& b, const int32_t* part_off, const void* rows, const uint64_t* keys, int32_t n_kept, lcr_junction* junc,
                       lcr_junction* host_junc /* pinned (device pointer) */, hipStream_t s);
 
+// k7_ase.hip: haplotype and parent-of-origin counts per region over the phased rows (lcr_ase)
+void launch_k7_check(const int64_t* pos0, const uint8_t* pat, const uint8_t* mat, int32_t n_sites, int32_t* bad /* zeroed */, hipStream_t s);
+void launch_k7_pick(const int32_t* row_region_off, const lcr_read_record* rec, int32_t ng, lcr_ase_region* out,
+                    lcr_ase_region* host_out /* pinned (device pointer), or nullptr */, int32_t* row_tag /* n_rows, or nullptr: no votes follow */, hipStream_t s);
+void launch_k7_sites(const lcr_candidate* cand, int32_t n_cand, double min_phase_score, const int64_t* pos0, const uint8_t* pat,
+                     const uint8_t* mat, int32_t n_sites, lcr_ase_region* ase, uint8_t* site /* n_cand */, hipStream_t s);
+void launch_k7_votes(const int32_t* row_tag, int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const uint8_t* site,
+                     uint32_t min_baseq, lcr_ase_region* ase, hipStream_t s);
+void launch_k7_export(const lcr_ase_region* ase, int32_t ng, lcr_ase_region* host_out /* pinned (device pointer) */, hipStream_t s);
+
 // device helpers shared by kernels -------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ int base_code(uint8_t b) {

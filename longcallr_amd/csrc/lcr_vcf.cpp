@@ -8,6 +8,8 @@
 //   * the value is inserted into contig -> 0-based POS, so a later sample or a later record at that position overwrites the
 //     earlier one, a code 4 included (vcf.rs:448-455);
 //   * quality = record.qual() as f32, NaN for a missing QUAL; the phase bit, REF and ALT are not used (an indel is a site at its POS).
+// Beside the reference's three values every site keeps REF, ALT and the phase bit of its winning record and sample for
+// lcr_vcf_contig_alleles (the loaders of allele_specific/longcallR-ase.py read them); lcr_vcf_contig does not see them.
 // Input: plain text, or gzip / BGZF (a sequence of gzip members, every member is inflated), parsed as it is read.  BCF input is refused, and so is a
 // record with samples but no GT key in its FORMAT (the reference panics there: `genotypes().expect`); a sites-only record has no
 // samples and yields nothing, as the reference's loop over zero samples does.
@@ -32,6 +34,7 @@ struct lcr_vcf {
     std::vector<int64_t> pos0;
     std::vector<uint8_t> gt;
     std::vector<float> qual;
+    std::vector<uint8_t> ref, alt, phase;   // lcr_vcf_contig_alleles: parallel to the three above
   };
   std::vector<std::string> names;          // in the order of their first record
   std::vector<const char*> name_ptrs;
@@ -42,8 +45,11 @@ struct lcr_vcf {
 namespace {
 
 // one GT value: "0/1", "1|2", "./.", "1", "." -> number of alleles and the reference's code (missing allele = 3)
-int gt_code(const char* s, const char* e, int* n_alleles) {
+// *phase (diploid GTs): 0 = unphased, 1 = 0|1, 2 = 1|0, 3 = phased with other alleles
+int gt_code(const char* s, const char* e, int* n_alleles, int* phase) {
   int n = 0, a[2] = {0, 0};
+  bool bar = false;
+  *phase = 0;
   const char* p = s;
   while (p < e) {
     int v;
@@ -52,10 +58,11 @@ int gt_code(const char* s, const char* e, int* n_alleles) {
     else { *n_alleles = -1; return 4; }
     if (n < 2) a[n] = v;
     n++;
-    if (p < e) { if (*p != '/' && *p != '|') { *n_alleles = -1; return 4; } p++; if (p == e) { *n_alleles = -1; return 4; } }
+    if (p < e) { if (*p != '/' && *p != '|') { *n_alleles = -1; return 4; } bar = *p == '|'; p++; if (p == e) { *n_alleles = -1; return 4; } }
   }
   *n_alleles = n;
   if (n != 2) return 4;
+  if (bar) *phase = (a[0] == 0 && a[1] == 1) ? 1 : (a[0] == 1 && a[1] == 0) ? 2 : 3;
   if (a[0] == 0 && a[1] == 0) return 0;
   if ((a[0] == 0 && a[1] == 1) || (a[0] == 1 && a[1] == 0)) return 1;
   if (a[0] == 1 && a[1] == 1) return 2;
@@ -63,7 +70,7 @@ int gt_code(const char* s, const char* e, int* n_alleles) {
   return 4;
 }
 
-struct Entry { int64_t pos0; uint32_t seq; uint8_t gt; float qual; };
+struct Entry { int64_t pos0; uint32_t seq; uint8_t gt; float qual; uint8_t ref, alt, phase; };
 
 // Lines are parsed as the (inflated) bytes arrive: what is held is one input chunk, one output chunk, the partial line between
 // them and one entry per record that yields a site -- not the file, nor its inflated text.
@@ -125,7 +132,7 @@ struct Parser {
       ent.emplace_back();
     } else ci = it->second;
     // samples in order; each one with a diploid GT overwrites the record's value, so only the last of them counts
-    int last = -1;
+    int last = -1, last_phase = 0;
     for (const char* smp = col[9]; smp <= e;) {
       const char* se = smp; while (se < e && *se != '\t') se++;
       // the sample's GT subfield (a sample with fewer subfields has a missing GT: one allele, skipped)
@@ -134,13 +141,23 @@ struct Parser {
       while (f < gt_key && p < se) { if (*p == ':') f++; p++; }
       if (f == gt_key) {
         const char* q = p; while (q < se && *q != ':') q++;
-        int n_alleles = 0;
-        const int code = gt_code(p, q, &n_alleles);
-        if (n_alleles == 2) last = code;
+        int n_alleles = 0, phase = 0;
+        const int code = gt_code(p, q, &n_alleles, &phase);
+        if (n_alleles == 2) { last = code; last_phase = phase; }
       }
       smp = se + 1;
     }
-    if (last >= 0) ent[ci].push_back(Entry{(int64_t)pos - 1, seq++, (uint8_t)last, qual});
+    if (last >= 0) {
+      // REF's byte when REF is one base; the first ALT's byte when every ALT allele is one base
+      const uint8_t ref = end_of(3) - col[3] == 1 ? (uint8_t)col[3][0] : 0;
+      uint8_t alt = end_of(4) > col[4] ? (uint8_t)col[4][0] : 0;
+      for (const char* a = col[4]; a <= end_of(4);) {
+        const char* ae = a; while (ae < end_of(4) && *ae != ',') ae++;
+        if (ae - a != 1) alt = 0;
+        a = ae + 1;
+      }
+      ent[ci].push_back(Entry{(int64_t)pos - 1, seq++, (uint8_t)last, qual, ref, alt, (uint8_t)last_phase});
+    }
     return true;
   }
 
@@ -176,6 +193,7 @@ struct Parser {
       for (size_t i = 0; i < v.size(); i++) {
         if (i + 1 < v.size() && v[i + 1].pos0 == v[i].pos0) continue;   // the last value at a position wins
         c.pos0.push_back(v[i].pos0); c.gt.push_back(v[i].gt); c.qual.push_back(v[i].qual);
+        c.ref.push_back(v[i].ref); c.alt.push_back(v[i].alt); c.phase.push_back(v[i].phase);
       }
       std::vector<Entry>().swap(v);
     }
@@ -269,6 +287,16 @@ int lcr_vcf_contig(lcr_vcf* h, const char* name, int32_t* n, const int64_t** pos
   const lcr_vcf::Contig& c = h->contigs[it->second];
   *n = (int32_t)c.pos0.size();
   *pos0 = c.pos0.data(); *genotype = c.gt.data(); *qual = c.qual.data();
+  return LCR_OK;
+}
+
+int lcr_vcf_contig_alleles(lcr_vcf* h, const char* name, int32_t* n, const uint8_t** ref, const uint8_t** alt, const uint8_t** phase) {
+  if (!h || !name || !n || !ref || !alt || !phase) return LCR_E_ARG;
+  auto it = h->index.find(name);
+  if (it == h->index.end()) { *n = 0; *ref = nullptr; *alt = nullptr; *phase = nullptr; return LCR_OK; }
+  const lcr_vcf::Contig& c = h->contigs[it->second];
+  *n = (int32_t)c.pos0.size();
+  *ref = c.ref.data(); *alt = c.alt.data(); *phase = c.phase.data();
   return LCR_OK;
 }
 

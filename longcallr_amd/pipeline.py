@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import _abi, api, asj, bamio, vcf
+from . import _abi, api, ase, asj, bamio, vcf
 
 VCF_HEADER_TAIL = (   # thread.rs:232-262, verbatim
     '##FILTER=<ID=PASS,Description="All filters passed">\n'
@@ -109,7 +109,8 @@ def _gather_names(name_off, blob, rows):
 def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs=None, device=0, threads=0, seed=2025,
         read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None,
         downsample=False, downsample_depth=10000, downsample_seed=2025, truncation=False, truncation_coverage=200000,
-        asj_out=None, asj_min_count=10, asj_min_junctions=2, **param_overrides):
+        asj_out=None, asj_min_count=10, asj_min_junctions=2,
+        ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -134,7 +135,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     a region stands where the script has a gene, there is no annotation: include/lcr.h, lcr_junctions) as that script's .asj.tsv, written
     to asj_out.  Every chunk calls Engine.junctions right behind phase(); that call waits for the phase stage, so the chunk's overlap with
     the next chunk's upload and pileup (async_phase) is given up.  Adds the stat junctions (kept junctions, summed over chunks).  VCF and
-    phased BAM do not depend on it; without asj_out nothing changes."""
+    phased BAM do not depend on it; without asj_out nothing changes.
+    ase_out / ase_min_support / ase_overdispersion: the allele-specific expression table of longcallR-ase.py (--min_support / -d; regions in
+    place of genes: include/lcr.h, lcr_ase), written to ase_out.  Every chunk calls Engine.ase right behind phase() (behind junctions() when
+    both are on).  Alone it is the script's .ase.tsv; with ase_parental_vcf (--vcf2, a whole-genome phased VCF) the .patmat_ase.tsv with
+    the parent-of-origin votes of every haplotype's reads over this run's own PASS phased sites; with ase_dna_vcf (--vcf3) the
+    .filter_ase.tsv, which drops the regions none of whose sites is a DNA heterozygote with a significant imbalance.  The two VCFs together
+    are a ValueError (the script takes one mode), and so is either without ase_out.  Adds the stat ase_regions (rows written).  VCF, phased
+    BAM and .asj.tsv do not depend on it; without ase_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -146,6 +154,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     if downsample and not params.read_assign_cutoff > 0:    # (lcr_phase would answer LCR_E_ARG in the first chunk: include/lcr.h)
         raise ValueError("downsample=True needs read_assign_cutoff > 0 (preset %r has %r): an unsampled read's haplotag carries no sign, "
                          "pass e.g. read_assign_cutoff=1e-6" % (preset, float(params.read_assign_cutoff)))
+    if ase_parental_vcf is not None and ase_dna_vcf is not None:
+        raise ValueError("ase_parental_vcf and ase_dna_vcf are two modes of one table: give one of them")
+    if ase_out is None and (ase_parental_vcf is not None or ase_dna_vcf is not None):
+        raise ValueError("ase_parental_vcf / ase_dna_vcf need ase_out")
     fai = ref_path + ".fai"
     if not os.path.exists(fai):
         raise FileNotFoundError("Reference index file .fai does not exist.")   # util.rs:575-577
@@ -173,6 +185,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["imported_sites"] = 0
     if truncation:
         stats["truncated_columns"] = 0
+    parental = ase.parental_sites(ase_parental_vcf) if ase_parental_vcf is not None else None    # {contig: (pos0, pat, mat)}
+    dna = ase.dna_het_sites(ase_dna_vcf) if ase_dna_vcf is not None else None                    # {contig: pos0}
     no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
     # Every engine is a long-lived worker with the ASYNCHRONOUS phase stage (lcr_ctx_set_async_phase, include/lcr.h): a chunk is uploaded
@@ -180,14 +194,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -201,6 +215,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
         if junc is not None:
             out["junc"] = (name, junc, batch.start0, batch.len)
+        if arec is not None:
+            out["ase"] = (name, arec, batch.start0, batch.len)
+            if dna is not None:
+                out["ase"] += (ase.filter_regions(arec, cands, dna.get(name, np.zeros(0, np.int64)), params.min_phase_score,
+                                                  ase_min_support, ase_overdispersion),)
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates)
@@ -227,7 +246,15 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 fm = dict(row_for_phasing=f["row_for_phasing"], row_read=f["row_read"])
             E.phase()
             junc = E.junctions(asj_min_count, asj_min_junctions)[0] if asj_out is not None else None   # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc)
+            arec = None
+            if ase_out is not None:
+                psites = None
+                if parental is not None:    # the contig's parental sites inside the chunk's span (none when the VCF does not name the contig)
+                    pp, ppat, pmat = parental.get(name, (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.uint8)))
+                    lo, hi = np.searchsorted(pp, [int(batch.start0[0]), int(batch.start0[-1]) + int(batch.len[-1])])
+                    psites = (pp[lo:hi], ppat[lo:hi], pmat[lo:hi]) if hi > lo else None
+                arec = E.ase(psites)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec)
         finally:
             with free_lock:
                 free.append(k)
@@ -285,6 +312,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["junctions"] = sum(int(r["junc"][1].size) for r in results)
         with open(asj_out, "w") as f:
             f.write(asj.format_tsv([r["junc"] for r in results], asj_min_count))
+    if ase_out is not None:
+        text = ase.format_tsv([r["ase"] for r in results], ase_min_support, ase_overdispersion, patmat=parental is not None)
+        stats["ase_regions"] = text.count("\n") - 1
+        with open(ase_out, "w") as f:
+            f.write(text)
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

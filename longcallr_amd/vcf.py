@@ -12,9 +12,10 @@ import numpy as np
 from . import _abi
 
 
-def read_sites(path):
+def read_sites(path, alleles=False):
     """A VCF / .vcf.gz -> {contig: (pos0 int64, genotype uint8, qual float32)}, every array sorted by position: the sites
-    lcr_import_candidates takes (genotype codes 0-4 and the overwrite rules of vcf.rs:400-462, see include/lcr.h)."""
+    lcr_import_candidates takes (genotype codes 0-4 and the overwrite rules of vcf.rs:400-462, see include/lcr.h).
+    alleles=True: three more uint8 arrays per contig, (..., ref, alt, phase) of lcr_vcf_contig_alleles."""
     from . import _lib
     lib = _lib.load()
     h = C.c_void_p()
@@ -37,6 +38,11 @@ def read_sites(path):
                     return np.zeros(0, dt)
                 return np.frombuffer((C.c_char * (k * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).copy()
             out[name.decode()] = (arr(pos, np.int64), arr(gt, np.uint8), arr(q, np.float32))
+            if alleles:
+                ref, alt, ph = C.c_void_p(), C.c_void_p(), C.c_void_p()
+                if lib.lcr_vcf_contig_alleles(h, name, C.byref(m), C.byref(ref), C.byref(alt), C.byref(ph)) or m.value != k:
+                    raise _lib.LcrError(lib.lcr_vcf_last_error(h).decode())
+                out[name.decode()] += (arr(ref, np.uint8), arr(alt, np.uint8), arr(ph, np.uint8))
         return out
     finally:
         if h:

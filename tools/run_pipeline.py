@@ -5,6 +5,8 @@
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
                                  [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]]   (allele-specific junction table)
+                                 [--ase-out out.ase.tsv [--ase-min-support N] [--ase-overdispersion R]
+                                  [--ase-parental-vcf phased.vcf.gz | --ase-dna-vcf dna.vcf.gz]]   (allele-specific expression table)
 """
 import argparse
 import json
@@ -34,14 +36,25 @@ def main():
     ap.add_argument("--asj-out", help="write the allele-specific junction table (longcallR-asj.py's .asj.tsv; regions in place of genes)")
     ap.add_argument("--asj-min-count", type=int, default=10, help="reads a junction needs to be kept, and a table needs to be written")
     ap.add_argument("--asj-min-junctions", type=int, default=2, help="a read takes part with MORE junctions than this")
+    ap.add_argument("--ase-out", help="write the allele-specific expression table (longcallR-ase.py's .ase.tsv; regions in place of genes)")
+    ap.add_argument("--ase-min-support", type=int, default=10, help="assigned reads a region's phase set needs to be written")
+    ap.add_argument("--ase-overdispersion", type=float, default=0.001, help="rho of the beta-binomial test")
+    ap.add_argument("--ase-parental-vcf", help="whole-genome phased VCF (0|1: ALT paternal): adds the parent-of-origin votes (.patmat_ase.tsv)")
+    ap.add_argument("--ase-dna-vcf", help="DNA VCF: keep the regions with a significant DNA-heterozygous site (.filter_ase.tsv)")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
+    if a.ase_parental_vcf and a.ase_dna_vcf:
+        ap.error("--ase-parental-vcf and --ase-dna-vcf are two modes of one table: give one of them")
+    if (a.ase_parental_vcf or a.ase_dna_vcf) and not a.ase_out:
+        ap.error("--ase-parental-vcf / --ase-dna-vcf need --ase-out")
     extra = {} if a.read_assign_cutoff is None else dict(read_assign_cutoff=a.read_assign_cutoff)
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
                       device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf,
                       downsample=a.downsample, downsample_depth=a.downsample_depth,
                       truncation=a.truncation, truncation_coverage=a.truncation_coverage,
-                      asj_out=a.asj_out, asj_min_count=a.asj_min_count, asj_min_junctions=a.asj_min_junctions, **extra)
+                      asj_out=a.asj_out, asj_min_count=a.asj_min_count, asj_min_junctions=a.asj_min_junctions,
+                      ase_out=a.ase_out, ase_min_support=a.ase_min_support, ase_overdispersion=a.ase_overdispersion,
+                      ase_parental_vcf=a.ase_parental_vcf, ase_dna_vcf=a.ase_dna_vcf, **extra)
     print(json.dumps(st))
 
 
