@@ -1,5 +1,6 @@
-// k4_dev.h — device code shared by the K4 translation units (k4_phase.hip, k4_grid.hip): counter-based RNG,
-// region / matrix descriptors, the one-workgroup cross_optimize (phase.rs:810-976), wave and workgroup scans.
+// k4_dev.h — device code shared by the K4 kernel units (k4_enum.hip, k4_stage.hip, k4_post.hip, k4_grid.hip): counter-based RNG,
+// region / matrix descriptors, the one-workgroup cross_optimize (phase.rs:810-976), wave and workgroup scans, the two scopes a step is
+// written against and the row-ordered column index both scopes build (ordered_index).
 // Plain kernel-argument structs are global types; functions live in an anonymous namespace (one copy per translation unit, no RDC).
 #pragma once
 #include <climits>
@@ -729,5 +730,73 @@ struct GridScope {
 
 // a wave's own stores, made by one lane, before loads of the same addresses by its other lanes
 __device__ __forceinline__ void wave_mem_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+
+
+// ------------------------------------------------------------------------------------------------------------
+// ordered column index: cent[cp[i] .. cp[i+1]) = the phase entries (indices into the CSR) of SNP i in row order,
+// erow[e] = phasing row of entry e.  Stable counting sort by column: the rows are cut into n_parts runs, entries
+// are counted per (part, SNP), and each part is filled by one wave, 64 entries at a time in CSR order.
+// ------------------------------------------------------------------------------------------------------------
+template <class SC>
+__device__ void ordered_index(SC& sc, int R, int S, const int32_t* rp, const int32_t* pc, const int32_t* cp /* or nullptr */, int32_t* cp_out,
+                              int32_t* erow, int32_t* cent, int32_t* pcnt, int np, int (*sm)[16]) {
+  const int rq = max(1, (R + np - 1) / np);
+  for (int64_t i = sc.tid(); i < (int64_t)np * S; i += sc.nt()) pcnt[i] = 0;
+  sc.sync();
+  for (int row = sc.tid(); row < R; row += sc.nt()) {
+    int32_t* cnt = pcnt + (int64_t)(row / rq) * S;
+    for (int e = rp[row]; e < rp[row + 1]; e++) { erow[e] = row; atomicAdd(&cnt[pc[e]], 1); }
+  }
+  sc.sync();
+  if (!cp) {   // column offsets from the counts
+    for (int i = sc.tid(); i < S; i += sc.nt()) { int t = 0; for (int q = 0; q < np; q++) t += pcnt[(int64_t)q * S + i]; cp_out[i] = t; }
+    sc.sync();
+    if (sc.blk() == 0) {
+      int carry = 0;
+      for (int base = 0; base < S; base += (int)blockDim.x) {
+        const int i = base + threadIdx.x;
+        const int d = i < S ? cp_out[i] : 0;
+        int ex, d0, tot, d1;
+        block_scan2_rt(d, 0, ex, d0, tot, d1, sm);
+        if (i < S) cp_out[i] = carry + ex;
+        carry += tot;
+      }
+      if (threadIdx.x == 0) cp_out[S] = carry;
+    }
+    sc.sync();
+    cp = cp_out;
+  }
+  for (int i = sc.tid(); i < S; i += sc.nt()) {
+    int at = cp[i];
+    for (int q = 0; q < np; q++) { int32_t* p = pcnt + (int64_t)q * S + i; const int n = *p; *p = at; at += n; }
+  }
+  sc.sync();
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int q = sc.wave(); q < np; q += sc.nwaves()) {
+    int32_t* cur = pcnt + (int64_t)q * S;
+    const int e_lo = rp[(int)min((int64_t)q * rq, (int64_t)R)], e_hi = rp[(int)min((int64_t)(q + 1) * rq, (int64_t)R)];
+    for (int base = e_lo; base < e_hi; base += 64) {
+      const int e = base + lane;
+      const bool valid = e < e_hi;
+      const int c = valid ? pc[e] : -1;
+      const int at = valid ? cur[c] : 0;          // all cursor reads of the chunk precede its cursor writes
+      unsigned long long rem = __ballot(valid), mine = 0;
+      while (rem) {                               // lanes with equal columns, in lane (= row) order
+        const int cc = __shfl(c, __ffsll((long long)rem) - 1, 64);
+        const unsigned long long m = __ballot(c == cc);
+        if (c == cc) mine = m;
+        rem &= ~m;
+      }
+      if (valid) {
+        const int rank = __popcll(mine & below);
+        cent[at + rank] = e;
+        if (rank == 0) cur[c] = at + __popcll(mine);
+      }
+      wave_mem_sync();
+    }
+  }
+  sc.sync();
+}
 
 }  // namespace

@@ -3,6 +3,7 @@
 #include <climits>
 #include <type_traits>
 #include "k4_dev.h"
+#include "k4_grid.h"
 #include "k4_kernels.h"
 
 #ifndef ENUM_OCC
@@ -1714,7 +1715,6 @@ void launch_k4_enum_bits(unsigned n_blocks, size_t dyn_lds, hipStream_t s, const
                          long long* region_best, uint32_t* redo, uint32_t redo_cap) {
   hipLaunchKernelGGL(k4_enum_bits, dim3(n_blocks), dim3(64 * ENUM_WAVES), dyn_lds, s, P, spans, n_spans, per, job_base, job_obj, st_base, st_words, region_best, redo, redo_cap);
 }
-hipError_t k4_set_dyn_lds_once(const void* fn, int bytes, int slot);   // (k4_grid.hip: once per device)
 void launch_k4_enum_redo(unsigned n_blocks, hipStream_t s, const PhaseDev& P, const uint32_t* redo, uint32_t redo_cap, int8_t* scratch, int32_t scratch_stride,
                          double* qrow, int64_t qrow_stride, const int64_t* job_base, long long* job_obj, const int64_t* st_base, unsigned long long* st_words,
                          uint32_t lds_bytes) {

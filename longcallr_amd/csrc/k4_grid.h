@@ -1,4 +1,5 @@
-// k4_grid.h — launchers of the chain-region kernels (k4_grid.hip) for the host control in k4_phase.hip.
+// k4_grid.h — launchers of the kernels that serve one region with all CUs, and of the chain-region kernels, for the host control in
+// k4_phase.hip: k4_chain_wg / k4_chain_grid (k4_grid.hip), k4_stage_grid (k4_stage.hip), k4_gpost (k4_post.hip).
 #pragma once
 #include "k4_dev.h"
 
@@ -13,11 +14,12 @@ inline size_t k4_grid_fast_lds(int64_t R, int64_t S) { return (size_t)(8 * ((R +
 constexpr int K4_GRID_BATCH_MAX_WG = 512;
 constexpr int K4_GRID_BATCH_CTL_BYTES = 128 + 2048 + 128 + K4_GRID_BATCH_MAX_WG * 128;
 inline size_t k4_grid_batch_lds(int64_t S) { return (size_t)(12 * (S + 2) + 24 * 1024); }
-// workgroups of a grid launch (co-resident by construction); 0 = no device
+// threads per workgroup / workgroups of a grid launch (co-resident by construction); 0 = no device
+constexpr int K4_GRID_THREADS = 1024;
 int k4_grid_blocks();
-// k4_stage for one large region with all CUs; blk_tot: 3 * k4_grid_blocks() + 1 int32 of scratch
+// k4_stage_grid (k4_stage.hip): one large region with all CUs; blk_tot: 3 * k4_grid_blocks() + 1 int32 of scratch
 hipError_t k4_stage_launch_grid(const StageIn& in, const StageOut& out, const PhaseLutDev& lut, int g, GridCtl* ctl, int32_t* blk_tot, hipStream_t s);
-// post-phase steps for one large region with all CUs
+// k4_gpost (k4_post.hip): post-phase steps for one large region with all CUs
 hipError_t k4_post_launch_grid(const PostIn& post_in, const PostScratch& ps, int g, const PostLut& lut, hipStream_t s);
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel slot 0..7, device)
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel slot 0..7, device) (k4_grid.hip)
 hipError_t k4_set_dyn_lds_once(const void* fn, int bytes, int slot);

@@ -6,7 +6,8 @@
 //
 // Kernel units (in launch order; one queue stages + enumerates + post-processes, a second queue carries the
 // few chain regions, see PhaseHost::run); k4_kernels.h / k4_grid.h hold their launchers and LDS layouts:
-//   k4_stage.hip  k4_stage      phase matrices (CSR + CSC, per-SNP constants) of every region from K3's fragment CSR
+//   k4_stage.hip  k4_stage / k4_stage_grid   phase matrices (CSR + CSC, per-SNP constants) of every region from K3's fragment CSR:
+//                               one workgroup per region, or all CUs on one large region
 //   k4_enum.hip   k4_enum_bits / k4_enum_reg   S <= max_enum_snps: all 2^S enumeration restarts (phase.rs:1097-1122), eight
 //                               restarts per wave as bit states / one wave64 per restart with the entries streamed from LDS;
 //                               every restart leaves its objective, final state and signature
@@ -16,7 +17,8 @@
 //                               decision, then the winner re-run to materialise its state
 //   k4_grid.hip   k4_chain_wg / k4_chain_grid   S > max_enum_snps: the sequential chain (phase.rs:1123-1233) with one
 //                               workgroup per region, or all CUs on one large region (LD-block flip pass, perturbation rounds)
-//   k4_post.hip   k4_post       post-phase assignment, rescue and phase sets (f64, reference observation order)
+//   k4_post.hip   k4_post / k4_gpost   post-phase assignment, rescue and phase sets (f64, reference observation order): one workgroup
+//                               per region with its image in LDS, or all CUs on one large region
 // cross_optimize alternates sigma / delta-eta Jacobi steps until neither improves (<= 21 iterations).
 // Its decision arithmetic is exact: every emission term log10(eps_q) / log10(1-eps_q) comes from a
 // 31-entry table in fixed point (scale 2^40, int64), so sums are order-free and every comparison

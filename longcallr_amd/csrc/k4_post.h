@@ -1,8 +1,8 @@
 // k4_post.h — the post-phase sequence of thread.rs:168-201 on the device, written once for two scopes:
 //   assign_reads_haplotype + assign_het_var_haplotype (x2), eval_rna_edit_var_phase, eval_low_frac_var_phase,
 //   assign_reads_haplotype + assign_het_var_haplotype, assign_phase_set   (snpfrags.rs:191-733).
-// WgScope  (k4_post, k4_phase.hip): one workgroup per region, the region's fragment rows in LDS (16-bit indices);
-// GridScope (k4_gpost, k4_grid.hip): all workgroups on one region, the same arrays in HBM (32-bit indices) — for
+// WgScope  (k4_post, k4_post.hip): one workgroup per region, the region's fragment rows in LDS (16-bit indices);
+// GridScope (k4_gpost, k4_post.hip): all workgroups on one region, the same arrays in HBM (32-bit indices) — for
 // regions beyond the LDS image (config C5).  These are f64 sum-of-ratio decisions: every log10(eps) / log10(1-eps)
 // term comes from the table of libm values the host path uses (kernel argument), sums run in the reference's
 // observation order (a read's entries in column order, a SNP's reads in row order) and -ffp-contract=off keeps

@@ -1,5 +1,6 @@
-// k4_post.hip — K4, post-phase steps with one workgroup per region (reference src/thread.rs:168-201, snpfrags.rs:191-733);
-// the steps themselves are k4_post.h's post_run.  Host control: k4_phase.hip; the all-CU form for one large region is in k4_grid.hip.
+// k4_post.hip — K4, post-phase steps (reference src/thread.rs:168-201, snpfrags.rs:191-733): k4_post, one workgroup per region with the
+// region image in LDS, and k4_gpost, all CUs on one large region with the image in HBM.  Both set up the same state (post_init) and run
+// k4_post.h's post_run; they differ in how the row-ordered column index is built.  Host control: k4_phase.hip.
 #include <climits>
 #include "k4_dev.h"
 #include "k4_grid.h"
@@ -8,10 +9,30 @@
 
 namespace {
 
+// What both kernels set up before post_run: the LUT, the SNPs' state, the fragment rows' offsets and flags, the optimiser's haplotags.
+template <class SC, class IDX>
+__device__ __forceinline__ void post_init(SC& sc, const PostIn& in, const PostLut& lut, PostView<IDX>& v, int64_t e_base) {
+  const int r0 = v.r0, c0 = v.c0;
+  if (threadIdx.x < 31) { v.le[threadIdx.x] = lut.le[threadIdx.x]; v.l1e[threadIdx.x] = lut.l1e[threadIdx.x]; }
+  for (int i = sc.tid(); i < v.S; i += sc.nt()) {
+    v.sflags[i] = v.soflags[i] = v.cand[i].flags;
+    v.shap[i] = in.st_delta[c0 + i]; v.sgt[i] = in.st_eta[c0 + i]; v.svt[i] = (int8_t)v.cand[i].variant_type;
+    v.sps[i] = v.cand[i].phase_score;
+    v.parent[i] = 0;
+  }
+  for (int r = sc.tid(); r < v.nrow; r += sc.nt()) {
+    const int isp = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
+    v.rptr[r] = (IDX)(in.row_ptr[r0 + r] - e_base);
+    v.lok[r] = (uint8_t)isp; v.fp[r] = (uint8_t)isp; v.asg[r] = 0; v.tag[r] = (int8_t)(isp && v.smp && !v.smp[r] ? 1 : 0);   // (an unsampled row's init_assignment tag: its sign is never read)
+  }
+  if (sc.tid() == 0) v.rptr[v.nrow] = (IDX)v.E;
+  sc.sync();
+  for (int k = sc.tid(); k < v.F; k += sc.nt()) v.tag[in.prow_src[r0 + k]] = in.st_sigma[r0 + k];   // the optimiser's haplotags
+}
+
 // ---------------------------------------------------------------------------------------------
 // k4_post: the post-phase sequence of thread.rs:168-201, one workgroup per region with the region's fragment rows
-// staged in LDS and a row-ordered column index (stable counting sort by one wave per row part); the steps
-// themselves are k4_post.h's post_run, shared with the all-CUs-on-one-region form (k4_gpost, k4_grid.hip).
+// staged in LDS and a row-ordered column index (stable counting sort by one wave per row part).
 // ---------------------------------------------------------------------------------------------
 template <int NT>
 __global__ void __launch_bounds__(NT) k4_post(PostIn in, const int32_t* __restrict__ slots, int32_t n_slots, PostLut lut) {
@@ -51,22 +72,9 @@ __global__ void __launch_bounds__(NT) k4_post(PostIn in, const int32_t* __restri
   int n_mark = 0;
   auto mark = [&]() { if (in.dbg_clk && tid == 0) in.dbg_clk[(size_t)g * 16 + n_mark] = (long long)wall_clock64(); n_mark++; };
   mark();
-  // ---- stage: LUT, SNP state, rows, entries, row-ordered column index
-  if (tid < 31) { v.le[tid] = lut.le[tid]; v.l1e[tid] = lut.l1e[tid]; }
-  for (int i = tid; i < S; i += NT) {
-    v.sflags[i] = v.soflags[i] = v.cand[i].flags;
-    v.shap[i] = in.st_delta[c0 + i]; v.sgt[i] = in.st_eta[c0 + i]; v.svt[i] = (int8_t)v.cand[i].variant_type;
-    v.sps[i] = v.cand[i].phase_score;
-    v.parent[i] = 0;
-  }
-  for (int r = tid; r < nrow; r += NT) {
-    const int isp = in.links[r0 + r] >= in.min_linkers ? 1 : 0;
-    rptr[r] = (uint16_t)(in.row_ptr[r0 + r] - e_base);
-    v.lok[r] = (uint8_t)isp; v.fp[r] = (uint8_t)isp; v.asg[r] = 0; v.tag[r] = (int8_t)(isp && v.smp && !v.smp[r] ? 1 : 0);   // (an unsampled row's init_assignment tag: its sign is never read)
-  }
-  if (tid == 0) rptr[nrow] = (uint16_t)E;
-  __syncthreads();
-  for (int k = tid; k < v.F; k += NT) v.tag[in.prow_src[r0 + k]] = in.st_sigma[r0 + k];   // the optimiser's haplotags
+  // ---- stage: LUT, SNP state, rows; then entries and the row-ordered column index
+  WgScope sc{red, &wg_bc};
+  post_init(sc, in, lut, v, e_base);
   mark();
   // row-ordered column index: wave q fills the entries of the q-th part of the rows (stable inside a
   // part: 64 entries at a time in (row, column) order, equal columns keep their order), the parts'
@@ -124,7 +132,42 @@ __global__ void __launch_bounds__(NT) k4_post(PostIn in, const int32_t* __restri
   }
   __syncthreads();
   mark();
-  WgScope sc{red, &wg_bc};
+  post_run(sc, in, lut, v, mark);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k4_gpost: the post-phase sequence (k4_post.h) with all CUs on ONE region, the region image in HBM
+// ------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(K4_GRID_THREADS) k4_gpost(PostIn in, PostScratch ps, int32_t g, PostLut lut) {
+  __shared__ long long red[K4_GRID_THREADS / 64];
+  __shared__ unsigned long long bc[2];
+  __shared__ int sm[2][16];
+  __shared__ double s_lut[64];
+  __shared__ double stage[(K4_GRID_THREADS / 64) * 4 * POST_SSTR];
+  GridScope sc{ps.ctl, red, bc, 0u};
+  const int r0 = in.row_region_off[g], nrow = in.row_region_off[g + 1] - r0;
+  const int c0 = in.cand_off[g], S = in.cand_off[g + 1] - c0;
+  const int64_t e_base = in.row_ptr[r0];
+  const int E = (int)(in.row_ptr[r0 + nrow] - e_base);
+  PostView<int32_t> v;
+  v.g = g; v.S = S; v.nrow = nrow; v.E = E; v.F = in.reg[g].R; v.FA = in.reg[g].F_all; v.r0 = r0; v.c0 = c0;
+  v.smp = in.sampled ? in.sampled + r0 : nullptr;
+  v.le = s_lut; v.l1e = s_lut + 32;
+  v.sps = ps.sps; v.rpa = ps.rpa; v.rpb = ps.rpb; v.sflags = ps.sflags; v.soflags = ps.soflags; v.parent = ps.parent;
+  v.rptr = ps.rptr; v.ecol = ps.ecol; v.erow = ps.erow; v.cent = ps.cent; v.ccptr = ps.ccptr; v.ev = ps.ev;
+  v.tag = ps.tag; v.asg = ps.asg; v.fp = ps.fp; v.lok = ps.lok; v.dirty = ps.dirty;
+  v.shap = ps.shap; v.sgt = ps.sgt; v.svt = ps.svt; v.rcode = ps.rcode;
+  v.fdirt = ps.fdirt; v.minf = ps.minf; v.ndraw = ps.ndraw; v.gwords = ps.gwords;
+  v.cand = in.cand + c0;
+  v.stage = stage;
+  int n_mark = 0;
+  auto mark = [&]() { if (in.dbg_clk && sc.tid() == 0) in.dbg_clk[(size_t)g * 16 + n_mark] = (long long)wall_clock64(); n_mark++; };
+  mark();
+  for (int e = sc.tid(); e < E; e += sc.nt()) { v.ecol[e] = in.col[e_base + e] - c0; v.ev[e] = in.val[e_base + e]; }   // (visible behind post_init's barrier)
+  post_init(sc, in, lut, v, e_base);
+  mark();
+  ordered_index(sc, nrow, S, v.rptr, v.ecol, nullptr, v.ccptr, v.erow, v.cent, ps.pcnt, ps.n_parts, sm);
+  mark();
   post_run(sc, in, lut, v, mark);
 }
 }  // namespace
@@ -141,4 +184,13 @@ hipError_t launch_k4_post(int threads, unsigned n_blocks, size_t dyn_lds, hipStr
     hipLaunchKernelGGL(k4_post<CHAIN_THREADS / 2>, dim3(n_blocks), dim3(CHAIN_THREADS / 2), dyn_lds, s, in, slots, n_slots, lut);
   }
   return hipSuccess;
+}
+
+hipError_t k4_post_launch_grid(const PostIn& post_in, const PostScratch& ps, int g, const PostLut& lut, hipStream_t s) {
+  const int nb = k4_grid_blocks();
+  if (nb <= 0) return hipErrorInvalidDevice;
+  hipError_t e = hipMemsetAsync(ps.ctl, 0, sizeof(GridCtl), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k4_gpost, dim3((unsigned)nb), dim3(K4_GRID_THREADS), 0, s, post_in, ps, (int32_t)g, lut);
+  return hipGetLastError();
 }

@@ -119,7 +119,7 @@ struct ChainDev {
 };
 
 
-// ---- staging of the phase matrices (k4_stage, k4_phase.hip; k4_stage_grid, k4_grid.hip)
+// ---- staging of the phase matrices (k4_stage / k4_stage_grid, k4_stage.hip)
 struct StageIn {
   const int64_t* row_ptr; const int32_t* col; const uint8_t* val; const uint32_t* links;
   const lcr_candidate* cand; const int32_t* cand_off; const int32_t* row_region_off; const int64_t* start0;

@@ -808,7 +808,7 @@ def test_contexts_on_concurrent_host_threads(engine_cls):
 
 def test_deep_region_beyond_the_lds_images(engine_cls, orc):
     """A region with more rows / entries than the LDS images of k4_stage (4096 rows, 8192 entries) and k4_post
-    hold: the phase stage then works from global memory and finishes with the host epilogue."""
+    hold: k4_stage then reads the fragment rows from global memory (its unstaged form) and the post-phase steps run in k4_gpost."""
     b = synth.make_batch("ont-cdna", n_genes=1, gene_len=9000, depth=600, seed=91)
     full_check(engine_cls, orc, b, _abi.make_params("ont-cdna", seed=9))
 
