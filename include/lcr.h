@@ -335,7 +335,8 @@ int lcr_collect_phase(lcr_ctx*, lcr_phase_collected* out);
  *   motif                 the reference bytes at s, s+1 and s+l-2, s+l-1 of the region's window, upper-cased: 1 = GT..AG, 2 = CT..AC,
  *       0 otherwise, for l < 2, or when either pair lies outside the window.
  *   order                 by region, then s, then l, ascending; independent of the batch's composition and bit-reproducible (integer adds).
- * Not the script's: no annotation (no gene assignment of reads, no exon-overlap filter, no Novel / Strand / Gene_name); the tie between
+ * Not the script's: no annotation (no gene assignment of reads -- lcr_get_read_genes exports the map a per-gene table would start from --,
+ * no exon-overlap filter, no Novel / Strand / Gene_name); the tie between
  * equally large phase sets goes to the smallest value (the script: a Python set's iteration order); zero-length N ops are ignored;
  * rows are not restricted to reads contained in the region (with --truncation a read that spans a cut is a row of both flanks).
  * lcr_junctions needs the bound batch after lcr_phase (LCR_E_STATE otherwise, nothing changed; params == NULL: LCR_E_ARG), collects an
@@ -374,8 +375,8 @@ int lcr_get_junctions(lcr_ctx*, lcr_junction_list* out);
  *       mat, else as nothing.  The row votes paternal if pat > mat, maternal if pat < mat, not at all if they are equal (a row without
  *       an eligible entry among them).  h1_pat, h1_mat, h2_pat, h2_mat count the votes by the row's haplotype.
  *   order              one record per region, in region order; integer adds only: bit-reproducible, independent of the batch's composition.
- * Not the script's: no annotation (no gene assignment of reads, no exon filter); the tie between equally large phase sets goes to the
- * smallest value (the script: a dict's order); a read's base is seen only where the fragment matrix has an entry -- the base is the
+ * Not the script's: no annotation here (no gene assignment of reads -- lcr_assign_genes / lcr_ase_genes below are the per-gene form --, no
+ * exon filter); the tie between equally large phase sets goes to the smallest value (the script: a dict's order); a read's base is seen only where the fragment matrix has an entry -- the base is the
  * site's reference or one of its two major alleles (fragment.rs:134-152) --, so a parental allele that is neither is never counted; only
  * single-base REF / ALT parental records are used; rows are not restricted to reads contained in the region.
  * lcr_ase needs the bound batch after lcr_phase (LCR_E_STATE otherwise, nothing changed; params == NULL or min_baseq > 30: LCR_E_ARG),
@@ -398,6 +399,67 @@ typedef struct {
 typedef struct { int32_t n_regions; const lcr_ase_region* rec; const lcr_ase_region* dev_rec; } lcr_ase_list;
 int lcr_ase(lcr_ctx*, const lcr_ase_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* pat, const uint8_t* mat);
 int lcr_get_ase(lcr_ctx*, lcr_ase_list* out);
+
+/* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
+ * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
+ * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.
+ *   annotation         one contig's genes (the rule of lcr_import_candidates: the batch lies on ONE contig), sorted by (span_start0,
+ *       span_end0); gene k's merged exons are exon_start0 / exon_end0 [exon_off[k], exon_off[k + 1]): at least one, ascending and disjoint
+ *       (abutting exons are allowed), the first one starting at span_start0[k], the last one ending at span_end0[k].  The index k is the
+ *       gene's id.  longcallr_amd/annotation.py builds these arrays from a GTF / GFF3.
+ *   blocks of a read   walk the CIGAR from pos: M, D, = and X add to the current block; an N op of ANY length, 0 included, ends the block
+ *       and starts the next one behind it (the script resets at every op 3; lcr_junctions' "zero-length N ignored" does not apply here);
+ *       I, S, H and P do nothing; a block of length 0 is no block.  rend = pos + all reference-consuming lengths (exclusive).
+ *   candidate genes    of a read [pos, rend): span_start0 < rend && span_end0 > pos.
+ *   overlap            a block [s, e) and a merged exon [x, y) contribute min(e, y) - max(s, x) iff e - s >= 2, y > s and x < e - 1 (the
+ *       script queries its interval tree with the block's inclusive end as an exclusive one: a one-base block contributes nothing, and
+ *       neither does an exon that meets only the block's last base; restated as it is, not repaired).  A read's overlap with a gene is
+ *       the sum over its blocks and the gene's exons.
+ *   choice             the candidate with the largest overlap, ties to the smallest gene index (the script: the iteration order of a
+ *       Python set); a largest overlap of 0 still assigns.  Without a candidate: gene -1, overlap 0.
+ * Per read of the batch, independent of the batch's composition, integer only.
+ * lcr_assign_genes needs a bound batch at any stage and does not move the stage (LCR_E_STATE without one; a NULL annotation, negative
+ * sizes or NULL arrays with n_genes > 0: LCR_E_ARG).  mem as in lcr_import_candidates: LCR_MEM_HOST arrays are copied before the call
+ * returns; LCR_MEM_DEVICE arrays are read in place on the context's stream, also by the kernel that runs BEHIND the call's return: they
+ * must be complete with respect to that stream when the call is made and stay valid and unchanged until lcr_get_read_genes or
+ * lcr_ctx_sync has returned.  The arrays are checked by a kernel whose verdict the call waits for (its one host wait): a refused
+ * annotation is LCR_E_ARG and changes nothing -- the last call's result still answers.  As in every stage, a read's pos plus its
+ * reference-consuming lengths is below 2^31 (the batch's int32 contig coordinates; lcr_junctions walks under the same bound): the walk
+ * sums the lengths of sixteen ops in 32 bits.
+ * n_genes == 0 is valid: every read gets -1.  The result dies at lcr_load_batch / lcr_bind_batch; lcr_get_read_genes answers LCR_E_STATE
+ * then; a successful call also drops the records of an earlier lcr_ase_genes, which counted the rows of the assignment it replaces.
+ * gene / overlap: pinned host memory, n_reads entries in the batch's read order, valid until the next lcr_assign_genes;
+ * dev_gene: the gene indices in HBM (the input of a per-gene consumer that stays on the device). */
+typedef struct { int32_t n_genes, n_exons; const int64_t *span_start0, *span_end0; const int32_t* exon_off;
+                 const int64_t *exon_start0, *exon_end0; } lcr_gene_annotation;   /* one contig's genes, the rule of lcr_import_candidates */
+int lcr_assign_genes(lcr_ctx*, int32_t mem, const lcr_gene_annotation*);
+int lcr_get_read_genes(lcr_ctx*, int32_t* n_reads, const int32_t** gene, const uint32_t** overlap, const int32_t** dev_gene);
+
+/* Per-gene allele-specific expression: the contract of lcr_ase with "region" read as "(region, gene) pair" and two changes.
+ *   pairs              one record per region g and gene k with at least one fragment row of g whose read is assigned to k (whatever the
+ *       row's haplotype), ordered by region, then gene; pair_region_off[g] .. [g + 1] are region g's records.
+ *   counting rows      of pair (g, k): rows of g with assignment 1 / 2, a phase set != 0 and gene[read of the row] == k.  phase_set,
+ *       n_phase_sets, h1, h2 as in lcr_ase over those rows.
+ *   eligible site      lcr_ase's (1) - (4) against the PAIR's phase set: a candidate of g may be eligible for several pairs of g.  No
+ *       restriction to the gene's coordinates (the script's pileup() call does not truncate).  n_sites counts them per pair.
+ *   votes              as in lcr_ase, over the pair's counting rows of its phase set.
+ * A gene that lies in several regions (or chunks) has several records: longcallr_amd/ase.py merge_gene_records picks the one with the
+ * most reads, which is exact because phase sets of different regions are distinct.  Same parameters, mem rule and site checks as lcr_ase.
+ * Needs lcr_phase and a valid lcr_assign_genes of the bound batch (LCR_E_STATE otherwise); one host wait on the number of pairs (beside
+ * the sites' verdict).  The records die with the phase stage's results and with the gene assignment -- at lcr_load_batch /
+ * lcr_bind_batch and at the next successful lcr_assign_genes --; lcr_get_ase_genes answers LCR_E_STATE then. */
+typedef struct {
+  int32_t region;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1, h2;
+  uint32_t n_sites;
+  uint32_t h1_pat, h1_mat, h2_pat, h2_mat;
+  int32_t gene;                       /* index into the annotation of lcr_assign_genes */
+  uint32_t pad_;
+} lcr_ase_gene;              /* 48 bytes: lcr_ase_region's fields, then the gene */
+typedef struct { int32_t n_regions, n_pairs; const lcr_ase_gene* rec; const int32_t* pair_region_off; const lcr_ase_gene* dev_rec; } lcr_ase_gene_list;
+int lcr_ase_genes(lcr_ctx*, const lcr_ase_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* pat, const uint8_t* mat);
+int lcr_get_ase_genes(lcr_ctx*, lcr_ase_gene_list* out);
 
 /* Down-sampling: phase deep regions on a read sample (longcallR --downsample / --downsample-depth: thread.rs:144-151, phase.rs:693-701).
  * A region with at least `depth` fragment rows (all rows of lcr_get_fragmat, empty ones included) is down-sampled: the optimiser
@@ -625,6 +687,12 @@ enum { LCR_K_SPANS = 0 /* K0: CIGAR decode + binning */, LCR_K_PILEUP, LCR_K_CAN
        LCR_K_BIND_TABLE /* lcr_load_batch of a device batch: region table + CIGAR layout check, before its one host wait */,
        LCR_K_CAND_IMPORT /* lcr_import_candidates: count, scan, emit */, LCR_K_JUNCTIONS /* lcr_junctions, first kernel to last */,
        LCR_K_ASE /* lcr_ase, first kernel to last behind the check of the parental sites */, LCR_NKERNELS };
+/* The two slots of the per-gene calls follow LCR_NKERNELS in a list of their own -- the slots above keep their numbers and LCR_K_ASE stays
+ * the last one in front of LCR_NKERNELS, which tests/test_ase_host.py pins --; lcr_kernel_ms and the "timing_mask" bits take every slot
+ * below LCR_NTIMERS. */
+enum { LCR_K_GENES = LCR_NKERNELS /* lcr_assign_genes: k8_assign and the two copies of its result, behind the annotation's check */,
+       LCR_K_ASE_GENES /* lcr_ase_genes, first kernel to last behind the check of the parental sites, the wait for the number of pairs included */,
+       LCR_NTIMERS };
 int lcr_enable_timing(lcr_ctx*, int on);
 int lcr_kernel_ms(lcr_ctx*, int kernel, float* ms);
 /* Bytes the pileup tally kernel (K1) of the last lcr_pileup has to move: read bases once (B) + 8-byte

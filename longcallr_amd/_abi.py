@@ -19,6 +19,7 @@ F_RNA_EDIT, F_DENSE, F_HET, F_FOR_PHASING, F_HOM, F_SINGLE, F_NON_SELECTED, F_CA
 
 (K_SPANS, K_PILEUP, K_CAND_FILTER, K_CAND_HIST, K_CAND_GT, K_FRAG_COUNT, K_FRAG_FILL, K_PHASE, K_BIND, K_BIND_TABLE,
  K_CAND_IMPORT, K_JUNCTIONS, K_ASE, NKERNELS) = range(14)
+K_GENES, K_ASE_GENES, NTIMERS = NKERNELS, NKERNELS + 1, NKERNELS + 2   # include/lcr.h: the per-gene calls' slots follow LCR_NKERNELS
 
 
 class LcrReads(C.Structure):
@@ -131,6 +132,21 @@ assert ASE_DTYPE.itemsize == 40, ASE_DTYPE.itemsize
 
 class LcrAseList(C.Structure):   # include/lcr.h: lcr_ase_list
     _fields_ = [("n_regions", C.c_int32), ("rec", C.c_void_p), ("dev_rec", C.c_void_p)]
+
+
+class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
+    _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
+                ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]
+
+
+# lcr_ase_gene (include/lcr.h): lcr_ase_region's fields for one (region, gene) pair, then the gene
+AGENE_DTYPE = np.dtype([("region", "<i4"), ("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("h1", "<u4"), ("h2", "<u4"), ("n_sites", "<u4"),
+                        ("h1_pat", "<u4"), ("h1_mat", "<u4"), ("h2_pat", "<u4"), ("h2_mat", "<u4"), ("gene", "<i4"), ("pad_", "<u4")], align=True)
+assert AGENE_DTYPE.itemsize == 48, AGENE_DTYPE.itemsize
+
+
+class LcrAseGeneList(C.Structure):   # include/lcr.h: lcr_ase_gene_list
+    _fields_ = [("n_regions", C.c_int32), ("n_pairs", C.c_int32), ("rec", C.c_void_p), ("pair_region_off", C.c_void_p), ("dev_rec", C.c_void_p)]
 
 
 # presets: the code values of main.rs:272-396 (not the help text)

@@ -1,0 +1,123 @@
+"""Gene annotation for the per-gene allele-specific tables: GTF / GFF3 -> per contig the arrays Engine.assign_genes takes
+(include/lcr.h: lcr_gene_annotation).  Plain Python, gene-scale only: the read-scale work -- every read against every candidate gene's
+exons -- is K8 on the GPU.
+
+Restates get_gene_regions and merge_gene_exon_regions of allele_specific/longcallR-ase.py (:64-194):
+  * lines that start with '#' are skipped; the feature is column 3, the attributes column 9;
+  * GTF attributes are `key value` pairs split on ";" and then on " " (quotes dropped), repeated `tag` keys joined with ","; GFF3
+    attributes are `key=value` pairs;
+  * `gene` and `exon` features are kept iff gene_type (else gene_biotype) is one of gene_types and no tag contains "readthrough";
+  * gene_name defaults to ".";
+  * a gene whose exons lie on more than one contig is dropped;
+  * per gene the exons of all its transcripts are merged when they share at least one base.  Abutting exons (end + 1 == next start)
+    stay separate: the script calls intervaltree's merge_overlaps() with its default strict=True, which joins only intervals that
+    overlap; that is the rule this project follows.
+
+Coordinates leave this module 0-based half-open (a GTF's 1-based inclusive [a, b] is [a - 1, b)).  Genes of a contig are sorted by (span
+start, span end, gene_id); that index is the gene's id in every per-gene result.  A gene that has exons but no kept `gene` feature
+competes for reads as in the script and, as there, is never printed: reported is False."""
+import gzip
+
+import numpy as np
+
+GENE_TYPES = ("protein_coding", "lncRNA")
+SUFFIXES = (".gff3", ".gtf", ".gff3.gz", ".gtf.gz")
+
+
+class ContigGenes:
+    """One contig's genes: span_start0 / span_end0 (first merged exon's start to last merged exon's end: what the script puts into its
+    per-contig tree), exon_off (n_genes + 1) into exon_start0 / exon_end0 (merged exons, ascending and disjoint), gene_id / gene_name /
+    strand (lists), reported (bool per gene)."""
+
+    def __init__(self, genes=()):
+        genes = sorted(genes, key=lambda g: (g[1][0][0], g[1][-1][1], g[0]))   # (gene_id, exons, name, strand, reported)
+        self.gene_id = [g[0] for g in genes]
+        self.gene_name = [g[2] for g in genes]
+        self.strand = [g[3] for g in genes]
+        self.reported = np.array([g[4] for g in genes], dtype=bool)
+        self.span_start0 = np.array([g[1][0][0] for g in genes], dtype=np.int64)
+        self.span_end0 = np.array([g[1][-1][1] for g in genes], dtype=np.int64)
+        self.exon_off = np.zeros(len(genes) + 1, dtype=np.int32)
+        np.cumsum([len(g[1]) for g in genes], out=self.exon_off[1:])
+        self.exon_start0 = np.array([x for g in genes for x, _ in g[1]], dtype=np.int64)
+        self.exon_end0 = np.array([y for g in genes for _, y in g[1]], dtype=np.int64)
+
+    @property
+    def n_genes(self):
+        return len(self.gene_id)
+
+    @classmethod
+    def from_exons(cls, genes):
+        """genes: [(gene_id, [(start0, end0), ...])] or [(gene_id, exons, gene_name, strand, reported)] -- exons in any order, merged here"""
+        return cls([(g[0], merge_exons(g[1])) + (tuple(g[2:]) if len(g) > 2 else (".", ".", True)) for g in genes])
+
+
+def merge_exons(exons):
+    """half-open exons of one gene -> ascending, disjoint; two are joined iff they share a base (abutting ones stay apart)"""
+    out = []
+    for x, y in sorted((int(x), int(y)) for x, y in exons):
+        if out and x < out[-1][1]:
+            out[-1][1] = max(out[-1][1], y)
+        else:
+            out.append([x, y])
+    return [(x, y) for x, y in out]
+
+
+def _attrs_gtf(text):
+    d, tags = {}, []
+    for attr in text.strip().split(";"):
+        attr = attr.strip()
+        if not attr:
+            continue
+        key, _, value = attr.partition(" ")
+        value = value.replace('"', "")
+        if key == "tag":
+            tags.append(value)
+        else:
+            d[key] = value
+    d["tag"] = ",".join(tags)
+    return d
+
+
+def _attrs_gff3(text):
+    d = {}
+    for attr in text.strip().split(";"):
+        attr = attr.strip()
+        if not attr:
+            continue
+        key, _, value = attr.partition("=")
+        d[key] = value.replace('"', "")
+    return d
+
+
+def load(path, gene_types=GENE_TYPES):
+    """-> {contig: ContigGenes}"""
+    path = str(path)
+    if not path.endswith(SUFFIXES):
+        raise ValueError("unknown annotation file format (want .gtf, .gff3, .gtf.gz or .gff3.gz): %r" % path)
+    parse = _attrs_gff3 if ".gff3" in path else _attrs_gtf
+    gene_types = set(gene_types)
+    genes = {}   # gene_id -> (name, strand) of the kept `gene` features
+    exons = {}   # gene_id -> [(contig, start0, end0)]
+    with (gzip.open if path.endswith(".gz") else open)(path, "rt") as f:
+        for line in f:
+            if line.startswith("#"):
+                continue
+            parts = line.strip().split("\t")
+            if len(parts) < 9 or parts[2] not in ("gene", "exon"):
+                continue
+            a = parse(parts[8])
+            if a.get("gene_type", a.get("gene_biotype")) not in gene_types or "readthrough" in a.get("tag", ""):
+                continue
+            if parts[2] == "gene":
+                genes[a["gene_id"]] = (a.get("gene_name", "."), parts[6])
+            else:
+                exons.setdefault(a["gene_id"], []).append((parts[0], int(parts[3]) - 1, int(parts[4])))
+    per_contig = {}
+    for gid, ex in exons.items():
+        contigs = {c for c, _, _ in ex}
+        if len(contigs) > 1:
+            continue
+        name, strand = genes.get(gid, (".", "."))
+        per_contig.setdefault(contigs.pop(), []).append((gid, merge_exons([(x, y) for _, x, y in ex]), name, strand, gid in genes))
+    return {c: ContigGenes(g) for c, g in per_contig.items()}

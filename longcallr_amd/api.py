@@ -215,9 +215,16 @@ class Engine:
         (pos0, pat, mat) of the batch's contig -- numpy arrays (converted), or contiguous int64 / uint8 / uint8 tensors on this engine's
         device, read in place.  min_phase_score: the VCF writer's (default: the engine's params).  Waits for an asynchronous phase stage
         in flight; may be repeated with other parameters or sites."""
+        self._ase_call(self.lib.lcr_ase, "lcr_ase", sites, min_baseq, min_phase_score)
+        o = _abi.LcrAseList()
+        self._chk(self.lib.lcr_get_ase(self.h, C.byref(o)), "lcr_get_ase")   # (waits for the call's kernels: device sites are read by then)
+        return _view(o.rec, _abi.ASE_DTYPE, o.n_regions)
+
+    def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
+        """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))
         if sites is None:
-            rc = self.lib.lcr_ase(self.h, C.byref(p), _abi.LCR_MEM_HOST, 0, None, None, None)
+            rc = fn(self.h, C.byref(p), _abi.LCR_MEM_HOST, 0, None, None, None)
         elif any(getattr(t, "is_cuda", False) for t in sites):
             import torch
             ts = tuple(sites)
@@ -227,18 +234,46 @@ class Engine:
             if len({t.numel() for t in ts}) != 1:
                 raise ValueError("pos0, pat and mat must have the same length")
             torch.cuda.current_stream(self.device).synchronize()   # (the tensors may still be being written on torch's stream)
-            rc = self.lib.lcr_ase(self.h, C.byref(p), _abi.LCR_MEM_DEVICE, int(ts[0].numel()), *[C.c_void_p(t.data_ptr()) for t in ts])
+            rc = fn(self.h, C.byref(p), _abi.LCR_MEM_DEVICE, int(ts[0].numel()), *[C.c_void_p(t.data_ptr()) for t in ts])
         else:
             pos = np.ascontiguousarray(sites[0], dtype=np.int64)
             pat = np.ascontiguousarray(sites[1], dtype=np.uint8)
             mat = np.ascontiguousarray(sites[2], dtype=np.uint8)
             if not (pos.size == pat.size == mat.size):
                 raise ValueError("pos0, pat and mat must have the same length")
-            rc = self.lib.lcr_ase(self.h, C.byref(p), _abi.LCR_MEM_HOST, int(pos.size), pos.ctypes.data, pat.ctypes.data, mat.ctypes.data)
-        self._chk(rc, "lcr_ase")
-        o = _abi.LcrAseList()
-        self._chk(self.lib.lcr_get_ase(self.h, C.byref(o)), "lcr_get_ase")   # (waits for the call's kernels: device sites are read by then)
-        return _view(o.rec, _abi.ASE_DTYPE, o.n_regions)
+            rc = fn(self.h, C.byref(p), _abi.LCR_MEM_HOST, int(pos.size), pos.ctypes.data, pat.ctypes.data, mat.ctypes.data)
+        self._chk(rc, what)
+
+    def assign_genes(self, genes):
+        """lcr_assign_genes on the bound batch (any stage; the stage does not move): every read goes to the candidate gene whose merged
+        exons its aligned blocks overlap most (include/lcr.h; longcallR-ase.py's assign_reads_to_gene).  genes: the contig's
+        annotation.ContigGenes (or any object with its five arrays), or None for no gene at all -- every read then gets -1."""
+        a = _abi.LcrGeneAnnotation()
+        keep = []
+        if genes is not None and len(genes.span_start0):
+            for f, dt in (("span_start0", np.int64), ("span_end0", np.int64), ("exon_off", np.int32), ("exon_start0", np.int64), ("exon_end0", np.int64)):
+                keep.append(np.ascontiguousarray(getattr(genes, f), dtype=dt))
+                setattr(a, f, keep[-1].ctypes.data)
+            a.n_genes, a.n_exons = int(keep[0].size), int(keep[3].size)
+            if keep[1].size != a.n_genes or keep[2].size != a.n_genes + 1 or keep[4].size != a.n_exons:
+                raise ValueError("annotation arrays: span_end0 needs n_genes, exon_off n_genes + 1, exon_end0 n_exons entries")
+        self._chk(self.lib.lcr_assign_genes(self.h, _abi.LCR_MEM_HOST, C.byref(a)), "lcr_assign_genes")   # (host arrays are copied before the call returns)
+        return self
+
+    def read_genes(self):
+        """lcr_get_read_genes after assign_genes(): (gene index per read of the batch, -1 = none; its overlap in bases), copied"""
+        n, g, ov, dg = C.c_int32(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.lcr_get_read_genes(self.h, C.byref(n), C.byref(g), C.byref(ov), C.byref(dg)), "lcr_get_read_genes")
+        return _view(g.value, np.int32, n.value), _view(ov.value, np.uint32, n.value)
+
+    def ase_genes(self, sites=None, min_baseq=13, min_phase_score=None):
+        """lcr_ase_genes + lcr_get_ase_genes after phase() and assign_genes(): ase()'s counts per (region, gene) pair that has a fragment
+        row assigned to the gene -> (records as a structured array of _abi.AGENE_DTYPE, ordered by region and then gene, copied;
+        pair_region_off, n_regions + 1).  Parameters as ase().  ase.merge_gene_records turns the pairs into one record per gene."""
+        self._ase_call(self.lib.lcr_ase_genes, "lcr_ase_genes", sites, min_baseq, min_phase_score)
+        o = _abi.LcrAseGeneList()
+        self._chk(self.lib.lcr_get_ase_genes(self.h, C.byref(o)), "lcr_get_ase_genes")
+        return _view(o.rec, _abi.AGENE_DTYPE, o.n_pairs), _view(o.pair_region_off, np.int32, o.n_regions + 1)
 
     def set_downsample(self, depth, seed=2025):
         """lcr_set_downsample: regions with at least `depth` fragment rows are phased on a sample of `depth` rows (longcallR --downsample /

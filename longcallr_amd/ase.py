@@ -4,8 +4,9 @@ The read-scale work -- the phase set with the most assigned reads, its haplotype
 the phased heterozygous sites -- is K7 on the GPU; what is left per region is small and plain: the beta-binomial test, the
 Benjamini-Hochberg adjustment, the VCF loaders and the three TSV texts of allele_specific/longcallR-ase.py (beta_binomial_p_value,
 load_whole_genome_phased_vcf, load_dna_vcf, calculate_ase_pvalue_filtering, the analyze_ase_genes* writers).  Standard library + NumPy
-only: scipy.stats.betabinom and multipletests are restated (the latter in asj.bh_adjust).  Not the script's: there is no annotation, so
-Gene_name is the region."""
+only: scipy.stats.betabinom and multipletests are restated (the latter in asj.bh_adjust).  Without an annotation a region stands where the
+script has a gene and Gene_name is the region; with one (annotation.py, Engine.assign_genes / ase_genes) the records are per gene:
+merge_gene_records, filter_pairs and the per-gene form of format_tsv."""
 import math
 
 import numpy as np
@@ -70,15 +71,16 @@ def dna_het_sites(vcf_path, contig=None):
     return _pick(vcf_path, contig, f)
 
 
-def eligible_candidates(cands, rec, min_phase_score):
+def eligible_candidates(cands, rec, min_phase_score, join=True):
     """Mask over the candidate records: what the VCF writer prints as PASS with a phased het GT (vcf.format_records), with a phase set,
-    and that phase set the one chosen for the candidate's region in `rec` (Engine.ase's records): lcr_ase's eligibility without the join."""
+    and (join) that phase set the one chosen for the candidate's region in `rec` (Engine.ase's records): lcr_ase's eligibility without
+    the join with the parental sites."""
     fl = cands["flags"]
     ok = ((fl & (_abi.F_DENSE | _abi.F_NON_SELECTED)) == 0) & (cands["variant_type"] == 1)
     ok &= cands["phase_score"] >= float(min_phase_score)
     ok &= (cands["allele1"] != cands["ref_base"]) | (cands["allele2"] != cands["ref_base"])
     ok &= cands["phase_set"] != 0
-    if len(cands):
+    if join and len(cands):
         ok &= cands["phase_set"] == rec["phase_set"][cands["region"]]
     return ok
 
@@ -91,17 +93,64 @@ def filter_regions(rec, cands, dna_pos0, min_phase_score, min_support=10, overdi
     dna = np.asarray(dna_pos0, dtype=np.int64)
     ok = eligible_candidates(cands, rec, min_phase_score) & np.isin(cands["pos"], dna)
     for i in np.flatnonzero(ok):
-        s = cands[i]
-        g = int(s["region"])
-        if keep[g]:
-            continue
-        dp = int(s["depth"])
-        af = float(vcf._f2(float(s["af1"] if s["allele1"] != s["ref_base"] else s["af2"])))
-        if dp == 0 or af != af:
-            continue
-        if dp >= min_support and betabinom_two_sided(int(dp * af), dp, 0.5, overdispersion) < 0.05:
+        g = int(cands["region"][i])
+        if not keep[g] and _site_imbalanced(cands[i], min_support, overdispersion):
             keep[g] = True
     return keep
+
+
+def _site_imbalanced(s, min_support, overdispersion):
+    """one candidate record under calculate_ase_pvalue_filtering's test: dp >= min_support and p < 0.05 for int(dp * af) of dp"""
+    dp = int(s["depth"])
+    af = float(vcf._f2(float(s["af1"] if s["allele1"] != s["ref_base"] else s["af2"])))
+    if dp == 0 or af != af:
+        return False
+    return dp >= min_support and betabinom_two_sided(int(dp * af), dp, 0.5, overdispersion) < 0.05
+
+
+def filter_pairs(pairs, cands, dna_pos0, min_phase_score, min_support=10, overdispersion=0.001):
+    """filter_regions for the (region, gene) pair records of Engine.ase_genes: a pair is kept when one of its region's PASS phased-het
+    sites of the PAIR's phase set lies in the DNA set and passes the same test.  -> bool per pair."""
+    ok = eligible_candidates(cands, None, min_phase_score, join=False)    # every candidate against its own phase set
+    ok &= np.isin(cands["pos"], np.asarray(dna_pos0, dtype=np.int64))
+    passing = set()     # (region, phase set) with a passing site
+    for i in np.flatnonzero(ok):
+        key = (int(cands["region"][i]), int(cands["phase_set"][i]))
+        if key not in passing and _site_imbalanced(cands[i], min_support, overdispersion):
+            passing.add(key)
+    return np.array([(int(r["region"]), int(r["phase_set"])) in passing for r in pairs], dtype=bool)
+
+
+def merge_gene_records(pairs, keep=None):
+    """The (region, gene) pair records of one contig -- Engine.ase_genes' records of all its chunks, concatenated -- -> one record per
+    gene, ascending by gene.  A gene's rows are the union of its pairs' rows, and phase sets of different regions of a contig are
+    distinct (a phase set is named after its first site's position), so the gene's phase set with the most reads is that of the pair
+    record with the largest h1 + h2, ties to the smallest phase set, and that record's counts, sites and votes are the gene's;
+    n_phase_sets is the sum over the pairs.  Exact across regions and across pipeline.run's chunks.  `region` is the chosen record's.
+    keep (filter_pairs' mask, parallel to pairs): -> (records, the chosen records' mask).
+    Not the script's: under --truncation a read that is a row of both flanks of a cut counts in both flanks' records."""
+    pairs = np.asarray(pairs, dtype=_abi.AGENE_DTYPE)
+    best = {}    # gene -> index of the chosen pair
+    nps = {}
+    for i in range(len(pairs)):
+        r = pairs[i]
+        k = int(r["gene"])
+        nps[k] = nps.get(k, 0) + int(r["n_phase_sets"])
+        j = best.get(k)
+        if j is None:
+            best[k] = i
+            continue
+        tot, tot_j = int(r["h1"]) + int(r["h2"]), int(pairs[j]["h1"]) + int(pairs[j]["h2"])
+        if tot > tot_j or (tot == tot_j and int(r["phase_set"]) < int(pairs[j]["phase_set"])):
+            best[k] = i
+    order = sorted(best)
+    out = pairs[[best[k] for k in order]].copy() if order else np.zeros(0, dtype=_abi.AGENE_DTYPE)
+    for n, k in enumerate(order):
+        out["n_phase_sets"][n] = nps[k]
+    if keep is None:
+        return out
+    keep = np.asarray(keep, dtype=bool)
+    return out, (keep[[best[k] for k in order]] if order else np.zeros(0, dtype=bool))
 
 
 def format_tsv(tables, min_support=10, overdispersion=0.001, patmat=False):
@@ -109,18 +158,35 @@ def format_tsv(tables, min_support=10, overdispersion=0.001, patmat=False):
     region_start0, region_len[, keep])] -- per batch the contig's name, the records of Engine.ase(), the batch's region arrays and, for
     the filter mode, filter_regions' mask (a region it drops is not written).  Written are the regions with h1 + h2 >= min_support, in the
     order given; P_value is the two-sided beta-binomial test of h1 among h1 + h2, Benjamini-Hochberg adjusted over all written regions.
-    Gene_name is the region in the script's 1-based inclusive coordinates (as asj.format_tsv names it), PS is "." for 0."""
+    Gene_name is the region in the script's 1-based inclusive coordinates (as asj.format_tsv names it), PS is "." for 0.
+    The per-gene form: tables of [(chrom, rec, genes[, keep])] -- rec the contig's merge_gene_records (a "gene" field tells the two forms
+    apart), genes its annotation.ContigGenes, keep the mask merge_gene_records returns.  Gene_name is the annotation's; only genes with
+    genes.reported are written (a gene without a `gene` feature takes reads and is never printed, as in the script); rows come in the
+    order given and inside a table in gene order (the script: in the order its workers finish).  The min_support / Benjamini-Hochberg
+    rule is the same."""
     rows, pvals = [], []
     for t in tables:
-        chrom, rec, start0, length = t[:4]
-        keep = t[4] if len(t) > 4 else None
+        chrom, rec = t[:2]
+        per_gene = "gene" in (rec.dtype.names or ())
+        if per_gene:
+            genes, keep = t[2], (t[3] if len(t) > 3 else None)
+        else:
+            start0, length = t[2:4]
+            keep = t[4] if len(t) > 4 else None
         for i in range(len(rec)):
             r = rec[i]
             h1, h2 = int(r["h1"]), int(r["h2"])
             if h1 + h2 < min_support or (keep is not None and not keep[i]):
                 continue
-            g, ps = int(r["region"]), int(r["phase_set"])
-            head = "%s:%d-%d\t%s\t%s\t%d\t%d" % (chrom, int(start0[g]) + 1, int(start0[g]) + int(length[g]), chrom, ps if ps else ".", h1, h2)
+            ps = int(r["phase_set"])
+            if per_gene:
+                k = int(r["gene"])
+                if not genes.reported[k]:
+                    continue
+                head = "%s\t%s\t%s\t%d\t%d" % (genes.gene_name[k], chrom, ps if ps else ".", h1, h2)
+            else:
+                g = int(r["region"])
+                head = "%s:%d-%d\t%s\t%s\t%d\t%d" % (chrom, int(start0[g]) + 1, int(start0[g]) + int(length[g]), chrom, ps if ps else ".", h1, h2)
             tail = "\t%d\t%d\t%d\t%d" % (int(r["h1_pat"]), int(r["h1_mat"]), int(r["h2_pat"]), int(r["h2_mat"])) if patmat else ""
             rows.append((head, tail))
             pvals.append(betabinom_two_sided(h1, h1 + h2, 0.5, overdispersion))

@@ -169,10 +169,10 @@ int lcr_ctx_create(int device, lcr_ctx** out) {
   c->device = device;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return LCR_E_DEVICE; }
   c->own_stream = true;
-  for (int k = 0; k < LCR_NKERNELS; k++)
+  for (int k = 0; k < LCR_NTIMERS; k++)
     for (int j = 0; j < 2; j++)
       if (hipEventCreate(&c->ev[k][j]) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
-  for (hipEvent_t* e : {&c->ev_ctl, &c->ev_sv, &c->ev_cand, &c->ev_nnz, &c->ev_imp, &c->ev_junc, &c->ev_ase})
+  for (hipEvent_t* e : {&c->ev_ctl, &c->ev_sv, &c->ev_cand, &c->ev_nnz, &c->ev_imp, &c->ev_junc, &c->ev_ase, &c->ev_genes, &c->ev_agene})
     if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
   *out = c;
   return LCR_OK;
@@ -187,10 +187,10 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
   for (auto& u : c->up) if (u.ev) (void)hipEventDestroy(u.ev);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  for (hipEvent_t e : {c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp, c->ev_junc, c->ev_ase}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp, c->ev_junc, c->ev_ase, c->ev_genes, c->ev_agene}) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2 * lcr_ctx::UP_LANES; k++) if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
   c->phase.release();
-  for (int k = 0; k < LCR_NKERNELS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);
+  for (int k = 0; k < LCR_NTIMERS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;   // (every queue is drained: the buffers give their blocks back)
 }
@@ -218,7 +218,7 @@ int lcr_ctx_sync(lcr_ctx* c) {
 int lcr_enable_timing(lcr_ctx* c, int on) { if (!c) return LCR_E_ARG; c->timing = on != 0; return LCR_OK; }
 
 int lcr_kernel_ms(lcr_ctx* c, int k, float* ms) {
-  if (!c || !ms || k < 0 || k >= LCR_NKERNELS) return LCR_E_ARG;
+  if (!c || !ms || k < 0 || k >= LCR_NTIMERS) return LCR_E_ARG;
   if (!c->ev_valid[k]) return LCR_E_STATE;
   HIPCHK(c, hipEventSynchronize(c->ev[k][1]));
   HIPCHK(c, hipEventElapsedTime(ms, c->ev[k][0], c->ev[k][1]));

@@ -1,7 +1,8 @@
 // lcr_ctx.h — the context behind the C ABI (include/lcr.h) and what its host units share: the stage state, timers, uploads, the settle
 // functions.  Private to lcr_api.hip (lifecycle, cache, fills, debug switches, phase entry, region discovery), lcr_batch.hip (binding and
 // upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns), lcr_calls.hip (candidate, import and fragment stages with their getters) and
-// lcr_junctions.hip (lcr_junctions, lcr_get_junctions) and lcr_ase.hip (lcr_ase, lcr_get_ase).
+// lcr_junctions.hip (lcr_junctions, lcr_get_junctions), lcr_ase.hip (lcr_ase, lcr_get_ase) and lcr_genes.hip (lcr_assign_genes, lcr_get_read_genes,
+// lcr_ase_genes, lcr_get_ase_genes).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -126,6 +127,18 @@ struct lcr_ctx {
   HostBuf h_ase, h_ase_bad;                            // pinned: the records; the verdict on the parental sites
   hipEvent_t ev_ase = nullptr;                         // behind the sites' check, then behind the call's last kernel
 
+  // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
+  bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
+  int32_t genes_nr = 0;
+  DevBuf g_span_s, g_span_e, g_exon_off, g_exon_s, g_exon_e, g_pmax, d_gene, d_gene_ov;   // host annotation copied to HBM; running maximum of the spans' ends; the result
+  HostBuf h_gene, h_gene_ov, h_gene_bad;   // pinned: the result; the verdict on the annotation
+  hipEvent_t ev_genes = nullptr;           // behind the annotation's check, then behind the copies of the result
+  bool agene_valid = false;  // lcr_get_ase_genes: the last lcr_ase_genes' records belong to the phase results and the gene assignment of the bound batch
+  int32_t agene_ng = 0, agene_n = 0;
+  DevBuf ag_pos, ag_pat, ag_mat, ag_cnt, ag_off, ag_tag, ag_site, ag_site_ps, d_agene;
+  HostBuf h_agene, h_agene_off, h_agene_ctl, h_agene_bad;   // pinned: the records; their offsets per region; the number of pairs; the verdict on the parental sites
+  hipEvent_t ev_agene = nullptr;
+
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
   std::vector<int64_t> rl_start0;
@@ -135,8 +148,8 @@ struct lcr_ctx {
   // timing
   bool timing = false;
   uint32_t timing_mask = 0;   // lcr_debug_set("timing_mask"): bit k = LCR_K_* k is timed; 0 = all of them (every timer is two event records on the stream)
-  hipEvent_t ev[LCR_NKERNELS][2] = {};
-  bool ev_valid[LCR_NKERNELS] = {};
+  hipEvent_t ev[LCR_NTIMERS][2] = {};
+  bool ev_valid[LCR_NTIMERS] = {};
   int64_t pileup_bytes = 0, stage_bytes = 0;
 };
 
@@ -156,6 +169,8 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_FRAGGED) c->ds_rows_set = false;   // a sample names the rows of ONE fragment stage
   if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
   if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
+  if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
+  if (to < ST_LOADED) { c->genes_valid = false; c->agene_valid = false; }   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and

@@ -324,6 +324,23 @@ void launch_k7_votes(const int32_t* row_tag, int32_t n_rows, const int64_t* row_
                      uint32_t min_baseq, lcr_ase_region* ase, hipStream_t s);
 void launch_k7_export(const lcr_ase_region* ase, int32_t ng, lcr_ase_region* host_out /* pinned (device pointer) */, hipStream_t s);
 
+// k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
+void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
+void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);
+void launch_k8_assign(const BatchView& b, const lcr_gene_annotation& a, const int64_t* pmax, int32_t* gene, uint32_t* overlap /* n_reads each */, hipStream_t s);
+void launch_k8_pair_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* gene, int32_t* n_pairs /* n_regions */,
+                          hipStream_t s);
+void launch_k8_pair_offsets(const int32_t* pair_off /* n_regions + 1 */, int32_t ng, int32_t* host_off, int32_t* host_ctl /* pinned (device pointers): the offsets, [0] pairs */,
+                            hipStream_t s);
+void launch_k8_pair_emit(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* gene, const int32_t* pair_off,
+                         lcr_ase_gene* out, lcr_ase_gene* host_out /* pinned (device pointer), or nullptr */, int32_t* row_tag /* n_rows, or nullptr: no votes follow */,
+                         hipStream_t s);
+void launch_k8_sites(const lcr_candidate* cand, int32_t n_cand, double min_phase_score, const int64_t* pos0, const uint8_t* pat, const uint8_t* mat,
+                     int32_t n_sites, const int32_t* pair_off, lcr_ase_gene* pairs, uint8_t* site /* n_cand */, uint32_t* site_ps /* n_cand */, hipStream_t s);
+void launch_k8_votes(const int32_t* row_tag, int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const uint8_t* site,
+                     const uint32_t* site_ps, uint32_t min_baseq, lcr_ase_gene* pairs, hipStream_t s);
+void launch_k8_export(const lcr_ase_gene* pairs, int32_t n, lcr_ase_gene* host_out /* pinned (device pointer) */, hipStream_t s);
+
 // device helpers shared by kernels -------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ int base_code(uint8_t b) {

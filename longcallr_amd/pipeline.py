@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import _abi, api, ase, asj, bamio, vcf
+from . import _abi, annotation, api, ase, asj, bamio, vcf
 
 VCF_HEADER_TAIL = (   # thread.rs:232-262, verbatim
     '##FILTER=<ID=PASS,Description="All filters passed">\n'
@@ -110,7 +110,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         read_filter=None, devices=None, chunk_cost=2.0e9, async_phase=True, input_vcf=None,
         downsample=False, downsample_depth=10000, downsample_seed=2025, truncation=False, truncation_coverage=200000,
         asj_out=None, asj_min_count=10, asj_min_junctions=2,
-        ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None, **param_overrides):
+        ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
+        ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -142,7 +143,13 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     the parent-of-origin votes of every haplotype's reads over this run's own PASS phased sites; with ase_dna_vcf (--vcf3) the
     .filter_ase.tsv, which drops the regions none of whose sites is a DNA heterozygote with a significant imbalance.  The two VCFs together
     are a ValueError (the script takes one mode), and so is either without ase_out.  Adds the stat ase_regions (rows written).  VCF, phased
-    BAM and .asj.tsv do not depend on it; without ase_out nothing changes."""
+    BAM and .asj.tsv do not depend on it; without ase_out nothing changes.
+    ase_annotation / ase_gene_types: a GTF / GFF3 (.gz) annotation and the gene types kept from it (the script's -a / --gene_types): the
+    table of ase_out is then per GENE, as the script's -- every chunk calls Engine.assign_genes after binding (every read to the gene
+    whose merged exons its aligned blocks overlap most, include/lcr.h: lcr_assign_genes) and Engine.ase_genes in place of Engine.ase;
+    the (region, gene) pair records of a contig's chunks are merged per gene (ase.merge_gene_records) and written in contig and then gene
+    order with the annotation's Gene_name, in each of the three modes.  Adds the stat ase_genes (rows written) in place of ase_regions.
+    ase_annotation without ase_out is a ValueError; without ase_annotation nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -158,6 +165,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         raise ValueError("ase_parental_vcf and ase_dna_vcf are two modes of one table: give one of them")
     if ase_out is None and (ase_parental_vcf is not None or ase_dna_vcf is not None):
         raise ValueError("ase_parental_vcf / ase_dna_vcf need ase_out")
+    if ase_out is None and ase_annotation is not None:
+        raise ValueError("ase_annotation needs ase_out")
     fai = ref_path + ".fai"
     if not os.path.exists(fai):
         raise FileNotFoundError("Reference index file .fai does not exist.")   # util.rs:575-577
@@ -187,6 +196,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["truncated_columns"] = 0
     parental = ase.parental_sites(ase_parental_vcf) if ase_parental_vcf is not None else None    # {contig: (pos0, pat, mat)}
     dna = ase.dna_het_sites(ase_dna_vcf) if ase_dna_vcf is not None else None                    # {contig: pos0}
+    genes = annotation.load(ase_annotation, ase_gene_types) if ase_annotation is not None else None   # {contig: annotation.ContigGenes}
     no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
     # Every engine is a long-lived worker with the ASYNCHRONOUS phase stage (lcr_ctx_set_async_phase, include/lcr.h): a chunk is uploaded
@@ -215,7 +225,12 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
         if junc is not None:
             out["junc"] = (name, junc, batch.start0, batch.len)
-        if arec is not None:
+        if arec is not None and genes is not None:      # (region, gene) pair records; merged per gene when every chunk is in
+            out["ase"] = (name, arec[0])
+            if dna is not None:
+                out["ase"] += (ase.filter_pairs(arec[0], cands, dna.get(name, np.zeros(0, np.int64)), params.min_phase_score,
+                                                ase_min_support, ase_overdispersion),)
+        elif arec is not None:
             out["ase"] = (name, arec, batch.start0, batch.len)
             if dna is not None:
                 out["ase"] += (ase.filter_regions(arec, cands, dna.get(name, np.zeros(0, np.int64)), params.min_phase_score,
@@ -232,6 +247,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             slot = n_slot[k] & 1
             n_slot[k] += 1
             E.load_batch_async(batch, slot).bind_batch(slot)
+            if genes is not None:
+                E.assign_genes(genes.get(name))
             E.fill_data_into_freq_vec()
             if in_flight[k] is not None:
                 finish(k)
@@ -253,7 +270,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     pp, ppat, pmat = parental.get(name, (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.uint8)))
                     lo, hi = np.searchsorted(pp, [int(batch.start0[0]), int(batch.start0[-1]) + int(batch.len[-1])])
                     psites = (pp[lo:hi], ppat[lo:hi], pmat[lo:hi]) if hi > lo else None
-                arec = E.ase(psites)
+                arec = E.ase_genes(psites) if genes is not None else E.ase(psites)
             in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec)
         finally:
             with free_lock:
@@ -312,7 +329,23 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["junctions"] = sum(int(r["junc"][1].size) for r in results)
         with open(asj_out, "w") as f:
             f.write(asj.format_tsv([r["junc"] for r in results], asj_min_count))
-    if ase_out is not None:
+    if ase_out is not None and genes is not None:
+        per_contig = {}     # contig -> its chunks' pair records (and masks), in chunk order
+        for r in results:
+            per_contig.setdefault(r["ase"][0], []).append(r["ase"][1:])
+        tables = []
+        for name, parts in per_contig.items():
+            pairs = np.concatenate([x[0] for x in parts])
+            if dna is not None:
+                tables.append((name,) + ase.merge_gene_records(pairs, np.concatenate([x[1] for x in parts])))
+            else:
+                tables.append((name, ase.merge_gene_records(pairs)))
+            tables[-1] = tables[-1][:2] + (genes.get(name, annotation.ContigGenes()),) + tables[-1][2:]
+        text = ase.format_tsv(tables, ase_min_support, ase_overdispersion, patmat=parental is not None)
+        stats["ase_genes"] = text.count("\n") - 1
+        with open(ase_out, "w") as f:
+            f.write(text)
+    elif ase_out is not None:
         text = ase.format_tsv([r["ase"] for r in results], ase_min_support, ase_overdispersion, patmat=parental is not None)
         stats["ase_regions"] = text.count("\n") - 1
         with open(ase_out, "w") as f:

@@ -6,7 +6,8 @@
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
                                  [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]]   (allele-specific junction table)
                                  [--ase-out out.ase.tsv [--ase-min-support N] [--ase-overdispersion R]
-                                  [--ase-parental-vcf phased.vcf.gz | --ase-dna-vcf dna.vcf.gz]]   (allele-specific expression table)
+                                  [--ase-parental-vcf phased.vcf.gz | --ase-dna-vcf dna.vcf.gz]   (allele-specific expression table)
+                                  [--ase-annotation genes.gtf.gz [--ase-gene-types protein_coding,lncRNA]]]   (... per annotated gene)
 """
 import argparse
 import json
@@ -41,12 +42,16 @@ def main():
     ap.add_argument("--ase-overdispersion", type=float, default=0.001, help="rho of the beta-binomial test")
     ap.add_argument("--ase-parental-vcf", help="whole-genome phased VCF (0|1: ALT paternal): adds the parent-of-origin votes (.patmat_ase.tsv)")
     ap.add_argument("--ase-dna-vcf", help="DNA VCF: keep the regions with a significant DNA-heterozygous site (.filter_ase.tsv)")
+    ap.add_argument("--ase-annotation", help="GTF / GFF3 (.gz) annotation: the table gets one row per gene, reads assigned to genes on the GPU")
+    ap.add_argument("--ase-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.ase_parental_vcf and a.ase_dna_vcf:
         ap.error("--ase-parental-vcf and --ase-dna-vcf are two modes of one table: give one of them")
     if (a.ase_parental_vcf or a.ase_dna_vcf) and not a.ase_out:
         ap.error("--ase-parental-vcf / --ase-dna-vcf need --ase-out")
+    if a.ase_annotation and not a.ase_out:
+        ap.error("--ase-annotation needs --ase-out")
     extra = {} if a.read_assign_cutoff is None else dict(read_assign_cutoff=a.read_assign_cutoff)
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
                       device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf,
@@ -54,7 +59,8 @@ def main():
                       truncation=a.truncation, truncation_coverage=a.truncation_coverage,
                       asj_out=a.asj_out, asj_min_count=a.asj_min_count, asj_min_junctions=a.asj_min_junctions,
                       ase_out=a.ase_out, ase_min_support=a.ase_min_support, ase_overdispersion=a.ase_overdispersion,
-                      ase_parental_vcf=a.ase_parental_vcf, ase_dna_vcf=a.ase_dna_vcf, **extra)
+                      ase_parental_vcf=a.ase_parental_vcf, ase_dna_vcf=a.ase_dna_vcf,
+                      ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t), **extra)
     print(json.dumps(st))
 
 
