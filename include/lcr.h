@@ -335,8 +335,8 @@ int lcr_collect_phase(lcr_ctx*, lcr_phase_collected* out);
  *   motif                 the reference bytes at s, s+1 and s+l-2, s+l-1 of the region's window, upper-cased: 1 = GT..AG, 2 = CT..AC,
  *       0 otherwise, for l < 2, or when either pair lies outside the window.
  *   order                 by region, then s, then l, ascending; independent of the batch's composition and bit-reproducible (integer adds).
- * Not the script's: no annotation (no gene assignment of reads -- lcr_get_read_genes exports the map a per-gene table would start from --,
- * no exon-overlap filter, no Novel / Strand / Gene_name); the tie between
+ * Not the script's: no annotation here (no gene assignment of reads, no exon-overlap filter, no Novel / Strand / Gene_name --
+ * lcr_junctions_genes below is the per-gene form, on top of lcr_assign_genes); the tie between
  * equally large phase sets goes to the smallest value (the script: a Python set's iteration order); zero-length N ops are ignored;
  * rows are not restricted to reads contained in the region (with --truncation a read that spans a cut is a row of both flanks).
  * lcr_junctions needs the bound batch after lcr_phase (LCR_E_STATE otherwise, nothing changed; params == NULL: LCR_E_ARG), collects an
@@ -460,6 +460,52 @@ typedef struct {
 typedef struct { int32_t n_regions, n_pairs; const lcr_ase_gene* rec; const int32_t* pair_region_off; const lcr_ase_gene* dev_rec; } lcr_ase_gene_list;
 int lcr_ase_genes(lcr_ctx*, const lcr_ase_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* pat, const uint8_t* mat);
 int lcr_get_ase_genes(lcr_ctx*, lcr_ase_gene_list* out);
+
+/* Per-gene allele-specific junctions (K9): the contract of lcr_junctions with "region" read as "(region g, gene k) pair", plus the
+ * script's exon-overlap filter, in the script's order (longcallR-asj.py analyze_gene: junctions are counted and thresholded at :691
+ * BEFORE the filter at :696-717; absent / present are taken at :734 AFTER it).  DESIGN.md section 1e.
+ *   junctions of a read, rend, motif   as in lcr_junctions: N ops of length >= 1, zero-length N ignored.
+ *   participating rows    of pair (g, k): rows of g with assignment 1 or 2, more than min_junctions junctions and gene[read of the row]
+ *       == k, k >= 0 (the gene of lcr_assign_genes).  A read with gene -1 takes no part anywhere.
+ *   kept junctions        n_reads(g, k, s, l) = participating rows of the pair that have the junction; kept iff n_reads >= min_count.
+ *       The same (s, l) may be kept for two genes of a region, each with its own count.
+ *   counted rows          the participating rows that pass the filter: at least one reference base covered by an M, =, X or D op of the
+ *       read lies inside a merged exon of gene k.  That is the script's test (the read's exon blocks against every transcript's exons
+ *       through an interval tree): the union of a gene's transcript exons is the union of its merged exons, and how a read's bases are
+ *       grouped into blocks cannot change whether one of them is shared.  It is NOT overlap > 0 of lcr_assign_genes, whose overlap
+ *       restates a query quirk (one-base blocks, an exon met only by a block's last base): a read with overlap 0 can share a base.  A
+ *       participating row without a shared base is not counted but did count toward n_reads.
+ *   overlap, presence, phase set, n_phase_sets, the four cells   as in lcr_junctions, over the COUNTED rows of the pair; ties between
+ *       equally large phase sets go to the smallest value, 0 a value like any other.  A kept junction that no counted row overlaps
+ *       still has a record: phase_set 0, n_phase_sets 0, the four cells 0 (the script's haplotype_event_test returns None there;
+ *       longcallr_amd/asj.py drops such records).
+ *   order                 by region, then gene, then s, then l; junc_region_off[g] .. [g + 1] are region g's records.  Independent of the
+ *       batch's composition and bit-reproducible: nothing depends on the order in which atomics land.
+ * Needs lcr_phase and a valid lcr_assign_genes of the bound batch (LCR_E_STATE otherwise, nothing changed); collects an asynchronous
+ * phase stage in flight first, as lcr_junctions does; may be repeated with other parameters.  The filter needs the annotation's exons
+ * at call time and lcr_assign_genes does not keep them (a LCR_MEM_DEVICE annotation is read in place), so the call takes the annotation
+ * again: mem, the NULL / negative-size rules and the check of the arrays are lcr_assign_genes' (one verdict wait; a refused call is
+ * LCR_E_ARG and changes nothing); n_genes must equal the n_genes of the valid assignment (LCR_E_ARG otherwise) -- that it is the SAME
+ * annotation beyond that is the caller's duty.  LCR_MEM_DEVICE arrays stay valid and unchanged until lcr_get_junctions_genes or
+ * lcr_ctx_sync has returned.  n_genes == 0 is valid and gives no records.  More than 2^28 junction occurrences in a batch: LCR_E_ARG.
+ * The records die with the phase stage's results and at the next successful lcr_assign_genes; lcr_get_junctions_genes answers
+ * LCR_E_STATE then.  The call writes no buffer another stage or getter reads: lcr_junctions / lcr_get_junctions on the same context
+ * keep working before and after it.  junc / junc_region_off: pinned host memory the call's last kernels wrote, valid until the next
+ * lcr_junctions_genes; dev_junc: the same records in HBM.  kernel_ms: the HIP-event time from the first kernel to the last of the
+ * last call (its host waits included) when timing is enabled, -1 otherwise (no slot of lcr_kernel_ms). */
+typedef struct {
+  int32_t region; uint8_t motif; uint8_t pad_[3];
+  int64_t start0;
+  int32_t len; uint32_t n_reads;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1_absent, h1_present, h2_absent, h2_present;
+  int32_t gene;              /* index into the annotation of lcr_assign_genes */
+  uint32_t pad2_;
+} lcr_junction_gene;         /* 56 bytes: lcr_junction's fields, then the gene */
+typedef struct { int32_t n_regions, n_junctions; const lcr_junction_gene* junc; const int32_t* junc_region_off;
+                 const lcr_junction_gene* dev_junc; float kernel_ms; } lcr_junction_gene_list;
+int lcr_junctions_genes(lcr_ctx*, const lcr_junction_params*, int32_t mem, const lcr_gene_annotation*);
+int lcr_get_junctions_genes(lcr_ctx*, lcr_junction_gene_list* out);
 
 /* Down-sampling: phase deep regions on a read sample (longcallR --downsample / --downsample-depth: thread.rs:144-151, phase.rs:693-701).
  * A region with at least `depth` fragment rows (all rows of lcr_get_fragmat, empty ones included) is down-sampled: the optimiser

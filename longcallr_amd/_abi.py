@@ -149,6 +149,18 @@ class LcrAseGeneList(C.Structure):   # include/lcr.h: lcr_ase_gene_list
     _fields_ = [("n_regions", C.c_int32), ("n_pairs", C.c_int32), ("rec", C.c_void_p), ("pair_region_off", C.c_void_p), ("dev_rec", C.c_void_p)]
 
 
+# lcr_junction_gene (include/lcr.h): lcr_junction's fields for one (region, gene) pair, then the gene
+JUNC_GENE_DTYPE = np.dtype([("region", "<i4"), ("motif", "u1"), ("pad_", "u1", 3), ("start0", "<i8"), ("len", "<i4"), ("n_reads", "<u4"),
+                            ("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("h1_absent", "<u4"), ("h1_present", "<u4"),
+                            ("h2_absent", "<u4"), ("h2_present", "<u4"), ("gene", "<i4"), ("pad2_", "<u4")], align=True)
+assert JUNC_GENE_DTYPE.itemsize == 56, JUNC_GENE_DTYPE.itemsize
+
+
+class LcrJunctionGeneList(C.Structure):   # include/lcr.h: lcr_junction_gene_list
+    _fields_ = [("n_regions", C.c_int32), ("n_junctions", C.c_int32), ("junc", C.c_void_p), ("junc_region_off", C.c_void_p),
+                ("dev_junc", C.c_void_p), ("kernel_ms", C.c_float)]
+
+
 # presets: the code values of main.rs:272-396 (not the help text)
 PRESETS = {
     "hifi-isoseq": dict(platform=LCR_PLATFORM_HIFI, min_depth=6, min_phase_score=11.0, min_af=0.15,

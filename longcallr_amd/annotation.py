@@ -15,7 +15,11 @@ Restates get_gene_regions and merge_gene_exon_regions of allele_specific/longcal
 
 Coordinates leave this module 0-based half-open (a GTF's 1-based inclusive [a, b] is [a - 1, b)).  Genes of a contig are sorted by (span
 start, span end, gene_id); that index is the gene's id in every per-gene result.  A gene that has exons but no kept `gene` feature
-competes for reads as in the script and, as there, is never printed: reported is False."""
+competes for reads as in the script and, as there, is never printed: reported is False.
+
+For the per-gene junction table (longcallR-asj.py's get_gene_regions :106-116) every gene also keeps its annotated introns: per transcript
+(transcript_id; exons without one form one nameless transcript of their gene) the exons sorted by start, every consecutive pair gives the
+gap between them, kept when the script's 1-based intron_start < intron_end holds, i.e. when it is at least two bases long."""
 import gzip
 
 import numpy as np
@@ -27,10 +31,11 @@ SUFFIXES = (".gff3", ".gtf", ".gff3.gz", ".gtf.gz")
 class ContigGenes:
     """One contig's genes: span_start0 / span_end0 (first merged exon's start to last merged exon's end: what the script puts into its
     per-contig tree), exon_off (n_genes + 1) into exon_start0 / exon_end0 (merged exons, ascending and disjoint), gene_id / gene_name /
-    strand (lists), reported (bool per gene)."""
+    strand (lists), reported (bool per gene), introns (per gene a frozenset of (start0, len): the annotated introns of its transcripts)."""
 
     def __init__(self, genes=()):
-        genes = sorted(genes, key=lambda g: (g[1][0][0], g[1][-1][1], g[0]))   # (gene_id, exons, name, strand, reported)
+        genes = sorted(genes, key=lambda g: (g[1][0][0], g[1][-1][1], g[0]))   # (gene_id, exons, name, strand, reported[, transcripts])
+        self.introns = [transcript_introns(g[5]) if len(g) > 5 else frozenset() for g in genes]
         self.gene_id = [g[0] for g in genes]
         self.gene_name = [g[2] for g in genes]
         self.strand = [g[3] for g in genes]
@@ -48,8 +53,22 @@ class ContigGenes:
 
     @classmethod
     def from_exons(cls, genes):
-        """genes: [(gene_id, [(start0, end0), ...])] or [(gene_id, exons, gene_name, strand, reported)] -- exons in any order, merged here"""
+        """genes: [(gene_id, [(start0, end0), ...])] or [(gene_id, exons, gene_name, strand, reported)] or the same with a sixth entry, the
+        gene's transcripts as a list of exon lists (the source of its annotated introns; without it the gene has none) -- exons in any
+        order, merged here"""
         return cls([(g[0], merge_exons(g[1])) + (tuple(g[2:]) if len(g) > 2 else (".", ".", True)) for g in genes])
+
+
+def transcript_introns(transcripts):
+    """[[(start0, end0), ...] per transcript] -> frozenset of (start0, len): between consecutive exons of a transcript sorted by start (a
+    stable sort, as the script's), gaps of at least two bases"""
+    out = set()
+    for exons in transcripts:
+        ex = sorted(((int(x), int(y)) for x, y in exons), key=lambda e: e[0])
+        for (_, y0), (x1, _) in zip(ex, ex[1:]):
+            if x1 - y0 >= 2:     # 1-based inclusive [y0 + 1, x1]: intron_start < intron_end
+                out.add((y0, x1 - y0))
+    return frozenset(out)
 
 
 def merge_exons(exons):
@@ -98,7 +117,7 @@ def load(path, gene_types=GENE_TYPES):
     parse = _attrs_gff3 if ".gff3" in path else _attrs_gtf
     gene_types = set(gene_types)
     genes = {}   # gene_id -> (name, strand) of the kept `gene` features
-    exons = {}   # gene_id -> [(contig, start0, end0)]
+    exons = {}   # gene_id -> [(contig, start0, end0, transcript_id or None)]
     with (gzip.open if path.endswith(".gz") else open)(path, "rt") as f:
         for line in f:
             if line.startswith("#"):
@@ -112,12 +131,16 @@ def load(path, gene_types=GENE_TYPES):
             if parts[2] == "gene":
                 genes[a["gene_id"]] = (a.get("gene_name", "."), parts[6])
             else:
-                exons.setdefault(a["gene_id"], []).append((parts[0], int(parts[3]) - 1, int(parts[4])))
+                exons.setdefault(a["gene_id"], []).append((parts[0], int(parts[3]) - 1, int(parts[4]), a.get("transcript_id")))
     per_contig = {}
     for gid, ex in exons.items():
-        contigs = {c for c, _, _ in ex}
+        contigs = {e[0] for e in ex}
         if len(contigs) > 1:
             continue
         name, strand = genes.get(gid, (".", "."))
-        per_contig.setdefault(contigs.pop(), []).append((gid, merge_exons([(x, y) for _, x, y in ex]), name, strand, gid in genes))
+        transcripts = {}
+        for _, x, y, tid in ex:
+            transcripts.setdefault(tid, []).append((x, y))
+        per_contig.setdefault(contigs.pop(), []).append((gid, merge_exons([(x, y) for _, x, y, _ in ex]), name, strand, gid in genes,
+                                                         list(transcripts.values())))
     return {c: ContigGenes(g) for c, g in per_contig.items()}

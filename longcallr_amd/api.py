@@ -248,6 +248,13 @@ class Engine:
         """lcr_assign_genes on the bound batch (any stage; the stage does not move): every read goes to the candidate gene whose merged
         exons its aligned blocks overlap most (include/lcr.h; longcallR-ase.py's assign_reads_to_gene).  genes: the contig's
         annotation.ContigGenes (or any object with its five arrays), or None for no gene at all -- every read then gets -1."""
+        a, keep = self._annotation(genes)
+        self._chk(self.lib.lcr_assign_genes(self.h, _abi.LCR_MEM_HOST, C.byref(a)), "lcr_assign_genes")   # (host arrays are copied before the call returns)
+        return self
+
+    @staticmethod
+    def _annotation(genes):
+        """lcr_gene_annotation over host arrays -> (the struct, the arrays it points to)"""
         a = _abi.LcrGeneAnnotation()
         keep = []
         if genes is not None and len(genes.span_start0):
@@ -257,8 +264,7 @@ class Engine:
             a.n_genes, a.n_exons = int(keep[0].size), int(keep[3].size)
             if keep[1].size != a.n_genes or keep[2].size != a.n_genes + 1 or keep[4].size != a.n_exons:
                 raise ValueError("annotation arrays: span_end0 needs n_genes, exon_off n_genes + 1, exon_end0 n_exons entries")
-        self._chk(self.lib.lcr_assign_genes(self.h, _abi.LCR_MEM_HOST, C.byref(a)), "lcr_assign_genes")   # (host arrays are copied before the call returns)
-        return self
+        return a, keep
 
     def read_genes(self):
         """lcr_get_read_genes after assign_genes(): (gene index per read of the batch, -1 = none; its overlap in bases), copied"""
@@ -274,6 +280,20 @@ class Engine:
         o = _abi.LcrAseGeneList()
         self._chk(self.lib.lcr_get_ase_genes(self.h, C.byref(o)), "lcr_get_ase_genes")
         return _view(o.rec, _abi.AGENE_DTYPE, o.n_pairs), _view(o.pair_region_off, np.int32, o.n_regions + 1)
+
+    def junctions_genes(self, genes, min_count=10, min_junctions=2):
+        """lcr_junctions_genes + lcr_get_junctions_genes after phase() and assign_genes(genes): junctions()'s table per (region, gene) pair
+        with the script's exon-overlap filter (include/lcr.h; the table longcallR-asj.py builds per gene) -> (records as a structured array
+        of _abi.JUNC_GENE_DTYPE, ordered by region, gene, start0 and len, copied; junc_region_off, n_regions + 1).  genes: the annotation
+        assign_genes() was called with -- the filter reads its exons.  Waits for an asynchronous phase stage in flight; may be repeated
+        with other parameters.  last_junctions_genes_ms holds the call's HIP-event time when timing is on, else -1."""
+        p = _abi.LcrJunctionParams(int(min_count), int(min_junctions))
+        a, keep = self._annotation(genes)
+        self._chk(self.lib.lcr_junctions_genes(self.h, C.byref(p), _abi.LCR_MEM_HOST, C.byref(a)), "lcr_junctions_genes")   # (host arrays are copied before the call returns)
+        o = _abi.LcrJunctionGeneList()
+        self._chk(self.lib.lcr_get_junctions_genes(self.h, C.byref(o)), "lcr_get_junctions_genes")
+        self.last_junctions_genes_ms = float(o.kernel_ms)
+        return _view(o.junc, _abi.JUNC_GENE_DTYPE, o.n_junctions), _view(o.junc_region_off, np.int32, o.n_regions + 1)
 
     def set_downsample(self, depth, seed=2025):
         """lcr_set_downsample: regions with at least `depth` fragment rows are phased on a sample of `depth` rows (longcallR --downsample /

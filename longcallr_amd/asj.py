@@ -4,7 +4,9 @@ The read-scale work -- junction walk, dedupe and count, overlap and presence per
 kept junction is small and plain: the clusters, the two tests, the Benjamini-Hochberg adjustment and the TSV text of
 allele_specific/longcallR-asj.py (cluster_junctions_connected_components, haplotype_event_test, calc_sor, g_test_2x2, the
 multipletests(method="fdr_bh") call and AseEvent).  Standard library + NumPy only: fisher_exact, chi2 and multipletests are
-restated below.  Not the script's: there is no annotation, so Strand and Novel are "." and Gene_name is the region."""
+restated below.  Not the script's in format_tsv: there is no annotation, so Strand and Novel are "." and Gene_name is the region.
+format_tsv_genes / format_gene_tsv are the per-gene form over Engine.junctions_genes() (include/lcr.h: lcr_junctions_genes) and an
+annotation.ContigGenes: the script's .asj.tsv and .asj_gene.tsv."""
 import math
 
 import numpy as np
@@ -15,9 +17,11 @@ HEADER = ("#Junction\tStrand\tJunction_set\tPhase_set\tHap1_absent\tHap1_present
 
 def cluster(junc):
     """Connected components of the kept junctions (records of Engine.junctions(), any number of regions) where two junctions of a
-    region are joined when they share s or share s + l (donor or acceptor).  Returns an int array: for every junction the index
-    of its component's first junction in output order."""
+    region are joined when they share s or share s + l (donor or acceptor).  Records of Engine.junctions_genes() are joined inside
+    their (region, gene) pair only: the script clusters the junctions of one gene's reads.  Returns an int array: for every junction
+    the index of its component's first junction in output order."""
     n = len(junc)
+    gene = junc["gene"] if "gene" in (junc.dtype.names or ()) else None
     parent = list(range(n))
 
     def find(x):
@@ -28,6 +32,8 @@ def cluster(junc):
     seen = {}
     for i in range(n):
         g, s, l = int(junc["region"][i]), int(junc["start0"][i]), int(junc["len"][i])
+        if gene is not None:
+            g = (g, int(gene[i]))
         for key in ((g, 0, s), (g, 1, s + l)):
             j = seen.setdefault(key, i)
             a, b = find(i), find(j)
@@ -129,3 +135,105 @@ def format_tsv(tables, min_count=10):
     for (head, s_or, tail), p in zip(rows, adj):
         lines.append("%s\t%s\t%s\t.\t%s\n" % (head, float(p), s_or, tail))
     return "".join(lines)
+
+
+def _cells(r):
+    return [int(r["h1_absent"]), int(r["h1_present"]), int(r["h2_absent"]), int(r["h2_present"])]
+
+
+def merge_gene_junctions(records, return_index=False):
+    """One record per (gene, start0, len) out of the (region, gene) records of one contig (Engine.junctions_genes() of its chunks,
+    concatenated): where the same junction of a gene occurs in more than one region or chunk, the record with the largest sum of its
+    four cells is kept, ties to the first.  That happens only under truncation or with user regions: discovered coverage islands are
+    connected by read spans, introns included, so every read that overlaps a junction lies in the junction's island.  -> the kept
+    records in (gene, start0, len) order (with return_index: and their indices in `records`)."""
+    best = {}
+    for i in range(len(records)):
+        r = records[i]
+        key = (int(r["gene"]), int(r["start0"]), int(r["len"]))
+        tot = sum(_cells(r))
+        if key not in best or tot > best[key][0]:
+            best[key] = (tot, i)
+    idx = np.array([best[k][1] for k in sorted(best)], dtype=np.int64)
+    out = records[idx] if len(idx) else records[:0]
+    return (out, idx) if return_index else out
+
+
+def gene_events(tables, min_count=10):
+    """The events the script writes, with their adjusted p-values.  tables: [(chrom, junc, genes)] -- per batch the contig's name, the
+    records of Engine.junctions_genes() and the contig's annotation.ContigGenes (junc["gene"] indexes it); the batches of a contig follow
+    one another.  In the script's order of steps: Junction_set is the first junction (smallest s, then l) of the record's connected
+    component inside its (region, gene) pair; the records of a contig are merged per gene (merge_gene_junctions); records without a
+    phase set (n_phase_sets == 0: haplotype_event_test returns None) and those of genes that are not reported are dropped; of two
+    genes with the same Gene_name and the same junction the later one replaces the earlier (the script's dict keyed by name); events
+    whose table sums to less than min_count are dropped; P_value is max(Fisher, G-test), Benjamini-Hochberg adjusted over what is
+    left.  -> a list of dicts in contig, gene, s, l order."""
+    per_contig, order = {}, []
+    for chrom, junc, genes in tables:
+        comp = cluster(junc)
+        first = np.zeros((len(junc), 2), dtype=np.int64)
+        for i in range(len(junc)):
+            first[i] = (int(junc["start0"][comp[i]]), int(junc["len"][comp[i]]))
+        if chrom not in per_contig:
+            per_contig[chrom] = [[], [], genes]
+            order.append(chrom)
+        per_contig[chrom][0].append(junc)
+        per_contig[chrom][1].append(first)
+    events = []
+    for chrom in order:
+        parts, firsts, genes = per_contig[chrom]
+        rec, idx = merge_gene_junctions(np.concatenate(parts), return_index=True)
+        first = np.concatenate(firsts)[idx] if len(idx) else np.zeros((0, 2), np.int64)
+        by_name = {}     # (s, l, Gene_name) -> position in `kept`
+        kept = []
+        for i in range(len(rec)):
+            r = rec[i]
+            k = int(r["gene"])
+            if int(r["n_phase_sets"]) == 0 or not genes.reported[k]:
+                continue
+            s, l = int(r["start0"]), int(r["len"])
+            ev = dict(chrom=chrom, start0=s, len=l, strand=genes.strand[k], set_start0=int(first[i][0]), set_len=int(first[i][1]),
+                      phase_set=int(r["phase_set"]), cells=_cells(r), novel=(s, l) not in genes.introns[k], gt_ag=int(r["motif"]) != 0,
+                      gene_name=genes.gene_name[k], p=junction_p(r))
+            key = (s, l, ev["gene_name"])
+            if key in by_name:
+                kept[by_name[key]] = None
+            by_name[key] = len(kept)
+            kept.append(ev)
+        events += [ev for ev in kept if ev is not None and sum(ev["cells"]) >= min_count]
+    adj = bh_adjust([ev["p"] for ev in events])
+    for ev, p in zip(events, adj):
+        ev["p_adj"] = float(p)
+        ev["sor"] = sor(*ev["cells"])
+    return events
+
+
+def format_tsv_genes(tables, min_count=10, events=None):
+    """The script's .asj.tsv text with an annotation: format_tsv's header, tests, SOR and Benjamini-Hochberg adjustment over the
+    written rows, with Strand and Gene_name from the annotation and Novel = the junction is no annotated intron of its gene.
+    tables as in gene_events (or its result as `events`)."""
+    events = gene_events(tables, min_count) if events is None else events
+    lines = [HEADER + "\n"]
+    for ev in events:
+        c, s, l, ps = ev["chrom"], ev["start0"], ev["len"], ev["phase_set"]
+        lines.append("%s:%d-%d\t%s\t%s:%d-%d\t%s\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%s\t%s\n" % (
+            (c, s + 1, s + l, ev["strand"], c, ev["set_start0"] + 1, ev["set_start0"] + ev["set_len"], ps if ps else ".") + tuple(ev["cells"])
+            + (ev["p_adj"], ev["sor"], ev["novel"], ev["gt_ag"], ev["gene_name"])))
+    return "".join(lines)
+
+
+GENE_HEADER = "#Gene_name\tChr\tP_value\tSOR"
+
+
+def format_gene_tsv(tables, min_count=10, no_gtag=False, events=None):
+    """The script's .asj_gene.tsv text: per Gene_name the written event with the smallest adjusted p-value (a strict <: the first seen
+    wins a tie) among the events with GT_AG true -- among all of them with no_gtag --, in the order in which the names are first seen."""
+    events = gene_events(tables, min_count) if events is None else events
+    best = {}
+    for ev in events:
+        if not no_gtag and not ev["gt_ag"]:
+            continue
+        name = ev["gene_name"]
+        if name not in best or ev["p_adj"] < best[name][1]:
+            best[name] = (ev["chrom"], ev["p_adj"], ev["sor"])
+    return "".join([GENE_HEADER + "\n"] + ["%s\t%s\t%s\t%s\n" % ((name,) + v) for name, v in best.items()])

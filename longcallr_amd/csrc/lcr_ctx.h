@@ -2,7 +2,7 @@
 // functions.  Private to lcr_api.hip (lifecycle, cache, fills, debug switches, phase entry, region discovery), lcr_batch.hip (binding and
 // upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns), lcr_calls.hip (candidate, import and fragment stages with their getters) and
 // lcr_junctions.hip (lcr_junctions, lcr_get_junctions), lcr_ase.hip (lcr_ase, lcr_get_ase) and lcr_genes.hip (lcr_assign_genes, lcr_get_read_genes,
-// lcr_ase_genes, lcr_get_ase_genes).
+// lcr_ase_genes, lcr_get_ase_genes) and lcr_junctions_genes.hip (lcr_junctions_genes, lcr_get_junctions_genes).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -129,7 +129,7 @@ struct lcr_ctx {
 
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
-  int32_t genes_nr = 0;
+  int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
   DevBuf g_span_s, g_span_e, g_exon_off, g_exon_s, g_exon_e, g_pmax, d_gene, d_gene_ov;   // host annotation copied to HBM; running maximum of the spans' ends; the result
   HostBuf h_gene, h_gene_ov, h_gene_bad;   // pinned: the result; the verdict on the annotation
   hipEvent_t ev_genes = nullptr;           // behind the annotation's check, then behind the copies of the result
@@ -138,6 +138,17 @@ struct lcr_ctx {
   DevBuf ag_pos, ag_pat, ag_mat, ag_cnt, ag_off, ag_tag, ag_site, ag_site_ps, d_agene;
   HostBuf h_agene, h_agene_off, h_agene_ctl, h_agene_bad;   // pinned: the records; their offsets per region; the number of pairs; the verdict on the parental sites
   hipEvent_t ev_agene = nullptr;
+
+  // K9 (lcr_junctions_genes): scratch and results of its own -- no other stage or getter reads them
+  bool jgene_valid = false;  // lcr_get_junctions_genes: the last call's table belongs to the phase results and the gene assignment of the bound batch
+  int32_t jgene_n = 0, jgene_ng = 0;
+  DevBuf jg_span_s, jg_span_e, jg_exon_off, jg_exon_s, jg_exon_e;   // host annotation copied to HBM
+  DevBuf jg_part, jg_nocc, jg_part_off, jg_occ_off, jg_cnt, jg_pair_off, jg_read_pair, jg_row_slot, jg_pregion, jg_pgene, jg_prow0, jg_prows, jg_pocc;
+  DevBuf jg_tsz, jg_tbl_off, jg_rows, jg_keys, jg_tbl_key, jg_tbl_cnt, jg_flag, jg_koff, jg_ck, jg_cc, jg_cp, jg_off, jg_jpair, d_jgene;
+  HostBuf h_jgene_ctl, h_jgene, h_jgene_off, h_jgene_bad;   // pinned: {participating rows, occurrences, kept junctions, pairs}; the records; their offsets per region; the annotation's verdict
+  hipEvent_t ev_jgene = nullptr;              // behind the annotation's check, the two size waits, then the call's last kernel
+  hipEvent_t ev_jgene_t[2] = {};              // timing enabled: first kernel to last of the last call (lcr_junction_gene_list.kernel_ms; no lcr_kernel_ms slot)
+  bool jgene_timed = false;
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
@@ -170,7 +181,8 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
   if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
   if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
-  if (to < ST_LOADED) { c->genes_valid = false; c->agene_valid = false; }   // read -> gene names the reads of ONE bound batch
+  if (to < ST_PHASED) c->jgene_valid = false;    // ... and the per-gene junction table
+  if (to < ST_LOADED) { c->genes_valid = false; c->agene_valid = false; c->jgene_valid = false; }   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and

@@ -341,6 +341,30 @@ void launch_k8_votes(const int32_t* row_tag, int32_t n_rows, const int64_t* row_
                      const uint32_t* site_ps, uint32_t min_baseq, lcr_ase_gene* pairs, hipStream_t s);
 void launch_k8_export(const lcr_ase_gene* pairs, int32_t n, lcr_ase_gene* host_out /* pinned (device pointer) */, hipStream_t s);
 
+// k9_gene_junctions.hip: haplotype x junction counts per (region, gene) pair over the phased rows (lcr_junctions_genes)
+struct K9Pairs {   // what k9_pairs<true> writes: per read its pair and row slot (n_reads each); per pair its region, gene, first row, rows and
+  int32_t *read_pair, *row_slot, *region, *gene, *row0, *rows, *occ;   // junction occurrences (sized by n_reads, an upper bound of the pairs)
+};
+void launch_k9_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* gene, uint32_t min_junctions,
+                     int32_t* part_flag, int32_t* nocc, hipStream_t s);
+void launch_k9_pair_count(const BatchView& b, const int32_t* gene, const int32_t* part_flag, int32_t* n_pairs /* n_regions */, hipStream_t s);
+void launch_k9_pair_emit(const BatchView& b, const int32_t* gene, const int32_t* part_flag, const int32_t* nocc, const int32_t* pair_off /* n_regions + 1 */,
+                         const int32_t* part_off /* n_reads + 1 */, const K9Pairs& pr, hipStream_t s);
+void launch_k9_sizes(const BatchView& b, const int32_t* pair_off, const int32_t* part_off, const int32_t* occ_off /* n_reads + 1 */, const int32_t* pair_occ,
+                     int32_t* tsz /* n_reads */, int32_t* host_ctl /* pinned (device pointer): [0] participating rows, [1] occurrences, [3] pairs */,
+                     hipStream_t s);
+size_t launch_k9_row_bytes();   // bytes of a participating row's record
+void launch_k9_emit(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* gene, const int32_t* part_flag,
+                    const int32_t* occ_off, const K9Pairs& pr, const int32_t* tbl_off /* n_reads + 1 */, const lcr_gene_annotation& a /* device arrays */,
+                    void* rows, uint64_t* keys, uint64_t* tbl_key /* 0xff-filled */, uint32_t* tbl_cnt /* zeroed */, hipStream_t s);
+void launch_k9_offsets(const int32_t* pair_off, const int32_t* tbl_off, const int32_t* koff /* n_slots + 1 */, int32_t ng, int32_t n_slots, int32_t* joff,
+                       int32_t* host_joff, int32_t* host_ctl /* [2] kept junctions */, hipStream_t s);
+void launch_k9_place(const BatchView& b, const uint64_t* tbl_key, const uint32_t* tbl_cnt, const int32_t* flag, const int32_t* koff,
+                     const int32_t* tbl_off, const int32_t* pair_off, const K9Pairs& pr, int32_t n_slots, int32_t n_kept, uint64_t* ck, uint32_t* cc,
+                     int32_t* cp, lcr_junction_gene* junc, int32_t* junc_pair /* n_kept: the pair of every record */, hipStream_t s);
+void launch_k9_tables(const int32_t* junc_pair, const K9Pairs& pr, const void* rows, const uint64_t* keys, int32_t n_kept, lcr_junction_gene* junc,
+                      lcr_junction_gene* host_junc /* pinned (device pointer) */, hipStream_t s);
+
 // device helpers shared by kernels -------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ int base_code(uint8_t b) {

@@ -111,7 +111,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         downsample=False, downsample_depth=10000, downsample_seed=2025, truncation=False, truncation_coverage=200000,
         asj_out=None, asj_min_count=10, asj_min_junctions=2,
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
-        ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, **param_overrides):
+        ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
+        **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -149,7 +150,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     whose merged exons its aligned blocks overlap most, include/lcr.h: lcr_assign_genes) and Engine.ase_genes in place of Engine.ase;
     the (region, gene) pair records of a contig's chunks are merged per gene (ase.merge_gene_records) and written in contig and then gene
     order with the annotation's Gene_name, in each of the three modes.  Adds the stat ase_genes (rows written) in place of ase_regions.
-    ase_annotation without ase_out is a ValueError; without ase_annotation nothing changes."""
+    ase_annotation without ase_out is a ValueError; without ase_annotation nothing changes.
+    asj_annotation / asj_gene_types: the same for the junction table (the script's longcallR-asj.py -a / --gene_types): the table of
+    asj_out is then per GENE -- every chunk calls Engine.assign_genes after binding (once, also when ase_annotation is given: the two
+    must then name the same file and gene types, ValueError otherwise) and Engine.junctions_genes in place of Engine.junctions (include/lcr.h:
+    lcr_junctions_genes); asj_out gets asj.format_tsv_genes' text with the annotation's Strand, Novel and Gene_name, and the script's
+    .asj_gene.tsv goes beside it (X.asj.tsv -> X.asj_gene.tsv, any other name -> name + ".gene.tsv").  junctions stays the number of
+    records; adds the stat asj_genes (rows of the gene file).  asj_annotation without asj_out is a ValueError; without asj_annotation
+    nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -167,6 +175,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         raise ValueError("ase_parental_vcf / ase_dna_vcf need ase_out")
     if ase_out is None and ase_annotation is not None:
         raise ValueError("ase_annotation needs ase_out")
+    if asj_out is None and asj_annotation is not None:
+        raise ValueError("asj_annotation needs asj_out")
+    if asj_annotation is not None and ase_annotation is not None and (
+            os.path.abspath(str(asj_annotation)) != os.path.abspath(str(ase_annotation)) or tuple(asj_gene_types) != tuple(ase_gene_types)):
+        raise ValueError("asj_annotation and ase_annotation must be the same file with the same gene types: a chunk has one gene assignment")
     fai = ref_path + ".fai"
     if not os.path.exists(fai):
         raise FileNotFoundError("Reference index file .fai does not exist.")   # util.rs:575-577
@@ -197,6 +210,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     parental = ase.parental_sites(ase_parental_vcf) if ase_parental_vcf is not None else None    # {contig: (pos0, pat, mat)}
     dna = ase.dna_het_sites(ase_dna_vcf) if ase_dna_vcf is not None else None                    # {contig: pos0}
     genes = annotation.load(ase_annotation, ase_gene_types) if ase_annotation is not None else None   # {contig: annotation.ContigGenes}
+    jgenes = None                                                                                      # the same for the junction table
+    if asj_annotation is not None:
+        jgenes = genes if genes is not None else annotation.load(asj_annotation, asj_gene_types)
     no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
     # Every engine is a long-lived worker with the ASYNCHRONOUS phase stage (lcr_ctx_set_async_phase, include/lcr.h): a chunk is uploaded
@@ -223,7 +239,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["hp"] = np.where((fm["row_for_phasing"] != 0) | (asg != 0), asg, -1)
             out["ps"] = res["phase_set"].copy()
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
-        if junc is not None:
+        if junc is not None and jgenes is not None:
+            out["junc"] = (name, junc, jgenes.get(name, annotation.ContigGenes()))
+        elif junc is not None:
             out["junc"] = (name, junc, batch.start0, batch.len)
         if arec is not None and genes is not None:      # (region, gene) pair records; merged per gene when every chunk is in
             out["ase"] = (name, arec[0])
@@ -247,8 +265,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             slot = n_slot[k] & 1
             n_slot[k] += 1
             E.load_batch_async(batch, slot).bind_batch(slot)
-            if genes is not None:
-                E.assign_genes(genes.get(name))
+            if genes is not None or jgenes is not None:     # one assignment per chunk, whichever table asks for it
+                E.assign_genes((genes if genes is not None else jgenes).get(name))
             E.fill_data_into_freq_vec()
             if in_flight[k] is not None:
                 finish(k)
@@ -262,7 +280,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 f = E.fragmat()
                 fm = dict(row_for_phasing=f["row_for_phasing"], row_read=f["row_read"])
             E.phase()
-            junc = E.junctions(asj_min_count, asj_min_junctions)[0] if asj_out is not None else None   # (waits for the phase stage)
+            junc = None
+            if asj_out is not None and jgenes is not None:
+                junc = E.junctions_genes(jgenes.get(name), asj_min_count, asj_min_junctions)[0]           # (waits for the phase stage)
+            elif asj_out is not None:
+                junc = E.junctions(asj_min_count, asj_min_junctions)[0]                                    # (waits for the phase stage)
             arec = None
             if ase_out is not None:
                 psites = None
@@ -327,8 +349,17 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     write_vcf(out_vcf, contig_lengths, [text])
     if asj_out is not None:
         stats["junctions"] = sum(int(r["junc"][1].size) for r in results)
+        if jgenes is not None:
+            events = asj.gene_events([r["junc"] for r in results], asj_min_count)
+            text, gene_text = asj.format_tsv_genes(None, events=events), asj.format_gene_tsv(None, events=events)
+            stats["asj_genes"] = gene_text.count("\n") - 1
+            asj_out = str(asj_out)
+            with open(asj_out[:-len(".asj.tsv")] + ".asj_gene.tsv" if asj_out.endswith(".asj.tsv") else asj_out + ".gene.tsv", "w") as f:
+                f.write(gene_text)
+        else:
+            text = asj.format_tsv([r["junc"] for r in results], asj_min_count)
         with open(asj_out, "w") as f:
-            f.write(asj.format_tsv([r["junc"] for r in results], asj_min_count))
+            f.write(text)
     if ase_out is not None and genes is not None:
         per_contig = {}     # contig -> its chunks' pair records (and masks), in chunk order
         for r in results:

@@ -4,7 +4,8 @@
   python tools/run_pipeline.py -b reads.bam -f ref.fa -o out.vcf [--out-bam phased.bam] [-p hifi-masseq] [-c chr20,chr21]
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
-                                 [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]]   (allele-specific junction table)
+                                 [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]   (allele-specific junction table)
+                                  [--asj-annotation genes.gtf.gz [--asj-gene-types protein_coding,lncRNA]]]   (... per annotated gene, + the gene file)
                                  [--ase-out out.ase.tsv [--ase-min-support N] [--ase-overdispersion R]
                                   [--ase-parental-vcf phased.vcf.gz | --ase-dna-vcf dna.vcf.gz]   (allele-specific expression table)
                                   [--ase-annotation genes.gtf.gz [--ase-gene-types protein_coding,lncRNA]]]   (... per annotated gene)
@@ -37,6 +38,8 @@ def main():
     ap.add_argument("--asj-out", help="write the allele-specific junction table (longcallR-asj.py's .asj.tsv; regions in place of genes)")
     ap.add_argument("--asj-min-count", type=int, default=10, help="reads a junction needs to be kept, and a table needs to be written")
     ap.add_argument("--asj-min-junctions", type=int, default=2, help="a read takes part with MORE junctions than this")
+    ap.add_argument("--asj-annotation", help="GTF / GFF3 (.gz) annotation: the junction table gets one row per (gene, junction) and the .asj_gene.tsv is written beside it")
+    ap.add_argument("--asj-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
     ap.add_argument("--ase-out", help="write the allele-specific expression table (longcallR-ase.py's .ase.tsv; regions in place of genes)")
     ap.add_argument("--ase-min-support", type=int, default=10, help="assigned reads a region's phase set needs to be written")
     ap.add_argument("--ase-overdispersion", type=float, default=0.001, help="rho of the beta-binomial test")
@@ -52,6 +55,8 @@ def main():
         ap.error("--ase-parental-vcf / --ase-dna-vcf need --ase-out")
     if a.ase_annotation and not a.ase_out:
         ap.error("--ase-annotation needs --ase-out")
+    if a.asj_annotation and not a.asj_out:
+        ap.error("--asj-annotation needs --asj-out")
     extra = {} if a.read_assign_cutoff is None else dict(read_assign_cutoff=a.read_assign_cutoff)
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
                       device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf,
@@ -60,7 +65,8 @@ def main():
                       asj_out=a.asj_out, asj_min_count=a.asj_min_count, asj_min_junctions=a.asj_min_junctions,
                       ase_out=a.ase_out, ase_min_support=a.ase_min_support, ase_overdispersion=a.ase_overdispersion,
                       ase_parental_vcf=a.ase_parental_vcf, ase_dna_vcf=a.ase_dna_vcf,
-                      ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t), **extra)
+                      ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t),
+                      asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t), **extra)
     print(json.dumps(st))
 
 
