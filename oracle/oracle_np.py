@@ -101,11 +101,20 @@ def pileup(batch, g, prm):
 
 
 def strand_odds_ratio(ref_fw, ref_rv, alt_fw, alt_rv):
+    """candidate.rs:24-35 in f32, scalars or arrays; each of the three logs is the f64 log rounded to f32.
+
+    The threshold is this expression at (5, 5, 9, 1): sym = 5.2, ratio = 5.  Many small count tuples equal it
+    mathematically, so rounding alone decides `sor > thr` for them, and the reference's value is that of whichever libm
+    it links to.  NumPy's own float32 log is not the host's logf: with it this function gave another verdict than the C++
+    oracle at 18 of the 646 249 tuples with total <= 64 (ranges 0..30, 0..30, 0..40, 0..40) -- tests/column_cases.py lists
+    them, (1,6,1,34), (3,13,1,34), (5,20,1,34), (6,3,34,3) and (0,6,0,34) among them.  The correctly rounded form gives the
+    host's verdict on every one of those tuples (tests/test_oracle_kat.py::test_sor_threshold)."""
     f = np.float32
-    x00, x01, x10, x11 = f(ref_fw + 1), f(ref_rv + 1), f(alt_fw + 1), f(alt_rv + 1)
-    sym = f(f(x00 * x11) / f(x01 * x10)) + f(f(x01 * x10) / f(x00 * x11))
-    rr = f(min(x00, x01) / max(x00, x01)); ar = f(min(x10, x11) / max(x10, x11))
-    return f(f(np.log(f(sym))) + f(np.log(rr))) - f(np.log(ar))
+    x00, x01, x10, x11 = (np.asarray(v, np.int64).astype(f) + f(1) for v in (ref_fw, ref_rv, alt_fw, alt_rv))
+    sym = (x00 * x11) / (x01 * x10) + (x01 * x10) / (x00 * x11)
+    rr = np.minimum(x00, x01) / np.maximum(x00, x01); ar = np.minimum(x10, x11) / np.maximum(x10, x11)
+    log = lambda v: np.log(v.astype(np.float64)).astype(f)
+    return (log(sym) + log(rr)) - log(ar)
 
 
 def binomial_two_tailed(k, n):
@@ -127,15 +136,20 @@ def two_major(cnt4, ref_base):
     return x[0], x[1]
 
 
-def candidates(pu, start0, prm):
-    """candidate.rs:75-463 (before the dense sweep).  Returns list of dicts in position order."""
+def candidates(pu, start0, prm, trace=None):
+    """candidate.rs:75-463 (before the dense sweep).  Returns list of dicts in position order.
+    trace: a dict that receives column -> the rule that dropped it, or "kind/variant_type/genotype class" of its record."""
     out = []
+    if trace is None:
+        trace = {}
     L = pu["cnt"].shape[1]
     thr = strand_odds_ratio(5, 5, 9, 1)
     f32 = np.float32
     depth = pu["cnt"].sum(axis=0)
+    trace.update((int(c), "min_depth") for c in np.flatnonzero(depth < prm.min_depth))
+    trace.update((int(c), "max_depth") for c in np.flatnonzero(depth > prm.max_depth))
     for col in np.flatnonzero((depth >= prm.min_depth) & (depth <= prm.max_depth)):
-        R = chr(pu["ref"][col]); tot = int(depth[col])
+        R = chr(pu["ref"][col]); tot = int(depth[col]); col = int(col)
         c4 = [int(v) for v in pu["cnt"][:, col]]
         (a1, c1), (a2, c2) = two_major(c4, R)
         af1, af2 = f32(c1) / f32(tot), f32(c2) / f32(tot)
@@ -146,36 +160,46 @@ def candidates(pu, start0, prm):
         else:
             nalt, refb, alts = 2, R, [(a1, c1, af1), (a2, c2, af2)]
         if refb not in "ACGTacgt":
+            trace[col] = "ref_base"
             continue
         if nalt == 1:
             if tot < 200 and alts[0][2] < f32(prm.low_frac_cut):
+                trace[col] = "low_frac"
                 continue
             if tot >= 200 and alts[0][1] < prm.low_cnt_cut:
+                trace[col] = "low_cnt"
                 continue
         dd, nn = int(pu["d"][col]), int(pu["n"][col])
         if dd >= alts[0][1]:
+            trace[col] = "deletion"
             continue
         if f32(c1 + c2) / f32(tot + dd + nn) < f32(prm.min_af_intron):
+            trace[col] = "af_intron"
             continue
         idx = "ACGT".index
         probe = a1 if a1 != R else (a2 if a2 != R else None)
         if probe is not None:
             pc = c1 if probe == a1 else c2
             if pc > 0 and int(pu["hist"][idx(probe), prm.min_baseq:, col].sum()) < 2:
+                trace[col] = "baseq"
                 continue
         if prm.use_strand_bias:
             st = lambda b: (int(pu["fwd"][idx(b.upper()), col]), int(pu["cnt"][idx(b.upper()), col] - pu["fwd"][idx(b.upper()), col]))
             rf, rr = st(refb)
             sor = max(strand_odds_ratio(rf, rr, *st(a[0])) for a in alts)
             if sor > thr:
+                trace[col] = "sor"
                 continue
             if nalt == 1:
                 afw, arv = st(alts[0][0])
                 if afw + arv <= 30 and binomial_two_tailed(afw, afw + arv) < 0.05:
+                    trace[col] = "binomial"
                     continue
                 if afw * arv == 0:
+                    trace[col] = "one_strand"
                     continue
         if R not in "ACGT":
+            trace[col] = "ref_base"
             continue
         ri = idx(R)
         hm = pu["hist"][ri, :, col]
@@ -204,7 +228,9 @@ def candidates(pu, start0, prm):
             vt, gt = 1, 0
         else:
             vt, gt = 0, 1
+        vt0 = vt
         if qual < prm.min_qual:
+            trace[col] = "min_qual"
             continue
         tf, tr = int(pu["ts"][0, col]), int(pu["ts"][1, col])
         kind = None
@@ -224,7 +250,9 @@ def candidates(pu, start0, prm):
             else:
                 kind = "het"
         if kind is None:
+            trace[col] = "hom_ref"
             continue
+        trace[col] = "%s/%d/%d" % (kind, vt, vt0)
         out.append(dict(pos=start0 + int(col), ref=R, a1=a1, a2=a2, depth=tot, vt=vt, gt=gt, kind=kind,
                         loglik=loglik, qual=qual, gq=gq, af1=float(af1), af2=float(af2)))
     return out

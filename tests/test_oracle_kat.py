@@ -5,8 +5,10 @@ import math
 import numpy as np
 import pytest
 
+import column_cases
 import helpers
 from longcallr_amd import _abi
+from oracle import oracle_np
 
 
 def test_sor_threshold(orc):
@@ -15,6 +17,13 @@ def test_sor_threshold(orc):
     assert abs(v - (math.log(5.2) + math.log(5.0))) < 2e-6
     assert orc.lib().orc_strand_odds_ratio(5, 5, 1, 9) == v  # symmetric in the alt strands
     assert orc.lib().orc_strand_odds_ratio(10, 10, 5, 5) == pytest.approx(math.log(2.0), abs=1e-6)
+    # with glibc's logf 816 count tuples of total <= 64 sit exactly on the threshold, 46 one ulp below it: rounding alone decides `sor > thr` there, and the
+    # two restatements (host logf; f64 log rounded to f32) give one verdict on every tuple of the census
+    t, sor, thr, ulp = column_cases.census(orc)
+    assert len(t) == 646249
+    mine, thr_np = oracle_np.strand_odds_ratio(*t.T), oracle_np.strand_odds_ratio(5, 5, 9, 1)
+    differ = t[(mine > thr_np) != (sor > thr)]
+    assert thr_np == thr and len(differ) == 0, differ[:20]
 
 
 def test_binomial_two_tailed(orc):
