@@ -507,6 +507,46 @@ typedef struct { int32_t n_regions, n_junctions; const lcr_junction_gene* junc; 
 int lcr_junctions_genes(lcr_ctx*, const lcr_junction_params*, int32_t mem, const lcr_gene_annotation*);
 int lcr_get_junctions_genes(lcr_ctx*, lcr_junction_gene_list* out);
 
+/* The other modes of the per-gene junction table (K10): longcallR-asj.py's --cluster_with_exons, its --dna_vcf / --rna_vcf filter and its
+ * .gene_coverage.tsv, each a flag of one more call behind lcr_junctions_genes.  The contract is lcr_junctions_genes', unchanged, plus
+ * what follows; with flags == 0 the junction records are lcr_junctions_genes' byte for byte.  DESIGN.md section 1f.
+ *   LCR_ASJ_EXONS         blocks of a read: the maximal runs of reference bases covered by M, =, X and D ops; an N op of length >= 1 ends
+ *       a run, I, S, H, P and a zero-length N end nothing (the script's "extend if contiguous" arm joins the two sides), a run of zero
+ *       bases is no block (zero-length M / D ops are ignored: the script can open an empty block there).  INTERIOR blocks are all but the
+ *       first and the last block of a read with more than two (cluster_junctions_exons_connected_components :399-403).
+ *       n_reads(g, k, start, len) = participating rows of the pair with this interior block, taken before both filters like a junction's;
+ *       a block is kept iff n_reads >= min_count.  One lcr_exon_gene per kept block, ordered by region, gene, start0, len;
+ *       exon_region_off[g] .. [g + 1] are region g's.  Without the flag n_exons is 0.  The junction records do not depend on the flag:
+ *       exons only change how the host clusters (longcallr_amd/asj.py cluster).
+ *   LCR_ASJ_DNA_FILTER    dna_pos0: one contig's heterozygous DNA SNV positions, 0-based, ascending and unique (n_dna of them; mem as for
+ *       the annotation; checked by a kernel beside the annotation's check -- unsorted or duplicate positions are LCR_E_ARG and the last
+ *       result stays valid; n_dna == 0 is valid).  A candidate of region g SUPPORTS its phase set when it is what lcr_ase's (1) - (2)
+ *       describe -- the VCF writer would print it PASS with a phased het GT under min_phase_score, phase_set != 0: the script's
+ *       load_longcallR_phased_vcf applied to the run's own VCF -- and its pos is one of dna_pos0.  A row of g with phase set ps != 0 is
+ *       supported iff a supporting candidate of g has phase_set == ps.  Counted rows are lcr_junctions_genes' counted rows that are also
+ *       supported (analyze_gene_with_filtering :781-790): an unsupported row still counts toward n_reads and the exon counts, is in no
+ *       cell and adds no phase set to n_phase_sets.  Not the script's: it keys the RNA variants by PS value across all contigs; here a
+ *       phase set belongs to its region.
+ *   LCR_ASJ_COVERAGE      gene_reads[k] = reads of the bound batch with gene[r] == k and more than min_junctions N ops of length >= 1,
+ *       rows and non-rows and every assignment alike (process_chunk :231-272).  Only reads that passed the batch's read filter exist, a
+ *       read in both flanks of a --truncation cut counts twice, zero-length N ops do not count.  n_genes entries in pinned host memory,
+ *       NULL without the flag.
+ * State and argument rules are lcr_junctions_genes' (lcr_phase and a valid lcr_assign_genes with the same n_genes; the annotation again,
+ * checked; a refused call changes nothing; the result dies with the phase stage's results and at the next successful lcr_assign_genes);
+ * flags outside the three bits and n_dna < 0 are LCR_E_ARG; dna_pos0 is not read without LCR_ASJ_DNA_FILTER.  The call writes no buffer
+ * another stage or getter reads: lcr_junctions_genes and its getter keep working before and after it.  The host waits are
+ * lcr_junctions_genes': the verdict (now for both lists) and two sets of sizes.  kernel_ms as in lcr_junction_gene_list. */
+enum { LCR_ASJ_EXONS = 1, LCR_ASJ_DNA_FILTER = 2, LCR_ASJ_COVERAGE = 4 };
+typedef struct { uint32_t min_count, min_junctions, flags; float min_phase_score;
+                 int32_t n_dna, pad_; const int64_t* dna_pos0; } lcr_asj_params;
+typedef struct { int32_t region, gene; int64_t start0; int32_t len; uint32_t n_reads; } lcr_exon_gene;   /* 24 bytes */
+typedef struct { int32_t n_regions, n_junctions; const lcr_junction_gene* junc; const int32_t* junc_region_off;
+                 const lcr_junction_gene* dev_junc;
+                 int32_t n_exons, n_genes; const lcr_exon_gene* exon; const int32_t* exon_region_off; const lcr_exon_gene* dev_exon;
+                 const int32_t* gene_reads; float kernel_ms; } lcr_asj_gene_list;
+int lcr_asj_genes(lcr_ctx*, const lcr_asj_params*, int32_t mem, const lcr_gene_annotation*);
+int lcr_get_asj_genes(lcr_ctx*, lcr_asj_gene_list* out);
+
 /* Down-sampling: phase deep regions on a read sample (longcallR --downsample / --downsample-depth: thread.rs:144-151, phase.rs:693-701).
  * A region with at least `depth` fragment rows (all rows of lcr_get_fragmat, empty ones included) is down-sampled: the optimiser
  * (cross_optimize and its checks, cal_overall_probability, cross_optimize_by_block), the first two post-phase rounds

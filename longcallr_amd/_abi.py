@@ -161,6 +161,25 @@ class LcrJunctionGeneList(C.Structure):   # include/lcr.h: lcr_junction_gene_lis
                 ("dev_junc", C.c_void_p), ("kernel_ms", C.c_float)]
 
 
+LCR_ASJ_EXONS, LCR_ASJ_DNA_FILTER, LCR_ASJ_COVERAGE = 1, 2, 4   # include/lcr.h: the flags of lcr_asj_params
+
+
+class LcrAsjParams(C.Structure):   # include/lcr.h: lcr_asj_params
+    _fields_ = [("min_count", C.c_uint32), ("min_junctions", C.c_uint32), ("flags", C.c_uint32), ("min_phase_score", C.c_float),
+                ("n_dna", C.c_int32), ("pad_", C.c_int32), ("dna_pos0", C.c_void_p)]
+
+
+# lcr_exon_gene (include/lcr.h): one kept interior exon block of a (region, gene) pair
+EXON_GENE_DTYPE = np.dtype([("region", "<i4"), ("gene", "<i4"), ("start0", "<i8"), ("len", "<i4"), ("n_reads", "<u4")], align=True)
+assert EXON_GENE_DTYPE.itemsize == 24, EXON_GENE_DTYPE.itemsize
+
+
+class LcrAsjGeneList(C.Structure):   # include/lcr.h: lcr_asj_gene_list
+    _fields_ = [("n_regions", C.c_int32), ("n_junctions", C.c_int32), ("junc", C.c_void_p), ("junc_region_off", C.c_void_p),
+                ("dev_junc", C.c_void_p), ("n_exons", C.c_int32), ("n_genes", C.c_int32), ("exon", C.c_void_p), ("exon_region_off", C.c_void_p),
+                ("dev_exon", C.c_void_p), ("gene_reads", C.c_void_p), ("kernel_ms", C.c_float)]
+
+
 # presets: the code values of main.rs:272-396 (not the help text)
 PRESETS = {
     "hifi-isoseq": dict(platform=LCR_PLATFORM_HIFI, min_depth=6, min_phase_score=11.0, min_af=0.15,

@@ -18,7 +18,7 @@ SYMBOLS = [
     "lcr_set_downsample", "lcr_set_downsample_rows", "lcr_get_downsample",
     "lcr_junctions", "lcr_get_junctions", "lcr_ase", "lcr_get_ase", "lcr_vcf_contig_alleles",
     "lcr_assign_genes", "lcr_get_read_genes", "lcr_ase_genes", "lcr_get_ase_genes",
-    "lcr_junctions_genes", "lcr_get_junctions_genes",
+    "lcr_junctions_genes", "lcr_get_junctions_genes", "lcr_asj_genes", "lcr_get_asj_genes",
     "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
 ]
 
@@ -122,6 +122,8 @@ def load():
     l.lcr_get_ase_genes.argtypes = [vp, C.POINTER(_abi.LcrAseGeneList)]
     l.lcr_junctions_genes.argtypes = [vp, C.POINTER(_abi.LcrJunctionParams), C.c_int32, C.POINTER(_abi.LcrGeneAnnotation)]
     l.lcr_get_junctions_genes.argtypes = [vp, C.POINTER(_abi.LcrJunctionGeneList)]
+    l.lcr_asj_genes.argtypes = [vp, C.POINTER(_abi.LcrAsjParams), C.c_int32, C.POINTER(_abi.LcrGeneAnnotation)]
+    l.lcr_get_asj_genes.argtypes = [vp, C.POINTER(_abi.LcrAsjGeneList)]
     l.lcr_vcf_contig_alleles.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     _lib = l
     return l

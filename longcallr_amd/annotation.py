@@ -144,3 +144,28 @@ def load(path, gene_types=GENE_TYPES):
         per_contig.setdefault(contigs.pop(), []).append((gid, merge_exons([(x, y) for _, x, y, _ in ex]), name, strand, gid in genes,
                                                          list(transcripts.values())))
     return {c: ContigGenes(g) for c, g in per_contig.items()}
+
+
+def gene_features(path, gene_types=GENE_TYPES):
+    """Every kept `gene` feature of the file, in file order, as (contig, gene_id, gene_name, start1, end1) with the line's own 1-based
+    inclusive coordinates: the genes longcallR-asj.py lists in its .gene_coverage.tsv (:870-878, anno_gene_regions' order).  Kept as in
+    load(): gene_type (else gene_biotype) in gene_types, no tag with "readthrough".  A gene_id seen twice keeps its first place and its
+    last line (a dict).  A gene without exons is listed (nobody is assigned to it); a gene that has exons only takes reads and is not."""
+    path = str(path)
+    if not path.endswith(SUFFIXES):
+        raise ValueError("unknown annotation file format (want .gtf, .gff3, .gtf.gz or .gff3.gz): %r" % path)
+    parse = _attrs_gff3 if ".gff3" in path else _attrs_gtf
+    gene_types = set(gene_types)
+    genes = {}
+    with (gzip.open if path.endswith(".gz") else open)(path, "rt") as f:
+        for line in f:
+            if line.startswith("#"):
+                continue
+            parts = line.strip().split("\t")
+            if len(parts) < 9 or parts[2] != "gene":
+                continue
+            a = parse(parts[8])
+            if a.get("gene_type", a.get("gene_biotype")) not in gene_types or "readthrough" in a.get("tag", ""):
+                continue
+            genes[a["gene_id"]] = (parts[0], a["gene_id"], a.get("gene_name", "."), int(parts[3]), int(parts[4]))
+    return list(genes.values())

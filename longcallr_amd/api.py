@@ -295,6 +295,29 @@ class Engine:
         self.last_junctions_genes_ms = float(o.kernel_ms)
         return _view(o.junc, _abi.JUNC_GENE_DTYPE, o.n_junctions), _view(o.junc_region_off, np.int32, o.n_regions + 1)
 
+    def asj_genes(self, genes, min_count=10, min_junctions=2, exons=False, dna_pos0=None, coverage=False, min_phase_score=None):
+        """lcr_asj_genes + lcr_get_asj_genes after phase() and assign_genes(genes): junctions_genes()'s table with the script's other modes
+        (include/lcr.h).  exons: the interior exon blocks of the participating rows kept by min_count (--cluster_with_exons; the junction
+        records do not change, asj.cluster takes the exons).  dna_pos0: the contig's heterozygous DNA SNV positions, 0-based, ascending and
+        unique (ase.dna_het_sites) -- rows whose phase set no PASS phased het candidate at one of them supports are not counted
+        (--dna_vcf / --rna_vcf); None = no filter, an empty array = nothing is supported.  coverage: reads per gene with more than
+        min_junctions junctions (.gene_coverage.tsv).  min_phase_score: the VCF writer's (default: the engine's params).
+        -> dict(junc, junc_region_off, exon (_abi.EXON_GENE_DTYPE), exon_region_off, gene_reads (int32 per gene, or None), kernel_ms),
+        copied.  With every option off junc / junc_region_off are junctions_genes()'s byte for byte."""
+        flags = (_abi.LCR_ASJ_EXONS if exons else 0) | (_abi.LCR_ASJ_DNA_FILTER if dna_pos0 is not None else 0) | (_abi.LCR_ASJ_COVERAGE if coverage else 0)
+        p = _abi.LcrAsjParams(int(min_count), int(min_junctions), flags, float(self.params.min_phase_score if min_phase_score is None else min_phase_score))
+        dna = None
+        if dna_pos0 is not None:
+            dna = np.ascontiguousarray(dna_pos0, dtype=np.int64)
+            p.n_dna, p.dna_pos0 = int(dna.size), (dna.ctypes.data if dna.size else None)
+        a, keep = self._annotation(genes)
+        self._chk(self.lib.lcr_asj_genes(self.h, C.byref(p), _abi.LCR_MEM_HOST, C.byref(a)), "lcr_asj_genes")   # (host arrays are copied before the call returns)
+        o = _abi.LcrAsjGeneList()
+        self._chk(self.lib.lcr_get_asj_genes(self.h, C.byref(o)), "lcr_get_asj_genes")
+        return {"junc": _view(o.junc, _abi.JUNC_GENE_DTYPE, o.n_junctions), "junc_region_off": _view(o.junc_region_off, np.int32, o.n_regions + 1),
+                "exon": _view(o.exon, _abi.EXON_GENE_DTYPE, o.n_exons), "exon_region_off": _view(o.exon_region_off, np.int32, o.n_regions + 1),
+                "gene_reads": _view(o.gene_reads, np.int32, o.n_genes) if o.gene_reads else None, "kernel_ms": float(o.kernel_ms)}
+
     def set_downsample(self, depth, seed=2025):
         """lcr_set_downsample: regions with at least `depth` fragment rows are phased on a sample of `depth` rows (longcallR --downsample /
         --downsample-depth; thread.rs:149 passes seed 2025).  Sticky; depth = 0 turns it off."""

@@ -15,14 +15,20 @@ HEADER = ("#Junction\tStrand\tJunction_set\tPhase_set\tHap1_absent\tHap1_present
           "P_value\tSOR\tNovel\tGT_AG\tGene_name")
 
 
-def cluster(junc):
+def cluster(junc, exons=None):
     """Connected components of the kept junctions (records of Engine.junctions(), any number of regions) where two junctions of a
     region are joined when they share s or share s + l (donor or acceptor).  Records of Engine.junctions_genes() are joined inside
-    their (region, gene) pair only: the script clusters the junctions of one gene's reads.  Returns an int array: for every junction
-    the index of its component's first junction in output order."""
+    their (region, gene) pair only: the script clusters the junctions of one gene's reads.  exons: the kept interior exon blocks of
+    Engine.asj_genes(exons=True) (--cluster_with_exons: cluster_junctions_exons_connected_components) -- an exon [a, b) is one more node
+    of its pair, joined to an exon that shares a or shares b and to a junction with s == b or s + l == a (the script's +-1 node trick
+    in half-open terms), so two junctions on either side of a kept exon fall into one component.  Returns an int array: for every
+    junction the index of its component's first junction in output order."""
     n = len(junc)
     gene = junc["gene"] if "gene" in (junc.dtype.names or ()) else None
-    parent = list(range(n))
+    m = 0 if exons is None else len(exons)
+    if m and gene is None:
+        raise ValueError("exon records belong to (region, gene) pairs: the junction records need a gene field")
+    parent = list(range(n + m))
 
     def find(x):
         while parent[x] != x:
@@ -39,6 +45,14 @@ def cluster(junc):
             a, b = find(i), find(j)
             if a != b:
                 parent[max(a, b)] = min(a, b)    # the root is the component's first junction
+    for e in range(m):   # an exon's nodes come behind the junctions': the root of a component with a junction stays a junction
+        g = (int(exons["region"][e]), int(exons["gene"][e]))
+        a0, b0 = int(exons["start0"][e]), int(exons["start0"][e]) + int(exons["len"][e])
+        for key in ((g, 0, b0), (g, 1, a0)):     # junctions that start at its end / end at its start; exons with the same end / start
+            j = seen.setdefault(key, n + e)
+            a, b = find(n + e), find(j)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
     return np.array([find(i) for i in range(n)], dtype=np.int64)
 
 
@@ -162,15 +176,17 @@ def merge_gene_junctions(records, return_index=False):
 def gene_events(tables, min_count=10):
     """The events the script writes, with their adjusted p-values.  tables: [(chrom, junc, genes)] -- per batch the contig's name, the
     records of Engine.junctions_genes() and the contig's annotation.ContigGenes (junc["gene"] indexes it); the batches of a contig follow
-    one another.  In the script's order of steps: Junction_set is the first junction (smallest s, then l) of the record's connected
+    one another; a table may carry the batch's exon records of Engine.asj_genes(exons=True) as a fourth element, which cluster() then
+    takes.  In the script's order of steps: Junction_set is the first junction (smallest s, then l) of the record's connected
     component inside its (region, gene) pair; the records of a contig are merged per gene (merge_gene_junctions); records without a
     phase set (n_phase_sets == 0: haplotype_event_test returns None) and those of genes that are not reported are dropped; of two
     genes with the same Gene_name and the same junction the later one replaces the earlier (the script's dict keyed by name); events
     whose table sums to less than min_count are dropped; P_value is max(Fisher, G-test), Benjamini-Hochberg adjusted over what is
     left.  -> a list of dicts in contig, gene, s, l order."""
     per_contig, order = {}, []
-    for chrom, junc, genes in tables:
-        comp = cluster(junc)
+    for table in tables:
+        chrom, junc, genes = table[:3]
+        comp = cluster(junc, table[3] if len(table) > 3 else None)
         first = np.zeros((len(junc), 2), dtype=np.int64)
         for i in range(len(junc)):
             first[i] = (int(junc["start0"][comp[i]]), int(junc["len"][comp[i]]))
@@ -237,3 +253,13 @@ def format_gene_tsv(tables, min_count=10, no_gtag=False, events=None):
         if name not in best or ev["p_adj"] < best[name][1]:
             best[name] = (ev["chrom"], ev["p_adj"], ev["sor"])
     return "".join([GENE_HEADER + "\n"] + ["%s\t%s\t%s\t%s\n" % ((name,) + v) for name, v in best.items()])
+
+
+COVERAGE_HEADER = "#Gene_name\tChr\tStart\tEnd\tNum_reads"
+
+
+def format_gene_coverage(rows):
+    """The script's .gene_coverage.tsv text (:870-878).  rows: [(gene_name, chrom, start1, end1, n_reads)] -- every `gene` feature of the
+    annotation in file order (annotation.gene_features) with the reads Engine.asj_genes(coverage=True) counted for it, 0 for a gene
+    nobody was assigned to."""
+    return "".join([COVERAGE_HEADER + "\n"] + ["%s\t%s\t%d\t%d\t%d\n" % (name, chrom, int(s), int(e), int(n)) for name, chrom, s, e, n in rows])

@@ -31,14 +31,6 @@ namespace {
 
 constexpr unsigned long long K9_EMPTY = ~0ull;   // no key (the fill of K6's table: l < 2^28 keeps every key below it)
 
-struct K9Row {            // a participating row; a pair's rows are contiguous, in read order (= by pos)
-  int32_t pos, rend;      // [pos, rend) on the contig
-  uint32_t ps;            // phase set, 0 = none
-  int32_t first, n;       // its junction keys are keys[first .. first + n), ascending
-  int32_t hap;            // 1 / 2, + 4 when the row is counted (it shares a base with a merged exon of the pair's gene)
-};
-static_assert(sizeof(K9Row) == 24, "K9Row is six words");
-
 struct K9Exons { const int32_t* exon_off; const int64_t *exon_start0, *exon_end0; };
 
 __device__ __forceinline__ uint32_t k9_hash(unsigned long long key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32); }

@@ -2,7 +2,8 @@
 // functions.  Private to lcr_api.hip (lifecycle, cache, fills, debug switches, phase entry, region discovery), lcr_batch.hip (binding and
 // upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns), lcr_calls.hip (candidate, import and fragment stages with their getters) and
 // lcr_junctions.hip (lcr_junctions, lcr_get_junctions), lcr_ase.hip (lcr_ase, lcr_get_ase) and lcr_genes.hip (lcr_assign_genes, lcr_get_read_genes,
-// lcr_ase_genes, lcr_get_ase_genes) and lcr_junctions_genes.hip (lcr_junctions_genes, lcr_get_junctions_genes).
+// lcr_ase_genes, lcr_get_ase_genes), lcr_junctions_genes.hip (lcr_junctions_genes, lcr_get_junctions_genes) and lcr_asj_genes.hip
+// (lcr_asj_genes, lcr_get_asj_genes).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -150,6 +151,20 @@ struct lcr_ctx {
   hipEvent_t ev_jgene_t[2] = {};              // timing enabled: first kernel to last of the last call (lcr_junction_gene_list.kernel_ms; no lcr_kernel_ms slot)
   bool jgene_timed = false;
 
+  // K10 (lcr_asj_genes): K9's sequence on buffers of its own plus the exon table, the DNA support and the gene coverage -- no other stage
+  // or getter reads them, K9's included
+  bool ajgene_valid = false;   // lcr_get_asj_genes: as jgene_valid
+  int32_t ajgene_n = 0, ajgene_ng = 0, ajgene_nx = 0, ajgene_n_genes = 0;
+  bool ajgene_cov = false;     // the last call counted gene_reads
+  DevBuf aj_span_s, aj_span_e, aj_exon_off, aj_exon_s, aj_exon_e, aj_dna;   // host annotation and DNA sites copied to HBM
+  DevBuf aj_part, aj_nocc, aj_part_off, aj_occ_off, aj_cnt, aj_pair_off, aj_read_pair, aj_row_slot, aj_pregion, aj_pgene, aj_prow0, aj_prows, aj_pocc;
+  DevBuf aj_tsz, aj_tbl_off, aj_rows, aj_keys, aj_tbl_key, aj_tbl_cnt, aj_flag, aj_koff, aj_ck, aj_cc, aj_cp, aj_off, aj_jpair, d_ajgene;
+  DevBuf aj_nblk, aj_blk_off, aj_pblk, aj_xtsz, aj_xtbl_off, aj_xtbl_key, aj_xtbl_cnt, aj_xflag, aj_xkoff, aj_xck, aj_xcc, aj_xcp, aj_xoff, d_ajexon;   // the exon table
+  DevBuf aj_sup, aj_sup_uniq, aj_sup_n, aj_cov;   // per candidate its supported phase set; per region the distinct ones and their number; reads per gene
+  HostBuf h_ajgene_ctl, h_ajgene, h_ajgene_off, h_ajexon, h_ajexon_off, h_ajcov, h_ajgene_bad;   // pinned: sizes ([0..3] K9's, [4..7] the same for blocks / exons); records; offsets; verdicts
+  hipEvent_t ev_ajgene = nullptr, ev_ajgene_t[2] = {};
+  bool ajgene_timed = false;
+
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
   std::vector<int64_t> rl_start0;
@@ -181,8 +196,8 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
   if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
   if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
-  if (to < ST_PHASED) c->jgene_valid = false;    // ... and the per-gene junction table
-  if (to < ST_LOADED) { c->genes_valid = false; c->agene_valid = false; c->jgene_valid = false; }   // read -> gene names the reads of ONE bound batch
+  if (to < ST_PHASED) { c->jgene_valid = false; c->ajgene_valid = false; }   // ... and the per-gene junction tables
+  if (to < ST_LOADED) { c->genes_valid = false; c->agene_valid = false; c->jgene_valid = false; c->ajgene_valid = false; }   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and

@@ -345,6 +345,13 @@ void launch_k8_export(const lcr_ase_gene* pairs, int32_t n, lcr_ase_gene* host_o
 struct K9Pairs {   // what k9_pairs<true> writes: per read its pair and row slot (n_reads each); per pair its region, gene, first row, rows and
   int32_t *read_pair, *row_slot, *region, *gene, *row0, *rows, *occ;   // junction occurrences (sized by n_reads, an upper bound of the pairs)
 };
+struct K9Row {            // a participating row; a pair's rows are contiguous, in read order (= by pos).  K10's DNA filter clears bit 2 of hap
+  int32_t pos, rend;      // [pos, rend) on the contig
+  uint32_t ps;            // phase set, 0 = none
+  int32_t first, n;       // its junction keys are keys[first .. first + n), ascending
+  int32_t hap;            // 1 / 2, + 4 when the row is counted (it shares a base with a merged exon of the pair's gene)
+};
+static_assert(sizeof(K9Row) == 24, "K9Row is six words");
 void launch_k9_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* gene, uint32_t min_junctions,
                      int32_t* part_flag, int32_t* nocc, hipStream_t s);
 void launch_k9_pair_count(const BatchView& b, const int32_t* gene, const int32_t* part_flag, int32_t* n_pairs /* n_regions */, hipStream_t s);
@@ -364,6 +371,22 @@ void launch_k9_place(const BatchView& b, const uint64_t* tbl_key, const uint32_t
                      int32_t* cp, lcr_junction_gene* junc, int32_t* junc_pair /* n_kept: the pair of every record */, hipStream_t s);
 void launch_k9_tables(const int32_t* junc_pair, const K9Pairs& pr, const void* rows, const uint64_t* keys, int32_t n_kept, lcr_junction_gene* junc,
                       lcr_junction_gene* host_junc /* pinned (device pointer) */, hipStream_t s);
+
+// k10_asj_modes.hip: interior exon blocks, DNA support and gene coverage beside K9's table (lcr_asj_genes)
+void launch_k10_dna_check(const int64_t* dna_pos0, int32_t n_dna, int32_t* bad /* zeroed */, hipStream_t s);
+void launch_k10_count(const BatchView& b, const int32_t* gene, const int32_t* part_flag, uint32_t min_junctions, int32_t* nblk /* n_reads, or nullptr */,
+                      int32_t* gene_reads /* n_genes, zeroed, or nullptr */, hipStream_t s);
+void launch_k10_pair_blocks(const BatchView& b, const int32_t* part_flag, const int32_t* nblk, const int32_t* read_pair, int32_t* pair_blk /* zeroed */,
+                            hipStream_t s);
+void launch_k10_emit(const BatchView& b, const int32_t* part_flag, const int32_t* nblk, const int32_t* read_pair, const int32_t* xtbl_off,
+                     uint64_t* xtbl_key /* 0xff-filled */, uint32_t* xtbl_cnt /* zeroed */, hipStream_t s);
+void launch_k10_place(const uint64_t* xtbl_key, const uint32_t* xtbl_cnt, const int32_t* flag, const int32_t* koff, const int32_t* xtbl_off,
+                      const int32_t* pair_off, const K9Pairs& pr, int32_t ng, int32_t n_slots, int32_t n_kept, uint64_t* ck, uint32_t* cc, int32_t* cp,
+                      lcr_exon_gene* exon, lcr_exon_gene* host_exon /* pinned (device pointer) */, hipStream_t s);
+void launch_k10_support(const lcr_candidate* cand, int32_t n_cand, const int32_t* cand_off, int32_t ng, double min_phase_score, const int64_t* dna_pos0,
+                        int32_t n_dna, uint32_t* sup /* n_cand */, uint32_t* sup_uniq /* n_cand */, int32_t* sup_n /* n_regions */, hipStream_t s);
+void launch_k10_filter(const BatchView& b, const int32_t* part_flag, const int32_t* row_slot, const int32_t* cand_off, const uint32_t* sup_uniq,
+                       const int32_t* sup_n, void* rows, hipStream_t s);
 
 // device helpers shared by kernels -------------------------------------------------------------
 #ifdef __HIPCC__

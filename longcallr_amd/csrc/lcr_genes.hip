@@ -52,6 +52,7 @@ int lcr_assign_genes(lcr_ctx* c, int32_t mem, const lcr_gene_annotation* a) {
   c->genes_valid = false;   // (from here on the last call's result is overwritten)
   c->agene_valid = false;   // (... and the pair records of lcr_ase_genes counted the rows of that assignment)
   c->jgene_valid = false;   // (... and so did the junction table of lcr_junctions_genes)
+  c->ajgene_valid = false;  // (... and the one of lcr_asj_genes)
   const size_t n1 = (size_t)std::max(nr, 1);
   HIPCHK(c, c->d_gene.reserve(n1 * 4)); HIPCHK(c, c->d_gene_ov.reserve(n1 * 4));
   HIPCHK(c, c->h_gene.reserve(n1 * 4)); HIPCHK(c, c->h_gene_ov.reserve(n1 * 4));

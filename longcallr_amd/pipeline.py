@@ -112,7 +112,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         asj_out=None, asj_min_count=10, asj_min_junctions=2,
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
-        **param_overrides):
+        asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -157,7 +157,17 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     lcr_junctions_genes); asj_out gets asj.format_tsv_genes' text with the annotation's Strand, Novel and Gene_name, and the script's
     .asj_gene.tsv goes beside it (X.asj.tsv -> X.asj_gene.tsv, any other name -> name + ".gene.tsv").  junctions stays the number of
     records; adds the stat asj_genes (rows of the gene file).  asj_annotation without asj_out is a ValueError; without asj_annotation
-    nothing changes."""
+    nothing changes.
+    asj_cluster_with_exons / asj_dna_vcf / asj_gene_coverage: the other modes of the script's annotated run (--cluster_with_exons,
+    --dna_vcf with the run's own VCF as --rna_vcf, the .gene_coverage.tsv); each needs asj_annotation (ValueError without it).  With
+    any of them on a chunk calls Engine.asj_genes in place of Engine.junctions_genes (include/lcr.h: lcr_asj_genes); with none on the
+    code path is the one above.  asj_cluster_with_exons: the kept interior exon blocks join the clustering (asj.cluster), which changes
+    Junction_set only.  asj_dna_vcf: a DNA VCF read with ase.dna_het_sites; every chunk gets its contig's heterozygous SNV positions
+    inside its span, and rows whose phase set none of them supports are not counted.  asj_gene_coverage: reads with more than
+    asj_min_junctions junctions per gene, summed over a contig's chunks and written for every `gene` feature of the annotation in file
+    order (annotation.gene_features) beside the table (X.asj.tsv -> X.gene_coverage.tsv, any other name -> name +
+    ".gene_coverage.tsv").  Adds the stats asj_exons (kept exon records, summed over chunks) and asj_coverage_genes (rows of the
+    coverage file)."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -177,6 +187,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         raise ValueError("ase_annotation needs ase_out")
     if asj_out is None and asj_annotation is not None:
         raise ValueError("asj_annotation needs asj_out")
+    asj_modes = bool(asj_cluster_with_exons) or asj_dna_vcf is not None or bool(asj_gene_coverage)
+    if asj_modes and asj_annotation is None:
+        raise ValueError("asj_cluster_with_exons / asj_dna_vcf / asj_gene_coverage need asj_annotation")
     if asj_annotation is not None and ase_annotation is not None and (
             os.path.abspath(str(asj_annotation)) != os.path.abspath(str(ase_annotation)) or tuple(asj_gene_types) != tuple(ase_gene_types)):
         raise ValueError("asj_annotation and ase_annotation must be the same file with the same gene types: a chunk has one gene assignment")
@@ -213,6 +226,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     jgenes = None                                                                                      # the same for the junction table
     if asj_annotation is not None:
         jgenes = genes if genes is not None else annotation.load(asj_annotation, asj_gene_types)
+    jdna = ase.dna_het_sites(asj_dna_vcf) if asj_dna_vcf is not None else None                   # {contig: pos0} for the junction table's filter
     no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
     # Every engine is a long-lived worker with the ASYNCHRONOUS phase stage (lcr_ctx_set_async_phase, include/lcr.h): a chunk is uploaded
@@ -239,7 +253,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["hp"] = np.where((fm["row_for_phasing"] != 0) | (asg != 0), asg, -1)
             out["ps"] = res["phase_set"].copy()
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
-        if junc is not None and jgenes is not None:
+        if junc is not None and asj_modes:      # Engine.asj_genes' dict
+            out["junc"] = (name, junc["junc"], jgenes.get(name, annotation.ContigGenes())) + ((junc["exon"],) if asj_cluster_with_exons else ())
+            out["asj_exons"], out["gene_reads"] = int(junc["exon"].size), junc["gene_reads"]
+        elif junc is not None and jgenes is not None:
             out["junc"] = (name, junc, jgenes.get(name, annotation.ContigGenes()))
         elif junc is not None:
             out["junc"] = (name, junc, batch.start0, batch.len)
@@ -281,7 +298,15 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 fm = dict(row_for_phasing=f["row_for_phasing"], row_read=f["row_read"])
             E.phase()
             junc = None
-            if asj_out is not None and jgenes is not None:
+            if asj_out is not None and asj_modes:
+                dpos = None
+                if jdna is not None:        # the contig's DNA sites inside the chunk's span (none when the VCF does not name the contig)
+                    dp = jdna.get(name, np.zeros(0, np.int64))
+                    lo, hi = np.searchsorted(dp, [int(batch.start0[0]), int(batch.start0[-1]) + int(batch.len[-1])])
+                    dpos = dp[lo:hi]
+                junc = E.asj_genes(jgenes.get(name), asj_min_count, asj_min_junctions, exons=bool(asj_cluster_with_exons), dna_pos0=dpos,
+                                   coverage=bool(asj_gene_coverage))                                       # (waits for the phase stage)
+            elif asj_out is not None and jgenes is not None:
                 junc = E.junctions_genes(jgenes.get(name), asj_min_count, asj_min_junctions)[0]           # (waits for the phase stage)
             elif asj_out is not None:
                 junc = E.junctions(asj_min_count, asj_min_junctions)[0]                                    # (waits for the phase stage)
@@ -356,6 +381,18 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             asj_out = str(asj_out)
             with open(asj_out[:-len(".asj.tsv")] + ".asj_gene.tsv" if asj_out.endswith(".asj.tsv") else asj_out + ".gene.tsv", "w") as f:
                 f.write(gene_text)
+            if asj_modes:
+                stats["asj_exons"] = sum(r["asj_exons"] for r in results)
+            if asj_gene_coverage:
+                cov = {}    # (contig, gene_id) -> reads, summed over the contig's chunks
+                for r in results:
+                    g = r["junc"][2]
+                    for k, n in enumerate(r["gene_reads"].tolist()):
+                        cov[(r["junc"][0], g.gene_id[k])] = cov.get((r["junc"][0], g.gene_id[k]), 0) + n
+                rows = [(gname, c, s1, e1, cov.get((c, gid), 0)) for c, gid, gname, s1, e1 in annotation.gene_features(asj_annotation, asj_gene_types)]
+                stats["asj_coverage_genes"] = len(rows)
+                with open(asj_out[:-len(".asj.tsv")] + ".gene_coverage.tsv" if asj_out.endswith(".asj.tsv") else asj_out + ".gene_coverage.tsv", "w") as f:
+                    f.write(asj.format_gene_coverage(rows))
         else:
             text = asj.format_tsv([r["junc"] for r in results], asj_min_count)
         with open(asj_out, "w") as f:

@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--asj-min-junctions", type=int, default=2, help="a read takes part with MORE junctions than this")
     ap.add_argument("--asj-annotation", help="GTF / GFF3 (.gz) annotation: the junction table gets one row per (gene, junction) and the .asj_gene.tsv is written beside it")
     ap.add_argument("--asj-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
+    ap.add_argument("--asj-cluster-with-exons", action="store_true", help="cluster junctions through the kept interior exons of the reads too (needs --asj-annotation)")
+    ap.add_argument("--asj-dna-vcf", help="DNA VCF: count only reads whose phase set holds a DNA-heterozygous site (needs --asj-annotation)")
+    ap.add_argument("--asj-gene-coverage", action="store_true", help="write the reads per gene beside the table (.gene_coverage.tsv; needs --asj-annotation)")
     ap.add_argument("--ase-out", help="write the allele-specific expression table (longcallR-ase.py's .ase.tsv; regions in place of genes)")
     ap.add_argument("--ase-min-support", type=int, default=10, help="assigned reads a region's phase set needs to be written")
     ap.add_argument("--ase-overdispersion", type=float, default=0.001, help="rho of the beta-binomial test")
@@ -57,6 +60,8 @@ def main():
         ap.error("--ase-annotation needs --ase-out")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
+    if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
+        ap.error("--asj-cluster-with-exons / --asj-dna-vcf / --asj-gene-coverage need --asj-annotation")
     extra = {} if a.read_assign_cutoff is None else dict(read_assign_cutoff=a.read_assign_cutoff)
     st = pipeline.run(a.bam, a.ref, a.out_vcf, a.out_bam, preset=a.preset, contigs=a.contigs.split(",") if a.contigs else None,
                       device=a.device, threads=a.threads, seed=a.seed, input_vcf=a.input_vcf,
@@ -66,7 +71,8 @@ def main():
                       ase_out=a.ase_out, ase_min_support=a.ase_min_support, ase_overdispersion=a.ase_overdispersion,
                       ase_parental_vcf=a.ase_parental_vcf, ase_dna_vcf=a.ase_dna_vcf,
                       ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t),
-                      asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t), **extra)
+                      asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
+                      asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage, **extra)
     print(json.dumps(st))
 
 
