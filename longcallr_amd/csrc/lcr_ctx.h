@@ -3,7 +3,8 @@
 // upload), lcr_pileup.hip (lcr_pileup, lcr_get_columns), lcr_calls.hip (candidate, import and fragment stages with their getters) and
 // lcr_junctions.hip (lcr_junctions, lcr_get_junctions), lcr_ase.hip (lcr_ase, lcr_get_ase) and lcr_genes.hip (lcr_assign_genes, lcr_get_read_genes,
 // lcr_ase_genes, lcr_get_ase_genes), lcr_junctions_genes.hip (lcr_junctions_genes, lcr_get_junctions_genes) and lcr_asj_genes.hip
-// (lcr_asj_genes, lcr_get_asj_genes).
+// (lcr_asj_genes, lcr_get_asj_genes).  The last two fill one struct each, GeneJunctions, by the same steps (declared at the end), and the
+// three calls that take a gene annotation share its upload and verdict (annotation_queue, annotation_verdict).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -14,6 +15,50 @@
 // How far the bound batch has come.  Every driver asks for the stage it reads (stage >= X) and moves the value with rewind_to() /
 // by assignment at its successful end: nothing else says which buffers hold what.
 enum Stage { ST_NONE, ST_LOADED, ST_PILED, ST_CALLED, ST_FRAGGED, ST_PHASED };
+
+// A gene annotation's five arrays in HBM: where a call copies a host annotation (annotation_queue)
+struct AnnotationCopy { DevBuf span_s, span_e, exon_off, exon_s, exon_e; };
+
+// A hash table over the (region, gene) pairs' segments and what becomes of its slots: flagged, counted per region, placed in order.  Three
+// of them: K9's junctions, K10's junctions, K10's interior exon blocks.
+struct SlotTable {
+  int32_t n_slots = 0;                    // of the last fill (slot_table_clear)
+  DevBuf tbl_key, tbl_cnt, flag, koff;    // key and count per slot (0xff / 0: empty); kept && n_reads >= min_count; the flags' running sum
+  DevBuf ck, cc, cp;                      // the kept slots of a region as the place kernel orders them: key, count, pair
+  DevBuf off;                             // kept slots in front of every region (n_regions + 1)
+};
+
+// The per-gene junction table of one call (lcr_junctions_genes.hip: the gj_* steps).  The context holds two, lcr_junctions_genes' and
+// lcr_asj_genes', so each call keeps its table across the other's.
+struct GeneJunctions {
+  bool valid = false;    // the getter: the last call's table belongs to the phase results and the gene assignment of the bound batch (rewind_to)
+  bool timed = false;    // ev_t brackets the last call's kernels
+  int32_t n = 0, ng = 0;
+  AnnotationCopy ann;
+  DevBuf part, nocc, part_off, occ_off, cnt, pair_off, read_pair, row_slot, pregion, pgene, prow0, prows, pocc, tsz, tbl_off, rows, keys, jpair;
+  SlotTable t;
+  DevBuf d_junc;
+  HostBuf h_junc, h_off;   // pinned: the records; their offsets per region
+  HostBuf h_ctl;           // pinned sizes: [0] participating rows, [1] occurrences, [2] kept junctions, [3] pairs; K10: [4..7] the same for blocks / exons
+  HostBuf h_bad;           // pinned verdicts: [0] the annotation's; K10: [1] the DNA sites'
+  int32_t *d_off = nullptr, *d_ctl = nullptr;   // h_off and h_ctl as the device sees them (gj_begin)
+  hipEvent_t ev = nullptr;      // behind the verdict's kernels, the two size waits, then the call's last kernel
+  hipEvent_t ev_t[2] = {};      // timing enabled: first kernel to last of the last call (the list's kernel_ms; no lcr_kernel_ms slot)
+  K9Pairs pairs() const {
+    return {read_pair.as<int32_t>(), row_slot.as<int32_t>(), pregion.as<int32_t>(), pgene.as<int32_t>(), prow0.as<int32_t>(), prows.as<int32_t>(), pocc.as<int32_t>()};
+  }
+};
+
+// What lcr_asj_genes has beside its GeneJunctions: the exon table, the DNA support, the gene coverage
+struct AsjModes {
+  int32_t nx = 0, n_genes = 0;   // exon records; genes of the annotation (gene_reads' length)
+  bool cov = false;              // the last call counted gene_reads
+  DevBuf dna;                    // host DNA sites copied to HBM
+  DevBuf nblk, blk_off, pblk, xtsz, xtbl_off, d_exon;   // interior blocks per read, their running sum, per pair; the exon table's segments; the records
+  SlotTable x;
+  DevBuf sup, sup_uniq, sup_n, cov_n;   // per candidate its supported phase set; per region the distinct ones and their number; reads per gene
+  HostBuf h_exon, h_xoff, h_cov;        // pinned: the exon records; their offsets per region; reads per gene
+};
 
 struct lcr_ctx {
   int device = 0;
@@ -131,7 +176,8 @@ struct lcr_ctx {
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
-  DevBuf g_span_s, g_span_e, g_exon_off, g_exon_s, g_exon_e, g_pmax, d_gene, d_gene_ov;   // host annotation copied to HBM; running maximum of the spans' ends; the result
+  AnnotationCopy g_ann;
+  DevBuf g_pmax, d_gene, d_gene_ov;        // running maximum of the spans' ends; the result
   HostBuf h_gene, h_gene_ov, h_gene_bad;   // pinned: the result; the verdict on the annotation
   hipEvent_t ev_genes = nullptr;           // behind the annotation's check, then behind the copies of the result
   bool agene_valid = false;  // lcr_get_ase_genes: the last lcr_ase_genes' records belong to the phase results and the gene assignment of the bound batch
@@ -140,30 +186,10 @@ struct lcr_ctx {
   HostBuf h_agene, h_agene_off, h_agene_ctl, h_agene_bad;   // pinned: the records; their offsets per region; the number of pairs; the verdict on the parental sites
   hipEvent_t ev_agene = nullptr;
 
-  // K9 (lcr_junctions_genes): scratch and results of its own -- no other stage or getter reads them
-  bool jgene_valid = false;  // lcr_get_junctions_genes: the last call's table belongs to the phase results and the gene assignment of the bound batch
-  int32_t jgene_n = 0, jgene_ng = 0;
-  DevBuf jg_span_s, jg_span_e, jg_exon_off, jg_exon_s, jg_exon_e;   // host annotation copied to HBM
-  DevBuf jg_part, jg_nocc, jg_part_off, jg_occ_off, jg_cnt, jg_pair_off, jg_read_pair, jg_row_slot, jg_pregion, jg_pgene, jg_prow0, jg_prows, jg_pocc;
-  DevBuf jg_tsz, jg_tbl_off, jg_rows, jg_keys, jg_tbl_key, jg_tbl_cnt, jg_flag, jg_koff, jg_ck, jg_cc, jg_cp, jg_off, jg_jpair, d_jgene;
-  HostBuf h_jgene_ctl, h_jgene, h_jgene_off, h_jgene_bad;   // pinned: {participating rows, occurrences, kept junctions, pairs}; the records; their offsets per region; the annotation's verdict
-  hipEvent_t ev_jgene = nullptr;              // behind the annotation's check, the two size waits, then the call's last kernel
-  hipEvent_t ev_jgene_t[2] = {};              // timing enabled: first kernel to last of the last call (lcr_junction_gene_list.kernel_ms; no lcr_kernel_ms slot)
-  bool jgene_timed = false;
-
-  // K10 (lcr_asj_genes): K9's sequence on buffers of its own plus the exon table, the DNA support and the gene coverage -- no other stage
-  // or getter reads them, K9's included
-  bool ajgene_valid = false;   // lcr_get_asj_genes: as jgene_valid
-  int32_t ajgene_n = 0, ajgene_ng = 0, ajgene_nx = 0, ajgene_n_genes = 0;
-  bool ajgene_cov = false;     // the last call counted gene_reads
-  DevBuf aj_span_s, aj_span_e, aj_exon_off, aj_exon_s, aj_exon_e, aj_dna;   // host annotation and DNA sites copied to HBM
-  DevBuf aj_part, aj_nocc, aj_part_off, aj_occ_off, aj_cnt, aj_pair_off, aj_read_pair, aj_row_slot, aj_pregion, aj_pgene, aj_prow0, aj_prows, aj_pocc;
-  DevBuf aj_tsz, aj_tbl_off, aj_rows, aj_keys, aj_tbl_key, aj_tbl_cnt, aj_flag, aj_koff, aj_ck, aj_cc, aj_cp, aj_off, aj_jpair, d_ajgene;
-  DevBuf aj_nblk, aj_blk_off, aj_pblk, aj_xtsz, aj_xtbl_off, aj_xtbl_key, aj_xtbl_cnt, aj_xflag, aj_xkoff, aj_xck, aj_xcc, aj_xcp, aj_xoff, d_ajexon;   // the exon table
-  DevBuf aj_sup, aj_sup_uniq, aj_sup_n, aj_cov;   // per candidate its supported phase set; per region the distinct ones and their number; reads per gene
-  HostBuf h_ajgene_ctl, h_ajgene, h_ajgene_off, h_ajexon, h_ajexon_off, h_ajcov, h_ajgene_bad;   // pinned: sizes ([0..3] K9's, [4..7] the same for blocks / exons); records; offsets; verdicts
-  hipEvent_t ev_ajgene = nullptr, ev_ajgene_t[2] = {};
-  bool ajgene_timed = false;
+  // K9 (lcr_junctions_genes) and K10 (lcr_asj_genes): one per-gene junction table each (GeneJunctions: the same steps fill both), and beside
+  // K10's what its other modes add (AsjModes) -- scratch and results of their own, no other stage or getter reads them, each other's included
+  GeneJunctions jgene, ajgene;
+  AsjModes asj;
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
@@ -196,8 +222,8 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
   if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
   if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
-  if (to < ST_PHASED) { c->jgene_valid = false; c->ajgene_valid = false; }   // ... and the per-gene junction tables
-  if (to < ST_LOADED) { c->genes_valid = false; c->agene_valid = false; c->jgene_valid = false; c->ajgene_valid = false; }   // read -> gene names the reads of ONE bound batch
+  if (to < ST_PHASED) c->jgene.valid = c->ajgene.valid = false;   // ... and the per-gene junction tables
+  if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and
@@ -240,3 +266,51 @@ int upload(lcr_ctx* c, DevBuf& buf, const T* src, size_t n, const T** dst, int m
 inline int phase_settle(lcr_ctx* c) { return c->phase.settle(&c->err); }
 int cand_settle(lcr_ctx* c);   // the candidate stage's host copies (lcr_calls.hip)
 int frag_settle(lcr_ctx* c);   // lcr_fragments' entry count (lcr_calls.hip)
+
+// A host wait on the context's stream: what the kernels queued so far left in pinned memory is the host's to read
+inline int stream_wait(lcr_ctx* c, hipEvent_t ev) {
+  HIPCHK(c, hipEventRecord(ev, c->stream));
+  HIPCHK(c, hipEventSynchronize(ev));
+  HIPCHK(c, hipGetLastError());
+  return LCR_OK;
+}
+
+// A gene annotation on its way to the kernels (lcr_genes.hip; lcr_assign_genes, lcr_junctions_genes, lcr_asj_genes).  annotation_queue:
+// copied (host) or read in place (device) -> *d, and k8_check queued on it into word 0 of the pinned verdict block, whose two words are
+// zeroed here (-> *d_bad, the block as the device sees it; no kernel for an annotation without genes).  The caller queues what else
+// belongs in front of the wait, then annotation_verdict: the wait on `ev`, and LCR_E_ARG with `fn`'s name in the text when word 0 is set.
+int annotation_queue(lcr_ctx* c, AnnotationCopy& to, const lcr_gene_annotation* a, int32_t mem, HostBuf& h_bad, lcr_gene_annotation* d, int32_t** d_bad);
+int annotation_verdict(lcr_ctx* c, const HostBuf& h_bad, hipEvent_t ev, const char* fn);
+
+// The steps that fill a GeneJunctions, in the order of their launches (lcr_junctions_genes.hip).  lcr_junctions_genes is these and nothing
+// else; lcr_asj_genes queues K10's kernels between them.  The host waits twice in between: gj_wait_counts and a stream_wait.
+struct Bracket {   // HIP events around a call's kernels when timing is on: not a slot of lcr_kernel_ms (include/lcr.h)
+  lcr_ctx* c; GeneJunctions& g;
+  Bracket(lcr_ctx* c_, GeneJunctions& g_) : c(c_), g(g_) { if (c->timing) (void)hipEventRecord(g.ev_t[0], c->stream); }
+  ~Bracket() { if (c->timing) { (void)hipEventRecord(g.ev_t[1], c->stream); g.timed = true; } }
+};
+int gj_begin(lcr_ctx* c, GeneJunctions& g);   // from here on the last table is overwritten: valid = false, the pinned blocks reserved and quiet, h_ctl zeroed
+int gj_counts(lcr_ctx* c, GeneJunctions& g, uint32_t min_junctions);   // junctions per read, participating reads, the pairs, their table segments -> h_ctl[0], [1], [3]
+int gj_wait_counts(lcr_ctx* c, GeneJunctions& g, const char* fn, bool* empty);   // the first wait -> no participating row or no occurrence; LCR_E_ARG beyond 2^28 of them
+int slot_table_clear(lcr_ctx* c, SlotTable& t, int32_t n_slots);       // reserved for n_slots and emptied
+int gj_rows(lcr_ctx* c, GeneJunctions& g, const lcr_gene_annotation& d);   // row records, keys, the table: 4 x all occurrences bound its slots without a third wait
+int gj_keep(lcr_ctx* c, SlotTable& t, const int32_t* pair_off, const int32_t* tbl_off, uint32_t min_count, int32_t* d_hoff, int32_t* d_ctl);   // -> pinned offsets, d_ctl[2]
+int gj_tables(lcr_ctx* c, GeneJunctions& g, int32_t n_kept);           // order, motif, tables: the records go to HBM and to pinned host memory
+void no_records(const HostBuf& h_off, int32_t ng, int32_t* n);         // a table without a record: every region's offset and *n are 0
+int gj_finish(lcr_ctx* c, GeneJunctions& g);                           // the event the getter waits for; valid
+template <class List>   // lcr_junction_gene_list, lcr_asj_gene_list: the getter's wait, the fields both lists have, kernel_ms
+int gj_get(lcr_ctx* c, GeneJunctions& g, List* out) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(g.ev));
+  HIPCHK(c, hipGetLastError());
+  out->n_regions = g.ng; out->n_junctions = g.n;
+  out->junc = g.n ? g.h_junc.as<lcr_junction_gene>() : nullptr;
+  out->junc_region_off = g.h_off.as<int32_t>();
+  out->dev_junc = g.n ? g.d_junc.as<lcr_junction_gene>() : nullptr;
+  out->kernel_ms = -1.f;
+  if (c->timing && g.timed) {
+    HIPCHK(c, hipEventSynchronize(g.ev_t[1]));
+    HIPCHK(c, hipEventElapsedTime(&out->kernel_ms, g.ev_t[0], g.ev_t[1]));
+  }
+  return LCR_OK;
+}

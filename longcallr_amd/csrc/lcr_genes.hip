@@ -1,58 +1,61 @@
 // lcr_genes.hip — the host driver of K8 (k8_genes.hip): read -> gene over the bound batch (lcr_assign_genes, lcr_get_read_genes) and the
 // per-gene form of K7's counts on top of it (lcr_ase_genes, lcr_get_ase_genes).  lcr_assign_genes reads the bound batch's positions and
 // CIGARs only, at any stage, and does not move the stage; lcr_ase_genes is shaped like lcr_ase and reads what it reads plus the gene of
-// every read.  Both write buffers no other stage or getter reads (lcr_ctx: g_*, d_gene*, h_gene*; ag_*, d_agene, h_agene*).
+// every read.  Both write buffers no other stage or getter reads (lcr_ctx: g_ann, g_pmax, d_gene*, h_gene*; ag_*, d_agene, h_agene*).
+// annotation_queue / annotation_verdict (lcr_ctx.h): the upload and check of an annotation, for every call that takes one.
 #include "lcr_ctx.h"
+#include "lcr_asj_args.h"
+
+int annotation_queue(lcr_ctx* c, AnnotationCopy& to, const lcr_gene_annotation* a, int32_t mem, HostBuf& h_bad, lcr_gene_annotation* d, int32_t** d_bad) {
+  *d = lcr_gene_annotation{};
+  d->n_genes = a->n_genes; d->n_exons = a->n_exons;
+  HIPCHK(c, h_bad.reserve(64));
+  h_bad.as<int32_t>()[0] = h_bad.as<int32_t>()[1] = 0;
+  HIPCHK(c, h_bad.dev(d_bad));
+  if (a->n_genes == 0) return LCR_OK;
+  const size_t n = (size_t)a->n_genes, nx = (size_t)a->n_exons;
+  { int rc = upload(c, to.span_s, a->span_start0, n, &d->span_start0, mem); if (rc) return rc; }
+  { int rc = upload(c, to.span_e, a->span_end0, n, &d->span_end0, mem); if (rc) return rc; }
+  { int rc = upload(c, to.exon_off, a->exon_off, n + 1, &d->exon_off, mem); if (rc) return rc; }
+  { int rc = upload(c, to.exon_s, a->exon_start0, nx, &d->exon_start0, mem); if (rc) return rc; }
+  { int rc = upload(c, to.exon_e, a->exon_end0, nx, &d->exon_end0, mem); if (rc) return rc; }
+  launch_k8_check(*d, *d_bad, c->stream);
+  return LCR_OK;
+}
+
+int annotation_verdict(lcr_ctx* c, const HostBuf& h_bad, hipEvent_t ev, const char* fn) {
+  { int rc = stream_wait(c, ev); if (rc) return rc; }
+  if (!*(volatile int32_t*)h_bad.p) return LCR_OK;
+  c->err = std::string(fn) + ": genes must be sorted by (span_start0, span_end0), every gene needs exons that are ascending and disjoint, "
+           "the first one starting at its span_start0 and the last one ending at its span_end0, and exon_off must run from 0 to n_exons";
+  return LCR_E_ARG;
+}
 
 extern "C" {
 
 int lcr_assign_genes(lcr_ctx* c, int32_t mem, const lcr_gene_annotation* a) {
   if (!c) return LCR_E_ARG;
-  if (!a || (mem != LCR_MEM_HOST && mem != LCR_MEM_DEVICE) || a->n_genes < 0 || a->n_exons < 0) {
-    c->err = "lcr_assign_genes: null annotation, a negative size or mem not LCR_MEM_HOST / LCR_MEM_DEVICE";
-    return LCR_E_ARG;
-  }
-  if (a->n_genes > 0 && (!a->span_start0 || !a->span_end0 || !a->exon_off || !a->exon_start0 || !a->exon_end0 || a->n_exons < a->n_genes)) {
-    c->err = "lcr_assign_genes: null annotation array, or fewer exons than genes";
-    return LCR_E_ARG;
-  }
+  if (!lcr_annotation_sizes_ok(mem, a)) { c->err = "lcr_assign_genes: null annotation" LCR_ANNOTATION_SIZES_MSG; return LCR_E_ARG; }
+  if (!lcr_annotation_arrays_ok(a)) { c->err = "lcr_assign_genes" LCR_ANNOTATION_ARRAYS_MSG; return LCR_E_ARG; }
   if (c->stage < ST_LOADED) { c->err = "lcr_assign_genes before lcr_load_batch / lcr_bind_batch"; return LCR_E_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   const BatchView& b = c->bv;
   const int nr = b.n_reads, n_genes = a->n_genes;
   hipStream_t s = c->stream;
   // the annotation: copied (host) or read in place (device), then checked by a kernel -- the call's one host wait.  Nothing of the last
-  // call's result is touched before the verdict: a refused call changes nothing (the g_* copies of the last annotation are overwritten in
+  // call's result is touched before the verdict: a refused call changes nothing (the copies of the last annotation are overwritten in
   // front of it: nothing reads them once that call's k8_assign has run, and the stream orders the uploads behind it).
   lcr_gene_annotation d{};
-  d.n_genes = n_genes; d.n_exons = a->n_exons;
+  int32_t* d_bad = nullptr;
+  if (n_genes > 0) HIPCHK(c, c->g_pmax.reserve((size_t)n_genes * 8));
+  { int rc = annotation_queue(c, c->g_ann, a, mem, c->h_gene_bad, &d, &d_bad); if (rc) return rc; }
   if (n_genes > 0) {
-    { int rc = upload(c, c->g_span_s, a->span_start0, (size_t)n_genes, &d.span_start0, mem); if (rc) return rc; }
-    { int rc = upload(c, c->g_span_e, a->span_end0, (size_t)n_genes, &d.span_end0, mem); if (rc) return rc; }
-    { int rc = upload(c, c->g_exon_off, a->exon_off, (size_t)n_genes + 1, &d.exon_off, mem); if (rc) return rc; }
-    { int rc = upload(c, c->g_exon_s, a->exon_start0, (size_t)a->n_exons, &d.exon_start0, mem); if (rc) return rc; }
-    { int rc = upload(c, c->g_exon_e, a->exon_end0, (size_t)a->n_exons, &d.exon_end0, mem); if (rc) return rc; }
-    HIPCHK(c, c->g_pmax.reserve((size_t)n_genes * 8));
-    HIPCHK(c, c->h_gene_bad.reserve(64));
-    int32_t* bad = c->h_gene_bad.as<int32_t>();
-    *bad = 0;
-    int32_t* d_bad = nullptr;
-    HIPCHK(c, c->h_gene_bad.dev(&d_bad));
-    launch_k8_check(d, d_bad, s);
     launch_k8_prefix_max(d, c->g_pmax.as<int64_t>(), s);   // (gene-scale, built beside the check: the upload's part of the work)
-    HIPCHK(c, hipEventRecord(c->ev_genes, s));
-    HIPCHK(c, hipEventSynchronize(c->ev_genes));
-    HIPCHK(c, hipGetLastError());
-    if (*(volatile int32_t*)bad) {
-      c->err = "lcr_assign_genes: genes must be sorted by (span_start0, span_end0), every gene needs exons that are ascending and disjoint, "
-               "the first one starting at its span_start0 and the last one ending at its span_end0, and exon_off must run from 0 to n_exons";
-      return LCR_E_ARG;
-    }
+    { int rc = annotation_verdict(c, c->h_gene_bad, c->ev_genes, "lcr_assign_genes"); if (rc) return rc; }
   }
   c->genes_valid = false;   // (from here on the last call's result is overwritten)
   c->agene_valid = false;   // (... and the pair records of lcr_ase_genes counted the rows of that assignment)
-  c->jgene_valid = false;   // (... and so did the junction table of lcr_junctions_genes)
-  c->ajgene_valid = false;  // (... and the one of lcr_asj_genes)
+  c->jgene.valid = c->ajgene.valid = false;   // (... and so did the junction tables of lcr_junctions_genes and lcr_asj_genes)
   const size_t n1 = (size_t)std::max(nr, 1);
   HIPCHK(c, c->d_gene.reserve(n1 * 4)); HIPCHK(c, c->d_gene_ov.reserve(n1 * 4));
   HIPCHK(c, c->h_gene.reserve(n1 * 4)); HIPCHK(c, c->h_gene_ov.reserve(n1 * 4));

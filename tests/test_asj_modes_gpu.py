@@ -1,7 +1,7 @@
 """K10 lcr_asj_genes on the GPU against the plain-Python restatement of its contract (tests/asj_modes_ref.py), fed with the GPU's own
 phasing results, candidates and gene map: flags 0 against lcr_junctions_genes byte for byte, the rules of a read's blocks, the carry
 across rounds of sixteen ops, a retained intron, the DNA filter on two unlinked phase sets, the coverage count, all three flags on
-synthetic ONT cDNA and demo.bam, and the call's order and re-entry on one context.  Hand-built regions as in test_asj_genes_gpu (an
+synthetic ONT cDNA and demo.bam, the call's order and re-entry on one context, and both calls' empty exits between full calls.  Hand-built regions as in test_asj_genes_gpu (an
 anchor exon [0, 600) with five het sites, parameters (4, 1))."""
 import ctypes as C
 import re
@@ -291,6 +291,46 @@ def test_call_order_and_reentry(engine_cls):
     assert call() == 0 and lib.lcr_get_asj_genes(E.h, C.byref(ol)) == 0
     E.load_batch(b1)
     assert lib.lcr_get_asj_genes(E.h, C.byref(ol)) == -4
+    E.close()
+
+
+def test_empty_exits_between_full_calls(engine_cls):
+    """both calls leave through their empty exits -- no participating row (min_junctions 1000: in front of the row records), no kept slot
+    (min_count 1000: behind the second wait) -- between two full calls on one context, every call against the restatements"""
+    regs, genes, _ = tg.edge_case()
+    b = tj.batch_of(regs[:2])
+    E = hifi(engine_cls)
+    zeros = [0] * (len(regs[:2]) + 1)
+    # lcr_junctions_genes
+    k1 = tg.check(E, b, genes, 4, 1)
+    assert k1[0].size > 0
+    for mc, mj in ((4, 1000), (1000, 1)):
+        got, off = tg.check(E, b, genes, mc, mj, rerun=False)[:2]
+        jl = _abi.LcrJunctionGeneList()
+        assert E.lib.lcr_get_junctions_genes(E.h, C.byref(jl)) == 0 and jl.n_junctions == 0 and jl.n_regions == 2
+        assert got.size == 0 and off.tolist() == zeros
+    k4 = tg.check(E, b, genes, 4, 1, rerun=False)
+    assert k4[0].tobytes() == k1[0].tobytes() and k4[1].tobytes() == k1[1].tobytes()
+    # lcr_asj_genes with the exon table and the coverage
+    kw = dict(exons=True, coverage=True, rerun=False)
+    a1, res = check(E, b, genes, 4, 1, **kw)
+    assert a1["junc"].size > 0 and a1["exon"].size > 0
+    want_cov = numpy_coverage(b, res["gene"], len(genes.gene_id), 1)
+    for mc, mj, cov in ((4, 1000, [0] * len(genes.gene_id)), (1000, 1, want_cov)):
+        got, _ = check(E, b, genes, mc, mj, **kw)
+        ol = _abi.LcrAsjGeneList()
+        assert E.lib.lcr_get_asj_genes(E.h, C.byref(ol)) == 0 and ol.n_junctions == 0 and ol.n_exons == 0 and ol.n_regions == 2
+        assert got["junc"].size == 0 and got["exon"].size == 0
+        assert got["junc_region_off"].tolist() == zeros and got["exon_region_off"].tolist() == zeros
+        assert got["gene_reads"].tolist() == cov
+    assert sum(want_cov) > 0
+    a4, _ = check(E, b, genes, 4, 1, **kw)
+    for f in ("junc", "junc_region_off", "exon", "exon_region_off", "gene_reads"):
+        assert a4[f].tobytes() == a1[f].tobytes(), f
+    # lcr_junctions_genes' table from before the four lcr_asj_genes calls
+    jl = _abi.LcrJunctionGeneList()
+    assert E.lib.lcr_get_junctions_genes(E.h, C.byref(jl)) == 0 and tg.helpers_view(jl).tobytes() == k1[0].tobytes()
+    assert bytes((C.c_int32 * (jl.n_regions + 1)).from_address(jl.junc_region_off)) == k1[1].tobytes()
     E.close()
 
 
