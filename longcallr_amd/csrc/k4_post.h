@@ -448,14 +448,15 @@ __device__ void post_run(SC& sc, const PostIn& in, const PostLut& lut, PostView<
       parent[i] = node ? i : -1;
     }
     sc.sync();
-    // The reference adds an edge for every pair (x < y) among the first 64 PASS-het entries of a row whose alleles
-    // agree with the haplotypes: hap[x] * hap[y] == (alleles differ ? -1 : 1), i.e. hap[x] * allele[x] == hap[y] *
-    // allele[y].  So a row's entries fall into two classes by the sign of hap * allele and every class is a clique:
-    // the components (all that is used of the graph) are those of "class members joined to their class", O(n) per
-    // row instead of O(n^2).  for_classes visits the members of both classes and returns the number of valid entries.
+    // The reference adds an edge for every pair (x < y) among ALL the PASS-het entries of a row (snpfrags.rs:639-695
+    // walks the whole frag.list, and so do both oracles) whose alleles agree with the haplotypes: hap[x] * hap[y] ==
+    // (alleles differ ? -1 : 1), i.e. hap[x] * allele[x] == hap[y] * allele[y].  So a row's entries fall into two
+    // classes by the sign of hap * allele and every class is a clique: the components (all that is used of the graph)
+    // are those of "class members joined to their class", O(n) per row instead of O(n^2).  for_classes visits the
+    // members of both classes and returns the number of valid entries.
     auto for_classes = [&](int r, auto fn) -> int {
       int n = 0;
-      for (int e = rptr[r]; e < (int)rptr[r + 1] && n < 64; e++) {
+      for (int e = rptr[r]; e < (int)rptr[r + 1]; e++) {
         const int x = ecol[e];
         if (parent[x] < 0) continue;
         const int c = shap[x] * ((ev[e] & 32) ? -1 : 1);

@@ -732,16 +732,17 @@ class Graph:
         return order
 
 
-def run_region(batch, g, prm, cands):
+def run_region(batch, g, prm, cands, frag_cls=None):
     """thread.rs:136-201 for region g.  cands: the candidate records of the region as of get_candidate_snps (the
     candidate half is pinned separately, tests/test_oracle_np.py), e.g. orc.Region(...).candidates().cands().
+    frag_cls: a subclass of SNPFrag that observes the steps (tests/post_phase_cases.py counts the branches they take).
     Returns the SNPFrag after the post-phase steps and the read -> phase set map."""
     F = dict(edit=1, dense=2, het=4, fp=8, hom=16, single=32, nonsel=64, som=128)
     snps = [Snp(int(c["pos"]), chr(c["ref_base"]), (chr(c["allele1"]), chr(c["allele2"])), (float(c["af1"]), float(c["af2"])),
                 int(c["variant_type"]), int(c["genotype"]), bool(c["flags"] & F["edit"]), bool(c["flags"] & F["dense"]),
                 bool(c["flags"] & F["fp"]), bool(c["flags"] & F["hom"]), bool(c["flags"] & F["som"]), float(c["phase_score"]))
             for c in cands]
-    sf = SNPFrag(snps, int(prm.min_linkers), int(prm.seed), int(batch.start0[g]))
+    sf = (frag_cls or SNPFrag)(snps, int(prm.min_linkers), int(prm.seed), int(batch.start0[g]))
     sf.get_fragments(batch, g)
     sf.fragmat_snapshot = [(f.read, [(fe.snp_idx, fe.base, fe.baseq, fe.p) for fe in f.list], f.num_hete_links, f.for_phasing)
                            for f in sf.fragments]
