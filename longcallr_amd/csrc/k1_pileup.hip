@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k0_pack(BatchView b, ReadBin* __res
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= b.n_reads) return;
   const int g = region_of_read(b, r);
-  // precondition of k3_rows / lcr_fragments (binary searches on pos): a region's reads are sorted by position
+  // precondition of k3_rows_offsets / lcr_fragments (binary searches on pos): a region's reads are sorted by position
   if (r > b.read_begin[g] && b.pos[r] < b.pos[r - 1]) *order_flag = 1;
   ReadBin h;
   h.rel_pos = (int32_t)((int64_t)b.pos[r] - b.start0[g]);
@@ -149,7 +149,7 @@ void launch_k0_pack(const BatchView& b, ReadBin* out, int32_t* order_flag, hipSt
 //   k0_bind_a  (before the host's one wait) block 0: the region table -- first tile of every region, the four small region arrays
 //              into pinned host memory --, blocks >= 1: the layout check of the flat op space (k0_cig_check's three verdicts);
 //   k0_bind_b  (behind it) a thread per read: region of the read (binary search in read_begin: a region's reads are a range),
-//              read -> region table, the 64-byte header K0 reads (ReadBin), the order check of k3_rows' precondition, the op blocks'
+//              read -> region table, the 64-byte header K0 reads (ReadBin), the order check of k3_rows_offsets' precondition, the op blocks'
 //              first reads; the threads behind the reads fill the tile tables the same way (binary search in first_tile).
 __global__ void __launch_bounds__(1024) k0_bind_a(const int64_t* __restrict__ start0, const int32_t* __restrict__ len,
                                                    const int64_t* __restrict__ col_off, const int32_t* __restrict__ read_begin, int32_t ng,
@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k0_bind_b(BatchView b, ReadBin* __r
   const int g = last_le(b.read_begin, b.n_regions, r);
   read_region[r] = g;
   const int32_t pos = b.pos[r];
-  // precondition of k3_rows / lcr_fragments (binary searches on pos): a region's reads are sorted by position
+  // precondition of k3_rows_offsets / lcr_fragments (binary searches on pos): a region's reads are sorted by position
   if (r > b.read_begin[g] && pos < b.pos[r - 1]) *order_flag = 1;
   ReadBin h;
   h.rel_pos = (int32_t)((int64_t)pos - b.start0[g]);

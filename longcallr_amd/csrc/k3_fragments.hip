@@ -7,51 +7,9 @@
 // q5 | p-bit | base code).  Entries with p = 0 or at dense candidates are dropped (fragment.rs:148).
 #include "lcr_dev.h"
 
-// rows per region: reads with pos <= last candidate pos (reads are sorted by pos)
-__global__ void k3_rows(BatchView b, const lcr_candidate* __restrict__ cand, const int32_t* __restrict__ cand_region_off,
-                        int32_t* __restrict__ region_rows, int32_t* __restrict__ host_out) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= b.n_regions) return;
-  const int c0 = cand_region_off[g], c1 = cand_region_off[g + 1];
-  if (c1 <= c0) { region_rows[g] = 0; if (host_out) host_out[g] = 0; return; }  // fragment.rs:24-26
-  const int64_t last = cand[c1 - 1].pos;
-  int lo = b.read_begin[g], hi = b.read_begin[g + 1];
-  const int rb = lo;
-  while (lo < hi) { int mid = (lo + hi) >> 1; if ((int64_t)b.pos[mid] > last) hi = mid; else lo = mid + 1; }
-  region_rows[g] = lo - rb;
-  if (host_out) host_out[g] = lo - rb;
-}
-void launch_k3_rows(const BatchView& b, const lcr_candidate* cand, const int32_t* cand_region_off, int32_t* region_rows,
-                    hipStream_t s, int32_t* host_out) {
-  if (b.n_regions == 0) return;
-  hipLaunchKernelGGL(k3_rows, dim3((b.n_regions + 255) / 256), dim3(256), 0, s, b, cand, cand_region_off, region_rows, host_out);
-}
-
-// first row of every region: exclusive prefix sum of region_rows (one workgroup; a batch has at most a few
-// thousand regions), so that lcr_fragments starts without an upload
-__global__ void __launch_bounds__(1024) k3_row_offsets(const int32_t* __restrict__ region_rows, int32_t ng, int32_t* __restrict__ row_region_off) {
-  __shared__ int wsum[16];
-  __shared__ int base_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) { base_s = 0; row_region_off[0] = 0; }
-  __syncthreads();
-  for (int g0 = 0; g0 < ng; g0 += 1024) {
-    const int g = g0 + tid;
-    const int incl = wave_incl_scan(g < ng ? region_rows[g] : 0);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = base_s;
-    for (int w = 0; w < wave; w++) before += wsum[w];
-    if (g < ng) row_region_off[g + 1] = before + incl;
-    __syncthreads();
-    if (tid == 1023) base_s = before + incl;
-    __syncthreads();
-  }
-}
-void launch_k3_row_offsets(const int32_t* region_rows, int32_t ng, int32_t* row_region_off, hipStream_t s) {
-  hipLaunchKernelGGL(k3_row_offsets, dim3(1), dim3(1024), 0, s, region_rows, ng, row_region_off);
-}
-// k3_rows + k3_row_offsets in one launch (one workgroup: a thread per region finds its rows, then the prefix sums)
+// rows per region and the first row of every region in one launch: a thread per region finds its rows (the reads with pos <= the last
+// candidate's; reads are sorted by pos), then the exclusive prefix sums -- one workgroup that takes the regions 1 024 at a time, so that
+// lcr_fragments starts without an upload
 __global__ void __launch_bounds__(1024) k3_rows_offsets(BatchView b, const lcr_candidate* __restrict__ cand, const int32_t* __restrict__ cand_region_off,
                                                         int32_t* __restrict__ region_rows, int32_t* __restrict__ row_region_off, int32_t* __restrict__ host_rows) {
   __shared__ int wsum[16];

@@ -269,7 +269,6 @@ void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* p
                            int32_t n_sites, const int32_t* cand_off /* n_regions + 1 */, lcr_candidate* out, hipStream_t s,
                            lcr_candidate* h_cand /* pinned (device pointer): the records and ... */, int32_t* h_off /* ... their offsets, or nullptr */);
 void launch_k2_import_check(const int64_t* pos0, const uint8_t* gt, int32_t n_sites, int32_t* bad /* zeroed */, hipStream_t s);
-void launch_k3_row_offsets(const int32_t* region_rows, int32_t ng, int32_t* row_region_off, hipStream_t s);
 void launch_k3_region_entries(const int64_t* row_ptr, const int32_t* row_region_off, int32_t ng, int64_t* region_e_off, hipStream_t s, int64_t* host_out = nullptr);
 struct K3Hits {   // what k2_hist left for K3 (hit_cnt == nullptr: nothing -- K3 walks every read's CIGAR itself)
   const int32_t* hit_cnt; const void* hit_list; const int32_t* ovf_cnt; const int32_t* ovf_list;
@@ -282,10 +281,8 @@ void launch_k3_fill(const BatchView& b, const ReadBin* rbin, const lcr_candidate
                     const int32_t* row_region_off, int32_t n_rows, int32_t* row_cnt, const int64_t* row_ptr, const int32_t* tmp_col,
                     const uint8_t* tmp_val, int32_t* col, uint8_t* val, const K3Hits& hits, hipStream_t s);
 int launch_k3_inline();
-void launch_k3_rows(const BatchView& b, const lcr_candidate* cand, const int32_t* cand_region_off, int32_t* region_rows,
-                    hipStream_t s, int32_t* host_out = nullptr /* pinned host memory as the device sees it */);
 void launch_k3_rows_offsets(const BatchView& b, const lcr_candidate* cand, const int32_t* cand_region_off, int32_t* region_rows, int32_t* row_region_off,
-                            hipStream_t s, int32_t* host_rows = nullptr);   // launch_k3_rows + launch_k3_row_offsets in one kernel
+                            hipStream_t s, int32_t* host_rows = nullptr /* pinned host memory as the device sees it */);   // region_rows and their exclusive prefix sums
 void launch_scan_i32_to_i64(DevBuf& tmp, const int32_t* in, int64_t* out_excl, int32_t n, hipStream_t s);
 
 void launch_k5_span_window(const int32_t* ref_start, const int32_t* ref_end, int32_t n, int64_t contig_len, int32_t* out /* {INT_MAX, 0} */, hipStream_t s);

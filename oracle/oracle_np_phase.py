@@ -732,11 +732,9 @@ class Graph:
         return order
 
 
-def run_region(batch, g, prm, cands, frag_cls=None):
-    """thread.rs:136-201 for region g.  cands: the candidate records of the region as of get_candidate_snps (the
-    candidate half is pinned separately, tests/test_oracle_np.py), e.g. orc.Region(...).candidates().cands().
-    frag_cls: a subclass of SNPFrag that observes the steps (tests/post_phase_cases.py counts the branches they take).
-    Returns the SNPFrag after the post-phase steps and the read -> phase set map."""
+def fragment_rows(batch, g, prm, cands, frag_cls=None):
+    """get_fragments alone (fragment.rs:10-309) for region g over the candidate records `cands` (structured records or dicts with the
+    same fields): the SNPFrag with fragmat_snapshot = per row (read, [(snp_idx, base, baseq, p)], num_hete_links, for_phasing)."""
     F = dict(edit=1, dense=2, het=4, fp=8, hom=16, single=32, nonsel=64, som=128)
     snps = [Snp(int(c["pos"]), chr(c["ref_base"]), (chr(c["allele1"]), chr(c["allele2"])), (float(c["af1"]), float(c["af2"])),
                 int(c["variant_type"]), int(c["genotype"]), bool(c["flags"] & F["edit"]), bool(c["flags"] & F["dense"]),
@@ -746,7 +744,16 @@ def run_region(batch, g, prm, cands, frag_cls=None):
     sf.get_fragments(batch, g)
     sf.fragmat_snapshot = [(f.read, [(fe.snp_idx, fe.base, fe.baseq, fe.p) for fe in f.list], f.num_hete_links, f.for_phasing)
                            for f in sf.fragments]
-    if not snps:
+    return sf
+
+
+def run_region(batch, g, prm, cands, frag_cls=None):
+    """thread.rs:136-201 for region g.  cands: the candidate records of the region as of get_candidate_snps (the
+    candidate half is pinned separately, tests/test_oracle_np.py), e.g. orc.Region(...).candidates().cands().
+    frag_cls: a subclass of SNPFrag that observes the steps (tests/post_phase_cases.py counts the branches they take).
+    Returns the SNPFrag after the post-phase steps and the read -> phase set map."""
+    sf = fragment_rows(batch, g, prm, cands, frag_cls)
+    if not sf.candidate_snps:
         return sf, {}
     sf.init_haplotypes()        # thread.rs:162-163 (both are overwritten by phase(), but they consume draws)
     sf.init_assignment()
