@@ -110,11 +110,16 @@ int lcr_params_preset(int preset, lcr_params* out);
 /* Pileup columns (replaces Vec<BaseFreq>, util.rs:100-127) as u32 planes of n_cols each.
  * plane[k] = planes + k*n_cols.  Reverse-strand counts are cnt - fwd.  The never-read fields of
  * BaseFreq (forward_cnt, backward_cnt, distance_to_end, i) are not produced.
- * Materialised on request: lcr_pileup stores the planes of the tiles that hold records; the columns no
+ * Materialised on request: lcr_pileup stores at most the planes of the tiles that hold records; the columns no
  * record touches (uncovered, or inside introns only: 0 everywhere, n = introns across them) are stored by
- * lcr_get_columns itself, once per pileup, before it copies.  The getter returns every column, whenever it is
- * called between lcr_pileup and the next lcr_load_batch / lcr_bind_batch / lcr_pileup; like the stage calls it
- * reads the region arrays of a LCR_MEM_DEVICE batch.  No other call needs those columns. */
+ * lcr_get_columns itself, once per pileup, before it copies.  On the ONT presets, from a context's second batch
+ * on, lcr_pileup stores no plane at all (its candidate filter runs on the counts while they are on chip, and the
+ * columns that pass go to lcr_candidates directly): the planes of the tiles with records are then tallied from
+ * the pileup's records, bit for bit the same, by the first call that reads them -- lcr_get_columns,
+ * lcr_import_candidates, or a lcr_candidates with other filter parameters than lcr_pileup's.  The getter returns
+ * every column, whenever it is called between lcr_pileup and the next lcr_load_batch / lcr_bind_batch /
+ * lcr_pileup; like the stage calls it reads the arrays of a LCR_MEM_DEVICE batch (regions, and for that second
+ * tally the reads as well).  No other call needs those columns. */
 enum {
   LCR_PL_A = 0, LCR_PL_C, LCR_PL_G, LCR_PL_T, /* a,c,g,t                                            */
   LCR_PL_N,                                    /* n  (intron)                                        */
@@ -759,7 +764,8 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * csrc/lcr_phase_host.h), "hist_tiles" (quality histograms from K0's records: 0 = when the survivors are dense, 1 = whenever the
  * preset allows, -1 = never); round 6: "chain_ties" (0: chain regions of workgroup scope keep the tie contract of round 5: sigma ties
  * only), "redo_lds" (bytes of dynamic LDS of the enumeration branch's repair pass; 0: its matrices in global memory), "fuse_filter",
- * "spec_compact" (0: lcr_candidates waits for the survivors' number before it queues their compaction), "own_fill" (0: hipMemsetAsync instead of the
+ * "spec_compact" (0: lcr_candidates waits for the survivors' number before it queues their compaction), "lean_planes" (0: lcr_pileup always stores
+ * the planes of the tiles with records -- and, on the ONT presets, the filter flags -- instead of handing the filter's survivors to lcr_candidates), "own_fill" (0: hipMemsetAsync instead of the
  * library's fill kernels), "fill_selftest" (checks those kernels against the host; LCR_E_DEVICE on a difference), "host_trace" (1: a
  * "[host]" line of wall-clock marks per lcr_phase on stderr; process-wide like own_fill).  Unknown key: LCR_E_ARG.  The defaults are the
  * product behaviour. */
@@ -783,7 +789,10 @@ int lcr_enable_timing(lcr_ctx*, int on);
 int lcr_kernel_ms(lcr_ctx*, int kernel, float* ms);
 /* Bytes the pileup tally kernel (K1) of the last lcr_pileup has to move: read bases once (B) + 8-byte
  * records + (1 + 4 + 4*LCR_NPLANES)*L; and the implementation-independent figure of the whole pileup
- * stage (K0 + K1): B + 4C + 37R + (4*LCR_NPLANES + 1)*L.  See DESIGN.md. */
+ * stage (K0 + K1): B + 4C + 37R + (4*LCR_NPLANES + 1)*L.  The 4*LCR_NPLANES bytes count only at the columns whose
+ * planes that lcr_pileup stored itself (tiles with records); when it stored none (see lcr_columns) both figures
+ * carry 48 bytes per survivor handed to lcr_candidates instead, and the getters wait for the tally to learn their
+ * number if lcr_candidates has not run yet.  Planes stored later for a getter are not counted.  See DESIGN.md. */
 int lcr_pileup_bytes(lcr_ctx*, int64_t* bytes);
 int lcr_pileup_stage_bytes(lcr_ctx*, int64_t* bytes);
 

@@ -24,6 +24,9 @@
 //       bases from the finished planes with global atomics.
 // All arithmetic is u32 adds => bit-exact regardless of order.  Base qualities are NOT read here: they
 // are only needed at the < 1 % of columns that survive the count filters (k2_hist).
+// K1's epilogue has two forms (template parameter LEAN): the full one stores the 13 planes of the tile; the lean one -- ONT presets,
+// whose pass 1 of the candidate filters runs on the LDS counts anyway -- stores only the survivors' records for lcr_candidates, and the
+// full form is run again over the same records if somebody asks for the planes (lcr_pileup.hip: planes_tally).
 #include <algorithm>
 #include <climits>
 
@@ -264,12 +267,20 @@ __device__ __forceinline__ int block_incl_scan(int v, int* wsum /* K1_WAVES ints
   return s + add;
 }
 
+// Two forms of one body, by what the epilogue does with the finished counts:
+//   full (LEAN = false)  stores the 13 planes of every column; with flt_flags != nullptr also pass 1's flag per column and count per tile;
+//   lean (LEAN = true)   runs pass 1 on the counts in LDS and stores neither planes nor flags: a passing column's record (Survivor: what k2_compact
+//                        would rebuild from the planes) goes to a staging buffer, beside it its (tile, rank in tile), and flt_count is written as in the
+//                        full form.  A tile with survivors draws its run of staging slots with one atomicAdd on *n_staged; records beyond sv_cap are
+//                        dropped, the count stays exact (the host then falls back on the full form: lcr_candidates).
+struct K1Stage { Survivor* sv; int2* key; int32_t cap; int32_t* n_staged; };
+template <bool LEAN>
 __global__ void __launch_bounds__(K1_THREADS)
 k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, const int32_t* __restrict__ tile_col0,
           int64_t n_cols, const int32_t* __restrict__ tile_fill, const int32_t* __restrict__ ent_off, const uint2* __restrict__ ents,
           const unsigned long long* __restrict__ recs,
           const int32_t* __restrict__ tile_nbase, uint32_t* __restrict__ planes, const int32_t* __restrict__ order,
-          const int32_t* __restrict__ n_full, BinomTable bt, uint8_t* __restrict__ flt_flags, int32_t* __restrict__ flt_count) {
+          const int32_t* __restrict__ n_full, BinomTable bt, uint8_t* __restrict__ flt_flags, int32_t* __restrict__ flt_count, K1Stage stg) {
   // (tiles with records first, fullest first, the record-free ones behind them: k1_tiles_b.  Dealing the record-free
   // tiles -- pure streams of plane stores, 75 % of the stage's HBM writes -- between the full ones so that the stores run
   // under the tally was measured: 0.74 instead of 0.43 ms, XCD-aware or not; the full tiles' dependent loads then queue
@@ -504,6 +515,7 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
   const uint32_t nbase = (uint32_t)tile_nbase[tile];
   static_assert(K1_CPT == 1, "the fused filter counts one column per thread");
   int n_pass = 0;
+  Survivor sv;   // (lean form: this thread's column, if it passes)
   for (int col = tid; col < tlen; col += K1_THREADS) {
     const uint8_t R = refl[REF_PAD + col];
     const int ri = R == 'A' ? 0 : R == 'C' ? 1 : R == 'G' ? 2 : R == 'T' ? 3 : -1;
@@ -521,30 +533,59 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
       for (int k = 0; k < 4; k++) if (k == ri) { f[k] = mf; rv[k] = mr; }
     }
     const int64_t o = gcol0 + col;
+    if (!LEAN) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      planes[(int64_t)(LCR_PL_A + k) * n_cols + o] = f[k] + rv[k];
-      planes[(int64_t)(LCR_PL_FWD_A + k) * n_cols + o] = f[k];
+      for (int k = 0; k < 4; k++) {
+        planes[(int64_t)(LCR_PL_A + k) * n_cols + o] = f[k] + rv[k];
+        planes[(int64_t)(LCR_PL_FWD_A + k) * n_cols + o] = f[k];
+      }
+      // intron plane: introns that cover the whole tile + the runs that start or end inside it
+      planes[(int64_t)LCR_PL_N * n_cols + o] = nbase + pl[P_DIFF_N * TSTRIDE + col];
+      planes[(int64_t)LCR_PL_D * n_cols + o] = pl[P_DIFF_D * TSTRIDE + col];
+      planes[(int64_t)LCR_PL_NI * n_cols + o] = pl[P_NI * TSTRIDE + col];
+      planes[(int64_t)LCR_PL_TS_FWD * n_cols + o] = pl[P_DIFF_TS0 * TSTRIDE + col];
+      planes[(int64_t)LCR_PL_TS_REV * n_cols + o] = pl[P_DIFF_TS1 * TSTRIDE + col];
     }
-    // intron plane: introns that cover the whole tile + the runs that start or end inside it
-    planes[(int64_t)LCR_PL_N * n_cols + o] = nbase + pl[P_DIFF_N * TSTRIDE + col];
-    planes[(int64_t)LCR_PL_D * n_cols + o] = pl[P_DIFF_D * TSTRIDE + col];
-    planes[(int64_t)LCR_PL_NI * n_cols + o] = pl[P_NI * TSTRIDE + col];
-    planes[(int64_t)LCR_PL_TS_FWD * n_cols + o] = pl[P_DIFF_TS0 * TSTRIDE + col];
-    planes[(int64_t)LCR_PL_TS_REV * n_cols + o] = pl[P_DIFF_TS1 * TSTRIDE + col];
     // pass 1 of the candidate filters (candidate.rs:90-234, k2_eval.h) on the counts this thread holds: the presets without a poly-A pass
     // behind this kernel (ONT) get k2_filter's flags and per-tile counts here -- one pass over the planes less (round 6)
-    if (flt_flags) {
+    if (LEAN || flt_flags) {
       uint32_t cnt[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) cnt[k] = f[k] + rv[k];
       const ColEval ev = eval_counts(cnt, R, prm, bt, [&]() { return pl[P_DIFF_D * TSTRIDE + col]; }, [&]() { return nbase + pl[P_DIFF_N * TSTRIDE + col]; },
                                      [&](int k) { return f[k]; });
-      flt_flags[o] = ev.pass ? 1 : 0;
+      if (!LEAN) flt_flags[o] = ev.pass ? 1 : 0;
       n_pass += ev.pass ? 1 : 0;
+      if (LEAN && ev.pass) {   // (the record k2_compact builds from the planes: same fields, same values)
+        sv.gcol = o; sv.region = g; sv.col = tc0 + col;
+        sv.ref_base = ev.ref_base; sv.allele1 = ev.allele1; sv.allele2 = ev.allele2; sv.n_alt = ev.n_alt;
+        sv.cnt1 = ev.cnt1; sv.cnt2 = ev.cnt2; sv.depth = ev.depth; sv.af1 = ev.af1; sv.af2 = ev.af2;
+        sv.ts_fwd = pl[P_DIFF_TS0 * TSTRIDE + col]; sv.ts_rev = pl[P_DIFF_TS1 * TSTRIDE + col];
+      }
     }
   }
-  if (flt_flags) {
+  if (LEAN) {
+    // rank in tile = passing columns below this one (one column per thread: a ballot prefix + the waves in front); the tile's run of staging
+    // slots from one atomicAdd.  The order the tiles draw their runs in differs from run to run: k2_place puts the records in (tile, rank) order.
+    __shared__ int stage_base;
+    const int lane = tid & 63, w = tid >> 6;
+    const unsigned long long bal = __ballot(n_pass != 0);
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int i = 0; i < K1_WAVES; i++) { before += i < w ? wsum[i] : 0; total += wsum[i]; }
+    if (tid == 0) {
+      flt_count[tile] = total;
+      if (total > 0) stage_base = atomicAdd(stg.n_staged, total);
+    }
+    if (total > 0) {   // (block-uniform)
+      __syncthreads();
+      const int rank = before + __popcll(bal & ((1ull << lane) - 1ull));
+      const int slot = stage_base + rank;
+      if (n_pass != 0 && slot >= 0 && slot < stg.cap) { stg.sv[slot] = sv; stg.key[slot] = make_int2(tile, rank); }
+    }
+  } else if (flt_flags) {
     const int total = __syncthreads_count(n_pass);   // (one column per thread: n_pass is 0 or 1)
     if (tid == 0) flt_count[tile] = total;
   }
@@ -611,8 +652,10 @@ struct TileScanTmp {    // scratch in HBM, cleared with K0's counters
   int empty_cols;       // columns of the record-free tiles (pass A; its last block hands the sum to the host's control block).  32 bits hold it:
                         // lcr_load_batch refuses a batch whose columns + regions reach 2^31 (tile origins and the intron array are int32 as well)
   int done_a;           // blocks of pass A that have added theirs
-  int pad_[5];
+  int n_staged;         // k1_pileup's lean form: survivors that have drawn a staging slot (K1_TMP_STAGED)
+  int pad_[4];
 };
+static_assert(offsetof(TileScanTmp, n_full) == 4 * K1_TMP_NFULL && offsetof(TileScanTmp, n_staged) == 4 * K1_TMP_STAGED, "the launchers' word offsets");
 __device__ __forceinline__ int tile_class(int fill) { return fill > 0 ? __clz(fill) : 32; }   // more records, lower class
 
 __global__ void __launch_bounds__(256) k1_tiles_a(const int32_t* __restrict__ tile_fill, const int32_t* __restrict__ tile_ndiff,
@@ -737,14 +780,25 @@ void launch_k1_pileup(const BatchView& b, const DevParams& p, const int32_t* til
                       const int32_t* tiles_tmp, hipStream_t s, uint8_t* flt_flags, int32_t* flt_count) {
   static const BinomTable bt = make_binom_table();
   if (n_tiles == 0) return;
-  hipLaunchKernelGGL(k1_pileup, dim3(n_tiles), dim3(K1_THREADS), 0, s, b, p, tile_region, tile_col0, n_cols, tile_fill, ent_off,
-                     (const uint2*)ents, recs, tile_nbase, planes, order, tiles_tmp + 80 /* TileScanTmp::n_full */, bt, flt_flags, flt_count);
+  hipLaunchKernelGGL(k1_pileup<false>, dim3(n_tiles), dim3(K1_THREADS), 0, s, b, p, tile_region, tile_col0, n_cols, tile_fill, ent_off,
+                     (const uint2*)ents, recs, tile_nbase, planes, order, tiles_tmp + K1_TMP_NFULL, bt, flt_flags, flt_count, K1Stage{nullptr, nullptr, 0, nullptr});
+}
+// the tally in its lean form: no planes, no flags; flt_count and the staged survivors (tiles_tmp: cleared before K0, so TileScanTmp::n_staged starts at 0)
+void launch_k1_pileup_lean(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,
+                           int32_t n_tiles, int64_t n_cols, const int32_t* tile_fill, const int32_t* ent_off, const void* ents,
+                           const unsigned long long* recs, const int32_t* tile_nbase, const int32_t* order, int32_t* tiles_tmp, hipStream_t s,
+                           int32_t* flt_count, Survivor* stage, void* stage_key, int32_t stage_cap) {
+  static const BinomTable bt = make_binom_table();
+  if (n_tiles == 0) return;
+  hipLaunchKernelGGL(k1_pileup<true>, dim3(n_tiles), dim3(K1_THREADS), 0, s, b, p, tile_region, tile_col0, n_cols, tile_fill, ent_off,
+                     (const uint2*)ents, recs, tile_nbase, (uint32_t*)nullptr, order, tiles_tmp + K1_TMP_NFULL, bt, (uint8_t*)nullptr, flt_count,
+                     K1Stage{stage, (int2*)stage_key, stage_cap, tiles_tmp + K1_TMP_STAGED});
 }
 // the record-free tiles' planes, over the tables the last launch_k1_tiles_b / launch_k1_pileup left (lcr_get_columns)
 void launch_k1_empty_tiles(const BatchView& b, const int32_t* tile_region, const int32_t* tile_col0, int32_t n_tiles, int64_t n_cols,
                            const int32_t* tile_nbase, uint32_t* planes, const int32_t* order, const int32_t* tiles_tmp, hipStream_t s) {
   if (n_tiles == 0) return;
-  hipLaunchKernelGGL(k1_empty_tiles, dim3(n_tiles), dim3(128), 0, s, b, tile_region, tile_col0, n_cols, tile_nbase, planes, order, tiles_tmp + 80, n_tiles);
+  hipLaunchKernelGGL(k1_empty_tiles, dim3(n_tiles), dim3(128), 0, s, b, tile_region, tile_col0, n_cols, tile_nbase, planes, order, tiles_tmp + K1_TMP_NFULL, n_tiles);
 }
 // the tile-order / intron-base / accounting pass alone (the host fetches K0's control block behind it, before K1 is queued)
 // the tile passes alone (the host fetches K0's control block behind pass A, before the rest is queued)

@@ -245,6 +245,21 @@ k2_compact(BatchView b, DevParams prm, BinomTable bt, const int32_t* __restrict_
   }
 }
 
+// The same list from the records k1_pileup's lean form staged: a thread per staged record, out[survivors in front of its tile + its rank in the
+// tile] = record -- an ordered copy; nothing is evaluated and no plane is read.  Launched for the staging capacity before the host knows the number.
+__global__ void __launch_bounds__(LCR_BLOCK)
+k2_place(const uint4* __restrict__ stage, const int2* __restrict__ key, const int32_t* __restrict__ n_staged, int32_t stage_cap,
+         const int32_t* __restrict__ tile_off, uint4* __restrict__ out, int32_t out_cap) {
+  static_assert(sizeof(Survivor) == 48, "a survivor record is three 16-byte words");
+  const int i = blockIdx.x * LCR_BLOCK + threadIdx.x;
+  if (i >= min(*n_staged, stage_cap)) return;
+  const int2 k = key[i];
+  const int dst = tile_off[k.x] + k.y;
+  if (dst < 0 || dst >= out_cap) return;
+  const uint4 a = stage[3 * (size_t)i], b = stage[3 * (size_t)i + 1], c = stage[3 * (size_t)i + 2];
+  out[3 * (size_t)dst] = a; out[3 * (size_t)dst + 1] = b; out[3 * (size_t)dst + 2] = c;
+}
+
 
 // ---- pass 2a: per-survivor quality histograms --------------------------------------------------
 // Sixteen lanes per read (row16_walk_sites, lcr_dev.h): the region's survivors (sorted by column) that
@@ -539,6 +554,12 @@ void launch_k2_gt(const DevParams& p, const Survivor* sv, int32_t n_sv, const ui
   hipLaunchKernelGGL(k2_gt, dim3((n_sv + LCR_BLOCK - 1) / LCR_BLOCK), dim3(LCR_BLOCK), 0, s, p, g_gtc, sv, n_sv, hist, start0, out, keep);
 }
 
+void launch_k2_place(const Survivor* stage, const void* stage_key, const int32_t* n_staged, int32_t stage_cap, const int32_t* tile_off,
+                     Survivor* out, int32_t out_cap, hipStream_t s) {
+  if (stage_cap <= 0) return;
+  hipLaunchKernelGGL(k2_place, dim3((stage_cap + LCR_BLOCK - 1) / LCR_BLOCK), dim3(LCR_BLOCK), 0, s, (const uint4*)stage, (const int2*)stage_key, n_staged,
+                     stage_cap, tile_off, (uint4*)out, out_cap);
+}
 void launch_k2_compact(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,
                        int32_t n_tiles, int64_t n_cols, const uint32_t* planes, const uint8_t* flags,
                        const int32_t* tile_count, const int32_t* tile_off, Survivor* out, int32_t out_cap, hipStream_t s) {

@@ -230,14 +230,18 @@ int lcr_kernel_ms(lcr_ctx* c, int k, float* ms) {
 
 int lcr_pileup_bytes(lcr_ctx* c, int64_t* bytes) {
   if (!c || !bytes) return LCR_E_ARG;
-  *bytes = c->pileup_bytes;
-  return LCR_OK;
+  int64_t staged = 0;   // (a lean tally: 48 bytes per staged survivor instead of the planes)
+  const int rc = pile_staged_bytes(c, &staged);
+  *bytes = c->pileup_bytes + staged;
+  return rc;
 }
 
 int lcr_pileup_stage_bytes(lcr_ctx* c, int64_t* bytes) {
   if (!c || !bytes) return LCR_E_ARG;
-  *bytes = c->stage_bytes;
-  return LCR_OK;
+  int64_t staged = 0;
+  const int rc = pile_staged_bytes(c, &staged);
+  *bytes = c->stage_bytes + staged;
+  return rc;
 }
 
 int lcr_phase(lcr_ctx* c, const lcr_params* p) {
@@ -505,6 +509,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "k3_hits") c->dbg_k3_hits = value != 0;
   else if (k == "fuse_filter") c->dbg_fuse_filter = value != 0;
   else if (k == "spec_compact") c->dbg_spec_compact = value != 0;
+  else if (k == "lean_planes") c->dbg_lean_planes = value != 0;
   else if (k == "poison_planes") c->dbg_poison_planes = value != 0;
   else if (k == "grid_spec_batch") d.spec_batch = (int)value;
   else if (k == "grid_spec_lanes") d.spec_lanes = (int)std::max<int64_t>(1, std::min<int64_t>(value, 16));

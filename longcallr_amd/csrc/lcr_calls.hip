@@ -72,9 +72,11 @@ int cand_queue_pass1(lcr_ctx* c) {
   const DevParams &fa = c->flt_dp, &fb = c->dp;
   const bool have_flt = c->flt_fused && c->dbg_fuse_filter != 0 && fa.ont == fb.ont && fa.min_depth == fb.min_depth && fa.max_depth == fb.max_depth && fa.low_cnt_cut == fb.low_cnt_cut &&
                         fa.use_strand_bias == fb.use_strand_bias && fa.min_af_intron == fb.min_af_intron && fa.low_frac_cut == fb.low_frac_cut && fa.sor_threshold == fb.sor_threshold;
+  if (!have_flt) { const int rc = planes_tally(c, false); if (rc) return rc; }   // (k2_filter reads the planes: a lean tally has not stored them)
   Timer t(c, LCR_K_CAND_FILTER);
   if (!have_flt) {
     c->flt_fused = false;   // (the pass below overwrites the flags and tile counts of lcr_pileup's epilogue)
+    c->sv_staged = false;   // (... and the staged survivors are those of the pileup's parameters)
     launch_k2_filter(c->bv, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols,
                      c->planes.as<uint32_t>(), c->k0_tile_fill.as<int32_t>(), c->flags.as<uint8_t>(), c->tile_count.as<int32_t>(), c->stream);
   }
@@ -90,7 +92,8 @@ void queue_compact(lcr_ctx* c, int32_t cap) {
 // survivors per region = tile offsets at the regions' first tiles (gathered on the device, pinned D2H); waits for their number.
 // The survivors' compaction (and the fill of their histograms) is queued BEFORE the host knows how many there are, into buffers sized
 // by the last call's count + a quarter, and the host waits for an event in front of it: the round trip (28 us on C3) runs under that kernel
-// instead of in front of it.  More survivors than the guess (or no guess yet): the kernel dropped the rest, and runs again in cand_queue_genotypes.
+// instead of in front of it.  More survivors than the guess (or no guess yet): the kernel dropped the rest, and runs again in cand_queue_genotypes
+// (behind a lean pileup: behind a second tally in the full fused form, which leaves it the planes and flags it reads).
 // *compacted: survivors and a cleared hist are in place, or on their way.
 int cand_count_survivors(lcr_ctx* c, int32_t* n_sv_out, bool* compacted) {
   const int ng = c->bv.n_regions, nt = c->n_tiles;
@@ -101,18 +104,33 @@ int cand_count_survivors(lcr_ctx* c, int32_t* n_sv_out, bool* compacted) {
     HIPCHK(c, c->h_stage[0].dev(&d_sv));
     launch_scan_i32(c->scan_tmp, c->tile_count.as<int32_t>(), c->tile_off.as<int32_t>(), nt, c->total.as<int32_t>(), c->stream);
     launch_gather_i32(c->tile_off.as<int32_t>(), c->first_tile.as<int32_t>(), ng + 1, nt, c->total.as<int32_t>(), c->sv_region_off.as<int32_t>(), c->stream, d_sv); }
-  const int32_t cap_guess = (c->dbg_spec_compact && nt > 0) ? c->sv_cap_guess : 0;
+  // Behind a lean pileup (sv_staged; its parameters are this call's: cand_queue_pass1) the survivors' records exist already, staged by the tally in
+  // the order the tiles finished: k2_place copies them to their places -- (tile, column) order, the same from run to run -- in k2_compact's stead.
+  // The capacity is the staging's: the guess lcr_pileup sized it by.
+  const bool staged = c->sv_staged && nt > 0;
+  const int32_t cap_guess = staged ? c->sv_stage_cap : (c->dbg_spec_compact && nt > 0) ? c->sv_cap_guess : 0;
   if (cap_guess > 0) {
     HIPCHK(c, hipEventRecord(c->ev_sv, c->stream));
     HIPCHK(c, c->survivors.reserve((size_t)cap_guess * sizeof(Survivor)));
     HIPCHK(c, c->hist.reserve((size_t)cap_guess * 124 * 4 + 64));
     HIPCHK(c, lcr_fill_async(c->hist.p, 0, (size_t)cap_guess * 124 * 4 + 64, c->stream));
-    queue_compact(c, cap_guess);
+    if (staged)
+      launch_k2_place(c->sv_stage.as<Survivor>(), c->sv_stage_key.p, c->k0_tile_fill.as<int32_t>() + pile_scratch(nt).tmp + K1_TMP_STAGED, c->sv_stage_cap,
+                      c->tile_off.as<int32_t>(), c->survivors.as<Survivor>(), cap_guess, c->stream);
+    else queue_compact(c, cap_guess);
     HIPCHK(c, hipEventSynchronize(c->ev_sv));
   } else HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
   const int32_t n_sv = sv_off[ng];
   *compacted = cap_guess > 0 && n_sv <= cap_guess;
+  if (staged) {
+    c->sv_stage_n = std::min(n_sv, c->sv_stage_cap);   // (the tile counts' sum is the tally's counter)
+    if (!*compacted) {   // more survivors than the staging holds: the tally again in its full fused form -- planes, flags, counts --, then k2_compact (cand_queue_genotypes)
+      const int rc = planes_tally(c, true);
+      if (rc) return rc;
+      c->sv_staged = false;
+    }
+  }
   c->sv_cap_guess = n_sv > 0 ? n_sv + n_sv / 4 + 64 : 0;
   *n_sv_out = n_sv;
   HT("cand:n_sv");
@@ -252,6 +270,7 @@ int lcr_import_candidates(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t 
   { int rc = cand_host_blocks(c, (size_t)n_sites, &hp, &ho); if (rc) return rc; }
   c->h_cand.clear();
   c->h_cand_off.assign(ng + 1, 0);
+  { const int rc = planes_tally(c, false); if (rc) return rc; }   // (k2_import_emit reads the sites' counts: a lean tally has not stored them)
   { Timer t(c, LCR_K_CAND_IMPORT);
     launch_k2_import_count(c->bv, d_pos, d_gt, d_q, n_sites, c->imp_cnt.as<int32_t>(), c->stream);
     launch_scan_i32(c->scan_tmp, c->imp_cnt.as<int32_t>(), c->d_cand_off.as<int32_t>(), ng, c->d_cand_off.as<int32_t>() + ng, c->stream);

@@ -87,26 +87,42 @@ struct lcr_ctx {
   int64_t n_items = 0;
 
   // K1
-  // lcr_pileup writes the planes of the tiles that hold records (K0's fill counter > 0) and nothing else: a record-free tile's planes are
-  // constants -- 0, the intron plane tile_nbase[tile] -- and what lies at its columns after lcr_pileup is whatever an earlier batch left
-  // there.  planes_dense: the constants have been stored for the current pileup (planes_materialise: k1_empty_tiles over the tile order,
-  // tile_nbase and n_full of that pileup -- tile_order / tile_nbase / k0_tile_fill are rewritten by lcr_pileup only, tile_region / tile_col0
-  // by lcr_load_batch only, and both clear the flag: rewind_to).  Who reads c->planes, and why a tile that was never written is safe with each:
-  //   k1_pileup's fused filter epilogue   runs in the workgroups of tiles with records, on their LDS counters;
-  //   k1_zonefix / _ends / _slots         atomicSub at the column of an aligned base inside the region: that base's M record is in the tile;
-  //   k2_filter (eval_column)             leaves at tile_fill == 0 with tile_count = 0;
-  //   k2_compact (eval_column, ts planes) leaves at tile_count == 0 -- k2_filter's 0, or k1_tiles_b's on the fused path;
-  //   k2_hist / k2_hist_tiles / k2_gt, K3, K4   never touch the planes (k2_hist_tiles walks K0's records of tiles with tile_count > 0);
-  //   k2_import_emit                      takes the four counts of a site in a tile with tile_fill == 0 as 0 without loading them;
-  //   lcr_get_columns                     the one reader of every column: calls planes_materialise first.
-  // planes_materialise itself (k1_empty_tiles) reads, beside those tables, bv.error_flag (K0Ctl::error in k0_tile_fill, 0 after a pileup that returned
-  // LCR_OK) and the region arrays bv.len / bv.col_off: the context's copies of a host batch, the caller's arrays of a LCR_MEM_DEVICE batch, which
-  // therefore have to stay alive for lcr_get_columns as for every stage call (include/lcr.h).
+  // Which planes exist after lcr_pileup ("Which planes exist when"):
+  //   record-free tiles (K0's fill counter == 0)   never written by the stage: their planes are constants -- 0, the intron plane tile_nbase[tile] --
+  //                     and what lies at their columns is whatever an earlier batch left there.  planes_dense: the constants have been stored for the
+  //                     current pileup (planes_materialise: k1_empty_tiles over the tile order, tile_nbase and n_full of that pileup);
+  //   tiles with records   written by the tally in its full form.  In its lean form (sv_staged: ONT presets, fused filter, a survivor guess, "lean_planes")
+  //                     the tally keeps its counts in LDS, hands the pass-1 survivors to lcr_candidates as staged records and stores no plane and no
+  //                     flag: planes_tallied says whether these tiles' planes are in c->planes.  planes_tally replays k1_pileup in the full form over
+  //                     the tables the pileup left -- tile_order / tile_nbase / chunk_off / chunks / k0_items / k0_tile_fill are rewritten by lcr_pileup
+  //                     only, tile_region / tile_col0 by lcr_load_batch only, no other stage uses them as scratch, and both calls clear the three flags:
+  //                     rewind_to.  All counts are u32 sums, so the replay's planes are the tally's bit for bit.
+  // Who reads c->planes, what each calls first, and why a record-free tile that was never written is safe with it:
+  //   k1_pileup's fused filter epilogue   nothing: runs in the workgroups of tiles with records, on their LDS counters;
+  //   k1_zonefix / _ends / _slots         nothing (HiFi presets: always the full form): atomicSub at the column of an aligned base inside the region: that base's
+  //                                       M record is in the tile;
+  //   k2_filter (eval_column)             planes_tally (reached only when the fused verdicts cannot be used); leaves at tile_fill == 0 with tile_count = 0;
+  //   k2_compact (eval_column, ts planes) planes_tally with the filter outputs when it runs behind a lean pileup (more survivors than the staging buffer holds);
+  //                                       leaves at tile_count == 0 -- k2_filter's 0, or k1_tiles_b's on the fused path;
+  //   k2_place / k2_hist / k2_hist_tiles / k2_gt, K3, K4   never touch the planes (k2_hist_tiles walks K0's records of tiles with tile_count > 0);
+  //   k2_import_emit                      planes_tally; takes the four counts of a site in a tile with tile_fill == 0 as 0 without loading them;
+  //   lcr_get_columns                     planes_materialise (planes_tally + the constants): the one reader of every column.
+  // planes_tally / planes_materialise read, beside those tables, bv.error_flag (K0Ctl::error in k0_tile_fill, 0 after a pileup that returned LCR_OK), the
+  // batch's bases and reference, and the region arrays bv.len / bv.col_off: the context's copies of a host batch, the caller's arrays of a LCR_MEM_DEVICE
+  // batch, which therefore have to stay alive for lcr_get_columns as for every stage call (include/lcr.h).
   // lcr_debug_set("poison_planes", 1) fills the whole buffer with 0xA5 in front of every pileup: a reader that looks at an unwritten tile
-  // then differs from a run without it, whatever the previous batch was (tests/test_sparse_planes.py).
+  // then differs from a run without it, whatever the previous batch was (tests/test_sparse_planes.py, tests/test_lean_planes_gpu.py).
   bool planes_dense = false;
+  bool planes_tallied = false;
   int dbg_poison_planes = 0;
+  int dbg_lean_planes = 1;    // lcr_debug_set("lean_planes"): 0 = the tally always stores its planes (and, fused, the flags)
   DevBuf planes;
+  // the lean tally's hand-over: survivor records in the order the tiles drew their slots, beside each its (tile, rank in tile); their number is
+  // TileScanTmp::n_staged in the cleared pileup scratch (exact even beyond the capacity)
+  bool sv_staged = false;     // the last lcr_pileup left them, with flt_count, for the parameters flt_dp
+  int32_t sv_stage_cap = 0;   // records the two buffers hold (the survivor guess of that pileup)
+  int64_t sv_stage_n = -1;    // records stored: min(n_staged, capacity) once the host has read n_staged (lcr_candidates, or the byte getters), -1 before
+  DevBuf sv_stage, sv_stage_key;
   DevParams dp{};
   int32_t pile_platform = -1; uint32_t pile_dist_to_end = 0;   // lcr_pileup's platform / dist_to_end: lcr_candidates must be called with the same
   float sor_thr = -1.f;
@@ -202,7 +218,8 @@ struct lcr_ctx {
   uint32_t timing_mask = 0;   // lcr_debug_set("timing_mask"): bit k = LCR_K_* k is timed; 0 = all of them (every timer is two event records on the stream)
   hipEvent_t ev[LCR_NTIMERS][2] = {};
   bool ev_valid[LCR_NTIMERS] = {};
-  int64_t pileup_bytes = 0, stage_bytes = 0;
+  int64_t pileup_bytes = 0, stage_bytes = 0;   // of the last lcr_pileup; behind a lean tally (pile_lean) without the 48 bytes per staged survivor (sv_stage_n)
+  bool pile_lean = false;
 };
 
 // Back to stage `to` (no-op above it): a driver calls this at the point where it begins to overwrite what the stages behind `to` read --
@@ -212,6 +229,8 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (c->stage > to) c->stage = to;
   if (to < ST_PILED) {
     c->planes_dense = false;   // tile order / tile_nbase / tile tables are rewritten: the stored constants are another pileup's (or batch's)
+    c->planes_tallied = false; // ... and so are the planes of the tiles with records
+    c->sv_staged = false;      // ... and the staged survivors
     c->flt_fused = false;      // the tally's epilogue has not left this pileup's pass-1 flags yet
   }
   if (to < ST_CALLED) {
@@ -265,6 +284,13 @@ int upload(lcr_ctx* c, DevBuf& buf, const T* src, size_t n, const T** dst, int m
 // to overwrite what it reads / writes, collects them first
 inline int phase_settle(lcr_ctx* c) { return c->phase.settle(&c->err); }
 int cand_settle(lcr_ctx* c);   // the candidate stage's host copies (lcr_calls.hip)
+// lcr_pileup.hip.  planes_tally: the planes of the tiles with records are in c->planes -- behind a lean pileup it queues k1_pileup's full form once
+// (with_filter: with pass 1's flags and per-tile counts for the pileup's parameters, as a full fused pileup leaves them).  planes_materialise: that and
+// the record-free tiles' constants.  pile_staged_bytes: what the byte getters add behind a lean tally, 48 sv_stage_n (waits for the tally if nobody has
+// read the count yet); 0 otherwise.
+int planes_tally(lcr_ctx* c, bool with_filter);
+int planes_materialise(lcr_ctx* c);
+int pile_staged_bytes(lcr_ctx* c, int64_t* bytes);
 int frag_settle(lcr_ctx* c);   // lcr_fragments' entry count (lcr_calls.hip)
 
 // A host wait on the context's stream: what the kernels queued so far left in pinned memory is the host's to read

@@ -237,6 +237,17 @@ void launch_k1_pileup(const BatchView& b, const DevParams& p, const int32_t* til
                       const unsigned long long* recs, const int32_t* tile_nbase, uint32_t* planes, const int32_t* order,
                       const int32_t* tiles_tmp /* scratch of launch_k1_tiles_a / _b */, hipStream_t s,
                       uint8_t* flt_flags /* n_cols: != nullptr = pass 1 of the candidate filters in the tally's epilogue (k2_filter's flags) */, int32_t* flt_count /* n_tiles: survivors per tile */);
+#define K1_TMP_NFULL 80    // words of the tile passes' scratch (TileScanTmp, k1_pileup.hip): tiles with records ...
+#define K1_TMP_STAGED 83   // ... and the survivors the lean tally has staged (exact beyond the staging capacity)
+// the tally's lean form (fused-filter presets): no plane and no flag is stored; flt_count as above, and every pass-1 survivor's record in `stage`
+// with its (tile, rank in tile) in `stage_key` (int2), in the order the tiles drew their slots -- launch_k2_place orders them
+void launch_k1_pileup_lean(const BatchView& b, const DevParams& p, const int32_t* tile_region, const int32_t* tile_col0,
+                           int32_t n_tiles, int64_t n_cols, const int32_t* tile_fill, const int32_t* chunk_off, const void* chunks,
+                           const unsigned long long* recs, const int32_t* tile_nbase, const int32_t* order, int32_t* tiles_tmp /* zeroed before K0 */, hipStream_t s,
+                           int32_t* flt_count, Survivor* stage, void* stage_key, int32_t stage_cap);
+// staged record i < min(*n_staged, stage_cap) -> out[tile_off[tile] + rank] (dropped at out_cap and beyond): (tile, column) order whatever the staging order was
+void launch_k2_place(const Survivor* stage, const void* stage_key, const int32_t* n_staged, int32_t stage_cap, const int32_t* tile_off,
+                     Survivor* out, int32_t out_cap, hipStream_t s);
 void launch_k1_empty_tiles(const BatchView& b, const int32_t* tile_region, const int32_t* tile_col0, int32_t n_tiles, int64_t n_cols,
                            const int32_t* tile_nbase, uint32_t* planes, const int32_t* order, const int32_t* tiles_tmp, hipStream_t s);
 void launch_k1_zonefix(const BatchView& b, const ReadBin* rbin, int D, int L, int64_t n_cols, uint32_t* planes, hipStream_t s);

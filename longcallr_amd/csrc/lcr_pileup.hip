@@ -1,5 +1,6 @@
 // lcr_pileup.hip — the pileup stage's host driver (K0: CIGAR decode into per-tile records, the tile passes, K1: the tally) and
-// lcr_get_columns.  lcr_pileup is a short sequence of steps; each step's name says what it queues or waits for.
+// lcr_get_columns, with the two functions that bring c->planes up to date for a reader (planes_tally, planes_materialise).  lcr_pileup is a
+// short sequence of steps; each step's name says what it queues or waits for.
 #include "lcr_ctx.h"
 
 namespace {
@@ -71,7 +72,7 @@ int pile_queue_k0(lcr_ctx* c, const PileScratch& L, const PilePools& P, bool& ga
 // tile order for K1, introns per whole tile, chunk offsets, K0's accounting (one workgroup); K0's verdict (CIGAR
 // validation, pool overflow) and counts then leave for the host before the rest is queued: the host waits for them while
 // K1 runs and returns without waiting for K1 -- later calls queue behind it
-int pile_queue_tally(lcr_ctx* c, const PileScratch& L, const PilePools& P, bool fuse) {
+int pile_queue_tally(lcr_ctx* c, const PileScratch& L, const PilePools& P, bool fuse, bool lean) {
   BatchView& b = c->bv;
   const int nt = c->n_tiles;
   int32_t* const fill = c->k0_tile_fill.as<int32_t>();
@@ -90,10 +91,16 @@ int pile_queue_tally(lcr_ctx* c, const PileScratch& L, const PilePools& P, bool 
       launch_k0_desc_bin(d_ctl, (const unsigned int*)(fill + L.acct), P.desc_sub, c->desc_tile.as<uint32_t>(), c->desc_val.p, c->chunk_off.as<int32_t>(), fill + L.cur,
                          c->chunks.p, P.n_blocks / 8 + 1, c->stream);
     // ---- K1: per-tile tally from the records (leaves at once if K0 flagged an error) -- the record-free tiles' planes stay
-    // unwritten (planes_dense) --; K1z: poly-A / homopolymer mask of the HiFi presets
-    launch_k1_pileup(b, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols, fill, c->chunk_off.as<int32_t>(),
-                     c->chunks.p, c->k0_items.as<unsigned long long>(), c->tile_nbase.as<int32_t>(), c->planes.as<uint32_t>(),
-                     c->tile_order.as<int32_t>(), fill + L.tmp, c->stream, fuse ? c->flags.as<uint8_t>() : nullptr, fuse ? c->tile_count.as<int32_t>() : nullptr);
+    // unwritten (planes_dense), and in the lean form those of the tiles with records as well (planes_tallied): the survivors of pass 1 are staged
+    // for lcr_candidates instead --; K1z: poly-A / homopolymer mask of the HiFi presets
+    if (lean)
+      launch_k1_pileup_lean(b, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols, fill, c->chunk_off.as<int32_t>(),
+                            c->chunks.p, c->k0_items.as<unsigned long long>(), c->tile_nbase.as<int32_t>(), c->tile_order.as<int32_t>(), fill + L.tmp,
+                            c->stream, c->tile_count.as<int32_t>(), c->sv_stage.as<Survivor>(), c->sv_stage_key.p, c->sv_stage_cap);
+    else
+      launch_k1_pileup(b, c->dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), nt, c->n_cols, fill, c->chunk_off.as<int32_t>(),
+                       c->chunks.p, c->k0_items.as<unsigned long long>(), c->tile_nbase.as<int32_t>(), c->planes.as<uint32_t>(),
+                       c->tile_order.as<int32_t>(), fill + L.tmp, c->stream, fuse ? c->flags.as<uint8_t>() : nullptr, fuse ? c->tile_count.as<int32_t>() : nullptr);
     if (!c->dp.ont && c->dp.dist_to_end > 0)
       launch_k1_zonefix(b, c->read_bin.as<ReadBin>(), c->dp.dist_to_end, c->dp.polya_len, c->n_cols, c->planes.as<uint32_t>(), c->stream); }
   HIPCHK(c, hipGetLastError());
@@ -113,8 +120,26 @@ int pile_read_verdict(lcr_ctx* c, K0Ctl* out, bool* retry) {
   return LCR_OK;
 }
 
-// the record-free tiles' constant planes of the current pileup, stored once when somebody asks for every column (lcr_ctx::planes_dense)
+}  // namespace
+
+// the planes of the tiles with records, when the current pileup's tally ran in its lean form: the same kernel in its full form over the tile order,
+// n_full, chunk tables and record pool that pileup left (lcr_ctx.h: nothing else rewrites them) -- once, when a reader of the planes turns up.
+// with_filter: pass 1's flags and per-tile counts too, for the pileup's own parameters (lcr_candidates' fallback on k2_compact).
+int planes_tally(lcr_ctx* c, bool with_filter) {
+  if (c->planes_tallied && !with_filter) return LCR_OK;   // (with_filter is asked for behind a lean tally only: the flags were never stored)
+  if (with_filter) HIPCHK(c, c->flags.reserve(std::max<size_t>(c->n_cols, 1)));
+  launch_k1_pileup(c->bv, c->flt_dp, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), c->n_tiles, c->n_cols, c->k0_tile_fill.as<int32_t>(),
+                   c->chunk_off.as<int32_t>(), c->chunks.p, c->k0_items.as<unsigned long long>(), c->tile_nbase.as<int32_t>(), c->planes.as<uint32_t>(),
+                   c->tile_order.as<int32_t>(), c->k0_tile_fill.as<int32_t>() + pile_scratch(c->n_tiles).tmp, c->stream,
+                   with_filter ? c->flags.as<uint8_t>() : nullptr, with_filter ? c->tile_count.as<int32_t>() : nullptr);
+  HIPCHK(c, hipGetLastError());
+  c->planes_tallied = true;
+  return LCR_OK;
+}
+
+// ... and the record-free tiles' constant planes of the current pileup behind them, stored once when somebody asks for every column (lcr_ctx::planes_dense)
 int planes_materialise(lcr_ctx* c) {
+  { int rc = planes_tally(c, false); if (rc) return rc; }
   if (c->planes_dense) return LCR_OK;
   launch_k1_empty_tiles(c->bv, c->tile_region.as<int32_t>(), c->tile_col0.as<int32_t>(), c->n_tiles, c->n_cols, c->tile_nbase.as<int32_t>(),
                         c->planes.as<uint32_t>(), c->tile_order.as<int32_t>(), c->k0_tile_fill.as<int32_t>() + pile_scratch(c->n_tiles).tmp, c->stream);
@@ -123,7 +148,21 @@ int planes_materialise(lcr_ctx* c) {
   return LCR_OK;
 }
 
-}  // namespace
+// what the byte getters add behind a lean tally: 48 bytes per survivor it stored (S').  The host reads the tally's counter once, unless
+// lcr_candidates has had the number already.
+int pile_staged_bytes(lcr_ctx* c, int64_t* bytes) {
+  *bytes = 0;
+  if (!c->pile_lean || c->stage < ST_PILED) return LCR_OK;
+  if (c->sv_stage_n < 0) {
+    int32_t n = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(&n, c->k0_tile_fill.as<int32_t>() + pile_scratch(c->n_tiles).tmp + K1_TMP_STAGED, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sv_stage_n = std::min(n, c->sv_stage_cap);
+  }
+  *bytes = (int64_t)sizeof(Survivor) * c->sv_stage_n;
+  return LCR_OK;
+}
 
 extern "C" {
 
@@ -150,13 +189,22 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   // pass 1 of the candidate filters inside the tally's epilogue (k2_eval.h): presets whose planes are final when K1 stores them (ONT: the
   // HiFi presets subtract the poly-A mask afterwards, k1_zonefix); lcr_candidates uses the flags if it is called with the same filters
   const bool fuse = c->dbg_fuse_filter != 0 && c->dp.ont && nt > 0;
-  if (fuse) { HIPCHK(c, c->flags.reserve(std::max<size_t>(c->n_cols, 1))); HIPCHK(c, c->tile_count.reserve(std::max(nt, 1) * 4)); }
+  // the tally's lean form (k1_pileup.hip): no planes and no flags for the tiles with records either, the survivors of pass 1 handed to lcr_candidates
+  // as staged records -- from a context's second batch on, when the last candidate stage left a guess of their number to size the staging by
+  const bool lean = fuse && c->sv_cap_guess > 0 && c->dbg_lean_planes != 0;
+  if (fuse) HIPCHK(c, c->tile_count.reserve(std::max(nt, 1) * 4));
+  if (fuse && !lean) HIPCHK(c, c->flags.reserve(std::max<size_t>(c->n_cols, 1)));
+  if (lean) {
+    c->sv_stage_cap = c->sv_cap_guess;
+    HIPCHK(c, c->sv_stage.reserve((size_t)c->sv_stage_cap * sizeof(Survivor)));
+    HIPCHK(c, c->sv_stage_key.reserve((size_t)c->sv_stage_cap * 8));
+  }
   K0Ctl ctl{};
   bool gated = false;   // (the gate on a phase stage in flight is queued once: pile_queue_k0)
   for (bool retry = true; retry;) {
     if ((rc = pile_reserve_pools(c, P))) return rc;
     if ((rc = pile_queue_k0(c, L, P, gated))) return rc;
-    if ((rc = pile_queue_tally(c, L, P, fuse))) return rc;
+    if ((rc = pile_queue_tally(c, L, P, fuse, lean))) return rc;
     if ((rc = pile_read_verdict(c, &ctl, &retry))) return rc;
     if (retry) {   // grow to what the fullest shard asked for
       P.pool_cap64 = std::max<size_t>(P.pool_cap64 * 2, ((size_t)ctl.pool_top + 1024) * P.n_shards);
@@ -167,10 +215,13 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   // bytes K1 itself has to move: read bases once + 8-byte records + reference byte per column, 13 u32
   // planes written per column of a tile with records (the record-free tiles' planes are not written by this stage)
   // (8 bytes per M / D / I / N item: the extra records of items that cross a tile boundary are overhead, not algorithm)
-  const int64_t plane_cols = c->n_cols - (int64_t)ctl.empty_cols;
+  // A lean tally stores no plane: 48 bytes per staged survivor instead, added by the getters (lcr_api.hip) once their number is known -- the tally
+  // is still running here.  A later replay of the planes for a getter is not the stage's traffic, as k1_empty_tiles is not.
+  const int64_t plane_cols = lean ? 0 : c->n_cols - (int64_t)ctl.empty_cols;
   c->pileup_bytes = c->n_bases + 8 * (int64_t)(int32_t)ctl.n_items + c->n_cols + 4 * LCR_NPLANES * plane_cols;
   c->stage_bytes = c->n_bases + 4 * c->n_cigar + 37 * (int64_t)c->bv.n_reads + c->n_cols + 4 * LCR_NPLANES * plane_cols;
   c->stage = ST_PILED;
+  c->planes_tallied = !lean; c->sv_staged = c->pile_lean = lean; c->sv_stage_n = -1;
   c->flt_fused = fuse; c->flt_dp = c->dp;
   c->pile_platform = p->platform; c->pile_dist_to_end = p->dist_to_end;
   return LCR_OK;
