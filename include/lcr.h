@@ -271,6 +271,30 @@ int lcr_get_candidates_device(lcr_ctx*, const lcr_candidate** dev_cand, int32_t*
 int lcr_import_candidates(lcr_ctx*, const lcr_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* genotype,
                           const float* qual);
 
+/* The exon-only mask (longcallR --exon-only -a annotation; candidate.rs:73-89): lcr_candidates drops, first of all its filters, every
+ * column that lies in no interval of its region's list.  Region g of the BOUND batch owns intervals [iv_off[g], iv_off[g + 1]) of
+ * iv_start0 / iv_end0 (iv_off: n_regions + 1 entries, iv_off[0] == 0, ascending), in reference coordinates, 0-based half-open -- in any
+ * order, overlapping, nested or abutting; an interval that reaches past the region is clipped to it, one outside it is ignored, one with
+ * end0 == start0 sets nothing.  A region without an interval has every column masked out: no record.  iv_off == NULL clears the mask (the
+ * other two arguments are not read); so do lcr_load_batch of any batch and lcr_bind_batch -- the mask belongs to the bound batch.
+ * A masked column is absent from the dense-cluster sweep too (candidate.rs:465-526): the result is not the unmasked record list with
+ * records deleted.  The pileup does not depend on the mask -- lcr_get_columns behind a masked pileup returns what it returns without
+ * one -- and lcr_import_candidates ignores it (thread.rs:107-116 gives the imported sites no mask).
+ * mem = LCR_MEM_HOST: the arrays are copied before the call returns (no host wait).  mem = LCR_MEM_DEVICE: the arrays are read in
+ * place on the context's stream -- complete with respect to that stream when the call is made, valid and unchanged until the stream
+ * has passed the call (any lcr_get_*, lcr_pileup, lcr_ctx_sync) --; they are checked by a kernel whose verdict the call waits for
+ * (its one host wait).
+ * Needs a bound batch (LCR_E_STATE).  LCR_E_ARG, nothing changed: iv_off[0] != 0, a descending iv_off, end0 < start0, NULL interval
+ * arrays beside a non-zero count, a mem that is neither.  Stage: before lcr_pileup a set or clear moves nothing.  After lcr_pileup it
+ * leaves the pileup valid and the context AT the pileup: the stage calls and getters behind it return LCR_E_STATE until a candidate
+ * stage has run again (lcr_collect_phase keeps the last lcr_phase's results until then, as across lcr_load_batch).  The filter
+ * verdicts lcr_pileup computed in passing on the ONT presets count as made under another filter: the next lcr_candidates takes its
+ * own pass over the planes. */
+int lcr_set_exon_mask(lcr_ctx*, int32_t mem, const int32_t* iv_off, const int64_t* iv_start0, const int64_t* iv_end0);
+/* HIP-event time (ms) of the last lcr_set_exon_mask's kernels (the plane's clear and the builder) with timing enabled (lcr_enable_timing);
+ * LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_exon_mask_ms(lcr_ctx*, float* ms);
+
 /* replaces SNPFrag::get_fragments (fragment.rs:10-309); thread.rs:136-143.
  * Reads the records of the last candidate stage (lcr_candidates or lcr_import_candidates); may be repeated until lcr_phase runs.
  * lcr_phase rewrites those records (FOR_PHASING, variant type, genotype: the post-phase steps), so after it lcr_fragments returns

@@ -19,7 +19,7 @@ SYMBOLS = [
     "lcr_junctions", "lcr_get_junctions", "lcr_ase", "lcr_get_ase", "lcr_vcf_contig_alleles",
     "lcr_assign_genes", "lcr_get_read_genes", "lcr_ase_genes", "lcr_get_ase_genes",
     "lcr_junctions_genes", "lcr_get_junctions_genes", "lcr_asj_genes", "lcr_get_asj_genes",
-    "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
+    "lcr_set_exon_mask", "lcr_exon_mask_ms", "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
 ]
 
 _lib = None
@@ -102,6 +102,8 @@ def load():
     l.lcr_bam_write_phased.argtypes = [vp, C.c_char_p, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_char_p, vp, vp, C.c_int32, C.c_int32]
     l.lcr_bam_write_reads.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(_abi.LcrReads), C.c_int32, C.c_int32]
     l.lcr_import_candidates.argtypes = [vp, C.POINTER(_abi.LcrParams), C.c_int32, C.c_int32, vp, vp, vp]
+    l.lcr_set_exon_mask.argtypes = [vp, C.c_int32, vp, vp, vp]
+    l.lcr_exon_mask_ms.argtypes = [vp, C.POINTER(C.c_float)]
     l.lcr_set_downsample.argtypes = [vp, C.c_uint32, C.c_uint64]
     l.lcr_set_downsample_rows.argtypes = [vp, C.c_int32, C.c_int32, vp]
     l.lcr_get_downsample.argtypes = [vp, C.POINTER(_abi.LcrDownsampleInfo)]

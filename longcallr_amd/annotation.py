@@ -1,5 +1,6 @@
 """Gene annotation for the per-gene allele-specific tables: GTF / GFF3 -> per contig the arrays Engine.assign_genes takes
-(include/lcr.h: lcr_gene_annotation).  Plain Python, gene-scale only: the read-scale work -- every read against every candidate gene's
+(include/lcr.h: lcr_gene_annotation) -- and, at the end of the file and with rules of its own, the calling annotation of --exon-only
+(calling_annotation, intersect_regions, region_intervals).  Plain Python, gene-scale only: the read-scale work -- every read against every candidate gene's
 exons -- is K8 on the GPU.
 
 Restates get_gene_regions and merge_gene_exon_regions of allele_specific/longcallR-ase.py (:64-194):
@@ -169,3 +170,103 @@ def gene_features(path, gene_types=GENE_TYPES):
                 continue
             genes[a["gene_id"]] = (parts[0], a["gene_id"], a.get("gene_name", "."), int(parts[3]), int(parts[4]))
     return list(genes.values())
+
+
+# ---- the calling annotation of --exon-only (longcallR -a / --exon-only): another parser than the scripts' above ----------------------------
+# Restates parse_annotation, intersect_gene_regions(merge = true) and the per-region CDS list of the reference (util.rs:334-556,
+# thread.rs:80-92) as they are, oddities included:
+#   * lines that start with '#' are skipped, every other line is split on tabs; only the features `gene` and `CDS` count, no gene type filter;
+#   * a `gene` line first stores the CDS list collected so far under the CURRENT gene id, if it is not empty -- a plain insert: a gene id that
+#     comes again replaces its earlier list --, then takes its id from the first attribute that starts with `gene_id=` (GFF3) or `gene_id `
+#     (GTF, quotes trimmed); without one the previous gene's id stays.  Its span joins the contig's stack of clusters: behind the top
+#     cluster's end (abutting included) it starts a new one, else it extends or lies inside the top one, whose id string grows by ",id";
+#   * a `CDS` line must carry the current gene id and adds its interval to the list; the last list is stored at the end of the file.
+# Coordinates leave this module 0-based half-open: a line's 1-based inclusive [a, b] is [a - 1, b).
+
+def _calling_gene_id(attrs):
+    for part in attrs.rstrip().split(";"):
+        part = part.strip()
+        if part.startswith("gene_id="):
+            return part[len("gene_id="):]
+        if part.startswith("gene_id "):
+            return part[len("gene_id "):].strip('"')
+    return None
+
+
+def calling_annotation(path):
+    """-> (clusters, cds): clusters = {contig: [(start0, end0, (gene_id, ...)), ...]} in file order, the merged gene spans with the ids of
+    their genes (the reference's comma-joined id string, split on ","); cds = {gene_id: [(start0, end0), ...]} in file order, unmerged.
+    Plain or .gz.  ValueError with the line's number for: a gene that starts in front of the top cluster of its contig ("annotation file is
+    not sorted"), a CDS whose gene id is not the current gene's, a line without its five leading fields or with a start / end that is no
+    unsigned integer (the reference panics on each)."""
+    path = str(path)
+    stacks, cds = {}, {}     # contig -> [[start0, end0, id string]]
+    invs, gene_id = [], ""
+    with (gzip.open if path.endswith(".gz") else open)(path, "rt") as f:
+        for n, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if line.startswith("#"):
+                continue
+            parts = line.split("\t")
+            try:
+                contig, feature, start, end = parts[0], parts[2], int(parts[3]), int(parts[4])
+                if start < 0 or end < 0:
+                    raise ValueError
+            except (IndexError, ValueError):
+                raise ValueError("%s line %d: not an annotation line (want tab-separated fields with an unsigned start and end)" % (path, n)) from None
+            if feature not in ("gene", "CDS"):
+                continue
+            if len(parts) < 9:
+                raise ValueError("%s line %d: a %s line without an attribute field" % (path, n, feature))
+            if feature == "gene":
+                if invs:
+                    cds[gene_id] = invs
+                    invs = []
+                got = _calling_gene_id(parts[8])
+                if got is not None:
+                    gene_id = got
+                stack = stacks.setdefault(contig, [])
+                s0, e0 = start - 1, end
+                if not stack:
+                    stack.append([s0, e0, gene_id])
+                    continue
+                top = stack[-1]
+                if s0 < top[0]:
+                    raise ValueError("%s line %d: annotation file is not sorted. %s:%d-%d" % (path, n, contig, start, end))
+                if top[1] <= s0:              # (the top's end is exclusive: abutting is no overlap)
+                    stack.append([s0, e0, gene_id])
+                else:
+                    top[1] = max(top[1], e0)  # extends the top cluster, or lies inside it
+                    top[2] += "," + gene_id
+            else:
+                got = _calling_gene_id(parts[8])
+                if (got or "") != gene_id:
+                    raise ValueError("%s line %d: gene_id in gene and exon are different: gene_id:%s, exon_gene_id:%s" % (path, n, gene_id, got or ""))
+                invs.append((start - 1, end))
+    if invs:
+        cds[gene_id] = invs
+    return {c: [(s, e, tuple(ids.split(","))) for s, e, ids in st] for c, st in stacks.items()}, cds
+
+
+def intersect_regions(start0, length, clusters):
+    """One contig's discovered regions against its clusters (calling_annotation()[0][contig], or None / [] for a contig the annotation does
+    not name: it loses its regions).  start0 / length: the regions, in order.  -> [(start0, len, region index, ids)]: for every region q,
+    in order, one clipped region per cluster h with h.start < q.end and h.end > q.start, in cluster order -- [max(starts), min(ends)) with
+    h's ids; the region index says whose max_coverage it keeps."""
+    out = []
+    for q, (qs, ql) in enumerate(zip(start0, length)):
+        qs, qe = int(qs), int(qs) + int(ql)
+        for hs, he, ids in clusters or ():
+            if hs < qe and he > qs:
+                s, e = max(qs, hs), min(qe, he)
+                out.append((s, e - s, q, ids))
+    return out
+
+
+def region_intervals(ids, cds):
+    """thread.rs:80-92: the CDS list of a clipped region = the lists of its ids, one after the other (an id without a list gives nothing;
+    an id named twice gives its list twice).  Empty: the region is skipped altogether."""
+    out = []
+    for gid in ids:
+        out.extend(cds.get(gid, ()))
+    return out

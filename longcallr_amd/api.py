@@ -50,6 +50,8 @@ class Engine:
         self.params = params if params is not None else _abi.make_params()
         self._sites = None   # device tensors of the last import_external_candidates: its kernels read them after the call returns
         self._keep = None
+        self._n_regions = None   # regions of the bound batch (set_exon_mask sizes iv_off by it)
+        self._mask_keep = None
         self.last_truncated_columns = 0   # columns above the cap of the last discover_regions(truncation=True)
         if timing:
             self.lib.lcr_enable_timing(self.h, 1)
@@ -85,6 +87,7 @@ class Engine:
     def sync(self):
         self._chk(self.lib.lcr_ctx_sync(self.h), "lcr_ctx_sync")
         self._sites = None
+        self._mask_keep = None   # (device intervals of the last set_exon_mask: the builder has read them)
 
     def set_async_phase(self, on=True):
         """lcr_ctx_set_async_phase: phase() returns with its kernels in flight; getters / sync() collect the results (include/lcr.h)"""
@@ -104,6 +107,7 @@ class Engine:
             reads, regions, keep = batch
             self._keep = (keep, reads, regions)
         self._chk(self.lib.lcr_load_batch(self.h, C.byref(reads), C.byref(regions)), "lcr_load_batch")
+        self._n_regions = int(regions.n_regions)
         return self
 
     def load_batch_async(self, batch, slot):
@@ -118,6 +122,7 @@ class Engine:
 
     def bind_batch(self, slot):
         self._chk(self.lib.lcr_bind_batch(self.h, int(slot)), "lcr_bind_batch")
+        self._n_regions = int(self._keep_slot[int(slot)][2].n_regions)
         return self
 
     def discover_regions(self, ref_start, ref_end, contig_len, truncation=False, truncation_coverage=200000):
@@ -183,6 +188,59 @@ class Engine:
         self._chk(self.lib.lcr_import_candidates(self.h, C.byref(self.params), _abi.LCR_MEM_HOST, int(p.size), p.ctypes.data, g.ctypes.data,
                                                  q.ctypes.data), "lcr_import_candidates")   # (host arrays are copied before the call returns)
         return self
+
+    def set_exon_mask(self, iv_off, start0, end0, mem=None):
+        """lcr_set_exon_mask on the bound batch (longcallR --exon-only; include/lcr.h): region g owns intervals [iv_off[g], iv_off[g + 1])
+        of start0 / end0, reference coordinates, 0-based half-open, in any order; get_candidate_snps then drops every column outside them.
+        numpy arrays or sequences (converted to int32 / int64 / int64 and copied: LCR_MEM_HOST), or contiguous tensors of those types on
+        this engine's device, read in place (LCR_MEM_DEVICE) and held by the engine until sync() or the next mask.  mem: None = by the
+        arguments' kind, or _abi.LCR_MEM_HOST / LCR_MEM_DEVICE to insist.  The mask lasts until load_batch / bind_batch or clear_exon_mask()."""
+        if self._n_regions is None:
+            raise LcrError("set_exon_mask before load_batch / bind_batch")
+        if len(iv_off) != self._n_regions + 1:
+            raise ValueError("iv_off needs n_regions + 1 = %d entries, got %d" % (self._n_regions + 1, len(iv_off)))
+        ts = (iv_off, start0, end0)
+        dev = any(getattr(t, "is_cuda", False) for t in ts)
+        if mem is not None and mem not in (_abi.LCR_MEM_HOST, _abi.LCR_MEM_DEVICE):
+            raise ValueError("mem must be _abi.LCR_MEM_HOST or _abi.LCR_MEM_DEVICE, got %r" % (mem,))
+        if mem is not None and (mem == _abi.LCR_MEM_DEVICE) != dev:
+            raise ValueError("mem does not match the arrays: device tensors go with LCR_MEM_DEVICE, host arrays with LCR_MEM_HOST")
+        if dev:
+            import torch
+            for name, t, dt in zip(("iv_off", "start0", "end0"), ts, (torch.int32, torch.int64, torch.int64)):
+                if not getattr(t, "is_cuda", False) or t.dtype != dt or t.device.index != self.device or t.dim() != 1 or not t.is_contiguous():
+                    raise ValueError("device intervals: %s must be a contiguous 1-d %s tensor on device %d" % (name, dt, self.device))
+            if start0.numel() != end0.numel():
+                raise ValueError("start0 and end0 must have the same length")
+            torch.cuda.current_stream(self.device).synchronize()   # (the tensors may still be being written on torch's stream)
+            if int(iv_off[-1]) > start0.numel():   # (the library takes the interval count from iv_off: it must not read past the tensors)
+                raise ValueError("iv_off ends at %d, beyond the %d intervals" % (int(iv_off[-1]), start0.numel()))
+            self._chk(self.lib.lcr_set_exon_mask(self.h, _abi.LCR_MEM_DEVICE, C.c_void_p(iv_off.data_ptr()),
+                                                 C.c_void_p(start0.data_ptr()) if start0.numel() else None,
+                                                 C.c_void_p(end0.data_ptr()) if end0.numel() else None), "lcr_set_exon_mask")
+            self._mask_keep = ts
+            return self
+        o = np.ascontiguousarray(iv_off, dtype=np.int32)
+        s = np.ascontiguousarray(start0, dtype=np.int64)
+        e = np.ascontiguousarray(end0, dtype=np.int64)
+        if s.size != e.size:
+            raise ValueError("start0 and end0 must have the same length")
+        if o[-1] != s.size and o[0] == 0 and np.all(np.diff(o) >= 0):   # (offsets the library would refuse are left to it)
+            raise ValueError("iv_off must end at the number of intervals (%d), got %d" % (s.size, int(o[-1])))
+        self._chk(self.lib.lcr_set_exon_mask(self.h, _abi.LCR_MEM_HOST, o.ctypes.data, s.ctypes.data if s.size else None,
+                                             e.ctypes.data if e.size else None), "lcr_set_exon_mask")   # (host arrays are copied before the call returns)
+        return self
+
+    def clear_exon_mask(self):
+        """lcr_set_exon_mask(NULL): the bound batch has no exon mask any more"""
+        self._chk(self.lib.lcr_set_exon_mask(self.h, _abi.LCR_MEM_HOST, None, None, None), "lcr_set_exon_mask")
+        return self
+
+    def exon_mask_ms(self):
+        """lcr_exon_mask_ms: HIP-event time of the last set_exon_mask's kernels (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_exon_mask_ms(self.h, C.byref(ms)), "lcr_exon_mask_ms")
+        return float(ms.value)
 
     def _release_sites(self):
         """drop the device sites of the last import once its kernels are done (they are queued behind the call's return)"""

@@ -552,7 +552,7 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
       uint32_t cnt[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) cnt[k] = f[k] + rv[k];
-      const ColEval ev = eval_counts(cnt, R, prm, bt, [&]() { return pl[P_DIFF_D * TSTRIDE + col]; }, [&]() { return nbase + pl[P_DIFF_N * TSTRIDE + col]; },
+      const ColEval ev = eval_counts(cnt, R, prm, bt, b.exon_mask, o, [&]() { return pl[P_DIFF_D * TSTRIDE + col]; }, [&]() { return nbase + pl[P_DIFF_N * TSTRIDE + col]; },
                                      [&](int k) { return f[k]; });
       if (!LEAN) flt_flags[o] = ev.pass ? 1 : 0;
       n_pass += ev.pass ? 1 : 0;

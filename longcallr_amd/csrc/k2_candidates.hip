@@ -164,11 +164,11 @@ void launch_scan_i32_to_i64(DevBuf& tmp, const int32_t* in, int64_t* out_excl, i
 __global__ void k2_sor_threshold(float* out) { *out = strand_odds_ratio(5, 5, 9, 1); }  // candidate.rs:49-51
 
 __device__ __forceinline__ ColEval eval_column(const uint32_t* __restrict__ planes, int64_t n_cols, int64_t o, uint8_t ref_base,
-                                               const DevParams& prm, const BinomTable& bt) {
+                                               const DevParams& prm, const BinomTable& bt, const uint32_t* __restrict__ exon_mask) {
   uint32_t cnt[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) { cnt[k] = planes[(int64_t)(LCR_PL_A + k) * n_cols + o]; }
-  return eval_counts(cnt, ref_base, prm, bt,
+  return eval_counts(cnt, ref_base, prm, bt, exon_mask, o,
                      [&]() { return planes[(int64_t)LCR_PL_D * n_cols + o]; }, [&]() { return planes[(int64_t)LCR_PL_N * n_cols + o]; },
                      [&](int k) { return planes[(int64_t)(LCR_PL_FWD_A + k) * n_cols + o]; });
 }
@@ -188,7 +188,7 @@ k2_filter(BatchView b, DevParams prm, BinomTable bt, const int32_t* __restrict__
   __syncthreads();
   int mine = 0;
   for (int col = threadIdx.x; col < tlen; col += LCR_BLOCK) {
-    ColEval ev = eval_column(planes, n_cols, gcol0 + col, b.ref[gcol0 + col], prm, bt);
+    ColEval ev = eval_column(planes, n_cols, gcol0 + col, b.ref[gcol0 + col], prm, bt, b.exon_mask);
     flags[gcol0 + col] = ev.pass ? 1 : 0;
     mine += ev.pass ? 1 : 0;
   }
@@ -233,7 +233,7 @@ k2_compact(BatchView b, DevParams prm, BinomTable bt, const int32_t* __restrict_
   for (int k = 0; k < 4; k++) {
     if (!f[k]) continue;
     const int col = tid * 4 + k;
-    ColEval ev = eval_column(planes, n_cols, gcol0 + col, b.ref[gcol0 + col], prm, bt);
+    ColEval ev = eval_column(planes, n_cols, gcol0 + col, b.ref[gcol0 + col], prm, bt, b.exon_mask);
     Survivor sv;
     sv.gcol = gcol0 + col; sv.region = g; sv.col = tc0 + col;
     sv.ref_base = ev.ref_base; sv.allele1 = ev.allele1; sv.allele2 = ev.allele2; sv.n_alt = ev.n_alt;

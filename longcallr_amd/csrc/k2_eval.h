@@ -64,16 +64,24 @@ __device__ __forceinline__ void two_major(const uint32_t cnt[4], uint8_t ref_bas
   *a1 = ch[order[0]]; *c1 = cnt[order[0]]; *a2 = ch[order[second]]; *c2 = cnt[order[second]];
 }
 
+// The exon-only mask (lcr_set_exon_mask, k2_exon.hip): one bit per global column of the bound batch, bit (gcol & 31) of word gcol >> 5; a column
+// whose bit is 0 lies in no CDS interval of its region and is dropped first of all (candidate.rs:73-89).  No plane: no mask, every column is in.
+__device__ __forceinline__ bool exon_bit(const uint32_t* __restrict__ mask, int64_t gcol) {
+  return !mask || ((mask[gcol >> 5] >> (gcol & 31)) & 1u);
+}
+
 // cnt[4]: A, C, G, T of the column; get_d / get_n / get_fwd(k): deletions, intron bases, forward-strand count of allele k -- asked for
-// only behind the early exits (k2_filter reads them from HBM then; K1 has them in registers)
+// only behind the early exits (k2_filter reads them from HBM then; K1 has them in registers).  exon_mask / gcol: exon_bit's arguments -- the
+// mask's word is loaded behind the depth test only (the filters have no side effects: the order of the exits does not show)
 template <class GetD, class GetN, class GetFwd>
 __device__ __forceinline__ ColEval eval_counts(const uint32_t cnt[4], uint8_t ref_base, const DevParams& prm, const BinomTable& bt,
-                                               GetD get_d, GetN get_n, GetFwd get_fwd) {
+                                               const uint32_t* __restrict__ exon_mask, int64_t gcol, GetD get_d, GetN get_n, GetFwd get_fwd) {
   ColEval ev;
   ev.pass = false;
   const uint32_t total = cnt[0] + cnt[1] + cnt[2] + cnt[3];
   ev.depth = total;
   if (total < prm.min_depth || total > prm.max_depth) return ev;  // candidate.rs:90-94
+  if (!exon_bit(exon_mask, gcol)) return ev;                      // candidate.rs:73-89
   // a reference byte other than upper-case ACGT never reaches a candidate (candidate.rs:132,243-265)
   if (!(ref_base == 'A' || ref_base == 'C' || ref_base == 'G' || ref_base == 'T')) return ev;
   two_major(cnt, ref_base, &ev.allele1, &ev.cnt1, &ev.allele2, &ev.cnt2);

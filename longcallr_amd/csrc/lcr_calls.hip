@@ -1,5 +1,6 @@
-// lcr_calls.hip — the host drivers of the candidate stage (lcr_candidates: K2 on the pileup; lcr_import_candidates: the caller's sites)
-// and of the fragment stage (lcr_fragments: K3), with their getters and the settle functions of the copies they leave in flight.
+// lcr_calls.hip — the host drivers of the candidate stage (lcr_candidates: K2 on the pileup; lcr_import_candidates: the caller's sites;
+// lcr_set_exon_mask: the column mask lcr_candidates' first filter pass reads) and of the fragment stage (lcr_fragments: K3), with their getters and
+// the settle functions of the copies they leave in flight.
 #include "lcr_ctx.h"
 
 // lcr_candidates / lcr_import_candidates leave their last copies in flight: candidate records, per-region offsets, rows per region
@@ -62,7 +63,7 @@ int cand_host_blocks(lcr_ctx* c, size_t n_max, lcr_candidate** hp, int32_t** ho)
 }
 
 // pass 1 of the candidate filters: flags per column, survivors per tile -- k2_filter, unless the tally's epilogue has taken the pass
-// already (lcr_pileup ran with the same filter parameters: ONT presets, k2_eval.h)
+// already (lcr_pileup ran with the same filter parameters and under the same exon mask: ONT presets, k2_eval.h)
 int cand_queue_pass1(lcr_ctx* c) {
   const int nt = c->n_tiles;
   HIPCHK(c, c->flags.reserve(std::max<size_t>(c->n_cols, 1)));
@@ -71,7 +72,8 @@ int cand_queue_pass1(lcr_ctx* c) {
   HIPCHK(c, c->total.reserve(16));
   const DevParams &fa = c->flt_dp, &fb = c->dp;
   const bool have_flt = c->flt_fused && c->dbg_fuse_filter != 0 && fa.ont == fb.ont && fa.min_depth == fb.min_depth && fa.max_depth == fb.max_depth && fa.low_cnt_cut == fb.low_cnt_cut &&
-                        fa.use_strand_bias == fb.use_strand_bias && fa.min_af_intron == fb.min_af_intron && fa.low_frac_cut == fb.low_frac_cut && fa.sor_threshold == fb.sor_threshold;
+                        fa.use_strand_bias == fb.use_strand_bias && fa.min_af_intron == fb.min_af_intron && fa.low_frac_cut == fb.low_frac_cut && fa.sor_threshold == fb.sor_threshold &&
+                        c->flt_mask_gen == c->mask_gen;
   if (!have_flt) { const int rc = planes_tally(c, false); if (rc) return rc; }   // (k2_filter reads the planes: a lean tally has not stored them)
   Timer t(c, LCR_K_CAND_FILTER);
   if (!have_flt) {
@@ -279,6 +281,68 @@ int lcr_import_candidates(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t 
   const int rc = cand_tail(c);
   HT("import:ret");
   return rc;
+}
+
+// The exon-only mask of the bound batch (include/lcr.h).  Refused calls change nothing: the lists are checked -- on the host, or by k2_exon_check,
+// whose verdict is the call's one wait -- before the plane is touched.  A set or clear behind lcr_pileup puts the context back at the pileup: the
+// candidate records were made under another mask.  The pileup itself does not depend on the mask; its fused verdicts do (mask_gen).
+int lcr_set_exon_mask(lcr_ctx* c, int32_t mem, const int32_t* iv_off, const int64_t* iv_start0, const int64_t* iv_end0) {
+  if (!c) return LCR_E_ARG;
+  if (mem != LCR_MEM_HOST && mem != LCR_MEM_DEVICE) { c->err = "lcr_set_exon_mask: mem not LCR_MEM_HOST / LCR_MEM_DEVICE"; return LCR_E_ARG; }
+  if (c->stage < ST_LOADED) { c->err = "lcr_set_exon_mask before lcr_load_batch"; return LCR_E_STATE; }
+  const char* const bad_lists = "lcr_set_exon_mask: iv_off must start at 0 and ascend, every interval needs end0 >= start0, and a non-zero count its two arrays";
+  const int ng = c->bv.n_regions;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t* plane = nullptr;
+  if (iv_off) {
+    int32_t n_iv = 0;
+    const int32_t* d_off = nullptr; const int64_t *d_s = nullptr, *d_e = nullptr;
+    if (mem == LCR_MEM_HOST) {
+      bool ok = iv_off[0] == 0;
+      for (int g = 0; g < ng && ok; g++) ok = iv_off[g] <= iv_off[g + 1];
+      n_iv = ok ? iv_off[ng] : 0;
+      ok = ok && (n_iv == 0 || (iv_start0 && iv_end0));
+      for (int32_t i = 0; i < n_iv && ok; i++) ok = iv_end0[i] >= iv_start0[i];
+      if (!ok) { c->err = bad_lists; return LCR_E_ARG; }
+    } else {   // (the one host wait of device-resident lists: their contract, as lcr_import_candidates checks its sites)
+      HIPCHK(c, c->h_imp_bad.reserve(64));
+      int32_t* verdict = c->h_imp_bad.as<int32_t>();
+      verdict[0] = verdict[1] = 0;
+      int32_t* d_verdict = nullptr;
+      HIPCHK(c, c->h_imp_bad.dev(&d_verdict));
+      launch_k2_exon_check(iv_off, iv_start0, iv_end0, ng, d_verdict, c->stream);
+      { const int rc = stream_wait(c, c->ev_imp); if (rc) return rc; }
+      if (((volatile int32_t*)verdict)[0]) { c->err = bad_lists; return LCR_E_ARG; }
+      n_iv = ((volatile int32_t*)verdict)[1];
+    }
+    { int rc = upload(c, c->ex_off, iv_off, (size_t)ng + 1, &d_off, mem); if (rc) return rc; }
+    { int rc = upload(c, c->ex_s, iv_start0, (size_t)n_iv, &d_s, mem); if (rc) return rc; }
+    { int rc = upload(c, c->ex_e, iv_end0, (size_t)n_iv, &d_e, mem); if (rc) return rc; }
+    const size_t words = (size_t)((c->n_cols + 31) / 32);
+    HIPCHK(c, c->exon_plane.reserve(std::max<size_t>(words, 1) * 4));
+    if (c->timing && !c->ev_mask_t[0]) for (hipEvent_t& e : c->ev_mask_t) HIPCHK(c, hipEventCreate(&e));
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev_mask_t[0], c->stream));
+    if (words) HIPCHK(c, lcr_fill_async(c->exon_plane.p, 0, words * 4, c->stream));
+    launch_k2_exon_build(c->bv, d_off, d_s, d_e, n_iv, c->exon_plane.as<uint32_t>(), c->stream);
+    if (c->timing) { HIPCHK(c, hipEventRecord(c->ev_mask_t[1], c->stream)); c->mask_timed = true; }
+    HIPCHK(c, hipGetLastError());
+    plane = c->exon_plane.as<uint32_t>();
+  }
+  c->bv.exon_mask = plane;
+  c->mask_gen++;
+  // behind the pileup: its planes stay, what the candidate stages made of them under the other mask goes (lcr_collect_phase keeps the last
+  // lcr_phase's results until the next candidate stage, as it does across lcr_load_batch)
+  rewind_to(c, ST_PILED);
+  return LCR_OK;
+}
+
+int lcr_exon_mask_ms(lcr_ctx* c, float* ms) {
+  if (!c || !ms) return LCR_E_ARG;
+  if (!c->timing || !c->mask_timed) { c->err = "lcr_exon_mask_ms: no lcr_set_exon_mask with timing enabled"; return LCR_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->ev_mask_t[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, c->ev_mask_t[0], c->ev_mask_t[1]));
+  return LCR_OK;
 }
 
 int lcr_get_candidates(lcr_ctx* c, lcr_candidate_list* out) {

@@ -150,6 +150,12 @@ struct lcr_ctx {
   int dbg_fuse_filter = 1;  // lcr_debug_set("fuse_filter"): 0 = pass 1 of the candidate filters always by k2_filter (its own pass over the planes)
   bool flt_fused = false;   // the last lcr_pileup left k2_filter's flags and per-tile counts (ONT presets: no poly-A pass behind the tally)
   DevParams flt_dp{};       // ... computed with these parameters
+  // the exon-only mask (lcr_set_exon_mask): bv.exon_mask names the plane while a mask is set (nullptr: none; rewind_to clears it with the binding).
+  // Every set or clear draws a new mask_gen; lcr_pileup notes the one its epilogue filtered under (flt_mask_gen), cand_queue_pass1 compares.
+  uint64_t mask_gen = 0, flt_mask_gen = 0;
+  DevBuf exon_plane, ex_off, ex_s, ex_e;   // the bit plane; host interval lists copied to HBM
+  hipEvent_t ev_mask_t[2] = {};            // timing enabled: around the last build (clear + k2_exon_build), created on first use
+  bool mask_timed = false;
   int dbg_k3_hits = 1;      // lcr_debug_set("k3_hits"): 0 = K3's count pass walks every read's CIGAR itself (the path of batches without hit lists)
   std::vector<lcr_candidate> h_cand;
   std::vector<int32_t> h_cand_off;
@@ -233,6 +239,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
     c->sv_staged = false;      // ... and the staged survivors
     c->flt_fused = false;      // the tally's epilogue has not left this pileup's pass-1 flags yet
   }
+  if (to < ST_LOADED) c->bv.exon_mask = nullptr;   // the exon mask names the columns of ONE bound batch
   if (to < ST_CALLED) {
     c->hits_valid = false;     // k2_hist's hit lists name the survivors of the candidate stage that is going away
     c->cand_used = false;      // the records lcr_phase rewrote are replaced by the next candidate stage

@@ -41,6 +41,8 @@ struct BatchView {
   const int32_t* read_region;        // n_reads: region index of each read
   int32_t* error_flag;               // != 0 -> unknown CIGAR op seen
   int32_t* read_rend;                // n_reads: region-relative column one past the read's last reference base (K0 pass 0)
+  // lcr_set_exon_mask: one bit per global column (k2_eval.h: exon_bit), or nullptr = no mask; read by pass 1 of the candidate filters only
+  const uint32_t* exon_mask;
 };
 
 // Per-read header packed once per batch (k0_pack) so that K0 needs a single 64-byte load per read.
@@ -280,6 +282,10 @@ void launch_k2_import_emit(const BatchView& b, int64_t n_cols, const uint32_t* p
                            int32_t n_sites, const int32_t* cand_off /* n_regions + 1 */, lcr_candidate* out, hipStream_t s,
                            lcr_candidate* h_cand /* pinned (device pointer): the records and ... */, int32_t* h_off /* ... their offsets, or nullptr */);
 void launch_k2_import_check(const int64_t* pos0, const uint8_t* gt, int32_t n_sites, int32_t* bad /* zeroed */, hipStream_t s);
+// k2_exon.hip: the exon-only mask (lcr_set_exon_mask).  The check of device-resident interval lists -> verdict[0] = 1 on a violation (zeroed by the
+// caller), verdict[1] = iv_off[n_regions]; the builder: the bits of every interval, clipped to its region, set in the cleared plane
+void launch_k2_exon_check(const int32_t* iv_off, const int64_t* iv_start0, const int64_t* iv_end0, int32_t n_regions, int32_t* verdict, hipStream_t s);
+void launch_k2_exon_build(const BatchView& b, const int32_t* iv_off, const int64_t* iv_start0, const int64_t* iv_end0, int32_t n_iv, uint32_t* plane /* (n_cols + 31) / 32 words, zeroed */, hipStream_t s);
 void launch_k3_region_entries(const int64_t* row_ptr, const int32_t* row_region_off, int32_t ng, int64_t* region_e_off, hipStream_t s, int64_t* host_out = nullptr);
 struct K3Hits {   // what k2_hist left for K3 (hit_cnt == nullptr: nothing -- K3 walks every read's CIGAR itself)
   const int32_t* hit_cnt; const void* hit_list; const int32_t* ovf_cnt; const int32_t* ovf_list;

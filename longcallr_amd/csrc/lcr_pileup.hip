@@ -222,7 +222,7 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
   c->stage_bytes = c->n_bases + 4 * c->n_cigar + 37 * (int64_t)c->bv.n_reads + c->n_cols + 4 * LCR_NPLANES * plane_cols;
   c->stage = ST_PILED;
   c->planes_tallied = !lean; c->sv_staged = c->pile_lean = lean; c->sv_stage_n = -1;
-  c->flt_fused = fuse; c->flt_dp = c->dp;
+  c->flt_fused = fuse; c->flt_dp = c->dp; c->flt_mask_gen = c->mask_gen;
   c->pile_platform = p->platform; c->pile_dist_to_end = p->dist_to_end;
   return LCR_OK;
 }

@@ -13,14 +13,18 @@ the five hot-path calls, with one context per GPU instead of one rayon task per 
   thread.rs:307-361 phased BAM                               -> lcr_bam_write_phased
 
   thread.rs:70-74,107-116 user-provided candidates (-v)   -> vcf.read_sites once + lcr_import_candidates per chunk
+  main.rs:216-225, thread.rs:80-92 -a / --exon-only          -> annotation.calling_annotation + intersect_regions per contig,
+                                                                lcr_set_exon_mask per chunk
 
-Not here (out of scope): gene annotation / exon filter, the somatic model.  Records are written in contig order of the .fai and position order inside
+Not here (out of scope): the somatic model.  Records are written in contig order of the .fai and position order inside
 a contig (the reference writes them in region-completion order, thread.rs:216-221: compare as a set)."""
 import os
 
 import numpy as np
 
 from . import _abi, annotation, api, ase, asj, bamio, vcf
+
+_ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
 VCF_HEADER_TAIL = (   # thread.rs:232-262, verbatim
     '##FILTER=<ID=PASS,Description="All filters passed">\n'
@@ -112,7 +116,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         asj_out=None, asj_min_count=10, asj_min_junctions=2,
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
-        asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, **param_overrides):
+        asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -167,10 +171,23 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     asj_min_junctions junctions per gene, summed over a contig's chunks and written for every `gene` feature of the annotation in file
     order (annotation.gene_features) beside the table (X.asj.tsv -> X.gene_coverage.tsv, any other name -> name +
     ".gene_coverage.tsv").  Adds the stats asj_exons (kept exon records, summed over chunks) and asj_coverage_genes (rows of the
-    coverage file)."""
+    coverage file).
+    annotation / exon_only: longcallR -a / --exon-only (main.rs:216-225, 436-438): a GTF / GFF3 (.gz) read by annotation.calling_annotation
+    -- every `gene` and `CDS` line, no gene type filter; not the parser of the two tables above.  exon_only without annotation is a
+    ValueError; annotation alone is parsed, so its errors surface, and changes nothing in any output.  With both, each contig's discovered
+    regions (plain or truncated) are clipped to the clusters of overlapping genes (annotation.intersect_regions: a contig the file does not
+    name loses its regions), a clipped region none of whose genes has a CDS is dropped before batching (thread.rs:88-91: no pileup, no
+    record, no phased read), and every chunk hands its regions' CDS lists to Engine.set_exon_mask between binding and the pileup:
+    candidates are called at CDS columns only, and a masked column does not count in the dense-cluster sweep either.  With input_vcf the
+    regions are clipped and dropped all the same, but no mask is set: the imported sites outside CDS are phased (thread.rs:107-116).  The
+    phased BAM tags the reads contained in a clipped region.  Adds the stats exon_regions (regions after clipping and dropping) and
+    exon_skipped_regions (dropped for want of CDS); regions stays the number discovered."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
+    if exon_only and annotation is None:
+        raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
+    gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
     if isinstance(truncation_coverage, bool) or int(truncation_coverage) != truncation_coverage or not 0 <= int(truncation_coverage) < 1 << 32:
         raise ValueError("truncation_coverage must be an integer in [0, 2^32) (the reference's u32), got %r" % (truncation_coverage,))
     truncation_coverage = int(truncation_coverage)
@@ -220,12 +237,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["imported_sites"] = 0
     if truncation:
         stats["truncated_columns"] = 0
+    if exon_only:
+        stats["exon_regions"] = stats["exon_skipped_regions"] = 0
     parental = ase.parental_sites(ase_parental_vcf) if ase_parental_vcf is not None else None    # {contig: (pos0, pat, mat)}
     dna = ase.dna_het_sites(ase_dna_vcf) if ase_dna_vcf is not None else None                    # {contig: pos0}
-    genes = annotation.load(ase_annotation, ase_gene_types) if ase_annotation is not None else None   # {contig: annotation.ContigGenes}
+    genes = _ann.load(ase_annotation, ase_gene_types) if ase_annotation is not None else None   # {contig: _ann.ContigGenes}
     jgenes = None                                                                                      # the same for the junction table
     if asj_annotation is not None:
-        jgenes = genes if genes is not None else annotation.load(asj_annotation, asj_gene_types)
+        jgenes = genes if genes is not None else _ann.load(asj_annotation, asj_gene_types)
     jdna = ase.dna_het_sites(asj_dna_vcf) if asj_dna_vcf is not None else None                   # {contig: pos0} for the junction table's filter
     no_sites = (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.float32))
 
@@ -254,10 +273,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["ps"] = res["phase_set"].copy()
             out["names"] = _gather_names(batch.name_off, batch.name_blob, fm["row_read"].astype(np.int64))
         if junc is not None and asj_modes:      # Engine.asj_genes' dict
-            out["junc"] = (name, junc["junc"], jgenes.get(name, annotation.ContigGenes())) + ((junc["exon"],) if asj_cluster_with_exons else ())
+            out["junc"] = (name, junc["junc"], jgenes.get(name, _ann.ContigGenes())) + ((junc["exon"],) if asj_cluster_with_exons else ())
             out["asj_exons"], out["gene_reads"] = int(junc["exon"].size), junc["gene_reads"]
         elif junc is not None and jgenes is not None:
-            out["junc"] = (name, junc, jgenes.get(name, annotation.ContigGenes()))
+            out["junc"] = (name, junc, jgenes.get(name, _ann.ContigGenes()))
         elif junc is not None:
             out["junc"] = (name, junc, batch.start0, batch.len)
         if arec is not None and genes is not None:      # (region, gene) pair records; merged per gene when every chunk is in
@@ -272,7 +291,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                                                   ase_min_support, ase_overdispersion),)
         results[idx] = out
 
-    def work(idx, batch, name, want_reads, imp):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates)
+    def work(idx, batch, name, want_reads, imp, mask):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None)
         with free_lock:
             while not free:
                 free_lock.wait()
@@ -284,6 +303,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             E.load_batch_async(batch, slot).bind_batch(slot)
             if genes is not None or jgenes is not None:     # one assignment per chunk, whichever table asks for it
                 E.assign_genes((genes if genes is not None else jgenes).get(name))
+            if mask is not None:
+                E.set_exon_mask(*mask)
             E.fill_data_into_freq_vec()
             if in_flight[k] is not None:
                 finish(k)
@@ -342,8 +363,22 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 stats["truncated_columns"] += scout.last_truncated_columns
             if not regions:
                 continue
-            ref = refs[name]
             stats["contigs"] += 1; stats["regions"] += len(regions)
+            cds_of = {}     # start0 of a clipped region -> its CDS list (clipped regions of a contig are disjoint)
+            if exon_only:   # main.rs:221-224, thread.rs:80-92
+                kept = []
+                for s0, l0, q, ids in _ann.intersect_regions([r[0] for r in regions], [r[1] for r in regions], gene_clusters.get(name)):
+                    iv = _ann.region_intervals(ids, gene_cds)
+                    if iv:
+                        kept.append((s0, l0, regions[q][2]))
+                        cds_of[s0] = iv
+                    else:
+                        stats["exon_skipped_regions"] += 1
+                regions = kept
+                stats["exon_regions"] += len(regions)
+                if not regions:
+                    continue
+            ref = refs[name]
             for chunk in chunk_regions(regions, max_cost=chunk_cost):
                 wins = [ref[s:s + l] if s + l <= ref.size else np.concatenate([ref[s:], np.full(s + l - ref.size, ord("N"), np.uint8)])
                         for s, l, _ in chunk]
@@ -355,9 +390,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     lo, hi = np.searchsorted(sp, [chunk[0][0], chunk[-1][0] + chunk[-1][1]])
                     imp = (sp[lo:hi], sg[lo:hi], sq[lo:hi])
                     stats["imported_sites"] += int(hi - lo)
+                mask = None
+                if exon_only and sites is None:     # (thread.rs:107-116: the imported sites get no mask)
+                    ivs = [cds_of[s] for s, _, _ in chunk]
+                    mask = (np.cumsum([0] + [len(v) for v in ivs], dtype=np.int64).astype(np.int32),
+                            np.array([a for v in ivs for a, _ in v], np.int64), np.array([b for v in ivs for _, b in v], np.int64))
                 while len(pending) > len(engines):     # bounded: at most one batch waiting per engine
                     pending.pop(0).result()
-                pending.append(pool.submit(work, n_chunks, batch, name, out_bam is not None, imp))
+                pending.append(pool.submit(work, n_chunks, batch, name, out_bam is not None, imp, mask))
                 n_chunks += 1
                 regions_out.extend((rid, s, l) for s, l, _ in chunk)
         for f in pending:
@@ -389,7 +429,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     g = r["junc"][2]
                     for k, n in enumerate(r["gene_reads"].tolist()):
                         cov[(r["junc"][0], g.gene_id[k])] = cov.get((r["junc"][0], g.gene_id[k]), 0) + n
-                rows = [(gname, c, s1, e1, cov.get((c, gid), 0)) for c, gid, gname, s1, e1 in annotation.gene_features(asj_annotation, asj_gene_types)]
+                rows = [(gname, c, s1, e1, cov.get((c, gid), 0)) for c, gid, gname, s1, e1 in _ann.gene_features(asj_annotation, asj_gene_types)]
                 stats["asj_coverage_genes"] = len(rows)
                 with open(asj_out[:-len(".asj.tsv")] + ".gene_coverage.tsv" if asj_out.endswith(".asj.tsv") else asj_out + ".gene_coverage.tsv", "w") as f:
                     f.write(asj.format_gene_coverage(rows))
@@ -408,7 +448,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 tables.append((name,) + ase.merge_gene_records(pairs, np.concatenate([x[1] for x in parts])))
             else:
                 tables.append((name, ase.merge_gene_records(pairs)))
-            tables[-1] = tables[-1][:2] + (genes.get(name, annotation.ContigGenes()),) + tables[-1][2:]
+            tables[-1] = tables[-1][:2] + (genes.get(name, _ann.ContigGenes()),) + tables[-1][2:]
         text = ase.format_tsv(tables, ase_min_support, ase_overdispersion, patmat=parental is not None)
         stats["ase_genes"] = text.count("\n") - 1
         with open(ase_out, "w") as f:

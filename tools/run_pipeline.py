@@ -4,6 +4,7 @@
   python tools/run_pipeline.py -b reads.bam -f ref.fa -o out.vcf [--out-bam phased.bam] [-p hifi-masseq] [-c chr20,chr21]
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
+                                 [-a genes.gtf.gz --exon-only]   (call inside annotated genes, at CDS columns only)
                                  [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]   (allele-specific junction table)
                                   [--asj-annotation genes.gtf.gz [--asj-gene-types protein_coding,lncRNA]]]   (... per annotated gene, + the gene file)
                                  [--ase-out out.ase.tsv [--ase-min-support N] [--ase-overdispersion R]
@@ -35,6 +36,8 @@ def main():
     ap.add_argument("--downsample-depth", type=int, default=10000)
     ap.add_argument("--truncation", action="store_true", help="end a region at columns deeper than --truncation-coverage, as at uncovered ones")
     ap.add_argument("--truncation-coverage", type=int, default=200000)
+    ap.add_argument("-a", "--annotation", help="GTF / GFF3 (.gz) annotation of --exon-only (its gene and CDS lines; sorted by start per contig)")
+    ap.add_argument("--exon-only", action="store_true", help="clip the regions to the annotated genes and call candidates at CDS columns only (needs -a)")
     ap.add_argument("--asj-out", help="write the allele-specific junction table (longcallR-asj.py's .asj.tsv; regions in place of genes)")
     ap.add_argument("--asj-min-count", type=int, default=10, help="reads a junction needs to be kept, and a table needs to be written")
     ap.add_argument("--asj-min-junctions", type=int, default=2, help="a read takes part with MORE junctions than this")
@@ -52,6 +55,8 @@ def main():
     ap.add_argument("--ase-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
+    if a.exon_only and not a.annotation:
+        ap.error("--exon-only needs -a / --annotation")
     if a.ase_parental_vcf and a.ase_dna_vcf:
         ap.error("--ase-parental-vcf and --ase-dna-vcf are two modes of one table: give one of them")
     if (a.ase_parental_vcf or a.ase_dna_vcf) and not a.ase_out:
@@ -72,7 +77,8 @@ def main():
                       ase_parental_vcf=a.ase_parental_vcf, ase_dna_vcf=a.ase_dna_vcf,
                       ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t),
                       asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
-                      asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage, **extra)
+                      asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage,
+                      annotation=a.annotation, exon_only=a.exon_only, **extra)
     print(json.dumps(st))
 
 
