@@ -217,6 +217,47 @@ int lcr_load_batch(lcr_ctx*, const lcr_reads*, const lcr_regions*);
  * So batch i + 1 crosses PCIe while batch i's kernels run; results are those of lcr_load_batch on the same arrays. */
 int lcr_load_batch_async(lcr_ctx*, const lcr_reads*, const lcr_regions*, int32_t slot);
 int lcr_bind_batch(lcr_ctx*, int32_t slot);
+/* Packed batches: a batch whose bases are still BAM's 4-bit codes.  The fields of lcr_reads with seq4 / pack_off / n_pack in place of
+ * bases; the library expands the nibbles on the GPU (csrc/k0_unpack.hip) into a buffer of its own, so half a byte per base crosses the
+ * link instead of one: a batch uploads n_bases - n_pack - 8 * n_reads fewer bytes, n_pack = sum of (seq_len + 1) / 2.  Any layout the
+ * plain form allows is allowed: gaps, and any order of seq_off and of pack_off. */
+typedef struct {
+  int32_t mem; int32_t n_reads;
+  int64_t n_bases;          /* bytes of quals, and of the UNPACKED bases the context will hold                              */
+  int64_t n_cigar;
+  int64_t n_pack;           /* bytes in seq4                                                                             */
+  const int32_t *pos, *seq_len, *lead_clip, *trail_clip; const uint8_t* flags;
+  const uint64_t *seq_off, *cig_off; const uint32_t* n_cig;   /* as in lcr_reads                                        */
+  const uint64_t* pack_off; /* byte of seq4 that holds the read's bases 0 and 1                                           */
+  const uint8_t* seq4;      /* BAM encoding: base i of a read sits in byte pack_off + i / 2, high nibble for even i; code k stands
+                               for "=ACMGRSVTWYHKDBN"[k]; the low nibble behind an odd-length read is ignored                 */
+  const uint8_t* quals; const uint32_t* cigar;
+} lcr_reads_packed;
+/* lcr_load_batch of the equivalent unpacked batch: afterwards the context is in exactly that state, every stage call and getter gives
+ * bit-identical results.  mem = LCR_MEM_HOST or LCR_MEM_DEVICE, equal in both structs.  The unpacked bases live in a buffer of the
+ * context and are never in the caller's memory.  LCR_E_ARG for seq_len[i] < 0, seq_off[i] + seq_len[i] > n_bases,
+ * pack_off[i] + (seq_len[i] + 1) / 2 > n_pack (sums in 64 bits), n_pack < 0 or n_bases < 0.  A host batch is checked on the host in
+ * front of any work: a refused call changes nothing, the batch bound before it still answers.  A device batch is checked by the
+ * unpack kernel -- a violating read is skipped whole, no load or store of it is issued -- whose verdict is read at the one host wait
+ * lcr_load_batch of a device batch makes; that wait lies behind the point where binding has begun to rewrite the context's tables, so
+ * a device batch refused there leaves NO batch bound (as a device batch whose region table is refused by lcr_load_batch does).
+ * With the asynchronous phase stage the call waits for the stage in flight, like a host batch: a device batch is unpacked into the one
+ * buffer that may hold the bases of the batch that stage belongs to (lcr_load_batch_packed_async has a buffer per slot and does not). */
+int lcr_load_batch_packed(lcr_ctx*, const lcr_reads_packed*, const lcr_regions*);
+/* lcr_load_batch_async of a packed LCR_MEM_HOST batch, into the same two slots: the packed bytes are uploaded on the upload stream, the
+ * unpack kernel is queued on that stream behind them, then the slot's event is recorded -- the slot holds an ordinary device-resident
+ * batch, and lcr_bind_batch(slot) is used unchanged.  Every rule of lcr_load_batch_async carries over; the layout is checked on the
+ * host in front of any work (LCR_E_ARG, nothing changed). */
+int lcr_load_batch_packed_async(lcr_ctx*, const lcr_reads_packed*, const lcr_regions*, int32_t slot);
+/* The unpack kernel by itself, for a caller that keeps BAM nibbles in HBM: all pointers are device memory, complete with respect to
+ * the context's stream.  Writes the bytes of every read's range [seq_off, seq_off + seq_len) of bases_out and no other byte; runs on
+ * the context's stream and returns after its verdict (one host wait): LCR_E_ARG when a read violates one of the three rules above --
+ * that read's range is left untouched, the other reads' ranges are written. */
+int lcr_unpack_bases(lcr_ctx*, int32_t n_reads, const int32_t* seq_len, const uint64_t* seq_off, const uint64_t* pack_off,
+                     const uint8_t* seq4, int64_t n_pack, uint8_t* bases_out, int64_t n_bases);
+/* HIP-event time (ms) of the last unpack kernel of this context (any of the three calls above) with timing enabled; LCR_E_STATE
+ * without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_unpack_ms(lcr_ctx*, float* ms);
 /* page-locked host memory for the arrays of lcr_reads / lcr_regions (hipHostMalloc), or page-lock memory the caller owns */
 int lcr_host_alloc(size_t bytes, void** out);
 void lcr_host_free(void* p);
@@ -712,6 +753,12 @@ int lcr_bam_spans(lcr_bam*, int32_t ref_id, const lcr_read_filter*, int32_t* n, 
 int lcr_bam_batch(lcr_bam*, int32_t ref_id, const lcr_read_filter*, int32_t n_regions, const int64_t* start0,
                   const int32_t* len, lcr_reads* reads, const int32_t** read_begin, const uint64_t** name_off,
                   const char** names);
+/* The same batch with the bases left as the file has them: selection, order, names and lifetime are lcr_bam_batch's; seq4 holds every
+ * record's own (l_seq + 1) / 2 sequence bytes, copied, pack_off back to back; seq_off, quals, cigar and the per-read arrays are what
+ * lcr_bam_batch yields for the same arguments.  No nibble is expanded on the host: input of lcr_load_batch_packed(_async). */
+int lcr_bam_batch_packed(lcr_bam*, int32_t ref_id, const lcr_read_filter*, int32_t n_regions, const int64_t* start0,
+                         const int32_t* len, lcr_reads_packed* reads, const int32_t** read_begin, const uint64_t** name_off,
+                         const char** names);
 
 /* ---- user-provided candidates: VCF reader, replaces get_genotype_quality_phase_from_vcf (vcf.rs:400-462) ----------------------
  * Reads a plain-text VCF or a gzip / BGZF .vcf.gz (every gzip member) into per-contig site lists for lcr_import_candidates.  For

@@ -32,6 +32,16 @@ class LcrReads(C.Structure):
     ]
 
 
+class LcrReadsPacked(C.Structure):   # include/lcr.h: lcr_reads_packed (lcr_reads with BAM nibbles in place of the bases)
+    _fields_ = [
+        ("mem", C.c_int32), ("n_reads", C.c_int32), ("n_bases", C.c_int64), ("n_cigar", C.c_int64), ("n_pack", C.c_int64),
+        ("pos", C.c_void_p), ("seq_len", C.c_void_p), ("lead_clip", C.c_void_p),
+        ("trail_clip", C.c_void_p), ("flags", C.c_void_p), ("seq_off", C.c_void_p),
+        ("cig_off", C.c_void_p), ("n_cig", C.c_void_p), ("pack_off", C.c_void_p), ("seq4", C.c_void_p),
+        ("quals", C.c_void_p), ("cigar", C.c_void_p),
+    ]
+
+
 class LcrReadFilter(C.Structure):   # include/lcr.h lcr_read_filter (util.rs:652-668)
     _fields_ = [("min_mapq", C.c_uint8), ("min_read_length", C.c_int32), ("divergence", C.c_float)]
 
@@ -270,3 +280,108 @@ class ReadBatch:
         """2B + 4C + 32R + (4*NPLANES + 1)*L  (DESIGN.md, K1)."""
         return (2 * int(self.bases.size) + 4 * int(self.cigar.size) + 32 * self.n_reads
                 + (4 * NPLANES + 1) * int(self.col_off[-1]))
+
+    def pack(self):
+        """The same batch with the bases as BAM nibbles (PackedReadBatch): pack_off back to back, (seq_len + 1) // 2 bytes per read, the
+        low nibble behind an odd-length read 0.  A base outside "=ACMGRSVTWYHKDBN" is a ValueError.  The other arrays are shared, not
+        copied.  (Tests and tools: the product path never expands the nibbles, NativeBam.batch(packed=True).)"""
+        ln = self.seq_len.astype(np.int64)
+        if ln.size and ln.min() < 0:
+            raise ValueError("negative seq_len")
+        pack_off = np.zeros(ln.size + 1, dtype=np.int64)
+        np.cumsum((ln + 1) // 2, out=pack_off[1:])
+        src, dst = _base_index(ln, self.seq_off, 2 * pack_off[:-1])
+        code = _NT16_CODE[self.bases[src]]
+        if code.size and code.max() > 15:
+            bad = int(np.flatnonzero(code > 15)[0])
+            raise ValueError("base %r (byte %d of bases) is not one of =ACMGRSVTWYHKDBN" % (chr(int(self.bases[src[bad]])), int(src[bad])))
+        nib = np.zeros(2 * int(pack_off[-1]), dtype=np.uint8)
+        nib[dst] = code
+        kw = {f: getattr(self, f) for f in PackedReadBatch.FIELDS if f not in ("seq4", "pack_off")}
+        out = PackedReadBatch(seq4=(nib[0::2] << 4) | nib[1::2], pack_off=pack_off[:-1].astype(np.uint64), start0=self.start0, len=self.len,
+                              read_begin=self.read_begin, ref=self.ref, names=self.names, **kw)
+        for f in ("name_off", "name_blob"):
+            if hasattr(self, f):
+                setattr(out, f, getattr(self, f))
+        return out
+
+
+_NT16 = np.frombuffer(b"=ACMGRSVTWYHKDBN", dtype=np.uint8)
+_NT16_CODE = np.full(256, 255, dtype=np.uint8)
+_NT16_CODE[_NT16] = np.arange(16, dtype=np.uint8)
+
+
+def _base_index(ln, seq_off, nib_off):
+    """for every base of every read, in read order: (its index in bases, its index in the nibble stream)"""
+    total = int(ln.sum())
+    first = np.zeros(ln.size, dtype=np.int64)
+    if ln.size:
+        np.cumsum(ln[:-1], out=first[1:])
+    j = np.arange(total, dtype=np.int64) - np.repeat(first, ln)
+    return np.repeat(seq_off.astype(np.int64), ln) + j, np.repeat(np.asarray(nib_off, dtype=np.int64), ln) + j
+
+
+class PackedReadBatch:
+    """ReadBatch with the bases as BAM stores them (include/lcr.h: lcr_reads_packed): `seq4` holds two bases per byte, read i's bases 0
+    and 1 in byte pack_off[i]; quals keep one byte per base at seq_off, and n_bases = quals.size is the size of the bases the engine
+    unpacks on the GPU.  Engine.load_batch / load_batch_async take it like a ReadBatch."""
+
+    FIELDS = ["pos", "seq_len", "lead_clip", "trail_clip", "flags", "seq_off", "cig_off", "n_cig",
+              "pack_off", "seq4", "quals", "cigar"]
+    DTYPES = dict(ReadBatch.DTYPES, pack_off=np.uint64, seq4=np.uint8)
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, np.ascontiguousarray(kw[f], dtype=self.DTYPES[f]))
+        self.start0 = np.ascontiguousarray(kw["start0"], dtype=np.int64)
+        self.len = np.ascontiguousarray(kw["len"], dtype=np.int32)
+        self.read_begin = np.ascontiguousarray(kw["read_begin"], dtype=np.int32)
+        self.ref = np.ascontiguousarray(kw["ref"], dtype=np.uint8)
+        self.col_off = np.zeros(len(self.len) + 1, dtype=np.int64)
+        np.cumsum(self.len, out=self.col_off[1:])
+        self.names = kw.get("names")
+        assert self.ref.size == self.col_off[-1]
+        assert self.read_begin[-1] == self.pos.size
+        assert self.pack_off.size == self.pos.size
+
+    n_reads = ReadBatch.n_reads
+    n_regions = ReadBatch.n_regions
+    c_regions = ReadBatch.c_regions
+
+    @property
+    def n_bases(self):
+        return int(self.quals.size)
+
+    @property
+    def n_pack(self):
+        return int(self.seq4.size)
+
+    def c_reads(self):
+        r = LcrReadsPacked()
+        r.mem = LCR_MEM_HOST
+        r.n_reads = self.n_reads
+        r.n_bases, r.n_cigar, r.n_pack = self.n_bases, int(self.cigar.size), self.n_pack
+        for f in self.FIELDS:
+            setattr(r, f, _ptr(getattr(self, f)))
+        return r
+
+    def upload_bytes_saved(self):
+        """bytes this batch uploads less than its unpacked form: n_bases - n_pack - 8 * n_reads (the pack_off array)"""
+        return self.n_bases - self.n_pack - 8 * self.n_reads
+
+    def unpack(self):
+        """The ReadBatch this batch stands for (the inverse of ReadBatch.pack): bases of n_bases bytes, a read's at seq_off; bytes that
+        belong to no read are 0.  The other arrays are shared, not copied."""
+        ln = self.seq_len.astype(np.int64)
+        dst, src = _base_index(ln, self.seq_off, 2 * self.pack_off.astype(np.int64))
+        nib = np.empty(2 * self.seq4.size, dtype=np.uint8)
+        nib[0::2] = self.seq4 >> 4
+        nib[1::2] = self.seq4 & 15
+        bases = np.zeros(self.n_bases, dtype=np.uint8)
+        bases[dst] = _NT16[nib[src]]
+        kw = {f: getattr(self, f) for f in ReadBatch.FIELDS if f != "bases"}
+        out = ReadBatch(bases=bases, start0=self.start0, len=self.len, read_begin=self.read_begin, ref=self.ref, names=self.names, **kw)
+        for f in ("name_off", "name_blob"):
+            if hasattr(self, f):
+                setattr(out, f, getattr(self, f))
+        return out

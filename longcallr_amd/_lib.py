@@ -19,6 +19,7 @@ SYMBOLS = [
     "lcr_junctions", "lcr_get_junctions", "lcr_ase", "lcr_get_ase", "lcr_vcf_contig_alleles",
     "lcr_assign_genes", "lcr_get_read_genes", "lcr_ase_genes", "lcr_get_ase_genes",
     "lcr_junctions_genes", "lcr_get_junctions_genes", "lcr_asj_genes", "lcr_get_asj_genes",
+    "lcr_load_batch_packed", "lcr_load_batch_packed_async", "lcr_unpack_bases", "lcr_unpack_ms", "lcr_bam_batch_packed",
     "lcr_set_exon_mask", "lcr_exon_mask_ms", "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
 ]
 
@@ -61,6 +62,10 @@ def load():
     l.lcr_load_batch.argtypes = [vp, C.POINTER(_abi.LcrReads), C.POINTER(_abi.LcrRegions)]
     l.lcr_load_batch_async.argtypes = [vp, C.POINTER(_abi.LcrReads), C.POINTER(_abi.LcrRegions), C.c_int32]
     l.lcr_bind_batch.argtypes = [vp, C.c_int32]
+    l.lcr_load_batch_packed.argtypes = [vp, C.POINTER(_abi.LcrReadsPacked), C.POINTER(_abi.LcrRegions)]
+    l.lcr_load_batch_packed_async.argtypes = [vp, C.POINTER(_abi.LcrReadsPacked), C.POINTER(_abi.LcrRegions), C.c_int32]
+    l.lcr_unpack_bases.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int64]
+    l.lcr_unpack_ms.argtypes = [vp, C.POINTER(C.c_float)]
     l.lcr_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
     l.lcr_host_free.argtypes = [vp]
     l.lcr_host_free.restype = None
@@ -99,6 +104,8 @@ def load():
     l.lcr_bam_spans.argtypes = [vp, C.c_int32, flt, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
     l.lcr_bam_batch.argtypes = [vp, C.c_int32, flt, C.c_int32, vp, vp, C.POINTER(_abi.LcrReads), C.POINTER(C.POINTER(C.c_int32)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_char_p)]
+    l.lcr_bam_batch_packed.argtypes = [vp, C.c_int32, flt, C.c_int32, vp, vp, C.POINTER(_abi.LcrReadsPacked), C.POINTER(C.POINTER(C.c_int32)),
+                                       C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_char_p)]
     l.lcr_bam_write_phased.argtypes = [vp, C.c_char_p, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_char_p, vp, vp, C.c_int32, C.c_int32]
     l.lcr_bam_write_reads.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(_abi.LcrReads), C.c_int32, C.c_int32]
     l.lcr_import_candidates.argtypes = [vp, C.POINTER(_abi.LcrParams), C.c_int32, C.c_int32, vp, vp, vp]

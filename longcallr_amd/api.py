@@ -99,26 +99,60 @@ class Engine:
 
     # ---- batch binding -------------------------------------------------------------------------
     def load_batch(self, batch):
-        """batch: _abi.ReadBatch (host numpy) or a (LcrReads, LcrRegions, keepalive) device triple."""
-        if isinstance(batch, _abi.ReadBatch):
+        """batch: _abi.ReadBatch or _abi.PackedReadBatch (host numpy), or a (LcrReads | LcrReadsPacked, LcrRegions, keepalive) device
+        triple.  A packed batch (bases as BAM nibbles) goes through lcr_load_batch_packed: the engine unpacks it on the GPU and is
+        afterwards in the state the unpacked batch would leave."""
+        if isinstance(batch, (_abi.ReadBatch, _abi.PackedReadBatch)):
             reads, regions = batch.c_reads(), batch.c_regions()
             self._keep = (batch, reads, regions)
         else:
             reads, regions, keep = batch
             self._keep = (keep, reads, regions)
-        self._chk(self.lib.lcr_load_batch(self.h, C.byref(reads), C.byref(regions)), "lcr_load_batch")
+        if isinstance(reads, _abi.LcrReadsPacked):
+            self._chk(self.lib.lcr_load_batch_packed(self.h, C.byref(reads), C.byref(regions)), "lcr_load_batch_packed")
+        else:
+            self._chk(self.lib.lcr_load_batch(self.h, C.byref(reads), C.byref(regions)), "lcr_load_batch")
         self._n_regions = int(regions.n_regions)
         return self
 
     def load_batch_async(self, batch, slot):
-        """Enqueue the upload of a host batch (_abi.ReadBatch) into staging slot 0 / 1 and return; bind_batch(slot) makes it the
-        current batch.  The batch's arrays should be page-locked (host_register) for the copy to run beside the kernels."""
+        """Enqueue the upload of a host batch (_abi.ReadBatch or _abi.PackedReadBatch) into staging slot 0 / 1 and return; bind_batch(slot)
+        makes it the current batch.  The batch's arrays should be page-locked (host_register) for the copy to run beside the kernels.
+        A packed batch crosses the link as nibbles and is unpacked on the upload stream (lcr_load_batch_packed_async)."""
         reads, regions = batch.c_reads(), batch.c_regions()
         if not hasattr(self, "_keep_slot"):
             self._keep_slot = {}
-        self._chk(self.lib.lcr_load_batch_async(self.h, C.byref(reads), C.byref(regions), int(slot)), "lcr_load_batch_async")
+        if isinstance(reads, _abi.LcrReadsPacked):
+            self._chk(self.lib.lcr_load_batch_packed_async(self.h, C.byref(reads), C.byref(regions), int(slot)), "lcr_load_batch_packed_async")
+        else:
+            self._chk(self.lib.lcr_load_batch_async(self.h, C.byref(reads), C.byref(regions), int(slot)), "lcr_load_batch_async")
         self._keep_slot[int(slot)] = (batch, reads, regions)
         return self
+
+    def unpack_bases(self, seq_len, seq_off, pack_off, seq4, bases_out):
+        """lcr_unpack_bases: the unpack kernel by itself, over contiguous 1-d tensors on this engine's device -- seq_len int32, seq_off
+        and pack_off uint64 or int64 (n_reads each), seq4 and bases_out uint8.  Writes read i's bases to bases_out[seq_off[i] :
+        seq_off[i] + seq_len[i]] and no other byte; returns after the kernel's verdict (LcrError for a read that leaves either array:
+        that read is skipped whole)."""
+        import torch
+        want = (("seq_len", seq_len, (torch.int32,)), ("seq_off", seq_off, (torch.int64, torch.uint64)), ("pack_off", pack_off, (torch.int64, torch.uint64)),
+                ("seq4", seq4, (torch.uint8,)), ("bases_out", bases_out, (torch.uint8,)))
+        for name, t, dts in want:
+            if not getattr(t, "is_cuda", False) or t.dtype not in dts or t.device.index != self.device or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("unpack_bases: %s must be a contiguous 1-d %s tensor on device %d" % (name, dts[0], self.device))
+        if not (seq_len.numel() == seq_off.numel() == pack_off.numel()):
+            raise ValueError("seq_len, seq_off and pack_off must have the same length")
+        torch.cuda.current_stream(self.device).synchronize()   # (the tensors may still be being written on torch's stream)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        self._chk(self.lib.lcr_unpack_bases(self.h, int(seq_len.numel()), ptr(seq_len), ptr(seq_off), ptr(pack_off), ptr(seq4), int(seq4.numel()),
+                                            ptr(bases_out), int(bases_out.numel())), "lcr_unpack_bases")
+        return self
+
+    def unpack_ms(self):
+        """lcr_unpack_ms: HIP-event time of the last unpack kernel (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_unpack_ms(self.h, C.byref(ms)), "lcr_unpack_ms")
+        return float(ms.value)
 
     def bind_batch(self, slot):
         self._chk(self.lib.lcr_bind_batch(self.h, int(slot)), "lcr_bind_batch")

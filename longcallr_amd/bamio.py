@@ -344,8 +344,10 @@ class NativeBam:
         return (np.ctypeslib.as_array(s, (n.value,)).copy() if n.value else np.zeros(0, np.int32),
                 np.ctypeslib.as_array(e, (n.value,)).copy() if n.value else np.zeros(0, np.int32))
 
-    def batch(self, ref_id, regions, ref_windows, name_format="list", copy=True, **flt):
+    def batch(self, ref_id, regions, ref_windows, name_format="list", copy=True, packed=False, **flt):
         """ReadBatch of the passing reads grouped by region (fetch rule of util.rs:637).
+        packed=True: a PackedReadBatch -- the bases stay the records' own 4-bit bytes (lcr_bam_batch_packed: `seq4`, `pack_off` in place
+        of `bases`; nothing is expanded on the host), every other array is what packed=False gives; `copy` covers seq4 like bases.
         copy=True: the arrays are copies; copy=False: the large arrays (bases, quals, cigar) are VIEWS of the decoder's buffers,
         as the C ABI hands them out -- valid until the next batch() / close() of this handle (a caller that loads the batch
         into an engine straight away saves a GB of memcpy).
@@ -356,10 +358,10 @@ class NativeBam:
         f = self._filter(**flt)
         start0 = np.ascontiguousarray([s for s, _ in regions], dtype=np.int64)
         length = np.ascontiguousarray([l for _, l in regions], dtype=np.int32)
-        rd, rb = _abi.LcrReads(), C.POINTER(C.c_int32)()
+        rd, rb = (_abi.LcrReadsPacked() if packed else _abi.LcrReads()), C.POINTER(C.c_int32)()
         noff, names = C.POINTER(C.c_uint64)(), C.c_char_p()
-        self._chk(self._l.lcr_bam_batch(self._h, ref_id, C.byref(f), len(regions), start0.ctypes.data, length.ctypes.data,
-                                        C.byref(rd), C.byref(rb), C.byref(noff), C.byref(names)))
+        self._chk((self._l.lcr_bam_batch_packed if packed else self._l.lcr_bam_batch)(
+            self._h, ref_id, C.byref(f), len(regions), start0.ctypes.data, length.ctypes.data, C.byref(rd), C.byref(rb), C.byref(noff), C.byref(names)))
         nr = rd.n_reads
 
         def arr(ptr, n, dt, view=False):
@@ -369,7 +371,11 @@ class NativeBam:
             return a if view else a.copy()
         kw = {fld: arr(getattr(rd, fld), nr, _abi.ReadBatch.DTYPES[fld])
               for fld in ("pos", "seq_len", "lead_clip", "trail_clip", "flags", "seq_off", "cig_off", "n_cig")}
-        kw["bases"] = arr(rd.bases, rd.n_bases, np.uint8, not copy)
+        if packed:
+            kw["pack_off"] = arr(rd.pack_off, nr, np.uint64)
+            kw["seq4"] = arr(rd.seq4, rd.n_pack, np.uint8, not copy)
+        else:
+            kw["bases"] = arr(rd.bases, rd.n_bases, np.uint8, not copy)
         kw["quals"] = arr(rd.quals, rd.n_bases, np.uint8, not copy)
         kw["cigar"] = arr(rd.cigar, rd.n_cigar, np.uint32, not copy)
         offs = np.ctypeslib.as_array(noff, (nr + 1,)).copy() if nr else np.zeros(1, np.uint64)
@@ -377,7 +383,7 @@ class NativeBam:
         nm = [blob[int(offs[i]):int(offs[i + 1]) - 1].decode() for i in range(nr)] if name_format == "list" else None
         read_begin = np.ctypeslib.as_array(rb, (len(regions) + 1,)).copy()
         cat = np.concatenate([np.asarray(w, np.uint8) for w in ref_windows]) if len(ref_windows) else np.zeros(0, np.uint8)
-        out = ReadBatch(start0=start0, len=length, read_begin=read_begin, ref=cat, names=nm, **kw)
+        out = (_abi.PackedReadBatch if packed else ReadBatch)(start0=start0, len=length, read_begin=read_begin, ref=cat, names=nm, **kw)
         if name_format == "blob":
             out.name_off, out.name_blob = offs, np.frombuffer(blob, dtype=np.uint8)
         return out

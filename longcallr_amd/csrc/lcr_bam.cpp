@@ -225,8 +225,8 @@ struct lcr_bam {
   std::vector<int32_t> sp_start, sp_end;
   std::vector<int32_t> b_pos, b_seq_len, b_lead, b_trail, b_read_begin;
   std::vector<uint8_t> b_flags;
-  RawBuf<uint8_t> b_bases, b_quals;
-  std::vector<uint64_t> b_seq_off, b_cig_off, b_name_off;
+  RawBuf<uint8_t> b_bases, b_quals, b_seq4;   // b_seq4 / b_pack_off: lcr_bam_batch_packed's nibbles in place of b_bases
+  std::vector<uint64_t> b_seq_off, b_cig_off, b_name_off, b_pack_off;
   std::vector<uint32_t> b_n_cig;
   RawBuf<uint32_t> b_cigar;
   RawBuf<char> b_names;
@@ -705,9 +705,10 @@ int lcr_bam_spans(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t*
   return LCR_OK;
 }
 
-int lcr_bam_batch(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t n_regions, const int64_t* start0, const int32_t* len,
-                  lcr_reads* reads, const int32_t** read_begin, const uint64_t** name_off, const char** names) {
-  if (!b || !f || !reads || !read_begin || n_regions < 0 || (n_regions && (!start0 || !len))) return LCR_E_ARG;
+// lcr_bam_batch and lcr_bam_batch_packed: the record selection, the per-read arrays, CIGARs, qualities and names into the handle's b_*
+// buffers.  The bases go to b_bases as ASCII (packed == false) or to b_seq4 as the records' own bytes, b_pack_off back to back.
+static int cut_batch(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t n_regions, const int64_t* start0, const int32_t* len, bool packed,
+                     size_t* n_reads, uint64_t* n_bases, uint64_t* n_cigar, uint64_t* n_pack) {
   { const int rc = load_contig(b, ref_id); if (rc != LCR_OK) return rc; }
   // passing records of the contig, by position (file order for a sorted file), with a running maximum of their ends
   std::vector<uint32_t> idx;
@@ -738,14 +739,18 @@ int lcr_bam_batch(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t 
   const size_t nr = take.size();
   b->b_pos.resize(nr); b->b_seq_len.resize(nr); b->b_lead.resize(nr); b->b_trail.resize(nr); b->b_flags.resize(nr);
   b->b_seq_off.resize(nr); b->b_cig_off.resize(nr); b->b_n_cig.resize(nr); b->b_name_off.resize(nr + 1);
-  uint64_t so = 0, co = 0, no = 0;
+  if (packed) b->b_pack_off.resize(nr);
+  uint64_t so = 0, co = 0, no = 0, po = 0;
   for (size_t k = 0; k < nr; k++) {
     const Rec& r = b->recs[take[k]];
     b->b_seq_off[k] = so; b->b_cig_off[k] = co; b->b_name_off[k] = no;
+    if (packed) b->b_pack_off[k] = po;
     so += (uint64_t)r.l_seq; co += r.n_cig; no += r.l_rn;   // names keep their NUL
+    po += ((uint64_t)r.l_seq + 1) / 2;
   }
   b->b_name_off[nr] = no;
-  if (!b->b_bases.resize(so) || !b->b_quals.resize(so) || !b->b_cigar.resize(co) || !b->b_names.resize(no)) return fail(b, LCR_E_NOMEM, "out of memory for the batch");
+  if (!(packed ? b->b_seq4.resize(po) : b->b_bases.resize(so)) || !b->b_quals.resize(so) || !b->b_cigar.resize(co) || !b->b_names.resize(no))
+    return fail(b, LCR_E_NOMEM, "out of memory for the batch");
   static const char NT16[] = "=ACMGRSVTWYHKDBN";
   const uint8_t* d = b->view;
   parallel_for((int64_t)nr, b->n_threads, 256, [&](int64_t k) {
@@ -759,11 +764,23 @@ int lcr_bam_batch(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t 
     uint32_t* co_ = b->b_cigar.data() + b->b_cig_off[k];
     for (uint32_t c = 0; c < r.n_cig; c++) co_[c] = rd32(cg + 4 * c);
     const uint8_t* sq = q + 32 + r.l_rn + 4 * (size_t)r.n_cig_core;
-    uint8_t* bo = b->b_bases.data() + b->b_seq_off[k];
-    for (int32_t i = 0; i + 1 < r.l_seq; i += 2) { const uint8_t v = sq[i >> 1]; bo[i] = (uint8_t)NT16[v >> 4]; bo[i + 1] = (uint8_t)NT16[v & 15]; }
-    if (r.l_seq & 1) bo[r.l_seq - 1] = (uint8_t)NT16[sq[r.l_seq >> 1] >> 4];
+    if (packed) memcpy(b->b_seq4.data() + b->b_pack_off[k], sq, ((size_t)r.l_seq + 1) / 2);
+    else {
+      uint8_t* bo = b->b_bases.data() + b->b_seq_off[k];
+      for (int32_t i = 0; i + 1 < r.l_seq; i += 2) { const uint8_t v = sq[i >> 1]; bo[i] = (uint8_t)NT16[v >> 4]; bo[i + 1] = (uint8_t)NT16[v & 15]; }
+      if (r.l_seq & 1) bo[r.l_seq - 1] = (uint8_t)NT16[sq[r.l_seq >> 1] >> 4];
+    }
     memcpy(b->b_quals.data() + b->b_seq_off[k], sq + (r.l_seq + 1) / 2, (size_t)r.l_seq);
   });
+  *n_reads = nr; *n_bases = so; *n_cigar = co; *n_pack = po;
+  return LCR_OK;
+}
+
+int lcr_bam_batch(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t n_regions, const int64_t* start0, const int32_t* len,
+                  lcr_reads* reads, const int32_t** read_begin, const uint64_t** name_off, const char** names) {
+  if (!b || !f || !reads || !read_begin || n_regions < 0 || (n_regions && (!start0 || !len))) return LCR_E_ARG;
+  size_t nr = 0; uint64_t so = 0, co = 0, po = 0;
+  { const int rc = cut_batch(b, ref_id, f, n_regions, start0, len, false, &nr, &so, &co, &po); if (rc != LCR_OK) return rc; }
   memset(reads, 0, sizeof(*reads));
   reads->mem = LCR_MEM_HOST;
   reads->n_reads = (int32_t)nr; reads->n_bases = (int64_t)so; reads->n_cigar = (int64_t)co;
@@ -776,6 +793,22 @@ int lcr_bam_batch(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t 
   return LCR_OK;
 }
 
+int lcr_bam_batch_packed(lcr_bam* b, int32_t ref_id, const lcr_read_filter* f, int32_t n_regions, const int64_t* start0, const int32_t* len,
+                         lcr_reads_packed* reads, const int32_t** read_begin, const uint64_t** name_off, const char** names) {
+  if (!b || !f || !reads || !read_begin || n_regions < 0 || (n_regions && (!start0 || !len))) return LCR_E_ARG;
+  size_t nr = 0; uint64_t so = 0, co = 0, po = 0;
+  { const int rc = cut_batch(b, ref_id, f, n_regions, start0, len, true, &nr, &so, &co, &po); if (rc != LCR_OK) return rc; }
+  memset(reads, 0, sizeof(*reads));
+  reads->mem = LCR_MEM_HOST;
+  reads->n_reads = (int32_t)nr; reads->n_bases = (int64_t)so; reads->n_cigar = (int64_t)co; reads->n_pack = (int64_t)po;
+  reads->pos = b->b_pos.data(); reads->seq_len = b->b_seq_len.data(); reads->lead_clip = b->b_lead.data(); reads->trail_clip = b->b_trail.data();
+  reads->flags = b->b_flags.data(); reads->seq_off = b->b_seq_off.data(); reads->cig_off = b->b_cig_off.data(); reads->n_cig = b->b_n_cig.data();
+  reads->pack_off = b->b_pack_off.data(); reads->seq4 = b->b_seq4.data(); reads->quals = b->b_quals.data(); reads->cigar = b->b_cigar.data();
+  *read_begin = b->b_read_begin.data();
+  if (name_off) *name_off = b->b_name_off.data();
+  if (names) *names = b->b_names.data();
+  return LCR_OK;
+}
 
 // ---- phased BAM (thread.rs:307-361) ---------------------------------------------------------
 int lcr_bam_write_phased(lcr_bam* b, const char* out_path, int32_t n_regions, const int32_t* region_ref, const int64_t* start0,

@@ -1,5 +1,6 @@
 // lcr_batch.hip — binding a batch: host uploads, the asynchronous input path, and the load-time kernels of K0 (region and tile tables,
-// packed read headers, the flat op space).  lcr_load_batch / lcr_load_batch_async / lcr_bind_batch of include/lcr.h.
+// packed read headers, the flat op space).  lcr_load_batch / lcr_load_batch_async / lcr_bind_batch of include/lcr.h, and their forms for
+// a batch whose bases are still BAM nibbles (lcr_load_batch_packed / _async, lcr_unpack_bases): the same code with one array exchanged.
 #include <atomic>
 #include <thread>
 
@@ -91,13 +92,65 @@ size_t array_bytes(const BatchArray& a, const lcr_reads* rd, const lcr_regions* 
 const void* get_ptr(const void* obj, size_t off) { const void* p; memcpy(&p, (const char*)obj + off, sizeof p); return p; }
 void set_ptr(void* obj, size_t off, const void* p) { memcpy((char*)obj + off, &p, sizeof p); }
 const void* array_src(const BatchArray& a, const lcr_reads* rd, const lcr_regions* rg) { return get_ptr(a.of_regions ? (const void*)rg : (const void*)rd, a.src); }
+constexpr int A_SEQ_LEN = 1, A_SEQ_OFF = 5, A_BASES = 8;   // places in BATCH_ARRAYS
 
-// BatchView's 16 input pointers: the caller's own arrays (LCR_MEM_DEVICE) or copies in in_[] queued on the context's stream
-int bind_arrays(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg) {
+// ---- a packed batch (lcr_reads_packed) is its plain header without bases, plus what stands in their place
+struct PackedSrc { const uint64_t* pack_off; const uint8_t* seq4; int64_t n_pack; };
+lcr_reads plain_header(const lcr_reads_packed* p) {
+  lcr_reads r{};
+  r.mem = p->mem; r.n_reads = p->n_reads; r.n_bases = p->n_bases; r.n_cigar = p->n_cigar;
+  r.pos = p->pos; r.seq_len = p->seq_len; r.lead_clip = p->lead_clip; r.trail_clip = p->trail_clip; r.flags = p->flags;
+  r.seq_off = p->seq_off; r.cig_off = p->cig_off; r.n_cig = p->n_cig; r.quals = p->quals; r.cigar = p->cigar;
+  return r;
+}
+// the three layout rules of include/lcr.h on a host batch, in front of any work (a device batch: the same test in k0_unpack)
+int check_packed_host(lcr_ctx* c, const lcr_reads* rd, const PackedSrc& pk) {
+  if (pk.n_pack < 0 || rd->n_bases < 0) { c->err = "packed batch: negative n_pack / n_bases"; return LCR_E_ARG; }
+  const int nr = rd->n_reads;
+  if (nr && (!rd->seq_len || !rd->seq_off || !pk.pack_off || (pk.n_pack && !pk.seq4))) { c->err = "packed batch: null array"; return LCR_E_ARG; }
+  for (int r = 0; r < nr; r++) {
+    const int64_t L = rd->seq_len[r];
+    const uint64_t so = rd->seq_off[r], po = pk.pack_off[r];
+    if (L < 0 || so > (uint64_t)rd->n_bases || (uint64_t)L > (uint64_t)rd->n_bases - so || po > (uint64_t)pk.n_pack ||
+        (uint64_t)((L + 1) >> 1) > (uint64_t)pk.n_pack - po) {
+      c->err = "packed batch: read " + std::to_string(r) + " leaves bases (seq_off + seq_len > n_bases), seq4 (pack_off + (seq_len + 1) / 2 > n_pack) or has a negative length";
+      return LCR_E_ARG;
+    }
+  }
+  return LCR_OK;
+}
+// the unpack kernel on queue q, with its verdict word cleared (every earlier launch that could raise it has been waited for) and, when
+// timing is on, its two events (lcr_unpack_ms)
+int queue_unpack(lcr_ctx* c, int32_t nr, const int32_t* seq_len, const uint64_t* seq_off, const uint64_t* pack_off, const uint8_t* seq4, int64_t n_pack,
+                 uint8_t* out, int64_t n_bases, hipStream_t q) {
+  HIPCHK(c, c->h_unpack_bad.reserve(64));
+  *c->h_unpack_bad.as<int32_t>() = 0;
+  if (nr == 0) return LCR_OK;
+  int32_t* d_bad = nullptr;
+  HIPCHK(c, c->h_unpack_bad.dev(&d_bad));
+  if (c->timing && !c->ev_unpack_t[0]) for (hipEvent_t& e : c->ev_unpack_t) HIPCHK(c, hipEventCreate(&e));
+  if (c->timing) HIPCHK(c, hipEventRecord(c->ev_unpack_t[0], q));
+  launch_k0_unpack(nr, seq_len, seq_off, pack_off, seq4, n_pack, out, n_bases, d_bad, q);
+  if (c->timing) { HIPCHK(c, hipEventRecord(c->ev_unpack_t[1], q)); c->unpack_timed = true; }
+  HIPCHK(c, hipGetLastError());
+  return LCR_OK;
+}
+
+// BatchView's 16 input pointers: the caller's own arrays (LCR_MEM_DEVICE) or copies in in_[] queued on the context's stream.  pk: a packed
+// host batch -- its nibbles are copied and unpacked into in_[] where a plain batch's bases are copied (seq_len and seq_off are queued by then).
+int bind_arrays(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg, const PackedSrc* pk) {
   for (int i = 0; i < 16; i++) {
     const BatchArray& a = BATCH_ARRAYS[i];
     const void* p = array_src(a, rd, rg);
-    if (rd->mem != LCR_MEM_DEVICE) {
+    if (rd->mem != LCR_MEM_DEVICE && pk && i == A_BASES) {
+      const uint64_t* d_po = nullptr; const uint8_t* d_s4 = nullptr;
+      HIPCHK(c, c->in_[i].reserve(std::max<size_t>((size_t)rd->n_bases, 1)));
+      { const int rc = upload(c, c->in_pack_off, pk->pack_off, (size_t)rd->n_reads, &d_po, LCR_MEM_HOST); if (rc) return rc; }
+      { const int rc = upload(c, c->in_seq4, pk->seq4, (size_t)pk->n_pack, &d_s4, LCR_MEM_HOST); if (rc) return rc; }
+      { const int rc = queue_unpack(c, rd->n_reads, c->in_[A_SEQ_LEN].as<int32_t>(), c->in_[A_SEQ_OFF].as<uint64_t>(), d_po, d_s4, pk->n_pack,
+                                    c->in_[i].as<uint8_t>(), rd->n_bases, c->stream); if (rc) return rc; }
+      p = c->in_[i].p;
+    } else if (rd->mem != LCR_MEM_DEVICE) {
       const size_t bytes = array_bytes(a, rd, rg, c->n_cols);
       HIPCHK(c, c->in_[i].reserve(std::max<size_t>(bytes, 1)));
       if (bytes) { const int rc = upload_bytes(c, c->in_[i].p, p, bytes); if (rc) return rc; }
@@ -238,28 +291,38 @@ int queue_bind_tables(lcr_ctx* c) {
   return LCR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lcr_load_batch(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg) {
-  if (!c || !rd || !rg) return LCR_E_ARG;
-  if (rd->n_reads < 0 || rg->n_regions < 0 || rd->mem != rg->mem) { c->err = "bad batch header"; return LCR_E_ARG; }
+// lcr_load_batch, and lcr_load_batch_packed with pk: the packed form differs in where the bases come from and in nothing else
+int load_common(lcr_ctx* c, const lcr_reads* rd_in, const lcr_regions* rg, const PackedSrc* pk) {
+  lcr_reads rd_ = *rd_in;
+  const lcr_reads* rd = &rd_;
+  if (rd->n_reads < 0 || rg->n_regions < 0 || rd->mem != rg->mem || (pk && rd->mem != LCR_MEM_HOST && rd->mem != LCR_MEM_DEVICE)) { c->err = "bad batch header"; return LCR_E_ARG; }
+  if (pk && rd->mem == LCR_MEM_HOST) { const int rc = check_packed_host(c, rd, *pk); if (rc) return rc; }
+  if (pk && rd->mem == LCR_MEM_DEVICE && (pk->n_pack < 0 || rd->n_bases < 0)) { c->err = "packed batch: negative n_pack / n_bases"; return LCR_E_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   // a device-resident batch may be bound (and its pileup queued) while the previous batch's phase stage is still running: nothing
   // here or in lcr_pileup touches what that stage reads.  A host batch is copied into the context's staging buffers, which hold
-  // the previous batch's region table: the stage has to be done first.
-  if (rd->mem == LCR_MEM_HOST) { int rc = phase_settle(c); if (rc) return rc; }
+  // the previous batch's region table: the stage has to be done first.  So it has for a packed device batch, which is unpacked into
+  // the one buffer that may hold the bases of the batch whose stage is in flight.
+  if (rd->mem == LCR_MEM_HOST || pk) { int rc = phase_settle(c); if (rc) return rc; }
   rewind_to(c, ST_NONE);   // (from here on the host tables, BatchView and -- a host batch -- in_[] are rewritten)
   c->bound_slot = -1;
   c->bound_host = rd->mem == LCR_MEM_HOST;
   const int nr = rd->n_reads, ng = rg->n_regions, mem = rd->mem;
   int rc;
+  if (pk && mem == LCR_MEM_DEVICE) {   // the unpack in front of the one wait of fetch_region_tables, which delivers its verdict too
+    HIPCHK(c, c->unpacked.reserve(std::max<size_t>((size_t)rd->n_bases, 1)));
+    if ((rc = queue_unpack(c, nr, rd->seq_len, rd->seq_off, pk->pack_off, pk->seq4, pk->n_pack, c->unpacked.as<uint8_t>(), rd->n_bases, c->stream))) return rc;
+    rd_.bases = c->unpacked.as<uint8_t>();
+  }
   if ((rc = fetch_region_tables(c, rd, rg))) return rc;
+  if (pk && mem == LCR_MEM_DEVICE && *c->h_unpack_bad.as<int32_t>()) {
+    c->err = "packed batch: a read leaves bases (seq_off + seq_len > n_bases), seq4 (pack_off + (seq_len + 1) / 2 > n_pack) or has a negative length";
+    return LCR_E_ARG;
+  }
   if ((rc = check_region_tables(c, nr, ng))) return rc;
   c->n_bases = rd->n_bases; c->n_cigar = rd->n_cigar;
   c->bv.n_reads = nr; c->bv.n_regions = ng; c->bv.n_bases = rd->n_bases;
-  if ((rc = bind_arrays(c, rd, rg))) return rc;
+  if ((rc = bind_arrays(c, rd, rg, pk))) return rc;
   if ((rc = reserve_tile_tables(c, mem))) return rc;
   if ((rc = bind_op_space(c, rd))) return rc;
   if ((rc = queue_bind_tables(c))) return rc;
@@ -271,11 +334,13 @@ int lcr_load_batch(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg) {
   return LCR_OK;
 }
 
-int lcr_load_batch_async(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg, int32_t slot) {
-  if (!c || !rd || !rg) return LCR_E_ARG;
+// lcr_load_batch_async, and lcr_load_batch_packed_async with pk: the nibbles cross the link in place of the bases, and the unpack kernel
+// writes the slot's bases on the upload stream in front of the slot's event
+int load_async_common(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg, int32_t slot, const PackedSrc* pk) {
   if (slot < 0 || slot > 1) { c->err = "lcr_load_batch_async: slot must be 0 or 1"; return LCR_E_ARG; }
   if (rd->mem != LCR_MEM_HOST || rg->mem != LCR_MEM_HOST) { c->err = "lcr_load_batch_async takes LCR_MEM_HOST batches (a device-resident batch needs no upload)"; return LCR_E_ARG; }
   if (rd->n_reads < 0 || rg->n_regions < 0 || rd->n_bases < 0 || rd->n_cigar < 0) { c->err = "bad batch header"; return LCR_E_ARG; }
+  if (pk) { const int rc = check_packed_host(c, rd, *pk); if (rc) return rc; }
   HIPCHK(c, hipSetDevice(c->device));
   // a phase stage in flight reads the region table of ITS batch: it has to be done only if that batch lives in the slot rewritten here
   // (two slots alternate: batch k + 1 is uploaded while batch k's stage runs -- lcr_collect_phase fetches batch k's results afterwards)
@@ -301,14 +366,76 @@ int lcr_load_batch_async(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg,
     const void* src = array_src(a, rd, rg);
     const size_t bytes = array_bytes(a, rd, rg, n_cols);
     HIPCHK(c, u.buf[i].reserve(std::max<size_t>(bytes, 1)));
-    if (bytes) {
+    if (bytes && !(pk && i == A_BASES)) {
       if (!src) { c->err = "lcr_load_batch_async: null array"; return LCR_E_ARG; }
       { const int rc2 = upload_bytes(c, u.buf[i].p, src, bytes, c->up_stream); if (rc2) return rc2; }   // (page-locked arrays: asynchronous; pageable ones are staged)
     }
     set_ptr(a.of_regions ? (void*)&u.rg : (void*)&u.rd, a.src, u.buf[i].p);
   }
+  if (pk) {
+    HIPCHK(c, u.pack_off.reserve(std::max<size_t>(nr, 1) * 8));
+    HIPCHK(c, u.seq4.reserve(std::max<size_t>((size_t)pk->n_pack, 1)));
+    if (nr) { const int rc2 = upload_bytes(c, u.pack_off.p, pk->pack_off, (size_t)nr * 8, c->up_stream); if (rc2) return rc2; }
+    if (pk->n_pack) { const int rc2 = upload_bytes(c, u.seq4.p, pk->seq4, (size_t)pk->n_pack, c->up_stream); if (rc2) return rc2; }
+    { const int rc2 = queue_unpack(c, nr, u.buf[A_SEQ_LEN].as<int32_t>(), u.buf[A_SEQ_OFF].as<uint64_t>(), u.pack_off.as<uint64_t>(), u.seq4.as<uint8_t>(),
+                                   pk->n_pack, u.buf[A_BASES].as<uint8_t>(), rd->n_bases, c->up_stream); if (rc2) return rc2; }
+  }
   HIPCHK(c, hipEventRecord(u.ev, c->up_stream));
   u.filled = true;
+  return LCR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lcr_load_batch(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg) {
+  if (!c || !rd || !rg) return LCR_E_ARG;
+  return load_common(c, rd, rg, nullptr);
+}
+
+int lcr_load_batch_packed(lcr_ctx* c, const lcr_reads_packed* rp, const lcr_regions* rg) {
+  if (!c || !rp || !rg) return LCR_E_ARG;
+  const lcr_reads rd = plain_header(rp);
+  const PackedSrc pk{rp->pack_off, rp->seq4, rp->n_pack};
+  return load_common(c, &rd, rg, &pk);
+}
+
+int lcr_load_batch_async(lcr_ctx* c, const lcr_reads* rd, const lcr_regions* rg, int32_t slot) {
+  if (!c || !rd || !rg) return LCR_E_ARG;
+  return load_async_common(c, rd, rg, slot, nullptr);
+}
+
+int lcr_load_batch_packed_async(lcr_ctx* c, const lcr_reads_packed* rp, const lcr_regions* rg, int32_t slot) {
+  if (!c || !rp || !rg) return LCR_E_ARG;
+  const lcr_reads rd = plain_header(rp);
+  const PackedSrc pk{rp->pack_off, rp->seq4, rp->n_pack};
+  return load_async_common(c, &rd, rg, slot, &pk);
+}
+
+int lcr_unpack_bases(lcr_ctx* c, int32_t n_reads, const int32_t* seq_len, const uint64_t* seq_off, const uint64_t* pack_off, const uint8_t* seq4,
+                     int64_t n_pack, uint8_t* bases_out, int64_t n_bases) {
+  if (!c) return LCR_E_ARG;
+  if (n_reads < 0 || n_pack < 0 || n_bases < 0) { c->err = "lcr_unpack_bases: negative size"; return LCR_E_ARG; }
+  if (n_reads && (!seq_len || !seq_off || !pack_off || (n_pack && !seq4) || (n_bases && !bases_out))) { c->err = "lcr_unpack_bases: null array"; return LCR_E_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rc = queue_unpack(c, n_reads, seq_len, seq_off, pack_off, seq4, n_pack, bases_out, n_bases, c->stream); if (rc) return rc; }
+  if (n_reads == 0) return LCR_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  if (*c->h_unpack_bad.as<int32_t>()) {
+    c->err = "lcr_unpack_bases: a read leaves bases_out (seq_off + seq_len > n_bases), seq4 (pack_off + (seq_len + 1) / 2 > n_pack) or has a negative length";
+    return LCR_E_ARG;
+  }
+  return LCR_OK;
+}
+
+int lcr_unpack_ms(lcr_ctx* c, float* ms) {
+  if (!c || !ms) return LCR_E_ARG;
+  if (!c->timing || !c->unpack_timed) { c->err = "lcr_unpack_ms: no unpack kernel with timing enabled"; return LCR_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->ev_unpack_t[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, c->ev_unpack_t[0], c->ev_unpack_t[1]));
   return LCR_OK;
 }
 

@@ -75,10 +75,17 @@ struct lcr_ctx {
   std::vector<int32_t> h_len, h_read_begin, h_region_first_tile;
   DevBuf in_[16];  // device copies of host inputs (LCR_MEM_HOST)
   // asynchronous input path (lcr_load_batch_async / lcr_bind_batch): two staging slots, filled on an upload stream
-  struct UploadSlot { DevBuf buf[16]; hipEvent_t ev = nullptr; bool filled = false; lcr_reads rd{}; lcr_regions rg{}; } up[2];
+  struct UploadSlot { DevBuf buf[16]; DevBuf seq4, pack_off;   // (a packed batch: its nibbles and their offsets; buf[] of the bases is the unpack kernel's output)
+                      hipEvent_t ev = nullptr; bool filled = false; lcr_reads rd{}; lcr_regions rg{}; } up[2];
   hipStream_t up_stream = nullptr;
   int bound_slot = -1;
   bool bound_host = false;   // the bound batch was copied into in_[] (LCR_MEM_HOST)
+  // packed batches (lcr_load_batch_packed, k0_unpack.hip): a host batch's nibbles and offsets in HBM (its bases are unpacked into in_[]);
+  // a device batch's unpacked bases; the kernel's verdict word; HIP events around the last unpack kernel when timing is on
+  DevBuf in_seq4, in_pack_off, unpacked;
+  HostBuf h_unpack_bad;
+  hipEvent_t ev_unpack_t[2] = {};
+  bool unpack_timed = false;
   DevBuf scan_tmp, read_region, read_bin, read_rend, tile_region, tile_col0, first_tile, k0_tile_fill, k0_items, tile_nbase, tile_order;
   DevBuf desc_tile, desc_val, chunks, chunk_off;   // K0's chunk descriptors, the same sorted by tile, their per-tile offsets
   DevBuf blk_first_read, read_scan, cig_compact, cig_off_new, cig_new_off32;   // K0 op blocks (k0_ops.hip)

@@ -194,6 +194,9 @@ void launch_k0_bind_a(const int64_t* start0, const int32_t* len, const int64_t* 
                       const uint64_t* cig_off, const uint32_t* n_cig, int32_t nr, int64_t n_cigar, int32_t* out, hipStream_t s);
 void launch_k0_bind_b(const BatchView& b, ReadBin* rbin, int32_t* order_flag, int32_t* read_region, int32_t n_tiles, int32_t* tile_region,
                       int32_t* tile_col0, uint64_t cig0, int32_t opb, int32_t n_blocks, int32_t* blk_first_read, hipStream_t s);
+// k0_unpack.hip: BAM 4-bit bases -> ASCII, one wave per read; no launch for nr == 0.  bad: raised for a read whose ranges leave the arrays (skipped)
+void launch_k0_unpack(int32_t nr, const int32_t* seq_len, const uint64_t* seq_off, const uint64_t* pack_off, const uint8_t* seq4, int64_t n_pack,
+                      uint8_t* out, int64_t n_bases, int32_t* bad /* pinned host memory, device address */, hipStream_t s);
 // K0 (k0_ops.hip): op-parallel CIGAR decode + per-tile record binning; load-time helpers
 void launch_k0_cig_check(const uint64_t* cig_off, const uint32_t* n_cig, int32_t nr, int64_t n_cigar, int32_t* out, hipStream_t s);
 void launch_k0_cig_compact(const uint32_t* cigar, const uint64_t* cig_off, const uint32_t* n_cig, const int32_t* new_off, int32_t nr,

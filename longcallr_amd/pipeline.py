@@ -116,7 +116,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         asj_out=None, asj_min_count=10, asj_min_junctions=2,
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
-        asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, **param_overrides):
+        asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
+        **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -181,7 +182,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     candidates are called at CDS columns only, and a masked column does not count in the dense-cluster sweep either.  With input_vcf the
     regions are clipped and dropped all the same, but no mask is set: the imported sites outside CDS are phased (thread.rs:107-116).  The
     phased BAM tags the reads contained in a clipped region.  Adds the stats exon_regions (regions after clipping and dropping) and
-    exon_skipped_regions (dropped for want of CDS); regions stays the number discovered."""
+    exon_skipped_regions (dropped for want of CDS); regions stays the number discovered.
+    packed_upload: every chunk is cut with the bases left as the BAM's 4-bit codes (NativeBam.batch(packed=True)) and loaded through the
+    asynchronous packed path (lcr_load_batch_packed_async: the nibbles cross the link, a kernel expands them in HBM).  Every output is
+    byte for byte the one of a run without it.  Adds the stat upload_bytes_saved: n_bases - n_pack - 8 n_reads, summed over chunks.
+    Off by default."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -239,6 +244,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["truncated_columns"] = 0
     if exon_only:
         stats["exon_regions"] = stats["exon_skipped_regions"] = 0
+    if packed_upload:
+        stats["upload_bytes_saved"] = 0
     parental = ase.parental_sites(ase_parental_vcf) if ase_parental_vcf is not None else None    # {contig: (pos0, pat, mat)}
     dna = ase.dna_het_sites(ase_dna_vcf) if ase_dna_vcf is not None else None                    # {contig: pos0}
     genes = _ann.load(ase_annotation, ase_gene_types) if ase_annotation is not None else None   # {contig: _ann.ContigGenes}
@@ -382,8 +389,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             for chunk in chunk_regions(regions, max_cost=chunk_cost):
                 wins = [ref[s:s + l] if s + l <= ref.size else np.concatenate([ref[s:], np.full(s + l - ref.size, ord("N"), np.uint8)])
                         for s, l, _ in chunk]
-                batch = nb.batch(rid, [(s, l) for s, l, _ in chunk], wins, name_format="blob", **flt)
+                batch = nb.batch(rid, [(s, l) for s, l, _ in chunk], wins, name_format="blob", packed=bool(packed_upload), **flt)
                 stats["reads"] += batch.n_reads; stats["chunks"] += 1
+                if packed_upload:
+                    stats["upload_bytes_saved"] += batch.upload_bytes_saved()
                 imp = None
                 if sites is not None:       # thread.rs:108: a contig the VCF does not name gets no candidates
                     sp, sg, sq = sites.get(name, no_sites)

@@ -5,6 +5,7 @@
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
                                  [-a genes.gtf.gz --exon-only]   (call inside annotated genes, at CDS columns only)
+                                 [--packed-upload]   (upload the BAM's 4-bit bases and unpack them on the GPU; same outputs)
                                  [--asj-out out.asj.tsv [--asj-min-count N] [--asj-min-junctions N]   (allele-specific junction table)
                                   [--asj-annotation genes.gtf.gz [--asj-gene-types protein_coding,lncRNA]]]   (... per annotated gene, + the gene file)
                                  [--ase-out out.ase.tsv [--ase-min-support N] [--ase-overdispersion R]
@@ -38,6 +39,7 @@ def main():
     ap.add_argument("--truncation-coverage", type=int, default=200000)
     ap.add_argument("-a", "--annotation", help="GTF / GFF3 (.gz) annotation of --exon-only (its gene and CDS lines; sorted by start per contig)")
     ap.add_argument("--exon-only", action="store_true", help="clip the regions to the annotated genes and call candidates at CDS columns only (needs -a)")
+    ap.add_argument("--packed-upload", action="store_true", help="upload the bases as the BAM's 4-bit codes and expand them on the GPU (outputs unchanged)")
     ap.add_argument("--asj-out", help="write the allele-specific junction table (longcallR-asj.py's .asj.tsv; regions in place of genes)")
     ap.add_argument("--asj-min-count", type=int, default=10, help="reads a junction needs to be kept, and a table needs to be written")
     ap.add_argument("--asj-min-junctions", type=int, default=2, help="a read takes part with MORE junctions than this")
@@ -78,7 +80,7 @@ def main():
                       ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t),
                       asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
                       asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage,
-                      annotation=a.annotation, exon_only=a.exon_only, **extra)
+                      annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, **extra)
     print(json.dumps(st))
 
 
