@@ -386,6 +386,52 @@ typedef struct {
 } lcr_phase_collected;
 int lcr_collect_phase(lcr_ctx*, lcr_phase_collected* out);
 
+/* Haplotagging against a phased VCF (K11): stands in place of lcr_phase when the caller HOLDS the phase -- longcallR -v with a DNA-phased
+ * file (trio, long-read WGS), the `whatshap haplotag` use.  The reference reads each site's phase bit (vcf.rs:397-451) and never uses it;
+ * lcr_phase infers haplotypes per coverage island, so "haplotype 1" is an arbitrary label per region.  Here the rows of lcr_get_fragmat are
+ * assigned to the caller's haplotypes and phase sets: labels are the same across regions, genes and contigs, and a site with monoallelic
+ * expression stays usable.  DESIGN.md section 1i.
+ *   sites              one contig's (the rule of lcr_import_candidates): pos0 0-based, ascending and unique; h1 / h2 the ASCII base A / C /
+ *       G / T on haplotype 1 / 2, h1 != h2; phase_set != 0.  n_sites == 0 (NULL arrays) is legal: every row is then unassigned.
+ *   usable candidate   variant_type == 1 with LCR_F_HET and LCR_F_FOR_PHASING both set, neither LCR_F_DENSE nor LCR_F_RNA_EDIT, pos one
+ *       of pos0, and the upper-cased ref_base equal to that site's h1 or h2.  Its record gets haplotype = +1 when ref_base is h1 (the VCF
+ *       writer prints 0|1), -1 when it is h2, and the site's phase_set.  Every other candidate keeps what the candidate stage wrote, with
+ *       LCR_F_NON_SELECTED set in its flags (haplotype, phase_set and phase_score stay 0).
+ *   usable entry       a CSR entry at a usable candidate whose base code (val bits 6-7) is the site's h1 or h2.  No quality threshold: q
+ *       = val bits 0-4, the table of the phase stage (fe[q] = log10 eps_q, f1e[q] = log10(1 - eps_q), scale 2^40, q = 0 as q = 1).
+ *       t1 = f1e[q] when the base is h1, else fe[q]; t2 the other one.
+ *   row's phase set    the phase_set value with the most usable entries in the row, ties to the smallest value; only its entries count.
+ *   sums               A1 = sum t1, A2 = sum t2, D = A1 + A2 (negative), int64.  A row takes part iff it has >= min_linkers counted
+ *       entries.  It is assigned iff A1 != A2 and fabs((double)(A1 - A2)) >= read_assign_cutoff * fabs((double)D) -- |q - qn| >= cutoff
+ *       of snpfrags.rs:590 with q = 1 - A / D; an exact tie is "no evidence" whatever the cutoff (snpfrags.rs:591 assigns it at cutoff 0:
+ *       a stated deviation).  A1 > A2: assignment 1, haplotag +1; otherwise 2 and -1; the row's phase set.  Every other row: 0 / 0 / 0.
+ *   site record        per candidate (zeros when not usable), over the assigned rows with a counted entry at it: n_h1 / n_h2 rows by
+ *       assignment, n_h*_match those whose base is their haplotype's allele, total_fx = sum (fe[q] + f1e[q]), match_fx = sum (match ?
+ *       f1e[q] : fe[q]).  The candidate's phase_score = -10 log10((double)match_fx / (double)total_fx) when n_h1 >= 1 and n_h2 >= 1
+ *       (cal_phase_score_log at the fixed delta, phase.rs:238-255), else the reference's constant 0.19940219.
+ * Every decision is taken on integers: the result is independent of the batch's composition and bit-reproducible.  The sums stay below
+ * 2^53 for rows and sites of up to about 2 000 entries (|fe[1]| < 2^40, so 2 000 terms of at most 2 * 2^40 stay below 2^52), so the
+ * int64 -> double conversions are exact there; beyond it they round to nearest, the same on every run.
+ * Needs lcr_fragments (LCR_E_STATE), after either candidate stage; settles an asynchronous phase stage in flight first; once per
+ * candidate stage like lcr_phase -- a second lcr_haplotag, lcr_phase or lcr_fragments returns LCR_E_STATE until a candidate stage has run.
+ * Afterwards lcr_get_phase_result, lcr_get_read_records_device, lcr_collect_phase, lcr_get_candidates*, lcr_junctions, lcr_ase,
+ * lcr_ase_genes, lcr_junctions_genes and lcr_asj_genes answer exactly as behind lcr_phase; objective is 0.0 per region, lcr_get_tie_census
+ * returns zeros, lcr_get_ld_blocks no blocks, lcr_get_downsample "no region".  Down-sampling (lcr_set_downsample*) is IGNORED: tagging is
+ * linear in the entries and sees every row.  Of params the call reads min_linkers and read_assign_cutoff.
+ * mem as in lcr_import_candidates: LCR_MEM_HOST arrays are copied before the call returns; LCR_MEM_DEVICE arrays are read in place on the
+ * context's stream and stay valid and unchanged until a getter or lcr_ctx_sync has returned.  A kernel checks them and writes its verdict
+ * to pinned memory: the call's one host wait, taken before anything the last stage left is touched -- unsorted or duplicate positions,
+ * a base outside ACGT, h1 == h2 or phase_set == 0 are LCR_E_ARG and change nothing.  The site records die with the phase results (the
+ * next candidate stage, lcr_load_batch / lcr_bind_batch): lcr_get_haplotag_sites answers LCR_E_STATE then.  rec: pinned host memory the
+ * call's last kernel wrote, one record per candidate of lcr_get_candidates, valid until the next lcr_haplotag; dev_rec: the same in HBM. */
+typedef struct { int64_t match_fx, total_fx; uint32_t n_h1, n_h2, n_h1_match, n_h2_match; } lcr_haplotag_site;  /* 32 bytes, one per candidate */
+int lcr_haplotag(lcr_ctx*, const lcr_params*, int32_t mem, int32_t n_sites, const int64_t* pos0,
+                 const uint8_t* h1, const uint8_t* h2, const uint32_t* phase_set);
+int lcr_get_haplotag_sites(lcr_ctx*, int32_t* n_cand, const lcr_haplotag_site** rec, const lcr_haplotag_site** dev_rec);
+/* HIP-event time (ms) of the last lcr_haplotag's kernels behind the check of the sites with timing enabled (lcr_enable_timing); LCR_E_STATE
+ * without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_haplotag_ms(lcr_ctx*, float* ms);
+
 /* Allele-specific junctions (K6): the haplotype x junction table of the allele-specific analysis that consumes the phased reads
  * (allele_specific/longcallR-asj.py: get_exon_intron_regions' N arm, process_chunk :229-236, analyze_gene :671-676 / :734,
  * check_absent_present, haplotype_event_test), counted on the GPU from what lcr_phase left there.  Defined per region -- a region
@@ -780,6 +826,9 @@ int lcr_vcf_contig(lcr_vcf*, const char* name, int32_t* n, const int64_t** pos0,
  * sample).  ref = REF's byte when REF is one base, else 0; alt = the first ALT's byte when EVERY ALT allele is one base, else 0 (the
  * indel test of longcallR-ase.py's VCF loaders); phase: 0 = the GT is unphased, 1 = `0|1`, 2 = `1|0`, 3 = phased, any other alleles. */
 int lcr_vcf_contig_alleles(lcr_vcf*, const char* name, int32_t* n, const uint8_t** ref, const uint8_t** alt, const uint8_t** phase);
+/* The phase sets of the same sites, one more parallel array: the FORMAT `PS` integer of the same winning record and sample; 0 when the
+ * record has no PS key, the sample's value is `.` or missing, or it is not an unsigned 32-bit decimal integer (the input of lcr_haplotag). */
+int lcr_vcf_contig_phase_sets(lcr_vcf*, const char* name, int32_t* n, const uint32_t** ps);
 
 /* ---- phased BAM, replaces thread.rs:307-361 ------------------------------------------------
  * Writes to out_path the header of the opened file and, region by region in the order given (region i = columns

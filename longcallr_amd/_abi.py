@@ -144,6 +144,12 @@ class LcrAseList(C.Structure):   # include/lcr.h: lcr_ase_list
     _fields_ = [("n_regions", C.c_int32), ("rec", C.c_void_p), ("dev_rec", C.c_void_p)]
 
 
+# lcr_haplotag_site (include/lcr.h): one candidate's evidence under the caller's phase (lcr_haplotag), zeros when it is not usable
+HAPSITE_DTYPE = np.dtype([("match_fx", "<i8"), ("total_fx", "<i8"), ("n_h1", "<u4"), ("n_h2", "<u4"), ("n_h1_match", "<u4"),
+                          ("n_h2_match", "<u4")], align=True)
+assert HAPSITE_DTYPE.itemsize == 32, HAPSITE_DTYPE.itemsize
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

@@ -21,6 +21,7 @@ SYMBOLS = [
     "lcr_junctions_genes", "lcr_get_junctions_genes", "lcr_asj_genes", "lcr_get_asj_genes",
     "lcr_load_batch_packed", "lcr_load_batch_packed_async", "lcr_unpack_bases", "lcr_unpack_ms", "lcr_bam_batch_packed",
     "lcr_set_exon_mask", "lcr_exon_mask_ms", "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
+    "lcr_haplotag", "lcr_get_haplotag_sites", "lcr_haplotag_ms", "lcr_vcf_contig_phase_sets",
 ]
 
 _lib = None
@@ -134,5 +135,9 @@ def load():
     l.lcr_asj_genes.argtypes = [vp, C.POINTER(_abi.LcrAsjParams), C.c_int32, C.POINTER(_abi.LcrGeneAnnotation)]
     l.lcr_get_asj_genes.argtypes = [vp, C.POINTER(_abi.LcrAsjGeneList)]
     l.lcr_vcf_contig_alleles.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    l.lcr_vcf_contig_phase_sets.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(vp)]
+    l.lcr_haplotag.argtypes = [vp, C.POINTER(_abi.LcrParams), C.c_int32, C.c_int32, vp, vp, vp, vp]
+    l.lcr_get_haplotag_sites.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp)]
+    l.lcr_haplotag_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

@@ -290,6 +290,56 @@ class Engine:
         self._chk(self.lib.lcr_phase(self.h, C.byref(self.params)), "lcr_phase")
         return self
 
+    def haplotag(self, sites):
+        """lcr_haplotag in place of phase(): the rows of fragmat() tagged on the haplotypes and phase sets of a phased VCF (include/lcr.h;
+        `whatshap haplotag` on the fragment matrix).  sites: (pos0, h1, h2, phase_set) of the batch's contig -- vcf.haplotag_sites gives
+        them --, pos0 ascending and unique, h1 / h2 the ASCII base on haplotype 1 / 2, phase_set != 0; None or empty arrays: every row is
+        unassigned.  numpy arrays (converted), or contiguous int64 / uint8 / uint8 / uint32 tensors on this engine's device, read in place
+        and held by the engine until sync().  Afterwards phase_result(), candidates(), collect_phase(), junctions(), ase() and the per-gene
+        calls answer as behind phase(); haplotag_sites() has the per-candidate evidence.  Down-sampling is ignored."""
+        if sites is None:
+            rc = self.lib.lcr_haplotag(self.h, C.byref(self.params), _abi.LCR_MEM_HOST, 0, None, None, None, None)
+        elif any(getattr(t, "is_cuda", False) for t in sites):
+            import torch
+            ts = tuple(sites)
+            u32 = tuple(d for d in (getattr(torch, "uint32", None), torch.int32) if d is not None)   # (the same 32 bits either way)
+            for name, t, dt in zip(("pos0", "h1", "h2", "phase_set"), ts, (torch.int64, torch.uint8, torch.uint8, u32)):
+                dts = dt if isinstance(dt, tuple) else (dt,)
+                if not getattr(t, "is_cuda", False) or t.dtype not in dts or t.device.index != self.device or t.dim() != 1 or not t.is_contiguous():
+                    raise ValueError("device sites: %s must be a contiguous 1-d %s tensor on device %d" % (name, dts[0], self.device))
+            if len({t.numel() for t in ts}) != 1:
+                raise ValueError("pos0, h1, h2 and phase_set must have the same length")
+            self._release_sites()
+            torch.cuda.current_stream(self.device).synchronize()   # (the tensors may still be being written on torch's stream)
+            n = int(ts[0].numel())
+            rc = self.lib.lcr_haplotag(self.h, C.byref(self.params), _abi.LCR_MEM_DEVICE, n, *[C.c_void_p(t.data_ptr()) if n else None for t in ts])
+            if rc == 0:
+                self._sites = ts   # (the kernels behind the call's return read them: released by sync())
+        else:
+            pos = np.ascontiguousarray(sites[0], dtype=np.int64)
+            h1 = np.ascontiguousarray(sites[1], dtype=np.uint8)
+            h2 = np.ascontiguousarray(sites[2], dtype=np.uint8)
+            ps = np.ascontiguousarray(sites[3], dtype=np.uint32)
+            if not (pos.size == h1.size == h2.size == ps.size):
+                raise ValueError("pos0, h1, h2 and phase_set must have the same length")
+            n = int(pos.size)
+            rc = self.lib.lcr_haplotag(self.h, C.byref(self.params), _abi.LCR_MEM_HOST, n, *[a.ctypes.data if n else None for a in (pos, h1, h2, ps)])
+        self._chk(rc, "lcr_haplotag")
+        return self
+
+    def haplotag_sites(self):
+        """lcr_get_haplotag_sites after haplotag(): one record per candidate of candidates() as a structured array of _abi.HAPSITE_DTYPE,
+        copied -- zeros for a candidate the tagging did not use."""
+        n, rec, dev = C.c_int32(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.lcr_get_haplotag_sites(self.h, C.byref(n), C.byref(rec), C.byref(dev)), "lcr_get_haplotag_sites")
+        return _view(rec.value, _abi.HAPSITE_DTYPE, n.value)
+
+    def haplotag_ms(self):
+        """lcr_haplotag_ms: HIP-event time of the last haplotag()'s kernels behind the check of the sites (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_haplotag_ms(self.h, C.byref(ms)), "lcr_haplotag_ms")
+        return float(ms.value)
+
     def junctions(self, min_count=10, min_junctions=2):
         """lcr_junctions + lcr_get_junctions after phase(): the kept junctions of every region with their haplotype x presence tables
         (include/lcr.h; the table longcallR-asj.py builds per gene) -> (records as a structured array of _abi.JUNC_DTYPE, copied;

@@ -121,15 +121,34 @@ def filter_pairs(pairs, cands, dna_pos0, min_phase_score, min_support=10, overdi
     return np.array([(int(r["region"]), int(r["phase_set"])) in passing for r in pairs], dtype=bool)
 
 
-def merge_gene_records(pairs, keep=None):
+def merge_gene_records(pairs, keep=None, shared_phase_sets=False):
     """The (region, gene) pair records of one contig -- Engine.ase_genes' records of all its chunks, concatenated -- -> one record per
     gene, ascending by gene.  A gene's rows are the union of its pairs' rows, and phase sets of different regions of a contig are
     distinct (a phase set is named after its first site's position), so the gene's phase set with the most reads is that of the pair
     record with the largest h1 + h2, ties to the smallest phase set, and that record's counts, sites and votes are the gene's;
     n_phase_sets is the sum over the pairs.  Exact across regions and across pipeline.run's chunks.  `region` is the chosen record's.
     keep (filter_pairs' mask, parallel to pairs): -> (records, the chosen records' mask).
-    Not the script's: under --truncation a read that is a row of both flanks of a cut counts in both flanks' records."""
+    Not the script's: under --truncation a read that is a row of both flanks of a cut counts in both flanks' records.
+    shared_phase_sets (pipeline.run(haplotag=True): the phase sets are the input VCF's and span the regions of a contig): the pair
+    records of one gene with the same phase set are summed first -- h1, h2, the four votes and n_sites added, `region` the first
+    one's, keep the OR of theirs -- and the choice above is made among the sums.  n_phase_sets stays the sum over the pairs."""
     pairs = np.asarray(pairs, dtype=_abi.AGENE_DTYPE)
+    if shared_phase_sets and len(pairs):
+        first = {}      # (gene, phase set) -> index of the summed record
+        rows, kept, nps_of = [], [], []
+        for i in range(len(pairs)):
+            r = pairs[i]
+            key = (int(r["gene"]), int(r["phase_set"]))
+            j = first.get(key)
+            if j is None:
+                first[key] = len(rows)
+                rows.append(r.copy()); kept.append(bool(keep[i]) if keep is not None else True)
+                continue
+            for f in ("h1", "h2", "n_sites", "h1_pat", "h1_mat", "h2_pat", "h2_mat", "n_phase_sets"):
+                rows[j][f] += r[f]
+            kept[j] = kept[j] or (bool(keep[i]) if keep is not None else True)
+        pairs = np.array(rows, dtype=_abi.AGENE_DTYPE)
+        keep = np.array(kept, dtype=bool) if keep is not None else None
     best = {}    # gene -> index of the chosen pair
     nps = {}
     for i in range(len(pairs)):

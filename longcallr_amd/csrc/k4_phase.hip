@@ -74,6 +74,8 @@ const HostLut& hlut() { static HostLut l; return l; }
 
 }  // namespace
 
+const PhaseLutDev& phase_lut_dev() { return hlut().dev; }
+
 // Persistent all-CU launches of different processes (or contexts) on one GPU would wait for each other's workgroups forever:
 // they are serialised per DEVICE -- a process-local mutex keyed by the PCI bus id, and across processes an flock on
 // <lock_dir>/grid_<bus id>.lock (lock_dir: lcr_ctx_set_lock_dir, created 0700; default the machine-wide /tmp/liblcr-locks, refused unless it

@@ -4,7 +4,8 @@
 // lcr_junctions.hip (lcr_junctions, lcr_get_junctions), lcr_ase.hip (lcr_ase, lcr_get_ase) and lcr_genes.hip (lcr_assign_genes, lcr_get_read_genes,
 // lcr_ase_genes, lcr_get_ase_genes), lcr_junctions_genes.hip (lcr_junctions_genes, lcr_get_junctions_genes) and lcr_asj_genes.hip
 // (lcr_asj_genes, lcr_get_asj_genes).  The last two fill one struct each, GeneJunctions, by the same steps (declared at the end), and the
-// three calls that take a gene annotation share its upload and verdict (annotation_queue, annotation_verdict).
+// three calls that take a gene annotation share its upload and verdict (annotation_queue, annotation_verdict).  lcr_haplotag.hip
+// (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -188,6 +189,17 @@ struct lcr_ctx {
   uint32_t ds_depth = 0; uint64_t ds_seed = 0;
   std::vector<uint8_t> ds_rows; bool ds_rows_set = false;
 
+  // K11 (lcr_haplotag, in place of lcr_phase): it fills what the phase stage fills -- the candidate records, PhaseHost's pinned result blocks
+  // and read records -- and owns the site arrays, the per-candidate site byte / phase set, and the site records
+  bool hap_valid = false;    // lcr_get_haplotag_sites: the last lcr_haplotag's site records belong to the phase results of the bound batch (rewind_to)
+  bool hap_pending = false;  // its kernels may be in flight: haplotag_settle waits for ev_hap and copies the candidate mirror into h_cand
+  bool hap_timed = false;    // ev_hap_t brackets the last call's kernels
+  int32_t hap_ncand = 0;
+  DevBuf ht_pos, ht_h1, ht_h2, ht_ps, ht_site, ht_site_ps, d_hsite;   // host sites copied to HBM; a byte and a word per candidate; the records
+  HostBuf h_hsite, h_hap_bad;            // pinned: the site records; the verdict on the sites
+  hipEvent_t ev_hap = nullptr;           // behind the sites' check, then behind the call's last kernel
+  hipEvent_t ev_hap_t[2] = {};           // timing enabled: around the kernels behind the check, created on first use
+
   // K6 (lcr_junctions): scratch and results of its own -- no other stage or getter reads them
   bool junc_valid = false;   // lcr_get_junctions: the last lcr_junctions' table belongs to the phase results of the bound batch (rewind_to)
   int32_t junc_n = 0, junc_ng = 0;
@@ -255,6 +267,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
   if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
   if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
+  if (to < ST_PHASED) c->hap_valid = false;      // lcr_haplotag's site records go with the phase results they describe
   if (to < ST_PHASED) c->jgene.valid = c->ajgene.valid = false;   // ... and the per-gene junction tables
   if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
@@ -296,7 +309,12 @@ int upload(lcr_ctx* c, DevBuf& buf, const T* src, size_t n, const T** dst, int m
 
 // lcr_phase leaves its kernels in flight on the phase stage's own queues (lcr_phase_host.h): whoever needs its results, or is about
 // to overwrite what it reads / writes, collects them first
-inline int phase_settle(lcr_ctx* c) { return c->phase.settle(&c->err); }
+int haplotag_settle(lcr_ctx* c);   // lcr_haplotag stands in place of lcr_phase and leaves its kernels in flight on the context's stream (lcr_haplotag.hip)
+inline int phase_settle(lcr_ctx* c) {
+  const int rc = c->phase.settle(&c->err);
+  if (rc || !c->hap_pending) return rc;
+  return haplotag_settle(c);
+}
 int cand_settle(lcr_ctx* c);   // the candidate stage's host copies (lcr_calls.hip)
 // lcr_pileup.hip.  planes_tally: the planes of the tiles with records are in c->planes -- behind a lean pileup it queues k1_pileup's full form once
 // (with_filter: with pass 1's flags and per-tile counts for the pileup's parameters, as a full fused pileup leaves them).  planes_materialise: that and

@@ -341,6 +341,20 @@ void launch_k7_votes(const int32_t* row_tag, int32_t n_rows, const int64_t* row_
                      uint32_t min_baseq, lcr_ase_region* ase, hipStream_t s);
 void launch_k7_export(const lcr_ase_region* ase, int32_t ng, lcr_ase_region* host_out /* pinned (device pointer) */, hipStream_t s);
 
+// k11_haplotag.hip: rows of the fragment matrix against the caller's phased sites (lcr_haplotag, in place of the phase stage)
+struct K11Sites { const int64_t* pos0; const uint8_t* h1; const uint8_t* h2; const uint32_t* ps; int32_t n; };
+struct K11Rows {   // what k11_rows writes per row: the phase stage's per-row results (PostIn's haplotag / assignment / phase_set / d_rec)
+  int8_t* haplotag; uint8_t* assignment; uint32_t* phase_set;   // pinned host memory (device pointers)
+  uint32_t* d_rec;                                              // lcr_read_record in HBM, three words per row
+};
+void launch_k11_check(const K11Sites& st, int32_t* bad /* zeroed, pinned (device pointer) */, hipStream_t s);
+void launch_k11_sites(lcr_candidate* cand, int32_t n_cand, const K11Sites& st, uint8_t* site /* n_cand */, uint32_t* site_ps /* n_cand */,
+                      lcr_haplotag_site* acc /* n_cand, cleared here */, hipStream_t s);
+void launch_k11_rows(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const uint8_t* site, const uint32_t* site_ps,
+                     const PhaseLutDev& lut /* the phase stage's table */, uint32_t min_linkers, double cutoff, const K11Rows& out, lcr_haplotag_site* acc, hipStream_t s);
+void launch_k11_finish(lcr_candidate* cand, int32_t n_cand, const uint8_t* site, const lcr_haplotag_site* acc, lcr_candidate* host_cand /* pinned */,
+                       lcr_haplotag_site* host_acc /* pinned */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

@@ -46,6 +46,7 @@ struct PhaseDebug {
 };
 
 struct PhaseCall;   // k4_phase.hip
+const PhaseLutDev& phase_lut_dev();   // the stage's fixed-point table (HostLut, k4_phase.hip); lcr_haplotag sums the same terms
 
 struct PhaseHost {
   PhaseDebug dbg;

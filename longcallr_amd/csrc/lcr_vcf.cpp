@@ -9,7 +9,8 @@
 //     earlier one, a code 4 included (vcf.rs:448-455);
 //   * quality = record.qual() as f32, NaN for a missing QUAL; the phase bit, REF and ALT are not used (an indel is a site at its POS).
 // Beside the reference's three values every site keeps REF, ALT and the phase bit of its winning record and sample for
-// lcr_vcf_contig_alleles (the loaders of allele_specific/longcallR-ase.py read them); lcr_vcf_contig does not see them.
+// lcr_vcf_contig_alleles (the loaders of allele_specific/longcallR-ase.py read them), and the sample's FORMAT PS integer for
+// lcr_vcf_contig_phase_sets (the phase sets lcr_haplotag tags reads with); lcr_vcf_contig does not see them.
 // Input: plain text, or gzip / BGZF (a sequence of gzip members, every member is inflated), parsed as it is read.  BCF input is refused, and so is a
 // record with samples but no GT key in its FORMAT (the reference panics there: `genotypes().expect`); a sites-only record has no
 // samples and yields nothing, as the reference's loop over zero samples does.
@@ -35,6 +36,7 @@ struct lcr_vcf {
     std::vector<uint8_t> gt;
     std::vector<float> qual;
     std::vector<uint8_t> ref, alt, phase;   // lcr_vcf_contig_alleles: parallel to the three above
+    std::vector<uint32_t> ps;               // lcr_vcf_contig_phase_sets: FORMAT PS of the winning record and sample, 0 = none
   };
   std::vector<std::string> names;          // in the order of their first record
   std::vector<const char*> name_ptrs;
@@ -70,7 +72,19 @@ int gt_code(const char* s, const char* e, int* n_alleles, int* phase) {
   return 4;
 }
 
-struct Entry { int64_t pos0; uint32_t seq; uint8_t gt; float qual; uint8_t ref, alt, phase; };
+struct Entry { int64_t pos0; uint32_t seq; uint8_t gt; float qual; uint8_t ref, alt, phase; uint32_t ps; };
+
+// a sample's PS subfield: an unsigned 32-bit decimal integer, anything else (".", empty, a sign, letters, overflow) -> 0
+uint32_t ps_value(const char* s, const char* e) {
+  if (s == e) return 0;
+  uint64_t v = 0;
+  for (const char* p = s; p < e; p++) {
+    if (*p < '0' || *p > '9') return 0;
+    v = v * 10 + (uint64_t)(*p - '0');
+    if (v > 0xffffffffull) return 0;
+  }
+  return (uint32_t)v;
+}
 
 // Lines are parsed as the (inflated) bytes arrive: what is held is one input chunk, one output chunk, the partial line between
 // them and one entry per record that yields a site -- not the file, nor its inflated text.
@@ -114,11 +128,12 @@ struct Parser {
       if (qe != qs.c_str() + qs.size()) { h->err = "line " + std::to_string(line_no) + ": bad QUAL"; return false; }
     }
     // index of GT among the FORMAT keys
-    int gt_key = -1;
+    int gt_key = -1, ps_key = -1;   // (PS: optional, for lcr_vcf_contig_phase_sets)
     { int k = 0; const char* p = col[8]; const char* fe = end_of(8);
       while (p <= fe) {
         const char* q = p; while (q < fe && *q != ':') q++;
-        if (q - p == 2 && p[0] == 'G' && p[1] == 'T') { gt_key = k; break; }
+        if (q - p == 2 && p[0] == 'G' && p[1] == 'T' && gt_key < 0) gt_key = k;
+        if (q - p == 2 && p[0] == 'P' && p[1] == 'S' && ps_key < 0) ps_key = k;
         k++; p = q + 1;
       } }
     if (gt_key < 0) { h->err = "line " + std::to_string(line_no) + ": no GT key in FORMAT (genotypes are required)"; return false; }
@@ -133,6 +148,7 @@ struct Parser {
     } else ci = it->second;
     // samples in order; each one with a diploid GT overwrites the record's value, so only the last of them counts
     int last = -1, last_phase = 0;
+    uint32_t last_ps = 0;
     for (const char* smp = col[9]; smp <= e;) {
       const char* se = smp; while (se < e && *se != '\t') se++;
       // the sample's GT subfield (a sample with fewer subfields has a missing GT: one allele, skipped)
@@ -143,7 +159,15 @@ struct Parser {
         const char* q = p; while (q < se && *q != ':') q++;
         int n_alleles = 0, phase = 0;
         const int code = gt_code(p, q, &n_alleles, &phase);
-        if (n_alleles == 2) { last = code; last_phase = phase; }
+        if (n_alleles == 2) {
+          last = code; last_phase = phase; last_ps = 0;
+          if (ps_key >= 0) {   // the same sample's PS subfield
+            const char* a = smp;
+            int g = 0;
+            while (g < ps_key && a < se) { if (*a == ':') g++; a++; }
+            if (g == ps_key) { const char* b = a; while (b < se && *b != ':') b++; last_ps = ps_value(a, b); }
+          }
+        }
       }
       smp = se + 1;
     }
@@ -156,7 +180,7 @@ struct Parser {
         if (ae - a != 1) alt = 0;
         a = ae + 1;
       }
-      ent[ci].push_back(Entry{(int64_t)pos - 1, seq++, (uint8_t)last, qual, ref, alt, (uint8_t)last_phase});
+      ent[ci].push_back(Entry{(int64_t)pos - 1, seq++, (uint8_t)last, qual, ref, alt, (uint8_t)last_phase, last_ps});
     }
     return true;
   }
@@ -194,6 +218,7 @@ struct Parser {
         if (i + 1 < v.size() && v[i + 1].pos0 == v[i].pos0) continue;   // the last value at a position wins
         c.pos0.push_back(v[i].pos0); c.gt.push_back(v[i].gt); c.qual.push_back(v[i].qual);
         c.ref.push_back(v[i].ref); c.alt.push_back(v[i].alt); c.phase.push_back(v[i].phase);
+        c.ps.push_back(v[i].ps);
       }
       std::vector<Entry>().swap(v);
     }
@@ -297,6 +322,16 @@ int lcr_vcf_contig_alleles(lcr_vcf* h, const char* name, int32_t* n, const uint8
   const lcr_vcf::Contig& c = h->contigs[it->second];
   *n = (int32_t)c.pos0.size();
   *ref = c.ref.data(); *alt = c.alt.data(); *phase = c.phase.data();
+  return LCR_OK;
+}
+
+int lcr_vcf_contig_phase_sets(lcr_vcf* h, const char* name, int32_t* n, const uint32_t** ps) {
+  if (!h || !name || !n || !ps) return LCR_E_ARG;
+  auto it = h->index.find(name);
+  if (it == h->index.end()) { *n = 0; *ps = nullptr; return LCR_OK; }
+  const lcr_vcf::Contig& c = h->contigs[it->second];
+  *n = (int32_t)c.ps.size();
+  *ps = c.ps.data();
   return LCR_OK;
 }
 

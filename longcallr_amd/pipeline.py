@@ -13,6 +13,7 @@ the five hot-path calls, with one context per GPU instead of one rayon task per 
   thread.rs:307-361 phased BAM                               -> lcr_bam_write_phased
 
   thread.rs:70-74,107-116 user-provided candidates (-v)   -> vcf.read_sites once + lcr_import_candidates per chunk
+  (no counterpart: the reference reads the phase bit and drops it) -> haplotag=True: lcr_haplotag per chunk in place of lcr_phase
   main.rs:216-225, thread.rs:80-92 -a / --exon-only          -> annotation.calling_annotation + intersect_regions per contig,
                                                                 lcr_set_exon_mask per chunk
 
@@ -117,7 +118,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
         asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
-        **param_overrides):
+        haplotag=False, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -186,10 +187,22 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     packed_upload: every chunk is cut with the bases left as the BAM's 4-bit codes (NativeBam.batch(packed=True)) and loaded through the
     asynchronous packed path (lcr_load_batch_packed_async: the nibbles cross the link, a kernel expands them in HBM).  Every output is
     byte for byte the one of a run without it.  Adds the stat upload_bytes_saved: n_bases - n_pack - 8 n_reads, summed over chunks.
-    Off by default."""
+    Off by default.
+    haplotag: with input_vcf, keep the input's phase (`whatshap haplotag` on the fragment matrix; include/lcr.h: lcr_haplotag): the file
+    is read with its alleles and PS (vcf.read_sites(alleles=True, phase_sets=True)), every chunk imports its sites as before and then
+    calls Engine.haplotag with the contig's phased heterozygous SNVs inside its span (vcf.haplotag_sites) where phase() stands otherwise.
+    Reads are tagged on the VCF's haplotypes with the VCF's phase sets -- the same labels in every region, gene and contig --, and the
+    junction / expression tables and the phased BAM behind it are keyed by them, unchanged code.  The VCF writer, the expression and the
+    junction-filter calls get min_phase_score = 0.0 in this mode: the phase is the input's, PQ is informational.  Per-gene expression
+    records are merged with ase.merge_gene_records(shared_phase_sets=True): a phase set now spans regions (the junction tables are
+    still merged per region: DESIGN.md section 1i).  Down-sampling does not apply to it.  Adds the stats haplotag_sites (candidates
+    tagged with the input's phase) and haplotag_reads (fragment rows assigned).  haplotag without input_vcf is a ValueError."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
+    haplotag = bool(haplotag)
+    if haplotag and input_vcf is None:
+        raise ValueError("haplotag needs input_vcf: the phase to keep is the input VCF's")
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -237,9 +250,15 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     stats = dict(contigs=0, regions=0, reads=0, candidates=0, vcf_records=0, chunks=0)
     sites = None
     if input_vcf is not None:
-        sites = vcf.read_sites(input_vcf)      # vcf.rs:400-462, once for the whole run (thread.rs:70-74)
+        sites = vcf.read_sites(input_vcf, alleles=haplotag, phase_sets=haplotag)      # vcf.rs:400-462, once for the whole run (thread.rs:70-74)
         stats["input_sites"] = sum(int(v[0].size) for v in sites.values())
         stats["imported_sites"] = 0
+    hap_sites = None
+    if haplotag:        # {contig: (pos0, h1, h2, ps)}: the phased heterozygous SNVs
+        hap_sites = {k: vcf.haplotag_sites(v) for k, v in sites.items()}
+        sites = {k: v[:3] for k, v in sites.items()}
+        stats["haplotag_sites"] = stats["haplotag_reads"] = 0
+    min_ps = 0.0 if haplotag else params.min_phase_score    # (the input's phase is not second-guessed by PQ)
     if truncation:
         stats["truncated_columns"] = 0
     if exon_only:
@@ -271,8 +290,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
-        lines = vcf.format_records(cands, name, params.min_phase_score)
+        lines = vcf.format_records(cands, name, min_ps)
         out = dict(text=lines if isinstance(lines, str) else "".join(lines), n_cand=int(cands.size))
+        if haplotag:
+            out["hap"] = (int(np.count_nonzero(cands["haplotype"])), int(np.count_nonzero(res["assignment"])))
         if want_reads:
             asg = res["assignment"].astype(np.int32)
             # thread.rs:204-214: every for_phasing fragment has an assignment entry (0 / 1 / 2), a phase set only if set
@@ -289,16 +310,16 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         if arec is not None and genes is not None:      # (region, gene) pair records; merged per gene when every chunk is in
             out["ase"] = (name, arec[0])
             if dna is not None:
-                out["ase"] += (ase.filter_pairs(arec[0], cands, dna.get(name, np.zeros(0, np.int64)), params.min_phase_score,
+                out["ase"] += (ase.filter_pairs(arec[0], cands, dna.get(name, np.zeros(0, np.int64)), min_ps,
                                                 ase_min_support, ase_overdispersion),)
         elif arec is not None:
             out["ase"] = (name, arec, batch.start0, batch.len)
             if dna is not None:
-                out["ase"] += (ase.filter_regions(arec, cands, dna.get(name, np.zeros(0, np.int64)), params.min_phase_score,
+                out["ase"] += (ase.filter_regions(arec, cands, dna.get(name, np.zeros(0, np.int64)), min_ps,
                                                   ase_min_support, ase_overdispersion),)
         results[idx] = out
 
-    def work(idx, batch, name, want_reads, imp, mask):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None)
+    def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
         with free_lock:
             while not free:
                 free_lock.wait()
@@ -324,7 +345,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             if want_reads:      # rows of the fragment matrix (read of every row, num_hete_links >= min_linkers): known before the phase stage
                 f = E.fragmat()
                 fm = dict(row_for_phasing=f["row_for_phasing"], row_read=f["row_read"])
-            E.phase()
+            if hs is not None:
+                E.haplotag(hs)
+            else:
+                E.phase()
             junc = None
             if asj_out is not None and asj_modes:
                 dpos = None
@@ -333,7 +357,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     lo, hi = np.searchsorted(dp, [int(batch.start0[0]), int(batch.start0[-1]) + int(batch.len[-1])])
                     dpos = dp[lo:hi]
                 junc = E.asj_genes(jgenes.get(name), asj_min_count, asj_min_junctions, exons=bool(asj_cluster_with_exons), dna_pos0=dpos,
-                                   coverage=bool(asj_gene_coverage))                                       # (waits for the phase stage)
+                                   coverage=bool(asj_gene_coverage), min_phase_score=min_ps)                                       # (waits for the phase stage)
             elif asj_out is not None and jgenes is not None:
                 junc = E.junctions_genes(jgenes.get(name), asj_min_count, asj_min_junctions)[0]           # (waits for the phase stage)
             elif asj_out is not None:
@@ -345,7 +369,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     pp, ppat, pmat = parental.get(name, (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.uint8)))
                     lo, hi = np.searchsorted(pp, [int(batch.start0[0]), int(batch.start0[-1]) + int(batch.len[-1])])
                     psites = (pp[lo:hi], ppat[lo:hi], pmat[lo:hi]) if hi > lo else None
-                arec = E.ase_genes(psites) if genes is not None else E.ase(psites)
+                arec = E.ase_genes(psites, min_phase_score=min_ps) if genes is not None else E.ase(psites, min_phase_score=min_ps)
             in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec)
         finally:
             with free_lock:
@@ -399,6 +423,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     lo, hi = np.searchsorted(sp, [chunk[0][0], chunk[-1][0] + chunk[-1][1]])
                     imp = (sp[lo:hi], sg[lo:hi], sq[lo:hi])
                     stats["imported_sites"] += int(hi - lo)
+                hs = None
+                if hap_sites is not None:
+                    hp_, h1_, h2_, hps_ = hap_sites.get(name, (np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros(0, np.uint32)))
+                    lo, hi = np.searchsorted(hp_, [chunk[0][0], chunk[-1][0] + chunk[-1][1]])
+                    hs = (hp_[lo:hi], h1_[lo:hi], h2_[lo:hi], hps_[lo:hi])
                 mask = None
                 if exon_only and sites is None:     # (thread.rs:107-116: the imported sites get no mask)
                     ivs = [cds_of[s] for s, _, _ in chunk]
@@ -406,7 +435,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                             np.array([a for v in ivs for a, _ in v], np.int64), np.array([b for v in ivs for _, b in v], np.int64))
                 while len(pending) > len(engines):     # bounded: at most one batch waiting per engine
                     pending.pop(0).result()
-                pending.append(pool.submit(work, n_chunks, batch, name, out_bam is not None, imp, mask))
+                pending.append(pool.submit(work, n_chunks, batch, name, out_bam is not None, imp, mask, hs))
                 n_chunks += 1
                 regions_out.extend((rid, s, l) for s, l, _ in chunk)
         for f in pending:
@@ -419,6 +448,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         E.close()
     text = "".join(r["text"] for r in results)
     stats["candidates"] = sum(r["n_cand"] for r in results)
+    if haplotag:
+        stats["haplotag_sites"] = sum(r["hap"][0] for r in results)
+        stats["haplotag_reads"] = sum(r["hap"][1] for r in results)
     stats["vcf_records"] = text.count("\n")
     write_vcf(out_vcf, contig_lengths, [text])
     if asj_out is not None:
@@ -454,9 +486,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         for name, parts in per_contig.items():
             pairs = np.concatenate([x[0] for x in parts])
             if dna is not None:
-                tables.append((name,) + ase.merge_gene_records(pairs, np.concatenate([x[1] for x in parts])))
+                tables.append((name,) + ase.merge_gene_records(pairs, np.concatenate([x[1] for x in parts]), shared_phase_sets=haplotag))
             else:
-                tables.append((name, ase.merge_gene_records(pairs)))
+                tables.append((name, ase.merge_gene_records(pairs, shared_phase_sets=haplotag)))
             tables[-1] = tables[-1][:2] + (genes.get(name, _ann.ContigGenes()),) + tables[-1][2:]
         text = ase.format_tsv(tables, ase_min_support, ase_overdispersion, patmat=parental is not None)
         stats["ase_genes"] = text.count("\n") - 1

@@ -12,10 +12,11 @@ import numpy as np
 from . import _abi
 
 
-def read_sites(path, alleles=False):
+def read_sites(path, alleles=False, phase_sets=False):
     """A VCF / .vcf.gz -> {contig: (pos0 int64, genotype uint8, qual float32)}, every array sorted by position: the sites
     lcr_import_candidates takes (genotype codes 0-4 and the overwrite rules of vcf.rs:400-462, see include/lcr.h).
-    alleles=True: three more uint8 arrays per contig, (..., ref, alt, phase) of lcr_vcf_contig_alleles."""
+    alleles=True: three more uint8 arrays per contig, (..., ref, alt, phase) of lcr_vcf_contig_alleles.
+    phase_sets=True: one more uint32 array behind them, the FORMAT PS of lcr_vcf_contig_phase_sets (0 = none)."""
     from . import _lib
     lib = _lib.load()
     h = C.c_void_p()
@@ -43,10 +44,33 @@ def read_sites(path, alleles=False):
                 if lib.lcr_vcf_contig_alleles(h, name, C.byref(m), C.byref(ref), C.byref(alt), C.byref(ph)) or m.value != k:
                     raise _lib.LcrError(lib.lcr_vcf_last_error(h).decode())
                 out[name.decode()] += (arr(ref, np.uint8), arr(alt, np.uint8), arr(ph, np.uint8))
+            if phase_sets:
+                ps = C.c_void_p()
+                if lib.lcr_vcf_contig_phase_sets(h, name, C.byref(m), C.byref(ps)) or m.value != k:
+                    raise _lib.LcrError(lib.lcr_vcf_last_error(h).decode())
+                out[name.decode()] += (arr(ps, np.uint32),)
         return out
     finally:
         if h:
             lib.lcr_vcf_close(h)
+
+
+def haplotag_sites(contig_arrays):
+    """One contig's read_sites(path, alleles=True, phase_sets=True) tuple -> (pos0 int64, h1 uint8, h2 uint8, ps uint32): the sites
+    Engine.haplotag takes.  Kept are the phased heterozygous SNVs: genotype code 1, phase 1 (`0|1`) or 2 (`1|0`), REF and ALT one base
+    each and both in ACGT after upper-casing.  `0|1` puts REF on haplotype 1 and ALT on haplotype 2, `1|0` the reverse.  ps is the
+    file's PS; a site without one (0) gets the 1-based position of the contig's first kept site -- one contig-wide set, named the way
+    the project names its own sets (after the first site's position)."""
+    pos0, gt, _q, ref, alt, phase, ps = contig_arrays
+    up = lambda a: np.where((a >= ord("a")) & (a <= ord("z")), a - 32, a).astype(np.uint8)
+    r, a = up(np.asarray(ref, np.uint8)), up(np.asarray(alt, np.uint8))
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    keep = (np.asarray(gt) == 1) & ((np.asarray(phase) == 1) | (np.asarray(phase) == 2)) & np.isin(r, acgt) & np.isin(a, acgt)
+    p, r, a, ph = np.asarray(pos0, np.int64)[keep], r[keep], a[keep], np.asarray(phase)[keep]
+    out_ps = np.asarray(ps, np.uint32)[keep].copy()
+    if p.size:
+        out_ps[out_ps == 0] = np.uint32(int(p[0]) + 1)
+    return p, np.where(ph == 1, r, a).astype(np.uint8), np.where(ph == 1, a, r).astype(np.uint8), out_ps
 
 
 def _f2(x):  # Rust `{:.2}` of an f32: NaN prints as "NaN" (an imported site at a column without A/C/G/T counts)

@@ -3,6 +3,7 @@
 
   python tools/run_pipeline.py -b reads.bam -f ref.fa -o out.vcf [--out-bam phased.bam] [-p hifi-masseq] [-c chr20,chr21]
                                  [-v known_snps.vcf.gz]   (phase these sites instead of calling candidates)
+                                 [-v phased.vcf.gz --haplotag]   (keep the file's phase: tag reads on its haplotypes and phase sets)
                                  [--truncation [--truncation-coverage N]]   (split regions at columns deeper than N)
                                  [-a genes.gtf.gz --exon-only]   (call inside annotated genes, at CDS columns only)
                                  [--packed-upload]   (upload the BAM's 4-bit bases and unpack them on the GPU; same outputs)
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("-v", "--input-vcf", help="user-provided candidate sites (VCF / .vcf.gz with GT): phased instead of called")
+    ap.add_argument("--haplotag", action="store_true", help="keep the phase of -v: tag reads on the VCF's haplotypes and phase sets instead of phasing its sites again (needs -v)")
     ap.add_argument("--downsample", action="store_true", help="phase regions of at least --downsample-depth fragments on a sample of that many (needs --read-assign-cutoff > 0)")
     ap.add_argument("--downsample-depth", type=int, default=10000)
     ap.add_argument("--truncation", action="store_true", help="end a region at columns deeper than --truncation-coverage, as at uncovered ones")
@@ -57,6 +59,8 @@ def main():
     ap.add_argument("--ase-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
+    if a.haplotag and not a.input_vcf:
+        ap.error("--haplotag needs -v / --input-vcf")
     if a.exon_only and not a.annotation:
         ap.error("--exon-only needs -a / --annotation")
     if a.ase_parental_vcf and a.ase_dna_vcf:
@@ -80,7 +84,7 @@ def main():
                       ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t),
                       asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
                       asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage,
-                      annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, **extra)
+                      annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, haplotag=a.haplotag, **extra)
     print(json.dumps(st))
 
 
