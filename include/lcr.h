@@ -878,7 +878,8 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * "grid_generic", "grid_spec_lanes", "post_half", "enum_force_big", "enum_force_stream" (1: every LDS-resident enumeration region by the
  * streaming kernel, one restart per wave), "enum_elide" (0: the enumeration restarts execute every sigma / delta step; default 1: a step whose inputs
  * have not changed since it last ran is skipped -- same results, same tie census), "tie_arith", "timing_mask",
- * "k3_hits" (0: the fragment stage walks the CIGARs itself), "async_phase" (1: lcr_phase returns with its kernels in flight),
+ * "k3_hits" (0: the fragment stage walks the CIGARs itself), "k3_list_blocks" (workgroups of the fragment stage's two passes that walk the
+ * reads beyond their hit lists; 0 = sized from the batch), "async_phase" (1: lcr_phase returns with its kernels in flight),
  * "grid_spec_batch" (0: the all-CU chain kernel's speculative half-rounds side by side on sub-grids; default 1: as eight bits of one state)
  * (bit k: only the kernel groups LCR_K_* k are timed when timing is enabled; 0 = all) (see PhaseDebug in
  * csrc/lcr_phase_host.h), "hist_tiles" (quality histograms from K0's records: 0 = when the survivors are dense, 1 = whenever the

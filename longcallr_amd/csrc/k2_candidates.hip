@@ -453,14 +453,9 @@ static GtConst make_gt_const() {
   return c;
 }
 
-__global__ void __launch_bounds__(LCR_BLOCK)
-k2_gt(DevParams prm, GtConst gc, const Survivor* __restrict__ sv, int32_t n_sv, const uint32_t* __restrict__ hist,
-      const int64_t* __restrict__ start0, lcr_candidate* __restrict__ out, int32_t* __restrict__ keep) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n_sv) return;
-  const Survivor v = sv[s];
-  const uint32_t* h = hist + (int64_t)s * 124;
-  keep[s] = 0;
+// One survivor: its record into c, true if it is kept.  h: the survivor's histogram row hist[4][31] (k2_gt: in LDS).
+__device__ __forceinline__ bool gt_survivor(const DevParams& prm, const GtConst& gc, const Survivor& v, const uint32_t* h,
+                                            const int64_t* __restrict__ start0, lcr_candidate& c) {
   const int ri = base_code(v.ref_base);
   // base-quality filter (candidate.rs:174-194): first non-reference major allele needs >= 2 quals >= min_baseq
   {
@@ -470,7 +465,7 @@ k2_gt(DevParams prm, GtConst gc, const Survivor* __restrict__ sv, int32_t n_sv, 
     if (ai >= 0) {
       uint32_t pass = 0;
       for (uint32_t q = prm.min_baseq; q <= 30; q++) pass += h[ai * 31 + q];
-      if (ac > 0 && pass < 2) return;
+      if (ac > 0 && pass < 2) return false;
     }
   }
   // log10 likelihoods: integer histogram x LUT, q ascending; zero counts are skipped so that
@@ -508,7 +503,6 @@ k2_gt(DevParams prm, GtConst gc, const Survivor* __restrict__ sv, int32_t n_sv, 
   }
   const double genotype_quality = ph[1] - ph[0];
 
-  lcr_candidate c;
   c.pos = start0[v.region] + v.col;  // 0-based reference position (candidate.rs:74,339)
   c.region = v.region;
   c.ref_base = v.ref_base; c.allele1 = v.allele1; c.allele2 = v.allele2; c.n_alt = v.n_alt;
@@ -520,7 +514,7 @@ k2_gt(DevParams prm, GtConst gc, const Survivor* __restrict__ sv, int32_t n_sv, 
   else if (gp[1] > gp[0] && gp[1] > gp[2]) { c.variant_type = 1; c.genotype = 0; }
   else { c.variant_type = 0; c.genotype = 1; }
   c.flags = 0;
-  if (variant_quality < (double)prm.min_qual) return;  // candidate.rs:374
+  if (variant_quality < (double)prm.min_qual) return false;  // candidate.rs:374
   // classification (candidate.rs:379-460)
   uint8_t ref_allele_base, alt0; float altf0, altf1 = 0.0f;
   if (v.allele1 == v.ref_base) { ref_allele_base = v.allele1; alt0 = v.allele2; altf0 = v.af2; }
@@ -542,16 +536,61 @@ k2_gt(DevParams prm, GtConst gc, const Survivor* __restrict__ sv, int32_t n_sv, 
     else c.flags = LCR_F_HET | LCR_F_FOR_PHASING;
     kept = true;
   }
-  if (!kept) return;  // variant_type 0 (candidate.rs:457-460)
-  out[s] = c;
-  keep[s] = 1;
+  return kept;  // (not kept: variant_type 0, candidate.rs:457-460)
+}
+
+// A wave per workgroup, a thread per survivor.  The workgroup's GT_ROWS histogram rows are one contiguous piece of `hist` (496 bytes each):
+// consecutive lanes copy its consecutive 16-byte words into LDS, and every thread runs the loops of gt_survivor over its own row there.  (A
+// thread that read its row from memory word by word made every load of the wave touch 64 cache lines 496 bytes apart.)  Rows are
+// GT_STRIDE = 125 words apart in LDS: at 124 the 64 lanes of a load fall on 16 banks.  The kept records leave the same way: staged in
+// LDS (over the rows, which nobody needs any more), stored as 16-byte words by consecutive lanes as in k2_scatter.
+#define GT_ROWS 64         // (C3: 19.6 us; half a wave of 32 rows per workgroup 18.8: what is left is a wave's serial pow / log10 chain, not the rows' way in)
+#define GT_STRIDE 125
+#define GT_REC_STRIDE 36   // words between staged records: 128 bytes + 16, so that sixteen lanes' 16-byte stores fall on distinct banks
+__global__ void __launch_bounds__(GT_ROWS)
+k2_gt(DevParams prm, GtConst gc, const Survivor* __restrict__ sv, int32_t n_sv, const uint32_t* __restrict__ hist,
+      const int64_t* __restrict__ start0, lcr_candidate* __restrict__ out, int32_t* __restrict__ keep) {
+  static_assert(sizeof(lcr_candidate) == 128 && GT_REC_STRIDE * 4 >= (int)sizeof(lcr_candidate) && GT_REC_STRIDE % 4 == 0, "a staged record is eight aligned 16-byte words");
+  static_assert(GT_ROWS * GT_REC_STRIDE <= GT_ROWS * GT_STRIDE, "the staged records fit where the rows were");
+  __shared__ __attribute__((aligned(16))) uint32_t lds[GT_ROWS * GT_STRIDE];
+  const int lane = threadIdx.x;
+  const int s0 = blockIdx.x * GT_ROWS, s = s0 + lane;
+  const int rows = min(GT_ROWS, n_sv - s0);                    // (the last workgroup: nothing is read beyond n_sv * 124 words)
+  const int n4 = rows * 31;                                    // 16-byte words of this workgroup's rows
+  const uint4* __restrict__ src = reinterpret_cast<const uint4*>(hist + (int64_t)s0 * 124);
+  uint4 w[31];
+#pragma unroll
+  for (int k = 0; k < 31; k++) w[k] = src[min(k * GT_ROWS + lane, n4 - 1)];   // every load in flight before the first is used
+#pragma unroll
+  for (int k = 0; k < 31; k++) {
+    const int i = k * GT_ROWS + lane;
+    if (i < n4) {
+      uint32_t* d = lds + (i / 31) * GT_STRIDE + (i % 31) * 4;
+      d[0] = w[k].x; d[1] = w[k].y; d[2] = w[k].z; d[3] = w[k].w;
+    }
+  }
+  __syncthreads();
+  lcr_candidate c;
+  bool kept = false;
+  if (s < n_sv) kept = gt_survivor(prm, gc, sv[s], lds + lane * GT_STRIDE, start0, c);
+  const unsigned long long km = __ballot(kept);
+  if (s < n_sv) keep[s] = kept ? 1 : 0;
+  __syncthreads();   // (every row has been read)
+  if (kept) *reinterpret_cast<lcr_candidate*>(lds + lane * GT_REC_STRIDE) = c;
+  __syncthreads();
+  uint4* __restrict__ dst = reinterpret_cast<uint4*>(out + s0);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {   // GT_ROWS / 8 records per turn, a 16-byte word per lane
+    const int rec = k * (GT_ROWS / 8) + (lane >> 3), wd = lane & 7;
+    if ((km >> rec) & 1ull) dst[rec * 8 + wd] = *reinterpret_cast<const uint4*>(lds + rec * GT_REC_STRIDE + wd * 4);
+  }
 }
 
 void launch_k2_gt(const DevParams& p, const Survivor* sv, int32_t n_sv, const uint32_t* hist, const int64_t* start0,
                   lcr_candidate* out, int32_t* keep, hipStream_t s) {
   static const GtConst g_gtc = make_gt_const();  // host libm values: the device only adds/multiplies them
   if (n_sv == 0) return;
-  hipLaunchKernelGGL(k2_gt, dim3((n_sv + LCR_BLOCK - 1) / LCR_BLOCK), dim3(LCR_BLOCK), 0, s, p, g_gtc, sv, n_sv, hist, start0, out, keep);
+  hipLaunchKernelGGL(k2_gt, dim3((n_sv + GT_ROWS - 1) / GT_ROWS), dim3(GT_ROWS), 0, s, p, g_gtc, sv, n_sv, hist, start0, out, keep);
 }
 
 void launch_k2_place(const Survivor* stage, const void* stage_key, const int32_t* n_staged, int32_t stage_cap, const int32_t* tile_off,

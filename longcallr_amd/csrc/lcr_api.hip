@@ -509,6 +509,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "timing_mask") c->timing_mask = (uint32_t)value;
   else if (k == "hist_tiles") c->dbg_hist_tiles = value > 0 ? 1 : value < 0 ? -1 : 0;
   else if (k == "k3_hits") c->dbg_k3_hits = value != 0;
+  else if (k == "k3_list_blocks") c->dbg_k3_list_blocks = (int)std::max<int64_t>(0, std::min<int64_t>(value, 65536));
   else if (k == "fuse_filter") c->dbg_fuse_filter = value != 0;
   else if (k == "spec_compact") c->dbg_spec_compact = value != 0;
   else if (k == "lean_planes") c->dbg_lean_planes = value != 0;

@@ -398,7 +398,7 @@ int lcr_fragments(lcr_ctx* c, const lcr_params* p) {
   }
   { Timer t(c, LCR_K_FRAG_COUNT);
     launch_k3_count(c->bv, c->read_bin.as<ReadBin>(), c->d_cand.as<lcr_candidate>(), c->d_cand_off.as<int32_t>(), c->row_region_off.as<int32_t>(), nr_cap,
-                    c->row_cnt.as<int32_t>(), c->row_links.as<uint32_t>(), c->frag_tmp_col.as<int32_t>(), c->frag_tmp_val.as<uint8_t>(), hits, c->stream);
+                    c->row_cnt.as<int32_t>(), c->row_links.as<uint32_t>(), c->frag_tmp_col.as<int32_t>(), c->frag_tmp_val.as<uint8_t>(), hits, c->dbg_k3_list_blocks, c->stream);
     launch_scan_i32_to_i64(c->scan_tmp, c->row_cnt.as<int32_t>(), c->row_ptr.as<int64_t>(), nr_cap, c->stream); }
   // the regions' first entries ([ng] = all entries) follow the count pass to the host: the phase stage sizes its
   // work from them without a round trip of its own
@@ -438,7 +438,7 @@ int lcr_fragments(lcr_ctx* c, const lcr_params* p) {
   { Timer t(c, LCR_K_FRAG_FILL);
     launch_k3_fill(c->bv, c->read_bin.as<ReadBin>(), c->d_cand.as<lcr_candidate>(), c->d_cand_off.as<int32_t>(), c->row_region_off.as<int32_t>(), nrow,
                    c->row_cnt.as<int32_t>(), c->row_ptr.as<int64_t>(), c->frag_tmp_col.as<int32_t>(), c->frag_tmp_val.as<uint8_t>(),
-                   c->col.as<int32_t>(), c->val.as<uint8_t>(), hits, c->stream); }
+                   c->col.as<int32_t>(), c->val.as<uint8_t>(), hits, c->dbg_k3_list_blocks, c->stream); }
   HIPCHK(c, hipGetLastError());
   c->stage = ST_FRAGGED;
   HT("frag:ret");

@@ -165,6 +165,7 @@ struct lcr_ctx {
   hipEvent_t ev_mask_t[2] = {};            // timing enabled: around the last build (clear + k2_exon_build), created on first use
   bool mask_timed = false;
   int dbg_k3_hits = 1;      // lcr_debug_set("k3_hits"): 0 = K3's count pass walks every read's CIGAR itself (the path of batches without hit lists)
+  int dbg_k3_list_blocks = 0;   // lcr_debug_set("k3_list_blocks"): workgroups that walk the overflow list in K3's two passes; 0 = sized from the batch's reads
   std::vector<lcr_candidate> h_cand;
   std::vector<int32_t> h_cand_off;
   DevBuf d_cand, d_cand_off;

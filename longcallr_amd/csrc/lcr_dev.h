@@ -296,10 +296,10 @@ struct K3Hits {   // what k2_hist left for K3 (hit_cnt == nullptr: nothing -- K3
 };
 void launch_k3_count(const BatchView& b, const ReadBin* rbin, const lcr_candidate* cand, const int32_t* cand_region_off,
                      const int32_t* row_region_off, int32_t n_rows, int32_t* row_cnt, uint32_t* row_links, int32_t* tmp_col,
-                     uint8_t* tmp_val, const K3Hits& hits, hipStream_t s);   // tmp_*: launch_k3_inline() provisional entries per row
+                     uint8_t* tmp_val, const K3Hits& hits, int list_blocks /* of the overflow-list role; 0: sized from the reads */, hipStream_t s);   // tmp_*: launch_k3_inline() provisional entries per row
 void launch_k3_fill(const BatchView& b, const ReadBin* rbin, const lcr_candidate* cand, const int32_t* cand_region_off,
                     const int32_t* row_region_off, int32_t n_rows, int32_t* row_cnt, const int64_t* row_ptr, const int32_t* tmp_col,
-                    const uint8_t* tmp_val, int32_t* col, uint8_t* val, const K3Hits& hits, hipStream_t s);
+                    const uint8_t* tmp_val, int32_t* col, uint8_t* val, const K3Hits& hits, int list_blocks, hipStream_t s);
 int launch_k3_inline();
 void launch_k3_rows_offsets(const BatchView& b, const lcr_candidate* cand, const int32_t* cand_region_off, int32_t* region_rows, int32_t* row_region_off,
                             hipStream_t s, int32_t* host_rows = nullptr /* pinned host memory as the device sees it */);   // region_rows and their exclusive prefix sums
