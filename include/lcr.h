@@ -516,6 +516,38 @@ typedef struct { int32_t n_regions; const lcr_ase_region* rec; const lcr_ase_reg
 int lcr_ase(lcr_ctx*, const lcr_ase_params*, int32_t mem, int32_t n_sites, const int64_t* pos0, const uint8_t* pat, const uint8_t* mat);
 int lcr_get_ase(lcr_ctx*, lcr_ase_list* out);
 
+/* Per-site allele x haplotype counts (K12): how often each base was seen on each haplotype at every candidate -- the SNP-level table
+ * that allelic-count tools consume, the 2 x 2 table behind "is this RNA edit allele-specific?", and the check of a phase --, counted on the
+ * GPU from what lcr_phase or lcr_haplotag left there.  DESIGN.md section 1j.  Row r of lcr_get_fragmat has assignment a and phase set ps
+ * (lcr_read_record); candidate c is an index into lcr_get_candidates.
+ *   entries of c       every CSR entry with col == c, from any row; n_entries is their number.  A LCR_F_DENSE candidate has none.
+ *   counted entry      q = val & 31 >= min_baseq; the entries below it are counted in n_lowq and take no further part.  min_baseq 0
+ *       counts everything; above 30 is LCR_E_ARG (the fragment matrix clamps qualities to 30), as in lcr_ase.
+ *   counting row       a is 1 or 2 and ps != 0 (lcr_ase's rule).
+ *   n_phase_sets       the number of distinct ps values among the counted entries of counting rows at c.
+ *   site's phase set   the candidate's own phase_set where it is not 0 -- also where another set has more rows at the site --; otherwise
+ *       the ps with the most counted entries of counting rows at c, ties to the smallest value; without any, 0.
+ *   counts             n[k][b], b = base code A, C, G, T (val >> 6), over the counted entries: k = 1 / 2 for counting rows of the site's
+ *       phase set with a = 1 / 2; k = 0 for every other row -- unassigned, assigned without a phase set, or in another set.
+ *   invariant          the twelve cells and n_lowq add up to n_entries.
+ *   order              one record per candidate, in candidate order; integer adds only: bit-reproducible, independent of the batch's
+ *       composition.
+ * Not a pileup: a read's base is seen only where the fragment matrix has an entry -- the base is the site's reference or one of its two
+ * major alleles (fragment.rs:134-152) --, and never at a dense candidate.
+ * lcr_site_counts needs the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed; params == NULL or
+ * min_baseq > 30: LCR_E_ARG, the last call's records stay valid), collects an asynchronous phase stage in flight first, queues a fixed
+ * number of kernels on the context's stream without a host wait of its own, writes no buffer another stage or getter reads, and may be
+ * repeated with another threshold.  The records die with the phase results: at the next candidate stage and at lcr_load_batch /
+ * lcr_bind_batch; lcr_get_site_counts answers LCR_E_STATE then.  rec: pinned host memory the call's last kernel wrote, valid until the
+ * next lcr_site_counts; dev_rec: the same records in HBM. */
+typedef struct { uint32_t min_baseq; } lcr_site_count_params;   /* 13, lcr_ase's default */
+typedef struct { uint32_t phase_set, n_phase_sets, n_entries, n_lowq; uint32_t n[3][4]; } lcr_site_count;   /* 64 bytes, one per candidate */
+int lcr_site_counts(lcr_ctx*, const lcr_site_count_params*);
+int lcr_get_site_counts(lcr_ctx*, int32_t* n_cand, const lcr_site_count** rec, const lcr_site_count** dev_rec);
+/* HIP-event time (ms) of the last lcr_site_counts' kernels with timing enabled (lcr_enable_timing); LCR_E_STATE without one.  Not a
+ * slot of lcr_kernel_ms: that list is closed. */
+int lcr_site_counts_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.

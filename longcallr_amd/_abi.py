@@ -150,6 +150,15 @@ HAPSITE_DTYPE = np.dtype([("match_fx", "<i8"), ("total_fx", "<i8"), ("n_h1", "<u
 assert HAPSITE_DTYPE.itemsize == 32, HAPSITE_DTYPE.itemsize
 
 
+class LcrSiteCountParams(C.Structure):   # include/lcr.h: lcr_site_count_params (13 = lcr_ase's default)
+    _fields_ = [("min_baseq", C.c_uint32)]
+
+
+# lcr_site_count (include/lcr.h): one candidate's allele x haplotype counts; n[k][b]: k = 0 other rows, 1 / 2 the site's set by haplotype, b = ACGT
+SITE_COUNT_DTYPE = np.dtype([("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("n_entries", "<u4"), ("n_lowq", "<u4"), ("n", "<u4", (3, 4))], align=True)
+assert SITE_COUNT_DTYPE.itemsize == 64, SITE_COUNT_DTYPE.itemsize
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

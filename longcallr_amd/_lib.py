@@ -22,6 +22,7 @@ SYMBOLS = [
     "lcr_load_batch_packed", "lcr_load_batch_packed_async", "lcr_unpack_bases", "lcr_unpack_ms", "lcr_bam_batch_packed",
     "lcr_set_exon_mask", "lcr_exon_mask_ms", "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
     "lcr_haplotag", "lcr_get_haplotag_sites", "lcr_haplotag_ms", "lcr_vcf_contig_phase_sets",
+    "lcr_site_counts", "lcr_get_site_counts", "lcr_site_counts_ms",
 ]
 
 _lib = None
@@ -139,5 +140,8 @@ def load():
     l.lcr_haplotag.argtypes = [vp, C.POINTER(_abi.LcrParams), C.c_int32, C.c_int32, vp, vp, vp, vp]
     l.lcr_get_haplotag_sites.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp)]
     l.lcr_haplotag_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_site_counts.argtypes = [vp, C.POINTER(_abi.LcrSiteCountParams)]
+    l.lcr_get_site_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp)]
+    l.lcr_site_counts_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

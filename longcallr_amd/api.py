@@ -362,6 +362,22 @@ class Engine:
         self._chk(self.lib.lcr_get_ase(self.h, C.byref(o)), "lcr_get_ase")   # (waits for the call's kernels: device sites are read by then)
         return _view(o.rec, _abi.ASE_DTYPE, o.n_regions)
 
+    def site_counts(self, min_baseq=13):
+        """lcr_site_counts + lcr_get_site_counts after phase() or haplotag(): per candidate of candidates() how often each base was seen
+        on each haplotype of the site's phase set, and on every other row (include/lcr.h) -> a structured array of _abi.SITE_COUNT_DTYPE,
+        one record per candidate, copied.  Waits for an asynchronous phase stage in flight; may be repeated with another threshold."""
+        p = _abi.LcrSiteCountParams(int(min_baseq))
+        self._chk(self.lib.lcr_site_counts(self.h, C.byref(p)), "lcr_site_counts")
+        n, rec, dev = C.c_int32(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.lcr_get_site_counts(self.h, C.byref(n), C.byref(rec), C.byref(dev)), "lcr_get_site_counts")
+        return _view(rec.value, _abi.SITE_COUNT_DTYPE, n.value)
+
+    def site_counts_ms(self):
+        """lcr_site_counts_ms: HIP-event time of the last site_counts()'s kernels (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_site_counts_ms(self.h, C.byref(ms)), "lcr_site_counts_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

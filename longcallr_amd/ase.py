@@ -15,6 +15,7 @@ from . import _abi, asj, vcf
 
 HEADER = "#Gene_name\tChr\tPS\tH1\tH2\tP_value"
 HEADER_PATMAT = HEADER + "\tH1_Paternal\tH1_Maternal\tH2_Paternal\tH2_Maternal"
+HEADER_SITES = "#Chr\tPos\tRef\tAlt\tFilter\tGT\tPS\tH1_ref\tH1_alt\tH2_ref\tH2_alt\tOther_ref\tOther_alt\tP_ase\tP_ase_adj\tP_hap\tP_hap_adj"
 
 
 def convert_mu_rho_to_alpha_beta(mu, rho):
@@ -213,4 +214,44 @@ def format_tsv(tables, min_support=10, overdispersion=0.001, patmat=False):
     lines = [(HEADER_PATMAT if patmat else HEADER) + "\n"]
     for (head, tail), p in zip(rows, adj):
         lines.append("%s\t%s%s\n" % (head, float(p), tail))
+    return "".join(lines)
+
+
+def format_sites_tsv(tables, min_support=10, overdispersion=0.001, min_phase_score=0.0):
+    """The per-site table of Engine.site_counts() (include/lcr.h: lcr_site_counts): allele x haplotype counts at every candidate the VCF
+    writer prints.  tables: [(chrom, cands, site_records)] -- per batch the contig's name, the candidate records behind the phase stage
+    and site_counts()'s records, parallel to them.  One row per candidate for which vcf.format_records(cands, chrom, min_phase_score)
+    prints a line, in that order -- min_phase_score is the value the VCF writer gets --, written only when H1_ref + H1_alt + H2_ref +
+    H2_alt >= min_support.  Pos (1-based), Ref, Alt, Filter and GT are the writer's own fields; PS is the record's phase set, "." for
+    0.  ref = the cell of the upper-cased ref_base (no cell when it is not one of ACGT), alt = the other cells together -- both alleles
+    of a triallelic site --, for haplotype 1, haplotype 2 and the other rows (unassigned, without a phase set, or in another set).
+    P_ase: betabinom_two_sided(alt, ref + alt, 0.5, overdispersion) over haplotypes 1 + 2, the SNP-level imbalance.  P_hap:
+    asj.fisher_two_sided([[H1_ref, H1_alt], [H2_ref, H2_alt]]): is the allele tied to a haplotype -- the question at RnaEdit and
+    low-fraction rows.  Each is Benjamini-Hochberg adjusted (asj.bh_adjust) over all written rows."""
+    rows, p_ase, p_hap = [], [], []
+    for chrom, cands, recs in tables:
+        if len(cands) != len(recs):
+            raise ValueError("site records and candidates of %s differ in number: %d and %d" % (chrom, len(recs), len(cands)))
+        for i in range(len(cands)):
+            line = vcf.format_records(cands[i:i + 1], chrom, min_phase_score)
+            if not line:
+                continue
+            f = line.rstrip("\n").split("\t")
+            code = "ACGT".find(chr(int(cands["ref_base"][i])).upper())
+            cells = []      # H1_ref, H1_alt, H2_ref, H2_alt, Other_ref, Other_alt
+            for k in (1, 2, 0):
+                n = [int(x) for x in recs["n"][i][k]]
+                ref = n[code] if code >= 0 else 0
+                cells += [ref, sum(n) - ref]
+            if sum(cells[:4]) < min_support:
+                continue
+            ps = int(recs["phase_set"][i])
+            rows.append("%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s" % (f[0], f[1], f[3], f[4], f[6], f[9].split(":")[0], ps if ps else ".",
+                                                          "\t".join("%d" % x for x in cells)))
+            p_ase.append(betabinom_two_sided(cells[1] + cells[3], sum(cells[:4]), 0.5, overdispersion))
+            p_hap.append(asj.fisher_two_sided([cells[0:2], cells[2:4]]))
+    adj_ase, adj_hap = asj.bh_adjust(p_ase), asj.bh_adjust(p_hap)
+    lines = [HEADER_SITES + "\n"]
+    for k, head in enumerate(rows):
+        lines.append("%s\t%s\t%s\t%s\t%s\n" % (head, float(p_ase[k]), float(adj_ase[k]), float(p_hap[k]), float(adj_hap[k])))
     return "".join(lines)

@@ -5,7 +5,8 @@
 // lcr_ase_genes, lcr_get_ase_genes), lcr_junctions_genes.hip (lcr_junctions_genes, lcr_get_junctions_genes) and lcr_asj_genes.hip
 // (lcr_asj_genes, lcr_get_asj_genes).  The last two fill one struct each, GeneJunctions, by the same steps (declared at the end), and the
 // three calls that take a gene annotation share its upload and verdict (annotation_queue, annotation_verdict).  lcr_haplotag.hip
-// (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks.
+// (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks;
+// lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) is one more call behind either of them.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -215,6 +216,15 @@ struct lcr_ctx {
   HostBuf h_ase, h_ase_bad;                            // pinned: the records; the verdict on the parental sites
   hipEvent_t ev_ase = nullptr;                         // behind the sites' check, then behind the call's last kernel
 
+  // K12 (lcr_site_counts): scratch and results of its own -- no other stage or getter reads them
+  bool sc_valid = false;     // lcr_get_site_counts: the last lcr_site_counts' records belong to the phase results of the bound batch (rewind_to)
+  bool sc_timed = false;     // ev_sc_t brackets the last call's kernels
+  int32_t sc_ncand = 0;
+  DevBuf sc_cnt, sc_off, sc_seg, d_sc;   // entries per candidate (counted up, then back down); their 64-bit offsets; a word per entry, by candidate; the records
+  HostBuf h_sc;                          // pinned: the records
+  hipEvent_t ev_sc = nullptr;            // behind the call's last kernel; created on first use
+  hipEvent_t ev_sc_t[2] = {};            // timing enabled: around the call's kernels, created on first use
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -270,6 +280,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
   if (to < ST_PHASED) c->hap_valid = false;      // lcr_haplotag's site records go with the phase results they describe
   if (to < ST_PHASED) c->jgene.valid = c->ajgene.valid = false;   // ... and the per-gene junction tables
+  if (to < ST_PHASED) c->sc_valid = false;       // ... and the per-site allele x haplotype counts
   if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),

@@ -355,6 +355,13 @@ void launch_k11_rows(int32_t n_rows, const int64_t* row_ptr, const int32_t* col,
 void launch_k11_finish(lcr_candidate* cand, int32_t n_cand, const uint8_t* site, const lcr_haplotag_site* acc, lcr_candidate* host_cand /* pinned */,
                        lcr_haplotag_site* host_acc /* pinned */, hipStream_t s);
 
+// k12_site_counts.hip: allele x haplotype counts per candidate over the fragment matrix (lcr_site_counts)
+void launch_k12_count(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, int32_t n_cand, uint32_t* cnt /* n_cand, zeroed */, hipStream_t s);
+void launch_k12_fill(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const lcr_read_record* rec, uint32_t min_baseq,
+                     int32_t n_cand, uint32_t* cnt /* k12_count's: counted back down to 0 */, const int64_t* off /* n_cand + 1 */, uint64_t* seg /* nnz */, hipStream_t s);
+void launch_k12_sites(const lcr_candidate* cand, int32_t n_cand, const int64_t* off, const uint64_t* seg, lcr_site_count* out,
+                      lcr_site_count* host_out /* pinned (device pointer) */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

@@ -118,7 +118,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
         asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
-        haplotag=False, **param_overrides):
+        haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -196,13 +196,22 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     junction-filter calls get min_phase_score = 0.0 in this mode: the phase is the input's, PQ is informational.  Per-gene expression
     records are merged with ase.merge_gene_records(shared_phase_sets=True): a phase set now spans regions (the junction tables are
     still merged per region: DESIGN.md section 1i).  Down-sampling does not apply to it.  Adds the stats haplotag_sites (candidates
-    tagged with the input's phase) and haplotag_reads (fragment rows assigned).  haplotag without input_vcf is a ValueError."""
+    tagged with the input's phase) and haplotag_reads (fragment rows assigned).  haplotag without input_vcf is a ValueError.
+    ase_sites_out / ase_sites_min_baseq: the per-site allele x haplotype table (include/lcr.h: lcr_site_counts; ase.format_sites_tsv),
+    written to ase_sites_out: one row per VCF record of the run with the reference / alternate counts on haplotype 1, haplotype 2 and
+    the other reads, the SNP-level imbalance test and the allele x haplotype Fisher test.  Every chunk calls Engine.site_counts right
+    behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Entries with a base
+    quality below ase_sites_min_baseq are not counted (0 - 30, ValueError otherwise); ase_min_support and ase_overdispersion are the
+    expression table's.  Adds the stat ase_sites (rows written).  No other output depends on it; without ase_sites_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
     haplotag = bool(haplotag)
     if haplotag and input_vcf is None:
         raise ValueError("haplotag needs input_vcf: the phase to keep is the input VCF's")
+    if ase_sites_out is not None and (isinstance(ase_sites_min_baseq, bool) or int(ase_sites_min_baseq) != ase_sites_min_baseq
+                                      or not 0 <= int(ase_sites_min_baseq) <= 30):
+        raise ValueError("ase_sites_min_baseq must be an integer in [0, 30] (the fragment matrix clamps qualities to 30), got %r" % (ase_sites_min_baseq,))
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -279,14 +288,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -317,6 +326,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             if dna is not None:
                 out["ase"] += (ase.filter_regions(arec, cands, dna.get(name, np.zeros(0, np.int64)), min_ps,
                                                   ase_min_support, ase_overdispersion),)
+        if srec is not None:
+            out["sites"] = (name, cands.copy(), srec)     # (cands is the context's buffer: the table is written when every chunk is in)
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -370,7 +381,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     lo, hi = np.searchsorted(pp, [int(batch.start0[0]), int(batch.start0[-1]) + int(batch.len[-1])])
                     psites = (pp[lo:hi], ppat[lo:hi], pmat[lo:hi]) if hi > lo else None
                 arec = E.ase_genes(psites, min_phase_score=min_ps) if genes is not None else E.ase(psites, min_phase_score=min_ps)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec)
+            srec = E.site_counts(ase_sites_min_baseq) if ase_sites_out is not None else None                  # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec)
         finally:
             with free_lock:
                 free.append(k)
@@ -498,6 +510,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         text = ase.format_tsv([r["ase"] for r in results], ase_min_support, ase_overdispersion, patmat=parental is not None)
         stats["ase_regions"] = text.count("\n") - 1
         with open(ase_out, "w") as f:
+            f.write(text)
+    if ase_sites_out is not None:
+        text = ase.format_sites_tsv([r["sites"] for r in results], ase_min_support, ase_overdispersion, min_ps)
+        stats["ase_sites"] = text.count("\n") - 1
+        with open(ase_sites_out, "w") as f:
             f.write(text)
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)

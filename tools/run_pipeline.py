@@ -12,6 +12,7 @@
                                  [--ase-out out.ase.tsv [--ase-min-support N] [--ase-overdispersion R]
                                   [--ase-parental-vcf phased.vcf.gz | --ase-dna-vcf dna.vcf.gz]   (allele-specific expression table)
                                   [--ase-annotation genes.gtf.gz [--ase-gene-types protein_coding,lncRNA]]]   (... per annotated gene)
+                                 [--ase-sites-out out.ase_sites.tsv [--ase-sites-min-baseq N]]   (allele x haplotype counts per VCF record)
 """
 import argparse
 import json
@@ -57,6 +58,8 @@ def main():
     ap.add_argument("--ase-dna-vcf", help="DNA VCF: keep the regions with a significant DNA-heterozygous site (.filter_ase.tsv)")
     ap.add_argument("--ase-annotation", help="GTF / GFF3 (.gz) annotation: the table gets one row per gene, reads assigned to genes on the GPU")
     ap.add_argument("--ase-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
+    ap.add_argument("--ase-sites-out", help="write the per-site table: reference / alternate counts per haplotype at every VCF record, with --ase-min-support and --ase-overdispersion")
+    ap.add_argument("--ase-sites-min-baseq", type=int, default=13, help="base quality an entry needs to be counted in --ase-sites-out (0 - 30)")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -69,6 +72,8 @@ def main():
         ap.error("--ase-parental-vcf / --ase-dna-vcf need --ase-out")
     if a.ase_annotation and not a.ase_out:
         ap.error("--ase-annotation needs --ase-out")
+    if not 0 <= a.ase_sites_min_baseq <= 30:
+        ap.error("--ase-sites-min-baseq must lie in 0 - 30 (the fragment matrix clamps qualities to 30)")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -84,7 +89,8 @@ def main():
                       ase_annotation=a.ase_annotation, ase_gene_types=tuple(t for t in a.ase_gene_types.split(",") if t),
                       asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
                       asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage,
-                      annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, haplotag=a.haplotag, **extra)
+                      annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, haplotag=a.haplotag,
+                      ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, **extra)
     print(json.dumps(st))
 
 
