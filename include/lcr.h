@@ -548,6 +548,46 @@ int lcr_get_site_counts(lcr_ctx*, int32_t* n_cand, const lcr_site_count** rec, c
  * slot of lcr_kernel_ms: that list is closed. */
 int lcr_site_counts_ms(lcr_ctx*, float* ms);
 
+/* Per-haplotype coverage (K13): covered depth per haplotype class at EVERY column of every region window, run-length encoded -- the
+ * bedGraph / bigWig pair that is loaded beside the junction and expression tables --, counted on the GPU from the bound batch's positions
+ * and CIGARs and from what lcr_phase or lcr_haplotag left there.  DESIGN.md section 1k.  All coordinates 0-based half-open; region g of the
+ * bound batch has the window [start0[g], start0[g] + len[g]) and the reads [read_begin[g], read_begin[g+1]) of lcr_regions.
+ *   class of a read    read i has class k = assignment[r] when a row r of lcr_get_fragmat has row_read[r] == i and assignment[r] is 1 or 2:
+ *       the rule by which an HP tag is written, and lcr_junctions' rule.  The phase set is not consulted.  Every other read has class 0:
+ *       rows with assignment 0, reads that are no row (they start behind the region's last candidate), all reads of a region without
+ *       candidates.  A read listed in two regions is classed in each by that region's own row.
+ *   covered columns    walk the CIGAR from pos: M, =, X and D of length >= 1 cover [p, p + l) and advance p; N advances p and covers
+ *       nothing; I, S, H, P and zero-length ops do neither.  Each covered block is clipped to the region's window; a block wholly outside
+ *       it contributes nothing (reads do reach outside: the flanks of a truncation cut, gene-clipped regions).
+ *   depth              depth[k][c] = the number of reads of class k that cover window column c; u32, no narrowing anywhere.
+ *   segments           within one region a segment is a maximal run of consecutive columns with the same triple (depth[0], depth[1],
+ *       depth[2]) other than (0, 0, 0); all-zero runs are not stored; a segment never crosses a region boundary; order: region, then start.
+ *   region record      n_reads[k]: the region's reads per class, those without a block inside the window included; bases[k]: the sum of
+ *       depth[k][c] over c (u64); max_depth[k]: the maximum over the window; seg_region_off[g] .. [g+1]: the region's segments.
+ *   reproducibility    integer adds only: bit-reproducible and independent of the batch's composition -- a region processed alone gives
+ *       the same records as inside any batch, apart from its region index.
+ * Instance: start0 = 1000, len = 40; r0 pos 1000 10M class 1; r1 pos 1005 5M10N5M class 2; r2 pos 1008 4M2D4M class 0; r3 pos 1020
+ * 3S5M2I5M class 1.  Six segments, [start, end) -> (n0, n1, n2): [1000,1005) (0,1,0); [1005,1008) (0,1,1); [1008,1010) (1,1,1);
+ * [1010,1018) (1,0,0); [1020,1025) (0,1,1); [1025,1030) (0,1,0).  bases = (10, 20, 10), max_depth = (1, 1, 1), n_reads = (1, 2, 1).
+ * lcr_hap_coverage needs the bound batch with the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed),
+ * collects an asynchronous phase stage in flight first, queues its kernels on the context's stream, writes no buffer another stage or
+ * getter reads, and may be repeated.  The number of segments is data dependent: the call is the count-pass form -- it waits ONCE on the
+ * host, like lcr_junctions, for the segment count, and sizes the records from it (no capacity bound is guessed).  Dense form: 12 bytes of
+ * HBM per window column of the batch while the call runs.  More than 2^31 - 1 segments in one batch: LCR_E_ARG.  The records die with the
+ * phase results: at the next candidate stage and at lcr_load_batch / lcr_bind_batch; lcr_get_hap_coverage answers LCR_E_STATE then.
+ * seg, seg_region_off (n_regions + 1) and reg (n_regions): pinned host memory the call's last kernels wrote, valid until the next
+ * lcr_hap_coverage; dev_*: the same records in HBM.  seg / dev_seg are NULL without a segment, reg / dev_reg without a region.
+ * Measured: 0.78 ms per warm call on the benchmark's C3 workload (DESIGN.md section 1k has the command and the sizes). */
+typedef struct { int32_t region; int32_t len; int64_t start0; uint32_t n[3]; uint32_t pad_; } lcr_hap_cov_segment;   /* 32 bytes */
+typedef struct { int32_t region; uint32_t n_reads[3]; uint32_t max_depth[3]; uint32_t pad_; uint64_t bases[3]; } lcr_hap_cov_region;  /* 56 bytes */
+typedef struct { int32_t n_regions, n_segments; const lcr_hap_cov_segment* seg; const int32_t* seg_region_off;
+                 const lcr_hap_cov_region* reg; const lcr_hap_cov_segment* dev_seg; const lcr_hap_cov_region* dev_reg; } lcr_hap_cov_list;
+int lcr_hap_coverage(lcr_ctx*);
+int lcr_get_hap_coverage(lcr_ctx*, lcr_hap_cov_list* out);
+/* HIP-event time (ms) from the first to the last kernel of the last lcr_hap_coverage with timing enabled (lcr_enable_timing), the host's
+ * wait for the segment count included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_hap_coverage_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.

@@ -159,6 +159,19 @@ SITE_COUNT_DTYPE = np.dtype([("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("n_
 assert SITE_COUNT_DTYPE.itemsize == 64, SITE_COUNT_DTYPE.itemsize
 
 
+# lcr_hap_cov_segment / lcr_hap_cov_region (include/lcr.h): a run of window columns with one depth triple n[k] (k = 0 unassigned, 1 / 2 the
+# haplotypes); a region's reads, maxima and covered bases per class
+HAP_COV_SEGMENT_DTYPE = np.dtype([("region", "<i4"), ("len", "<i4"), ("start0", "<i8"), ("n", "<u4", (3,)), ("pad_", "<u4")], align=True)
+assert HAP_COV_SEGMENT_DTYPE.itemsize == 32, HAP_COV_SEGMENT_DTYPE.itemsize
+HAP_COV_REGION_DTYPE = np.dtype([("region", "<i4"), ("n_reads", "<u4", (3,)), ("max_depth", "<u4", (3,)), ("pad_", "<u4"), ("bases", "<u8", (3,))], align=True)
+assert HAP_COV_REGION_DTYPE.itemsize == 56, HAP_COV_REGION_DTYPE.itemsize
+
+
+class LcrHapCovList(C.Structure):   # include/lcr.h: lcr_hap_cov_list
+    _fields_ = [("n_regions", C.c_int32), ("n_segments", C.c_int32), ("seg", C.c_void_p), ("seg_region_off", C.c_void_p),
+                ("reg", C.c_void_p), ("dev_seg", C.c_void_p), ("dev_reg", C.c_void_p)]
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

@@ -23,6 +23,7 @@ SYMBOLS = [
     "lcr_set_exon_mask", "lcr_exon_mask_ms", "lcr_import_candidates", "lcr_vcf_open", "lcr_vcf_close", "lcr_vcf_last_error", "lcr_vcf_contigs", "lcr_vcf_contig",
     "lcr_haplotag", "lcr_get_haplotag_sites", "lcr_haplotag_ms", "lcr_vcf_contig_phase_sets",
     "lcr_site_counts", "lcr_get_site_counts", "lcr_site_counts_ms",
+    "lcr_hap_coverage", "lcr_get_hap_coverage", "lcr_hap_coverage_ms",
 ]
 
 _lib = None
@@ -143,5 +144,8 @@ def load():
     l.lcr_site_counts.argtypes = [vp, C.POINTER(_abi.LcrSiteCountParams)]
     l.lcr_get_site_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp)]
     l.lcr_site_counts_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_hap_coverage.argtypes = [vp]
+    l.lcr_get_hap_coverage.argtypes = [vp, C.POINTER(_abi.LcrHapCovList)]
+    l.lcr_hap_coverage_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

@@ -378,6 +378,29 @@ class Engine:
         self._chk(self.lib.lcr_site_counts_ms(self.h, C.byref(ms)), "lcr_site_counts_ms")
         return float(ms.value)
 
+    def hap_coverage(self):
+        """lcr_hap_coverage + lcr_get_hap_coverage after phase() or haplotag(): the covered depth of every window column per haplotype
+        class (0 unassigned, 1 / 2 as the HP tag) as run-length segments, and per region the reads, maxima and covered bases per class
+        (include/lcr.h) -> (segments as a structured array of _abi.HAP_COV_SEGMENT_DTYPE, ordered by region and start; seg_region_off,
+        n_regions + 1; region records as _abi.HAP_COV_REGION_DTYPE), all copied.  Waits for an asynchronous phase stage in flight; may
+        be repeated."""
+        self._chk(self.lib.lcr_hap_coverage(self.h), "lcr_hap_coverage")
+        o = self._hap_coverage_list()
+        return (_view(o.seg, _abi.HAP_COV_SEGMENT_DTYPE, o.n_segments), _view(o.seg_region_off, np.int32, o.n_regions + 1),
+                _view(o.reg, _abi.HAP_COV_REGION_DTYPE, o.n_regions))
+
+    def _hap_coverage_list(self):
+        """lcr_get_hap_coverage: the last hap_coverage()'s list (pinned host and HBM pointers)"""
+        o = _abi.LcrHapCovList()
+        self._chk(self.lib.lcr_get_hap_coverage(self.h, C.byref(o)), "lcr_get_hap_coverage")
+        return o
+
+    def hap_coverage_ms(self):
+        """lcr_hap_coverage_ms: HIP-event time of the last hap_coverage()'s kernels, its host wait included (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_hap_coverage_ms(self.h, C.byref(ms)), "lcr_hap_coverage_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

@@ -9,8 +9,9 @@ SO = os.path.join(HERE, "liblcr.so")
 SOURCES = ["k0_ops.hip", "k0_unpack.hip", "k1_pileup.hip", "k2_candidates.hip", "k2_import.hip", "k2_exon.hip", "k3_fragments.hip", "k4_phase.hip", "k4_enum.hip", "k4_stage.hip", "k4_sample.hip", "k4_post.hip", "k4_grid.hip", "k5_regions.hip", "k6_junctions.hip", "k7_ase.hip", "k8_genes.hip", "k9_gene_junctions.hip", "k10_asj_modes.hip", "lcr_api.hip", "lcr_batch.hip", "lcr_pileup.hip", "lcr_calls.hip", "lcr_junctions.hip", "lcr_ase.hip", "lcr_genes.hip", "lcr_junctions_genes.hip", "lcr_asj_genes.hip",
            "lcr_bam.cpp", "lcr_vcf.cpp",   # lcr_bam.cpp / lcr_vcf.cpp: host-only BGZF / BAM decode and VCF reader (zlib)
            "k11_haplotag.hip", "lcr_haplotag.hip",
-           "k12_site_counts.hip", "lcr_site_counts.hip"]   # (new units go to the end: the link order moves the bench line)
-HEADERS = ["lcr_dev.h", "k0_unpack.h", "lcr_ctx.h", "lcr_phase_host.h", "k4_dev.h", "k4_types.h", "k4_grid.h", "k4_grid_batch.h", "k4_kernels.h", "k4_post.h", "k2_eval.h", "k7_sweep.h", "lcr_asj_args.h", os.path.join("..", "..", "include", "lcr.h")]
+           "k12_site_counts.hip", "lcr_site_counts.hip",
+           "k13_hap_coverage.hip", "lcr_hap_coverage.hip"]   # (new units go to the end: the link order moves the bench line)
+HEADERS = ["lcr_dev.h", "k0_unpack.h", "lcr_ctx.h", "lcr_phase_host.h", "k4_dev.h", "k4_types.h", "k4_grid.h", "k4_grid_batch.h", "k4_kernels.h", "k4_post.h", "k2_eval.h", "k7_sweep.h", "lcr_asj_args.h", "k13_hap_coverage.h", os.path.join("..", "..", "include", "lcr.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function"]
 

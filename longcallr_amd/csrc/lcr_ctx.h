@@ -6,7 +6,8 @@
 // (lcr_asj_genes, lcr_get_asj_genes).  The last two fill one struct each, GeneJunctions, by the same steps (declared at the end), and the
 // three calls that take a gene annotation share its upload and verdict (annotation_queue, annotation_verdict).  lcr_haplotag.hip
 // (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks;
-// lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) is one more call behind either of them.
+// lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) and lcr_hap_coverage.hip (lcr_hap_coverage,
+// lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -225,6 +226,15 @@ struct lcr_ctx {
   hipEvent_t ev_sc = nullptr;            // behind the call's last kernel; created on first use
   hipEvent_t ev_sc_t[2] = {};            // timing enabled: around the call's kernels, created on first use
 
+  // K13 (lcr_hap_coverage): scratch and results of its own -- no other stage or getter reads them
+  bool hc_valid = false;     // lcr_get_hap_coverage: the last lcr_hap_coverage's records belong to the phase results of the bound batch (rewind_to)
+  bool hc_timed = false;     // ev_hc_t brackets the last call's kernels
+  int32_t hc_ng = 0, hc_n = 0;
+  DevBuf hc_planes, hc_nseg, hc_off, hc_send, d_hc_seg, d_hc_reg;   // three u32 planes (differences, then depths); run starts per region; their offsets; a segment's end column; the records
+  HostBuf h_hc_seg, h_hc_off, h_hc_reg;   // pinned: the segments; their offsets per region; the region records
+  hipEvent_t ev_hc = nullptr;             // behind the count pass, then behind the call's last kernel; created on first use
+  hipEvent_t ev_hc_t[2] = {};             // timing enabled: around the call's kernels, created on first use
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -281,6 +291,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->hap_valid = false;      // lcr_haplotag's site records go with the phase results they describe
   if (to < ST_PHASED) c->jgene.valid = c->ajgene.valid = false;   // ... and the per-gene junction tables
   if (to < ST_PHASED) c->sc_valid = false;       // ... and the per-site allele x haplotype counts
+  if (to < ST_PHASED) c->hc_valid = false;       // ... and the per-haplotype coverage segments
   if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),

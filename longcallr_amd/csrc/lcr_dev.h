@@ -362,6 +362,15 @@ void launch_k12_fill(int32_t n_rows, const int64_t* row_ptr, const int32_t* col,
 void launch_k12_sites(const lcr_candidate* cand, int32_t n_cand, const int64_t* off, const uint64_t* seg, lcr_site_count* out,
                       lcr_site_count* host_out /* pinned (device pointer) */, hipStream_t s);
 
+// k13_hap_coverage.hip: covered depth per haplotype class at every window column, run-length encoded (lcr_hap_coverage)
+void launch_k13_blocks(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, int64_t n_cols,
+                       uint32_t* planes /* 3 x n_cols, zeroed: difference planes by class */, hipStream_t s);
+void launch_k13_scan(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, int64_t n_cols, uint32_t* planes /* -> depths */,
+                     lcr_hap_cov_region* reg, int32_t* nseg /* n_regions: run starts */, hipStream_t s);
+void launch_k13_offsets(int32_t ng, const int32_t* off /* ng + 1 */, const lcr_hap_cov_region* reg, int32_t* host_off, lcr_hap_cov_region* host_reg /* pinned (device pointers) */, hipStream_t s);
+void launch_k13_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int32_t* off, lcr_hap_cov_segment* seg, int32_t* send /* per segment: its end column */, hipStream_t s);
+void launch_k13_finish(int32_t n_seg, int32_t ng, const int64_t* start0, const int32_t* send, lcr_hap_cov_segment* seg, lcr_hap_cov_segment* host_seg /* pinned (device pointer) */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

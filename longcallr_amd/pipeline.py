@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import _abi, annotation, api, ase, asj, bamio, vcf
+from . import _abi, annotation, api, ase, asj, bamio, coverage, vcf
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -118,7 +118,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
         asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
-        haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, **param_overrides):
+        haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, hap_coverage_out=None, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -202,7 +202,16 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     the other reads, the SNP-level imbalance test and the allele x haplotype Fisher test.  Every chunk calls Engine.site_counts right
     behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Entries with a base
     quality below ase_sites_min_baseq are not counted (0 - 30, ValueError otherwise); ase_min_support and ase_overdispersion are the
-    expression table's.  Adds the stat ase_sites (rows written).  No other output depends on it; without ase_sites_out nothing changes."""
+    expression table's.  Adds the stat ase_sites (rows written).  No other output depends on it; without ase_sites_out nothing changes.
+    hap_coverage_out: a path prefix for the per-haplotype coverage tracks (include/lcr.h: lcr_hap_coverage; coverage.py): the covered
+    depth -- M, =, X and D columns, clipped to the region windows -- of the reads tagged HP 1, of those tagged HP 2 and of all other
+    reads, as PREFIX.h1.bedgraph, PREFIX.h2.bedgraph and PREFIX.unassigned.bedgraph (contig, start, end, value; 0-based half-open, no
+    header line; the .fai's contig order, then position; lines sorted and non-overlapping -- the writer raises ValueError otherwise).
+    The labels are the HP tag's: behind lcr_phase "haplotype 1" is a label per phase set, so a track mixes the arbitrary labels of
+    different sets; with haplotag=True it is the input VCF's haplotype 1 across the whole run.  Every chunk calls Engine.hap_coverage
+    right behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Adds the stats
+    hap_coverage_segments (segments of all chunks) and hap_coverage_bases (covered bases of class 0, 1, 2: a 3-tuple).  No other output
+    depends on it; without hap_coverage_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -212,6 +221,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     if ase_sites_out is not None and (isinstance(ase_sites_min_baseq, bool) or int(ase_sites_min_baseq) != ase_sites_min_baseq
                                       or not 0 <= int(ase_sites_min_baseq) <= 30):
         raise ValueError("ase_sites_min_baseq must be an integer in [0, 30] (the fragment matrix clamps qualities to 30), got %r" % (ase_sites_min_baseq,))
+    if hap_coverage_out is not None and (not str(hap_coverage_out) or str(hap_coverage_out).endswith(os.sep)
+                                         or not os.path.isdir(os.path.dirname(os.path.abspath(str(hap_coverage_out))))):
+        raise ValueError("hap_coverage_out must be a path prefix in an existing directory (PREFIX.h1.bedgraph, ...), got %r" % (hap_coverage_out,))
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -288,14 +300,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -328,6 +340,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                                                   ase_min_support, ase_overdispersion),)
         if srec is not None:
             out["sites"] = (name, cands.copy(), srec)     # (cands is the context's buffer: the table is written when every chunk is in)
+        if hcov is not None:
+            out["hap_cov"] = (name, hcov[0], hcov[2])     # (Engine.hap_coverage copied them out of the context's buffers)
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -382,7 +396,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                     psites = (pp[lo:hi], ppat[lo:hi], pmat[lo:hi]) if hi > lo else None
                 arec = E.ase_genes(psites, min_phase_score=min_ps) if genes is not None else E.ase(psites, min_phase_score=min_ps)
             srec = E.site_counts(ase_sites_min_baseq) if ase_sites_out is not None else None                  # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec)
+            hcov = E.hap_coverage() if hap_coverage_out is not None else None                                 # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov)
         finally:
             with free_lock:
                 free.append(k)
@@ -516,6 +531,20 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["ase_sites"] = text.count("\n") - 1
         with open(ase_sites_out, "w") as f:
             f.write(text)
+    if hap_coverage_out is not None:
+        per_contig = {}     # contig -> its chunks' segments, in chunk order (= the .fai's contig order, then position)
+        for r in results:
+            per_contig.setdefault(r["hap_cov"][0], []).append(r["hap_cov"][1])
+        w = coverage.TrackWriter(str(hap_coverage_out))
+        try:
+            for name, parts in per_contig.items():
+                w.add_contig(name, np.concatenate(parts))
+        finally:
+            w.close()
+        stats["hap_coverage_segments"] = w.segments
+        stats["hap_coverage_bases"] = tuple(sum(int(r["hap_cov"][2]["bases"][:, k].sum()) for r in results) for k in range(3))
+        if tuple(w.bases) != stats["hap_coverage_bases"]:      # (the lines' sum against the kernels' own per-region sums)
+            raise ValueError("hap coverage: the tracks hold %r bases, the region records %r" % (tuple(w.bases), stats["hap_coverage_bases"]))
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

@@ -13,6 +13,7 @@
                                   [--ase-parental-vcf phased.vcf.gz | --ase-dna-vcf dna.vcf.gz]   (allele-specific expression table)
                                   [--ase-annotation genes.gtf.gz [--ase-gene-types protein_coding,lncRNA]]]   (... per annotated gene)
                                  [--ase-sites-out out.ase_sites.tsv [--ase-sites-min-baseq N]]   (allele x haplotype counts per VCF record)
+                                 [--hap-coverage-out PREFIX]   (PREFIX.h1 / .h2 / .unassigned.bedgraph: covered depth per HP tag)
 """
 import argparse
 import json
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--ase-gene-types", default="protein_coding,lncRNA", help="comma-separated gene types kept from the annotation")
     ap.add_argument("--ase-sites-out", help="write the per-site table: reference / alternate counts per haplotype at every VCF record, with --ase-min-support and --ase-overdispersion")
     ap.add_argument("--ase-sites-min-baseq", type=int, default=13, help="base quality an entry needs to be counted in --ase-sites-out (0 - 30)")
+    ap.add_argument("--hap-coverage-out", metavar="PREFIX", help="write PREFIX.h1.bedgraph, PREFIX.h2.bedgraph and PREFIX.unassigned.bedgraph: the covered depth of the reads tagged HP 1, HP 2 and of all others")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -74,6 +76,9 @@ def main():
         ap.error("--ase-annotation needs --ase-out")
     if not 0 <= a.ase_sites_min_baseq <= 30:
         ap.error("--ase-sites-min-baseq must lie in 0 - 30 (the fragment matrix clamps qualities to 30)")
+    if a.hap_coverage_out is not None and (not a.hap_coverage_out or a.hap_coverage_out.endswith(os.sep)
+                                           or not os.path.isdir(os.path.dirname(os.path.abspath(a.hap_coverage_out)))):
+        ap.error("--hap-coverage-out takes a path prefix in an existing directory")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -90,7 +95,7 @@ def main():
                       asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
                       asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage,
                       annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, haplotag=a.haplotag,
-                      ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, **extra)
+                      ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, hap_coverage_out=a.hap_coverage_out, **extra)
     print(json.dumps(st))
 
 
