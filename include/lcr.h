@@ -588,6 +588,76 @@ int lcr_get_hap_coverage(lcr_ctx*, lcr_hap_cov_list* out);
  * wait for the segment count included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
 int lcr_hap_coverage_ms(lcr_ctx*, float* ms);
 
+/* Haplotype-resolved somatic scores (K14): at every candidate, per haplotype of the phased reads, is the site reference, heterozygous or
+ * somatic -- the stage the reference ends its per-region closure with (snpfrags.rs:735-771 detect_somatic_by_het, somatic.rs
+ * calculate_prob_somatic; commented out at its call site, thread.rs:187) --, computed on the GPU from what lcr_phase or lcr_haplotag left
+ * there.  DESIGN.md section 1l.  Row r of lcr_get_fragmat has assignment a and phase set ps (lcr_read_record); candidate c is an index
+ * into lcr_get_candidates.
+ *   entries of c       every CSR entry with col == c, from any row.  q = val & 31.  An entry with q < min_baseq is counted in n_lowq and
+ *       takes no further part; the others are the counted entries.  min_baseq 0 (the reference has no threshold) counts everything; above 30
+ *       is LCR_E_ARG (the fragment matrix clamps qualities to 30, as the reference's collector does, snpfrags.rs:118).
+ *   site's phase set   lcr_site_counts' rule at the same min_baseq: the candidate's own phase_set where it is not 0; otherwise the ps with
+ *       the most counted entries of counting rows at c, ties to the smallest value; without any, 0.  For the same min_baseq phase_set equals
+ *       lcr_site_count.phase_set at every candidate.  (The reference keys on the assignment alone; haplotype labels mean something only
+ *       inside one phase set.)
+ *   counting row       a is 1 or 2, ps != 0 and ps == the site's phase set.  n[a - 1][0 ref, 1 alt] counts its counted entries; the counted
+ *       entries of every other row go to n_other.
+ *   invariant          n[0][0] + n[0][1] + n[1][0] + n[1][1] + n_other + n_lowq = the number of entries of c.
+ *   allele of an entry ref when its base code (val >> 6) is the code of ref_base (A, C, G, T in either case), else alt.
+ *   status             LCR_SOM_ALLELES when neither allele1 nor allele2 equals ref_base (snpfrags.rs:121): the counts are filled; L, cls and
+ *       call are 0 and nothing else is evaluated.  LCR_SOM_DEEP when a haplotype has more than 2^20 counted entries at the site: likewise.
+ *       LCR_SOM_OK otherwise.
+ *   tables             four of 31 int64 each, built on the host per call as llround(log10(x) * 2^40) -- the phase stage's fixed point --:
+ *       eps_q = 10^(-q / 10), q = 0 treated as q = 1 (the phase stage's rule; the reference would take log 0 there); fe[q] = eps,
+ *       f1e[q] = 1 - eps, fs_ref[q] = purity * eps + (1 - purity) * (1 - eps), fs_alt[q] = purity * (1 - eps) + (1 - purity) * eps; the
+ *       priors log10(1 - het_rate - som_rate), log10(het_rate), log10(som_rate), rounded the same way.
+ *   sums               per haplotype h over the counted entries of its counting rows (somatic.rs:12-34 in logs; int64, any order):
+ *       L[h][0 ref] = prior_ref + sum over ref of f1e[q] + sum over alt of fe[q]
+ *       L[h][1 het] = prior_het + sum over ref of fe[q]  + sum over alt of f1e[q]
+ *       L[h][2 som] = prior_som + sum over ref of fs_ref[q] + sum over alt of fs_alt[q]
+ *       Every table entry is below 2^42 in magnitude, so the sums are exact up to 2^20 counted entries per haplotype (LCR_SOM_DEEP above).
+ *   class              cls[h] = 2 when L[h][2] > L[h][0] and L[h][2] > L[h][1]; else 1 when L[h][1] > L[h][0] and L[h][1] > L[h][2]; else 0
+ *       (somatic.rs:38-44, the same strict comparisons, on integers).  A haplotype without counted entries has its priors only: class 0.
+ *   call               only at a candidate whose flags hold LCR_F_CAND_SOMATIC when the call runs (a low-fraction site the rescue did not
+ *       promote): 2 when cls = {0, 2}, 1 when cls = {2, 0}, else 0 (snpfrags.rs:753-765).  cls and L are filled at EVERY candidate with
+ *       status LCR_SOM_OK, flagged or not: at an ordinary het site they read "ref on one haplotype, het on the other".  Candidate records
+ *       are not modified.  (The reference walks its candidate-time list, rescued sites included; that is not reproduced.)
+ *   score              not in the record, which holds integers only.  With l = L[call - 1][.] / 2^40:
+ *       SQ = -10 * (log10(10^l_ref + 10^l_het) - log10(10^l_ref + 10^l_het + 10^l_som)),
+ *       each log evaluated after subtracting the maximum of its own terms, so that nothing cancels or underflows: the reference's
+ *       -10 log10(1 - prob_som), whose f64 products of per-read probabilities are 0 from 108 reads at q30 on (NaN once all three are)
+ *       and whose 1 - prob cancels to 0 (a score of inf).  longcallr_amd/somatic.py: score().
+ *   order              one record per candidate, in candidate order; integer adds and compares only: bit-reproducible, independent of the
+ *       batch's composition.
+ * Instance (purity 0.3, the default rates, every q = 30): a LCR_F_CAND_SOMATIC site with 6 ref entries on haplotype 1 and 7 ref + 3 alt on
+ * haplotype 2: n = {{6, 0}, {7, 3}}, L[0] = {-3107708873, -23420730163838, -6852080807812}, L[1] = {-9899190109605,
+ * -26720698299410, -8745495261838}, cls = {0, 2}, call = 2, SQ = 10.8642 (10.86 in the VCF).
+ * lcr_somatic needs the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed; params == NULL, purity outside
+ * (0, 1], a rate <= 0, het_rate + som_rate >= 1 or min_baseq > 30: LCR_E_ARG, the last call's records stay valid), collects an
+ * asynchronous phase stage in flight first, queues a fixed number of kernels on the context's stream without a host wait of its own,
+ * writes no buffer another stage or getter reads, and may be repeated with other params.  The records die with the phase results: at the
+ * next candidate stage and at lcr_load_batch / lcr_bind_batch; lcr_get_somatic answers LCR_E_STATE then.  rec: pinned host memory the
+ * call's last kernel wrote, valid until the next lcr_somatic; dev_rec: the same records in HBM.
+ * Measured: 0.28 ms per warm call on the benchmark's C3 workload, beside lcr_site_counts' 0.27 ms in the same process (DESIGN.md
+ * section 1l). */
+enum { LCR_SOM_OK = 0, LCR_SOM_ALLELES = 1, LCR_SOM_DEEP = 2 };
+typedef struct { double purity, som_rate, het_rate; uint32_t min_baseq; uint32_t pad_; } lcr_somatic_params;
+   /* reference values: 0.3 (snpfrags.rs:752), 5e-6, 1/2000 (somatic.rs:8-9); min_baseq 0 (the reference has no threshold) */
+typedef struct {                      /* 80 bytes, one per candidate, candidate order */
+  uint32_t phase_set;                 /* the site's phase set, lcr_site_counts' rule */
+  uint32_t n[2][2];                   /* [hap-1][0 ref, 1 alt]: counted entries of counting rows */
+  uint32_t n_other, n_lowq;           /* counted entries of all other rows; entries below min_baseq */
+  uint8_t  cls[2];                    /* per haplotype: 0 ref, 1 het, 2 somatic (snp.rs:19) */
+  uint8_t  call;                      /* 0 none, 1 / 2: somatic allele on haplotype 1 / 2 */
+  uint8_t  status;                    /* LCR_SOM_OK 0, LCR_SOM_ALLELES 1, LCR_SOM_DEEP 2 */
+  int64_t  L[2][3];                   /* [hap-1][ref, het, som]: log10(likelihood x prior) x 2^40 */
+} lcr_somatic_site;
+int lcr_somatic(lcr_ctx*, const lcr_somatic_params*);
+int lcr_get_somatic(lcr_ctx*, int32_t* n_cand, const lcr_somatic_site** rec, const lcr_somatic_site** dev_rec);
+/* HIP-event time (ms) of the last lcr_somatic's kernels with timing enabled (lcr_enable_timing); LCR_E_STATE without one.  Not a slot of
+ * lcr_kernel_ms: that list is closed. */
+int lcr_somatic_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.

@@ -167,6 +167,17 @@ HAP_COV_REGION_DTYPE = np.dtype([("region", "<i4"), ("n_reads", "<u4", (3,)), ("
 assert HAP_COV_REGION_DTYPE.itemsize == 56, HAP_COV_REGION_DTYPE.itemsize
 
 
+class LcrSomaticParams(C.Structure):   # include/lcr.h: lcr_somatic_params (the reference's 0.3, 5e-6, 1 / 2000; no threshold)
+    _fields_ = [("purity", C.c_double), ("som_rate", C.c_double), ("het_rate", C.c_double), ("min_baseq", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+# lcr_somatic_site (include/lcr.h): one candidate's counts n[hap - 1][0 ref, 1 alt], classes per haplotype (0 ref, 1 het, 2 somatic), the
+# call (0 none, 1 / 2 the haplotype with the somatic allele), the status, and L[hap - 1][ref, het, som] = log10(likelihood x prior) x 2^40
+SOMATIC_SITE_DTYPE = np.dtype([("phase_set", "<u4"), ("n", "<u4", (2, 2)), ("n_other", "<u4"), ("n_lowq", "<u4"), ("cls", "u1", (2,)),
+                               ("call", "u1"), ("status", "u1"), ("L", "<i8", (2, 3))], align=True)
+assert SOMATIC_SITE_DTYPE.itemsize == 80, SOMATIC_SITE_DTYPE.itemsize
+
+
 class LcrHapCovList(C.Structure):   # include/lcr.h: lcr_hap_cov_list
     _fields_ = [("n_regions", C.c_int32), ("n_segments", C.c_int32), ("seg", C.c_void_p), ("seg_region_off", C.c_void_p),
                 ("reg", C.c_void_p), ("dev_seg", C.c_void_p), ("dev_reg", C.c_void_p)]

@@ -24,6 +24,7 @@ SYMBOLS = [
     "lcr_haplotag", "lcr_get_haplotag_sites", "lcr_haplotag_ms", "lcr_vcf_contig_phase_sets",
     "lcr_site_counts", "lcr_get_site_counts", "lcr_site_counts_ms",
     "lcr_hap_coverage", "lcr_get_hap_coverage", "lcr_hap_coverage_ms",
+    "lcr_somatic", "lcr_get_somatic", "lcr_somatic_ms",
 ]
 
 _lib = None
@@ -147,5 +148,8 @@ def load():
     l.lcr_hap_coverage.argtypes = [vp]
     l.lcr_get_hap_coverage.argtypes = [vp, C.POINTER(_abi.LcrHapCovList)]
     l.lcr_hap_coverage_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_somatic.argtypes = [vp, C.POINTER(_abi.LcrSomaticParams)]
+    l.lcr_get_somatic.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp)]
+    l.lcr_somatic_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

@@ -401,6 +401,24 @@ class Engine:
         self._chk(self.lib.lcr_hap_coverage_ms(self.h, C.byref(ms)), "lcr_hap_coverage_ms")
         return float(ms.value)
 
+    def somatic(self, purity=0.3, som_rate=5e-6, het_rate=5e-4, min_baseq=0):
+        """lcr_somatic + lcr_get_somatic after phase() or haplotag(): per candidate of candidates() the counted reference / alternate
+        entries per haplotype of the site's phase set, the class of each haplotype (0 reference, 1 heterozygous, 2 somatic), the
+        somatic call at a LCR_F_CAND_SOMATIC site, and the six fixed-point sums behind them (include/lcr.h; somatic.score for the
+        score) -> a structured array of _abi.SOMATIC_SITE_DTYPE, one record per candidate, copied.  Waits for an asynchronous phase
+        stage in flight; may be repeated with other parameters."""
+        p = _abi.LcrSomaticParams(float(purity), float(som_rate), float(het_rate), int(min_baseq), 0)
+        self._chk(self.lib.lcr_somatic(self.h, C.byref(p)), "lcr_somatic")
+        n, rec, dev = C.c_int32(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.lcr_get_somatic(self.h, C.byref(n), C.byref(rec), C.byref(dev)), "lcr_get_somatic")
+        return _view(rec.value, _abi.SOMATIC_SITE_DTYPE, n.value)
+
+    def somatic_ms(self):
+        """lcr_somatic_ms: HIP-event time of the last somatic()'s kernels (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_somatic_ms(self.h, C.byref(ms)), "lcr_somatic_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

@@ -195,6 +195,7 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   for (hipEvent_t e : c->ev_mask_t) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_sc, c->ev_sc_t[0], c->ev_sc_t[1]}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_hc, c->ev_hc_t[0], c->ev_hc_t[1]}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_som, c->ev_som_t[0], c->ev_som_t[1]}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_unpack_t) if (e) (void)hipEventDestroy(e);
   c->phase.release();
   for (int k = 0; k < LCR_NTIMERS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);

@@ -7,7 +7,8 @@
 // three calls that take a gene annotation share its upload and verdict (annotation_queue, annotation_verdict).  lcr_haplotag.hip
 // (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks;
 // lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) and lcr_hap_coverage.hip (lcr_hap_coverage,
-// lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them.
+// lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
+// lcr_somatic_ms) a third.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -235,6 +236,15 @@ struct lcr_ctx {
   hipEvent_t ev_hc = nullptr;             // behind the count pass, then behind the call's last kernel; created on first use
   hipEvent_t ev_hc_t[2] = {};             // timing enabled: around the call's kernels, created on first use
 
+  // K14 (lcr_somatic): scratch and results of its own -- no other stage or getter reads them
+  bool som_valid = false;    // lcr_get_somatic: the last lcr_somatic's records belong to the phase results of the bound batch (rewind_to)
+  bool som_timed = false;    // ev_som_t brackets the last call's kernels
+  int32_t som_ncand = 0;
+  DevBuf som_cnt, som_off, som_seg, d_som;   // entries per candidate (counted up, then back down); their 64-bit offsets; a word per entry, by candidate; the records
+  HostBuf h_som;                             // pinned: the records
+  hipEvent_t ev_som = nullptr;               // behind the call's last kernel; created on first use
+  hipEvent_t ev_som_t[2] = {};               // timing enabled: around the call's kernels, created on first use
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -292,6 +302,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->jgene.valid = c->ajgene.valid = false;   // ... and the per-gene junction tables
   if (to < ST_PHASED) c->sc_valid = false;       // ... and the per-site allele x haplotype counts
   if (to < ST_PHASED) c->hc_valid = false;       // ... and the per-haplotype coverage segments
+  if (to < ST_PHASED) c->som_valid = false;      // ... and the per-site somatic records
   if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),

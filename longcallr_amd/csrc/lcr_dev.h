@@ -362,6 +362,17 @@ void launch_k12_fill(int32_t n_rows, const int64_t* row_ptr, const int32_t* col,
 void launch_k12_sites(const lcr_candidate* cand, int32_t n_cand, const int64_t* off, const uint64_t* seg, lcr_site_count* out,
                       lcr_site_count* host_out /* pinned (device pointer) */, hipStream_t s);
 
+// k14_somatic.hip: reference / heterozygous / somatic per haplotype at every candidate (lcr_somatic); the entry counts and offsets are
+// launch_k12_count's and launch_scan_i32_to_i64's
+struct K14Tables {
+  int64_t tab[4 * 31];   // fe, f1e, fs_ref, fs_alt by q: llround(log10(x) * 2^40) (include/lcr.h); 992 bytes, a kernel argument
+  int64_t prior[3];      // ref, het, som
+};
+void launch_k14_fill(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const lcr_read_record* rec, const lcr_candidate* cand,
+                     int32_t n_cand, uint32_t* cnt /* launch_k12_count's: counted back down to 0 */, const int64_t* off /* n_cand + 1 */, uint64_t* seg /* nnz */, hipStream_t s);
+void launch_k14_sites(const lcr_candidate* cand, int32_t n_cand, const int64_t* off, const uint64_t* seg, const K14Tables& t, uint32_t min_baseq,
+                      lcr_somatic_site* out, lcr_somatic_site* host_out /* pinned (device pointer) */, hipStream_t s);
+
 // k13_hap_coverage.hip: covered depth per haplotype class at every window column, run-length encoded (lcr_hap_coverage)
 void launch_k13_blocks(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, int64_t n_cols,
                        uint32_t* planes /* 3 x n_cols, zeroed: difference planes by class */, hipStream_t s);

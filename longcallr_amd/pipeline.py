@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import _abi, annotation, api, ase, asj, bamio, coverage, vcf
+from . import _abi, annotation, api, ase, asj, bamio, coverage, somatic, vcf
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -73,12 +73,14 @@ def parse_fai(path):
     return out
 
 
-def write_vcf(path, contig_lengths, body_lines):
+def write_vcf(path, contig_lengths, body_lines, extra_header=""):
+    """extra_header: further ## lines, written in front of the #CHROM line (the somatic VCF's INFO tags)"""
     with open(path, "w") as f:
         f.write("##fileformat=VCFv4.3\n")
         for name, length in contig_lengths:   # thread.rs:225-230
             f.write("##contig=<ID=%s,length=%d>\n" % (name, length))
-        f.write(VCF_HEADER_TAIL)
+        at = VCF_HEADER_TAIL.index("#CHROM")
+        f.write(VCF_HEADER_TAIL[:at] + extra_header + VCF_HEADER_TAIL[at:])
         f.writelines(body_lines)
 
 
@@ -118,7 +120,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         ase_out=None, ase_min_support=10, ase_overdispersion=0.001, ase_parental_vcf=None, ase_dna_vcf=None,
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
         asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
-        haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, hap_coverage_out=None, **param_overrides):
+        haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, hap_coverage_out=None,
+        somatic_out=None, somatic_purity=0.3, somatic_min_baseq=0, somatic_min_score=0.0, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -211,7 +214,16 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     different sets; with haplotag=True it is the input VCF's haplotype 1 across the whole run.  Every chunk calls Engine.hap_coverage
     right behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Adds the stats
     hap_coverage_segments (segments of all chunks) and hap_coverage_bases (covered bases of class 0, 1, 2: a 3-tuple).  No other output
-    depends on it; without hap_coverage_out nothing changes."""
+    depends on it; without hap_coverage_out nothing changes.
+    somatic_out / somatic_purity / somatic_min_baseq / somatic_min_score: the haplotype-resolved somatic calls (include/lcr.h:
+    lcr_somatic; somatic.py), written to somatic_out: a VCF with the run's header plus the INFO tags SHP, H1 and H2, and one record per
+    low-fraction site (LCR_F_CAND_SOMATIC behind the phase stage: printed 0/1 LowQual RDS=noselect in the main VCF) at which one
+    haplotype reads "reference" and the other "somatic" at the given purity -- QUAL the candidate's, FILTER PASS when the score reaches
+    somatic_min_score, else LowQual, INFO RDS=somatic;SHP=h;H1=ref,alt;H2=ref,alt, FORMAT GT:DP:AF:PS:SQ --, in contig then position
+    order.  Every chunk calls Engine.somatic behind phase() / haplotag() and the other table calls; that call waits for the phase
+    stage, like theirs.  Purity outside (0, 1] or a somatic_min_baseq outside 0 - 30 is a ValueError before any GPU work.  Adds the
+    stats somatic_sites (flagged candidates evaluated with status OK) and somatic_calls.  No other output depends on it; without
+    somatic_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -224,6 +236,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     if hap_coverage_out is not None and (not str(hap_coverage_out) or str(hap_coverage_out).endswith(os.sep)
                                          or not os.path.isdir(os.path.dirname(os.path.abspath(str(hap_coverage_out))))):
         raise ValueError("hap_coverage_out must be a path prefix in an existing directory (PREFIX.h1.bedgraph, ...), got %r" % (hap_coverage_out,))
+    if somatic_out is not None:
+        somatic.check_params(somatic_purity, 5e-6, 5e-4, somatic_min_baseq)
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -300,14 +314,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records, somatic records) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec, hcov = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -342,6 +356,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["sites"] = (name, cands.copy(), srec)     # (cands is the context's buffer: the table is written when every chunk is in)
         if hcov is not None:
             out["hap_cov"] = (name, hcov[0], hcov[2])     # (Engine.hap_coverage copied them out of the context's buffers)
+        if som is not None:     # (the candidates are those the call saw: it ran behind the settled phase stage)
+            flagged = (cands["flags"] & _abi.F_CAND_SOMATIC) != 0
+            out["somatic"] = (somatic.format_vcf_records(cands, som, name, somatic_min_score),
+                              int(np.count_nonzero(flagged & (som["status"] == somatic.SOM_OK))), int(np.count_nonzero(som["call"])))
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -397,7 +415,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 arec = E.ase_genes(psites, min_phase_score=min_ps) if genes is not None else E.ase(psites, min_phase_score=min_ps)
             srec = E.site_counts(ase_sites_min_baseq) if ase_sites_out is not None else None                  # (waits for the phase stage)
             hcov = E.hap_coverage() if hap_coverage_out is not None else None                                 # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov)
+            som = E.somatic(purity=somatic_purity, min_baseq=somatic_min_baseq) if somatic_out is not None else None   # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som)
         finally:
             with free_lock:
                 free.append(k)
@@ -545,6 +564,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["hap_coverage_bases"] = tuple(sum(int(r["hap_cov"][2]["bases"][:, k].sum()) for r in results) for k in range(3))
         if tuple(w.bases) != stats["hap_coverage_bases"]:      # (the lines' sum against the kernels' own per-region sums)
             raise ValueError("hap coverage: the tracks hold %r bases, the region records %r" % (tuple(w.bases), stats["hap_coverage_bases"]))
+    if somatic_out is not None:
+        stats["somatic_sites"] = sum(r["somatic"][1] for r in results)
+        stats["somatic_calls"] = sum(r["somatic"][2] for r in results)
+        write_vcf(somatic_out, contig_lengths, [r["somatic"][0] for r in results], somatic.INFO_LINES)
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

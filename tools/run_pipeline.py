@@ -14,6 +14,7 @@
                                   [--ase-annotation genes.gtf.gz [--ase-gene-types protein_coding,lncRNA]]]   (... per annotated gene)
                                  [--ase-sites-out out.ase_sites.tsv [--ase-sites-min-baseq N]]   (allele x haplotype counts per VCF record)
                                  [--hap-coverage-out PREFIX]   (PREFIX.h1 / .h2 / .unassigned.bedgraph: covered depth per HP tag)
+                                 [--somatic-out out.somatic.vcf [--somatic-purity P] [--somatic-min-baseq N] [--somatic-min-score S]]   (haplotype-resolved somatic calls at low-fraction sites)
 """
 import argparse
 import json
@@ -62,6 +63,10 @@ def main():
     ap.add_argument("--ase-sites-out", help="write the per-site table: reference / alternate counts per haplotype at every VCF record, with --ase-min-support and --ase-overdispersion")
     ap.add_argument("--ase-sites-min-baseq", type=int, default=13, help="base quality an entry needs to be counted in --ase-sites-out (0 - 30)")
     ap.add_argument("--hap-coverage-out", metavar="PREFIX", help="write PREFIX.h1.bedgraph, PREFIX.h2.bedgraph and PREFIX.unassigned.bedgraph: the covered depth of the reads tagged HP 1, HP 2 and of all others")
+    ap.add_argument("--somatic-out", help="write a VCF of the low-fraction sites at which one haplotype reads reference and the other somatic (FORMAT/SQ: the somatic score)")
+    ap.add_argument("--somatic-purity", type=float, default=0.3, help="fraction of a somatic haplotype's reads that carry the allele, in (0, 1]")
+    ap.add_argument("--somatic-min-baseq", type=int, default=0, help="base quality an entry needs to be counted in --somatic-out (0 - 30)")
+    ap.add_argument("--somatic-min-score", type=float, default=0.0, help="records with a somatic score below it are LowQual")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -79,6 +84,10 @@ def main():
     if a.hap_coverage_out is not None and (not a.hap_coverage_out or a.hap_coverage_out.endswith(os.sep)
                                            or not os.path.isdir(os.path.dirname(os.path.abspath(a.hap_coverage_out)))):
         ap.error("--hap-coverage-out takes a path prefix in an existing directory")
+    if not (a.somatic_purity > 0.0 and a.somatic_purity <= 1.0):
+        ap.error("--somatic-purity must lie in (0, 1]")
+    if not 0 <= a.somatic_min_baseq <= 30:
+        ap.error("--somatic-min-baseq must lie in 0 - 30 (the fragment matrix clamps qualities to 30)")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -95,7 +104,9 @@ def main():
                       asj_annotation=a.asj_annotation, asj_gene_types=tuple(t for t in a.asj_gene_types.split(",") if t),
                       asj_cluster_with_exons=a.asj_cluster_with_exons, asj_dna_vcf=a.asj_dna_vcf, asj_gene_coverage=a.asj_gene_coverage,
                       annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, haplotag=a.haplotag,
-                      ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, hap_coverage_out=a.hap_coverage_out, **extra)
+                      ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, hap_coverage_out=a.hap_coverage_out,
+                      somatic_out=a.somatic_out, somatic_purity=a.somatic_purity, somatic_min_baseq=a.somatic_min_baseq,
+                      somatic_min_score=a.somatic_min_score, **extra)
     print(json.dumps(st))
 
 
