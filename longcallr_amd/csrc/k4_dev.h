@@ -142,7 +142,9 @@ __device__ __forceinline__ long long cross_optimize(const PhaseDev& P, const Reg
                                     double* qrow = nullptr /* 2 R doubles of scratch: the COMPLETE tie contract (classes 2 / 4 too) in the plain form below; S <= 32 */,
                                     unsigned long long* tie_local = nullptr /* two words of LDS: the class-2 ties and class-4 steps this call does NOT resolve are
                                                                               counted there instead of the census (the chain kernel decides what they mean) */,
-                                    double* qsnp = nullptr /* 2 S doubles */, int8_t* chs = nullptr /* 2 S bytes: with qrow, the complete contract for any S */) {
+                                    double* qsnp = nullptr /* 2 S doubles */, int8_t* chs = nullptr /* 2 S bytes: with qrow, the complete contract for any S */,
+                                    const int32_t* ocent = nullptr, const int32_t* oerow = nullptr /* ordered_index() of the matrix: the complete contract's f64
+                                                                              column sums run in ROW order (k4_stage fills cr / cv through atomic cursors: any order) */) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const int32_t* rp = mv.rp;
   const int32_t* pc = mv.pc;
@@ -375,9 +377,10 @@ __device__ __forceinline__ long long cross_optimize(const PhaseDev& P, const Reg
     auto col_scores = [&](int i, int d, double* q4) {
       double Sd = 0.0, Sn = 0.0, Shr = 0.0, Shv = 0.0;
       uint32_t cov = 0;
-      for (int e = cp[i]; e < cp[i + 1]; e++) {
-        const uint8_t v = cv[e];
-        const int p = (v & 32) ? 1 : -1, q = v & 31, x = sg[cr[e]] * d;
+      for (int k = cp[i]; k < cp[i + 1]; k++) {
+        const int e = ocent ? ocent[k] : k;
+        const uint8_t v = ocent ? pv[e] : cv[e];
+        const int p = (v & 32) ? 1 : -1, q = v & 31, x = sg[ocent ? oerow[e] : cr[e]] * d;
         Sd += p == x ? l1e64[q] : le64[q]; Sn += p == -x ? l1e64[q] : le64[q];
         Shr += p == 1 ? l1e64[q] : le64[q]; Shv += p == -1 ? l1e64[q] : le64[q];
         cov++;

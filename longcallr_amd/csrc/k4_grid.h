@@ -3,10 +3,16 @@
 #pragma once
 #include "k4_dev.h"
 
+constexpr int K4_CHAIN_WG_THREADS = 1024;   // = K4_GRID_THREADS (below)
+
 // one workgroup per chain region: regions desc[first .. first + n)
 hipError_t k4_chain_launch_wg(const ChainDev& C, int first, int n, size_t dyn_lds, hipStream_t s);
 // all CUs on the single region desc[which] (persistent launch with grid barriers; C.ctl is reset here)
 hipError_t k4_chain_launch_grid(const ChainDev& C, int which, size_t dyn_lds, hipStream_t s);
+// k4_chain_wg's static stage rows (sixteen waves x four rows of 65 doubles): racc of the row-balanced cross_optimize and the scratch of
+// the LDS pair table between block flips; SNPs whose constants it keeps in LDS
+constexpr int K4_CHAIN_STAGE_BYTES = (K4_CHAIN_WG_THREADS / 64) * 4 * 65 * 8;
+constexpr int K4_CHAIN_SCN = 256;
 // dynamic LDS the device-coherent perturbation rounds may use (sigma bit vector + delta / eta / het-delta bytes of the region)
 constexpr int K4_GRID_FAST_LDS_MAX = 96 * 1024;
 inline size_t k4_grid_fast_lds(int64_t R, int64_t S) { return (size_t)(8 * ((R + 63) / 64) + 3 * S + 64); }

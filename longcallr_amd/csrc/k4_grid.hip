@@ -36,6 +36,7 @@
 namespace {
 
 constexpr int CH_THREADS = K4_GRID_THREADS;
+static_assert(CH_THREADS == K4_CHAIN_WG_THREADS, "k4_chain_wg is launched with CH_THREADS");
 constexpr int CH_WAVES = CH_THREADS / 64;
 
 // region-relative views the chain steps work on
@@ -998,6 +999,7 @@ __global__ void __launch_bounds__(NT) k4_chain_wg(ChainDev C, int32_t first, int
   __shared__ FlipLut L;
   __shared__ int sm[2][16];
   __shared__ double stage[NW * 4 * SSTR];
+  static_assert(NT != K4_CHAIN_WG_THREADS || sizeof(stage) == K4_CHAIN_STAGE_BYTES, "the host reports the forms by this size");
   extern __shared__ __attribute__((aligned(16))) int8_t dyn_state[];
   if ((int)blockIdx.x >= n) return;
   const ChainDesc d = C.desc[first + blockIdx.x];
@@ -1010,7 +1012,7 @@ __global__ void __launch_bounds__(NT) k4_chain_wg(ChainDev C, int32_t first, int
   const RegionDev rd = C.P.reg[d.slot];
   const uint32_t E = (uint32_t)C.P.prow_ptr[rd.rp_off + rd.R];
   __shared__ int wg_bc;
-  constexpr int SCN = 256;   // SNPs whose constants (four words each, read by every delta step) are kept in LDS
+  constexpr int SCN = K4_CHAIN_SCN;   // SNPs whose constants (four words each, read by every delta step) are kept in LDS
   __shared__ long long scn[4 * SCN];
   if (rd.S <= SCN) for (int i = threadIdx.x; i < 4 * rd.S; i += blockDim.x) scn[i] = C.P.snp_const[4ll * rd.snp_off + i];
   // Two instantiations of the same body: with state and matrix in LDS every pointer of the sweeps has ONE provenance,
@@ -1035,7 +1037,7 @@ __global__ void __launch_bounds__(NT) k4_chain_wg(ChainDev C, int32_t first, int
       if constexpr (COMPLETE)
         obj = cross_optimize(C.P, rd, mvl, v.sg, v.dl, v.et, keep_conserved, with_genotype, red, wl, macc, MACC, nullptr, 0,
                              rd.S <= SCN ? scn : nullptr, &iters, nullptr, nullptr, C.tie_qrow + 2ll * rd.sig_off, nullptr,
-                             C.tie_qsnp + 2ll * rd.snp_off, C.tie_ch + 2ll * rd.snp_off);
+                             C.tie_qsnp + 2ll * rd.snp_off, C.tie_ch + 2ll * rd.snp_off, v.cent, v.erow);
       else
         obj = cross_optimize(C.P, rd, mvl, v.sg, v.dl, v.et, keep_conserved, with_genotype, red, wl, macc, MACC,
                              reinterpret_cast<unsigned long long*>(stage), NW * 4 * SSTR,   // (free outside block_flip)

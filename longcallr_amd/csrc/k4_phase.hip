@@ -661,6 +661,7 @@ int PhaseHost::launch_enum(PhaseCall& c) {
 // them (persistent launch with grid barriers); the others run side by side, one workgroup each.  LCR_GRID_MIN_ENTRIES moves the
 // boundary (tests: 0 = every region).
 int PhaseHost::launch_chain(PhaseCall& c) {
+  chain_forms.clear();
   if (c.chain_slots.empty()) { chain_desc.clear(); return LCR_OK; }
   const PhaseInputs& in = c.in; const int ng = c.ng; const StageStat* const stat = c.stat;
   const size_t nnz1 = c.nnz1, nc1 = c.nc1, nr1 = c.nr1;
@@ -783,10 +784,29 @@ int PhaseHost::launch_chain(PhaseCall& c) {
       if (dyn_state && dyn_state + m + 64 <= lds_budget) want = std::max(want, m);
     }
     Ck.P.lds_mat = (int32_t)want;
+    if (c.prof) {   // the forms k4_chain_wg takes from these values (k4_grid.hip, cross_optimize in k4_dev.h, ld_pair_table)
+      for (size_t k = 0; k < regs.size(); k++) {
+        const int g = regs[k], S = in.snps(g);
+        const bool mat = dyn_state && matview_bytes(stat[g].R, S, stat[g].E) <= want;
+        const bool cols = S <= CROSS_MACC, rows = cols && stat[g].R <= K4_CHAIN_STAGE_BYTES / 8;
+        const bool tbl = S < 32768 && stat[g].E_all < 65536 &&
+                         8ull * (uint64_t)S * (uint64_t)desc[first + k].W + 4ull * (uint64_t)stat[g].E_all + 16 <= (uint64_t)K4_CHAIN_STAGE_BYTES;
+        char line[256];
+        snprintf(line, sizeof(line), "chain region %d: scope workgroup, state %s, matrix %s, cross_optimize %s, constants %s, pair table %s", g,
+                 dyn_state ? "LDS" : "global", mat ? "LDS" : "global", rows ? "rows_balanced" : cols ? "cols_balanced" : "plain",
+                 S <= K4_CHAIN_SCN ? "LDS" : "global", tbl ? "LDS" : "global");
+        chain_forms.push_back(line);
+      }
+    }
     return k4_chain_launch_wg(Ck, first, (int)regs.size(), dyn_state + (size_t)want, side);
   };
   PCHK(launch_class(wide, 0, max_state, 64 * 1024));
   if (n_big) RCHK(c.lock_grid(*this));
+  if (c.prof) for (int k = 0; k < n_big; k++) {   // all CUs: state, matrix, constants and pair table in global memory, cross_optimize_scope
+    char line[256];
+    snprintf(line, sizeof(line), "chain region %d: scope all-CU, state global, matrix global, cross_optimize grid, constants global, pair table global", desc[n_small + k].slot);
+    chain_forms.push_back(line);
+  }
   for (int k = 0; k < n_big; k++) PCHK(k4_chain_launch_grid(C, n_small + k, (size_t)std::max(desc[n_small + k].fast_lds, desc[n_small + k].batch_lds), side));
   if (nps) {
     // 33 KB of static stage buffers + up to 64 KB of region image
@@ -861,6 +881,7 @@ int PhaseHost::report_prof(PhaseCall& c) {
     fprintf(stderr, "[phase]   enumeration regions: %zu, entries per lane min %d median %d p90 %d max %d; restarts with <= 32: %llu, 33-48: %llu, > 48: %llu\n",
             mn.size(), mn.front(), mn[mn.size() / 2], mn[mn.size() * 9 / 10], mn.back(), (unsigned long long)jobs[0], (unsigned long long)jobs[1], (unsigned long long)jobs[2]);
   }
+  for (const std::string& f : chain_forms) fprintf(stderr, "[phase]   %s\n", f.c_str());
   if (chain_dev.dbg && !chain_desc.empty()) {   // steps of the last grid-scope chain launch
     const ChainDesc& last = chain_desc.back();
     long long clk[16];

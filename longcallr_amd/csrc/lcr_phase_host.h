@@ -110,6 +110,7 @@ struct PhaseHost {
   int settle(std::string* err);
   ChainDev chain_dev{};                // chain-region buffers of the last run (LD blocks are read back from them)
   std::vector<ChainDesc> chain_desc;
+  std::vector<std::string> chain_forms;            // phase_prof: the form launch_chain gave each chain region (report_prof prints them)
   std::vector<uint64_t> enum_keys;                   // scratch of the enumeration launch preparation, kept across calls
   std::vector<int64_t> enum_job_base, enum_st_base;
   // LD blocks of one region of the last run in the reference's order (candidate.rs:733-745): off[n_blocks + 1], SNP indices
