@@ -1,17 +1,18 @@
-// k1_pileup.hip — K0 (CIGAR decode + binning), K1 (pileup tally), K1z (poly-A mask fix) for gfx950.
+// k1_pileup.hip — the bind kernels of a batch (region / tile / read tables for K0), K1 (pileup tally) and K1z (poly-A mask fix) for gfx950.
 //
-// Together they replace Profile::fill_data_into_freq_vec (reference src/util.rs:621-949).
+// With K0 (k0_ops.hip) they replace Profile::fill_data_into_freq_vec (reference src/util.rs:621-949).
 //
 // Design.  The reference walks every read base by base.  Here:
-//   K0  one wave64 per read scans the CIGAR 64 ops at a time (DPP prefix sums give every op's
-//       reference / query start) and emits, per pileup tile (LCR_TILE columns of one region), compact
-//       8-byte records:  M-segment (tile column, length, byte offset of its first read base, strand,
-//       transcript-strand class), D-run (column, length), I-point (column).  ONT end trimming
-//       (util.rs:745-751) is applied here by clipping M blocks to the untrimmed read interval.
-//       Intron (N) runs never reach a tile: they become +1/-1 pairs in a global difference array that
-//       is prefix-scanned once (introns dominate RNA-seq coverage).  Records are counting-sorted by
-//       tile (count pass -> scan -> fill pass; slots are allocated per run of equal tiles with one
-//       atomic per run).
+//   K0  lives in k0_ops.hip: a workgroup per block of consecutive CIGAR ops of the batch's flat op array, whatever reads they
+//       belong to, emits per pileup tile (LCR_TILE columns of one region) compact 8-byte records:  M-segment (tile column,
+//       length, byte offset of its first read base, strand, transcript-strand class), D-run (column, length), I-point (the
+//       column in front of the insertion), N-run (column, length).  ONT end trimming (util.rs:745-751) is applied there by
+//       clipping M blocks to the untrimmed read interval.  An intron leaves an N-run record in its first and in its last tile
+//       only; the tiles it covers entirely get +1 in a tile-level difference array (tile_ndiff), whose prefix sum K1 adds as
+//       tile_nbase.  A block's records lie back to back in the pool, grouped by tile; k0_desc_bin sorts the (block, tile) chunk
+//       descriptors by tile and cuts them into entries of at most 16 records, which K1 walks.  What this file keeps of K0 are
+//       the tables it reads: first tile of every region, tile -> region / first column, read -> region, the 64-byte read headers
+//       (ReadBin) and the first read of every op block (k0_bind_a / k0_bind_b and the single-purpose kernels they fuse).
 //   K1  one workgroup owns one tile and keeps all its counters in LDS.  It never sees a CIGAR:
 //       threads take one record each (coalesced 8-byte loads); whole M-segments and D-runs are
 //       difference-array range updates (2 LDS atomics per record, prefix-scanned at the end); then
@@ -461,9 +462,12 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
         const uint32_t lo = (jd & 2u) ? q.v.z : q.v.x, hi = (jd & 2u) ? q.v.w : q.v.y;
         const uint32_t base = __builtin_amdgcn_perm(hi, lo, 0x0c0c0c00u | ((jd & 1u) << 2) | kb);   // byte kb of (jd & 1 ? hi : lo)
         const uint32_t dcol = 4u * jd + kb;
-        // A,C,G,T (either case) -> plane h = bits 1-2 of the byte (A 0, C 1, T 2, G 3: the LDS mismatch planes are kept in THAT
+        // A,C,G,T -> plane h = bits 1-2 of the byte (A 0, C 1, T 2, G 3: the LDS mismatch planes are kept in THAT
         // order); anything else is "Invalid nucleotide base" (util.rs:890-892): no allele count (depth - 1), transcript strand
-        // still counted.  Valid iff the byte, upper-cased, is the letter of its own class (one v_perm_b32 from "ACTG").
+        // still counted.  Valid iff the byte, upper-cased, is the letter of its own class (one v_perm_b32 from "ACTG").  The ABI's
+        // read bases are upper case (lcr.h).  A lower-case a / c / g / t would pass this test too, but the counts are only right
+        // for it where it differs from the reference base: under the upper-case reference base of its own letter it lands on that
+        // base's mismatch plane, which the epilogue overwrites with depth - (sum of the mismatch planes) -- the base is lost.
         const uint32_t h = (base >> 1) & 3u;
         const bool acgt = (base & 0xDFu) == __builtin_amdgcn_perm(0u, 0x47544341u /* 'A','C','T','G' */, 0x0c0c0c00u | h);
         if (acgt) atomicAdd(mp + h * TSTRIDE + dcol, 1u);
@@ -847,6 +851,7 @@ k1_zonefix(BatchView b, int D, int L, int64_t n_cols, uint32_t* __restrict__ pla
                            __builtin_amdgcn_alignbyte(w3, w2, sh), w3 >> (8 * sh)};
     int run = 1;
     uint32_t prev = d[0] & 0xffu;
+    if (L <= 1) m |= prev == 'A' ? 1u : prev == 'C' ? 2u : prev == 'G' ? 4u : prev == 'T' ? 8u : 0u;   // (L = 1: the first byte is a window of its own)
 #pragma unroll
     for (int i = 1; i < 13; i++) {
       if (i <= 2 * L) {
@@ -861,6 +866,7 @@ k1_zonefix(BatchView b, int D, int L, int64_t n_cols, uint32_t* __restrict__ pla
     if (hi - lo + 1 < L) return;
     int run = 1;
     uint8_t prev = seq[lo];
+    if (L <= 1) m |= prev == 'A' ? 1u : prev == 'C' ? 2u : prev == 'G' ? 4u : prev == 'T' ? 8u : 0u;
     for (int i = lo + 1; i <= hi; i++) {
       const uint8_t cur = seq[i];
       run = (cur == prev) ? run + 1 : 1;
