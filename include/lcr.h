@@ -658,6 +658,58 @@ int lcr_get_somatic(lcr_ctx*, int32_t* n_cand, const lcr_somatic_site** rec, con
  * lcr_kernel_ms: that list is closed. */
 int lcr_somatic_ms(lcr_ctx*, float* ms);
 
+/* Allele-specific isoforms (K15): the haplotype x intron-chain table -- which whole transcript structure does each haplotype use --,
+ * counted on the GPU from what lcr_phase or lcr_haplotag left there.  DESIGN.md section 1m.  Defined per region, as lcr_junctions.  Row r
+ * of region g is a row of lcr_get_fragmat: its read is row_read[r], its haplotype assignment[r], its phase set phase_set[r] (0 = none).
+ *   junctions of a read, rend   exactly lcr_junctions': an N op of length >= 1 gives (s, l) in contig coordinates, zero-length N ops are
+ *       ignored, rend is exclusive, s rises along a read.
+ *   chain                 the ordered list of a read's junctions (s_1, l_1) ... (s_k, l_k).  Two chains are the same iff they have the same k
+ *       and are equal pair for pair: identity is exact (a hash routes a chain to its slot and never decides).
+ *   participating rows    assignment 1 or 2 and k >= min_junctions (">=": lcr_junctions has "more than").  min_junctions == 0 is LCR_E_ARG,
+ *       so an unspliced read never takes part.  Every other read takes no part, neither as present nor as absent.
+ *   kept chains           n_reads(g, chain) = participating rows of g whose chain is that chain; n_h1 / n_h2 the same per haplotype, over
+ *       every phase set; kept iff n_reads >= min_count.
+ *   extent                of a kept chain: a = s_1, e = s_k + l_k.
+ *   spanning              a participating row spans the chain iff pos <= a && rend >= e (a row that holds the chain always does).
+ *   presence              a junction (s, l) of the row meets the extent iff s < e && s + l > a; these form a contiguous run.  The row is
+ *       PRESENT iff that run, in order, equals the chain, ABSENT otherwise: a longer isoform that contains the chain unchanged inside the
+ *       extent is present; a read truncated inside the extent does not span and is neither; a junction that straddles a or e makes the row
+ *       absent.
+ *   phase set             lcr_junctions' rule over the spanning rows: count them per value of ps; phase_set is the value with the most rows,
+ *       ties to the smallest value, 0 a value like any other; n_phase_sets = distinct values; h1_absent, h1_present, h2_absent, h2_present
+ *       count the rows of that phase set only.
+ *   order                 by region, then lexicographically over the chain's (s, l) pairs, s before l, a proper prefix first;
+ *       bit-reproducible, independent of the batch's composition and of the order in which atomics land.
+ *   chain pool            chain[chain_first .. chain_first + n_junc) of a record are its keys s << 32 | l, in record order.
+ *   row_isoform           one int32 per fragment row of the batch: the index of the kept record whose chain the row holds exactly, -1 for
+ *       rows that do not participate or whose chain is not kept.
+ * Not here: splice-site wobble (near-identical chains stay apart), annotation matching, a per-gene form.
+ * lcr_isoforms needs the bound batch with the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed;
+ * params == NULL or min_junctions == 0: LCR_E_ARG, the last call's records stay valid; more than 2^28 junction occurrences of participating
+ * rows in a batch: LCR_E_ARG), collects an asynchronous phase stage in flight first, queues a fixed number of kernels on the context's
+ * stream around two host waits on sizes, writes no buffer another stage or getter reads, and may be repeated with other params.  The
+ * records die with the phase results: at the next candidate stage and at lcr_load_batch / lcr_bind_batch; lcr_get_isoforms answers
+ * LCR_E_STATE then.  iso / iso_region_off (n_regions + 1) / chain / row_isoform: pinned host memory, valid until the next lcr_isoforms --
+ * the call's last kernels' stores (the zero offsets of a call that keeps nothing are the host's) --; dev_*: the same bytes in HBM.  iso / dev_iso are NULL without a record, chain /
+ * dev_chain without a pool entry, row_isoform / dev_row_isoform without a fragment row. */
+typedef struct { uint32_t min_count, min_junctions; } lcr_isoform_params;      /* defaults 10, 1 */
+typedef struct {
+  int32_t region, n_junc;
+  int64_t start0, end0;          /* a, e */
+  int32_t chain_first;           /* chain[chain_first .. chain_first + n_junc) */
+  uint32_t n_reads, n_h1, n_h2;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1_absent, h1_present, h2_absent, h2_present;
+} lcr_isoform;                   /* 64 bytes */
+typedef struct { int32_t n_regions, n_isoforms, n_chain, n_rows;
+                 const lcr_isoform* iso; const int32_t* iso_region_off; const uint64_t* chain /* s << 32 | l */; const int32_t* row_isoform;
+                 const lcr_isoform* dev_iso; const uint64_t* dev_chain; const int32_t* dev_row_isoform; } lcr_isoform_list;
+int lcr_isoforms(lcr_ctx*, const lcr_isoform_params*);
+int lcr_get_isoforms(lcr_ctx*, lcr_isoform_list* out);
+/* HIP-event time (ms) from the first to the last kernel of the last lcr_isoforms with timing enabled (lcr_enable_timing), the host's two
+ * waits for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_isoforms_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.
@@ -1030,7 +1082,9 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * "spec_compact" (0: lcr_candidates waits for the survivors' number before it queues their compaction), "lean_planes" (0: lcr_pileup always stores
  * the planes of the tiles with records -- and, on the ONT presets, the filter flags -- instead of handing the filter's survivors to lcr_candidates), "own_fill" (0: hipMemsetAsync instead of the
  * library's fill kernels), "fill_selftest" (checks those kernels against the host; LCR_E_DEVICE on a difference), "host_trace" (1: a
- * "[host]" line of wall-clock marks per lcr_phase on stderr; process-wide like own_fill).  Unknown key: LCR_E_ARG.  The defaults are the
+ * "[host]" line of wall-clock marks per lcr_phase on stderr; process-wide like own_fill), "iso_hash_bits" (0 .. 64, default 64: lcr_isoforms
+ * routes a chain by the low n bits of its hash only -- 0 sends every chain of a region down one probe sequence; the results are the same
+ * bytes for every n, which is how the comparison of whole chains is tested).  Unknown key: LCR_E_ARG.  The defaults are the
  * product behaviour. */
 int lcr_debug_set(lcr_ctx*, const char* key, int64_t value);
 

@@ -183,6 +183,24 @@ class LcrHapCovList(C.Structure):   # include/lcr.h: lcr_hap_cov_list
                 ("reg", C.c_void_p), ("dev_seg", C.c_void_p), ("dev_reg", C.c_void_p)]
 
 
+class LcrIsoformParams(C.Structure):   # include/lcr.h: lcr_isoform_params (defaults 10, 1)
+    _fields_ = [("min_count", C.c_uint32), ("min_junctions", C.c_uint32)]
+
+
+# lcr_isoform (include/lcr.h): one kept intron chain of a region -- its extent [start0, end0), its keys chain[chain_first .. + n_junc) --
+# with its haplotype x presence table
+ISOFORM_DTYPE = np.dtype([("region", "<i4"), ("n_junc", "<i4"), ("start0", "<i8"), ("end0", "<i8"), ("chain_first", "<i4"), ("n_reads", "<u4"),
+                          ("n_h1", "<u4"), ("n_h2", "<u4"), ("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("h1_absent", "<u4"),
+                          ("h1_present", "<u4"), ("h2_absent", "<u4"), ("h2_present", "<u4")], align=True)
+assert ISOFORM_DTYPE.itemsize == 64, ISOFORM_DTYPE.itemsize
+
+
+class LcrIsoformList(C.Structure):   # include/lcr.h: lcr_isoform_list
+    _fields_ = [("n_regions", C.c_int32), ("n_isoforms", C.c_int32), ("n_chain", C.c_int32), ("n_rows", C.c_int32),
+                ("iso", C.c_void_p), ("iso_region_off", C.c_void_p), ("chain", C.c_void_p), ("row_isoform", C.c_void_p),
+                ("dev_iso", C.c_void_p), ("dev_chain", C.c_void_p), ("dev_row_isoform", C.c_void_p)]
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

@@ -25,6 +25,7 @@ SYMBOLS = [
     "lcr_site_counts", "lcr_get_site_counts", "lcr_site_counts_ms",
     "lcr_hap_coverage", "lcr_get_hap_coverage", "lcr_hap_coverage_ms",
     "lcr_somatic", "lcr_get_somatic", "lcr_somatic_ms",
+    "lcr_isoforms", "lcr_get_isoforms", "lcr_isoforms_ms",
 ]
 
 _lib = None
@@ -151,5 +152,8 @@ def load():
     l.lcr_somatic.argtypes = [vp, C.POINTER(_abi.LcrSomaticParams)]
     l.lcr_get_somatic.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp)]
     l.lcr_somatic_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_isoforms.argtypes = [vp, C.POINTER(_abi.LcrIsoformParams)]
+    l.lcr_get_isoforms.argtypes = [vp, C.POINTER(_abi.LcrIsoformList)]
+    l.lcr_isoforms_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

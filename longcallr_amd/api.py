@@ -419,6 +419,31 @@ class Engine:
         self._chk(self.lib.lcr_somatic_ms(self.h, C.byref(ms)), "lcr_somatic_ms")
         return float(ms.value)
 
+    def isoforms(self, min_count=10, min_junctions=1):
+        """lcr_isoforms + lcr_get_isoforms after phase() or haplotag(): the kept intron chains of every region -- which whole transcript
+        structure each haplotype uses -- with their haplotype x presence tables (include/lcr.h) -> (records as a structured array of
+        _abi.ISOFORM_DTYPE, ordered by region and chain; iso_region_off, n_regions + 1; chain, the records' keys s << 32 | l as uint64,
+        record r's at chain_first .. chain_first + n_junc; row_isoform, per row of fragmat() the record whose chain it holds or -1), all
+        copied (isoforms.chains unpacks the keys).  Waits for an asynchronous phase stage in flight; may be repeated with other
+        parameters."""
+        p = _abi.LcrIsoformParams(int(min_count), int(min_junctions))
+        self._chk(self.lib.lcr_isoforms(self.h, C.byref(p)), "lcr_isoforms")
+        o = self._isoform_list()
+        return (_view(o.iso, _abi.ISOFORM_DTYPE, o.n_isoforms), _view(o.iso_region_off, np.int32, o.n_regions + 1),
+                _view(o.chain, np.uint64, o.n_chain), _view(o.row_isoform, np.int32, o.n_rows))
+
+    def _isoform_list(self):
+        """lcr_get_isoforms: the last isoforms()'s list (pinned host and HBM pointers)"""
+        o = _abi.LcrIsoformList()
+        self._chk(self.lib.lcr_get_isoforms(self.h, C.byref(o)), "lcr_get_isoforms")
+        return o
+
+    def isoforms_ms(self):
+        """lcr_isoforms_ms: HIP-event time of the last isoforms()'s kernels, its two host waits included (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_isoforms_ms(self.h, C.byref(ms)), "lcr_isoforms_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

@@ -15,6 +15,7 @@
 // depends on the order in which atomics land: a slot's position inside its segment does, the sorted output does not.
 #include <algorithm>
 
+#include "k6_walk.h"
 #include "lcr_dev.h"
 
 namespace {
@@ -31,8 +32,7 @@ static_assert(sizeof(K6Row) == 24, "K6Row is six words");
 
 __device__ __forceinline__ uint32_t k6_hash(unsigned long long key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32); }
 
-// Sixteen lanes per read (one DPP row; four reads per wave64): ops spread over the lanes, reference offsets from a row scan of the
-// reference-consuming lengths (M D N = X), a carry between rounds of 16 ops.  Every lane of a row takes the same branches.
+// Sixteen lanes per read walk its junctions (k6_walk.h: row16_walk_junctions).
 template <bool EMIT>
 __global__ void __launch_bounds__(LCR_BLOCK) k6_walk(BatchView b, const int32_t* __restrict__ row_region_off, const lcr_read_record* __restrict__ rec,
                                                       uint32_t min_junctions, int32_t* __restrict__ part_flag, int32_t* __restrict__ npair,
@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k6_walk(BatchView b, const int32_t*
                                                       const int32_t* __restrict__ tbl_off, K6Row* __restrict__ rows,
                                                       unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tbl_key,
                                                       uint32_t* __restrict__ tbl_cnt) {
-  const int lane = threadIdx.x & 63, l16 = lane & 15, rbase = lane & 48;
+  const int l16 = threadIdx.x & 15;
   const long long rl = ((long long)blockIdx.x * LCR_BLOCK + threadIdx.x) >> 4;
   if (rl >= b.n_reads) return;   // (a whole row leaves)
   const int r = (int)rl;
@@ -57,34 +57,22 @@ __global__ void __launch_bounds__(LCR_BLOCK) k6_walk(BatchView b, const int32_t*
     const lcr_read_record rr = rec[row_region_off[g] + (r - b.read_begin[g])];
     hap = rr.assignment; ps = rr.phase_set;
   }
-  const uint32_t ncig = b.n_cig[r];
-  const uint32_t* __restrict__ cg = b.cigar + b.cig_off[r];
   const int pos = b.pos[r];
   const int first = EMIT ? pair_off[r] : 0;
   const int t0 = EMIT ? tbl_off[g] : 0;
   const uint32_t mask = EMIT ? (uint32_t)(tbl_off[g + 1] - t0) - 1u : 0u;   // (a participating row has a pair: the segment is not empty)
-  int ref_cur = pos, n_n = 0;
-  for (uint32_t c0 = 0; c0 < ncig; c0 += 16) {
-    const uint32_t w = c0 + l16 < ncig ? cg[c0 + l16] : 0u;   // (a padding word is a 0-length M)
-    const int op = w & 15, len = (int)(w >> 4);
-    const int dr = (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? len : 0;   // I S H P consume no reference
-    const int ir = row16_incl_scan(dr);
-    const bool is_n = op == 3 && len >= 1;
-    const unsigned int m = (unsigned int)(__ballot(is_n) >> rbase) & 0xffffu;
-    if (EMIT && is_n) {
-      const int s = ref_cur + ir - dr;
-      const unsigned long long key = ((unsigned long long)(uint32_t)s << 32) | (uint32_t)len;
-      keys[first + n_n + __popc(m & ((1u << l16) - 1u))] = key;
-      // the segment has at least twice the region's pairs in slots: an empty one is met before the probe comes round
-      uint32_t h = k6_hash(key) & mask;
-      for (uint32_t i = 0; i <= mask; i++, h = (h + 1) & mask) {
-        const unsigned long long prev = atomicCAS(&tbl_key[t0 + h], K6_EMPTY, key);
-        if (prev == K6_EMPTY || prev == key) { atomicAdd(&tbl_cnt[t0 + h], 1u); break; }   // (a read holds a key once: s rises along it)
-      }
+  int ref_cur, n_n;
+  row16_walk_junctions(b, r, [&](int s, int len, int k) {
+    if (!EMIT) return;
+    const unsigned long long key = ((unsigned long long)(uint32_t)s << 32) | (uint32_t)len;
+    keys[first + k] = key;
+    // the segment has at least twice the region's pairs in slots: an empty one is met before the probe comes round
+    uint32_t h = k6_hash(key) & mask;
+    for (uint32_t i = 0; i <= mask; i++, h = (h + 1) & mask) {
+      const unsigned long long prev = atomicCAS(&tbl_key[t0 + h], K6_EMPTY, key);
+      if (prev == K6_EMPTY || prev == key) { atomicAdd(&tbl_cnt[t0 + h], 1u); break; }   // (a read holds a key once: s rises along it)
     }
-    n_n += __popc(m);
-    ref_cur += __shfl(ir, rbase + 15, 64);
-  }
+  }, &n_n, &ref_cur);
   if (l16 != 0) return;
   if (!EMIT) {
     const int p = (uint32_t)n_n > min_junctions ? 1 : 0;

@@ -196,6 +196,7 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   for (hipEvent_t e : {c->ev_sc, c->ev_sc_t[0], c->ev_sc_t[1]}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_hc, c->ev_hc_t[0], c->ev_hc_t[1]}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_som, c->ev_som_t[0], c->ev_som_t[1]}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_iso, c->ev_iso_t[0], c->ev_iso_t[1]}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_unpack_t) if (e) (void)hipEventDestroy(e);
   c->phase.release();
   for (int k = 0; k < LCR_NTIMERS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);
@@ -517,6 +518,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "spec_compact") c->dbg_spec_compact = value != 0;
   else if (k == "lean_planes") c->dbg_lean_planes = value != 0;
   else if (k == "poison_planes") c->dbg_poison_planes = value != 0;
+  else if (k == "iso_hash_bits") c->dbg_iso_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
   else if (k == "grid_spec_batch") d.spec_batch = (int)value;
   else if (k == "grid_spec_lanes") d.spec_lanes = (int)std::max<int64_t>(1, std::min<int64_t>(value, 16));
   else { c->err = "lcr_debug_set: unknown key " + k; return LCR_E_ARG; }

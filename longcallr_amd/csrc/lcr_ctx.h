@@ -8,7 +8,7 @@
 // (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks;
 // lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) and lcr_hap_coverage.hip (lcr_hap_coverage,
 // lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
-// lcr_somatic_ms) a third.
+// lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -245,6 +245,20 @@ struct lcr_ctx {
   hipEvent_t ev_som = nullptr;               // behind the call's last kernel; created on first use
   hipEvent_t ev_som_t[2] = {};               // timing enabled: around the call's kernels, created on first use
 
+  // K15 (lcr_isoforms): scratch and results of its own -- no other stage or getter reads them
+  bool iso_valid = false;    // lcr_get_isoforms: the last lcr_isoforms' records belong to the phase results of the bound batch (rewind_to)
+  bool iso_timed = false;    // ev_iso_t brackets the last call's kernels
+  int32_t iso_ng = 0, iso_n = 0, iso_nchain = 0, iso_nrows = 0;
+  int dbg_iso_hash_bits = 64;   // lcr_debug_set("iso_hash_bits"): the low bits of a chain's hash that route it; identity never depends on them
+  DevBuf iso_part, iso_npair, iso_part_off, iso_pair_off, iso_tsz, iso_tbl_off;   // per read: participates, junctions, their running sums; per region: its table segment
+  DevBuf iso_rows, iso_keys, iso_hash, iso_row_slot;                              // per participating row: record, keys, chain hash, the slot it joined
+  DevBuf iso_tbl_rep, iso_tbl_cnt, iso_flag, iso_koff, iso_plen, iso_poff;        // per slot: representative row, n_h1 / n_h2, kept, kept in front, chain length, keys in front
+  DevBuf iso_off, iso_pbase, iso_cslot, iso_crank;                                // per region: kept chains / pool entries in front; per kept slot: its slot, its record
+  DevBuf d_iso, d_iso_chain, d_iso_row;                                           // the records, the pool, row_isoform
+  HostBuf h_iso_ctl, h_iso, h_iso_off, h_iso_chain, h_iso_row;   // pinned: {participating rows, pairs, kept chains, pool entries}; the four outputs
+  hipEvent_t ev_iso = nullptr;            // behind the two size waits, then behind the call's last kernel; created on first use
+  hipEvent_t ev_iso_t[2] = {};            // timing enabled: around the call's kernels, created on first use
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -303,6 +317,7 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
   if (to < ST_PHASED) c->sc_valid = false;       // ... and the per-site allele x haplotype counts
   if (to < ST_PHASED) c->hc_valid = false;       // ... and the per-haplotype coverage segments
   if (to < ST_PHASED) c->som_valid = false;      // ... and the per-site somatic records
+  if (to < ST_PHASED) c->iso_valid = false;      // ... and the haplotype x intron-chain records
   if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),

@@ -382,6 +382,30 @@ void launch_k13_offsets(int32_t ng, const int32_t* off /* ng + 1 */, const lcr_h
 void launch_k13_emit(const BatchView& b, int64_t n_cols, const uint32_t* planes, const int32_t* off, lcr_hap_cov_segment* seg, int32_t* send /* per segment: its end column */, hipStream_t s);
 void launch_k13_finish(int32_t n_seg, int32_t ng, const int64_t* start0, const int32_t* send, lcr_hap_cov_segment* seg, lcr_hap_cov_segment* host_seg /* pinned (device pointer) */, hipStream_t s);
 
+// k15_isoforms.hip: haplotype x intron-chain counts over the phased rows (lcr_isoforms); participating rows and junctions per read are
+// launch_k6_count's with min_junctions - 1
+void launch_k15_sizes(const BatchView& b, const int32_t* part_off /* n_reads + 1 */, const int32_t* pair_off /* n_reads + 1 */, int32_t* tsz /* n_regions */,
+                      int32_t* host_ctl /* pinned (device pointer): [0] participating rows, [1] pairs */, hipStream_t s);
+size_t launch_k15_row_bytes();   // bytes of a participating row's record
+void launch_k15_walk(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, const int32_t* part_flag, const int32_t* part_off,
+                     const int32_t* pair_off, void* rows, uint64_t* keys, uint64_t* hash /* per participating row */, hipStream_t s);
+void launch_k15_insert(int32_t n_part, const void* rows, const uint64_t* keys, const uint64_t* hash, uint64_t hash_mask /* the routing bits */,
+                       const int32_t* tbl_off /* n_regions + 1 */, int32_t* tbl_rep /* 0xff-filled */, uint32_t* tbl_cnt /* two per slot, zeroed */,
+                       int32_t* row_slot /* per participating row */, hipStream_t s);
+void launch_k15_flag(const int32_t* tbl_rep, const uint32_t* tbl_cnt, const void* rows, int32_t n_slots, uint32_t min_count, int32_t* flag,
+                     int32_t* plen /* keys of a kept slot's chain, else 0 */, hipStream_t s);
+void launch_k15_offsets(const int32_t* tbl_off, const int32_t* koff /* n_slots + 1 */, const int32_t* poff /* n_slots + 1 */, int32_t ng, int32_t n_slots,
+                        int32_t* off, int32_t* host_off, int32_t* pbase /* n_regions + 1: pool entries in front of every region */,
+                        int32_t* host_ctl /* [2] kept chains, [3] pool entries */, hipStream_t s);
+void launch_k15_place(const void* rows, const uint64_t* keys, const int32_t* tbl_rep, const uint32_t* tbl_cnt, const int32_t* flag, const int32_t* koff,
+                      int32_t n_slots, const int32_t* off, const int32_t* pbase, int32_t n_kept, int32_t* cslot /* n_kept */, int32_t* crank /* n_kept */,
+                      lcr_isoform* iso, uint64_t* chain, uint64_t* host_chain /* pinned (device pointer) */, hipStream_t s);
+void launch_k15_rows(int32_t n_part, const void* rows, const int32_t* row_slot, const int32_t* flag, const int32_t* koff, const int32_t* crank,
+                     int32_t* row_iso /* n_rows, 0xff-filled */, hipStream_t s);
+void launch_k15_export(int32_t n_rows, const int32_t* row_iso, int32_t* host_row_iso /* pinned (device pointer) */, hipStream_t s);
+void launch_k15_tables(const BatchView& b, const int32_t* part_off, const void* rows, const uint64_t* keys, const uint64_t* chain, int32_t n_kept,
+                       lcr_isoform* iso, lcr_isoform* host_iso /* pinned (device pointer) */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import _abi, annotation, api, ase, asj, bamio, coverage, somatic, vcf
+from . import _abi, annotation, api, ase, asj, bamio, coverage, isoforms, somatic, vcf
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -121,7 +121,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         ase_annotation=None, ase_gene_types=annotation.GENE_TYPES, asj_annotation=None, asj_gene_types=annotation.GENE_TYPES,
         asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
         haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, hap_coverage_out=None,
-        somatic_out=None, somatic_purity=0.3, somatic_min_baseq=0, somatic_min_score=0.0, **param_overrides):
+        somatic_out=None, somatic_purity=0.3, somatic_min_baseq=0, somatic_min_score=0.0,
+        isoforms_out=None, isoform_min_count=10, isoform_min_junctions=1, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -223,7 +224,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     order.  Every chunk calls Engine.somatic behind phase() / haplotag() and the other table calls; that call waits for the phase
     stage, like theirs.  Purity outside (0, 1] or a somatic_min_baseq outside 0 - 30 is a ValueError before any GPU work.  Adds the
     stats somatic_sites (flagged candidates evaluated with status OK) and somatic_calls.  No other output depends on it; without
-    somatic_out nothing changes."""
+    somatic_out nothing changes.
+    isoforms_out / isoform_min_count / isoform_min_junctions: the allele-specific isoform table (include/lcr.h: lcr_isoforms;
+    isoforms.format_tsv), written to isoforms_out: one row per intron chain that at least isoform_min_count tagged reads of a region hold
+    exactly, with the reads per haplotype and the absent / present table of the reads that span the chain, tested like a junction's.
+    Reads with fewer than isoform_min_junctions junctions take no part (at least 1: ValueError otherwise).  Every chunk calls
+    Engine.isoforms behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Adds the
+    stats isoforms (kept records, summed over chunks) and isoform_reads (fragment rows that hold a kept chain).  No other output depends
+    on it; without isoforms_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -238,6 +246,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         raise ValueError("hap_coverage_out must be a path prefix in an existing directory (PREFIX.h1.bedgraph, ...), got %r" % (hap_coverage_out,))
     if somatic_out is not None:
         somatic.check_params(somatic_purity, 5e-6, 5e-4, somatic_min_baseq)
+    if isoforms_out is not None:
+        for what, v, least in (("isoform_min_count", isoform_min_count, 0), ("isoform_min_junctions", isoform_min_junctions, 1)):
+            if isinstance(v, bool) or int(v) != v or not least <= int(v) < 1 << 32:
+                raise ValueError("%s must be an integer in [%d, 2^32), got %r" % (what, least, v))
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -314,14 +326,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records, somatic records) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records, somatic records, isoform results) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -360,6 +372,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             flagged = (cands["flags"] & _abi.F_CAND_SOMATIC) != 0
             out["somatic"] = (somatic.format_vcf_records(cands, som, name, somatic_min_score),
                               int(np.count_nonzero(flagged & (som["status"] == somatic.SOM_OK))), int(np.count_nonzero(som["call"])))
+        if iso is not None:     # (Engine.isoforms copied them out of the context's buffers)
+            out["iso"] = (name, iso[0], iso[2], batch.start0, batch.len, int(np.count_nonzero(iso[3] >= 0)))
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -416,7 +430,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             srec = E.site_counts(ase_sites_min_baseq) if ase_sites_out is not None else None                  # (waits for the phase stage)
             hcov = E.hap_coverage() if hap_coverage_out is not None else None                                 # (waits for the phase stage)
             som = E.somatic(purity=somatic_purity, min_baseq=somatic_min_baseq) if somatic_out is not None else None   # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som)
+            iso = E.isoforms(isoform_min_count, isoform_min_junctions) if isoforms_out is not None else None           # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso)
         finally:
             with free_lock:
                 free.append(k)
@@ -568,6 +583,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["somatic_sites"] = sum(r["somatic"][1] for r in results)
         stats["somatic_calls"] = sum(r["somatic"][2] for r in results)
         write_vcf(somatic_out, contig_lengths, [r["somatic"][0] for r in results], somatic.INFO_LINES)
+    if isoforms_out is not None:
+        stats["isoforms"] = sum(int(r["iso"][1].size) for r in results)
+        stats["isoform_reads"] = sum(r["iso"][5] for r in results)
+        with open(isoforms_out, "w") as f:
+            f.write(isoforms.format_tsv([r["iso"][:5] for r in results], isoform_min_count))
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

@@ -15,6 +15,7 @@
                                  [--ase-sites-out out.ase_sites.tsv [--ase-sites-min-baseq N]]   (allele x haplotype counts per VCF record)
                                  [--hap-coverage-out PREFIX]   (PREFIX.h1 / .h2 / .unassigned.bedgraph: covered depth per HP tag)
                                  [--somatic-out out.somatic.vcf [--somatic-purity P] [--somatic-min-baseq N] [--somatic-min-score S]]   (haplotype-resolved somatic calls at low-fraction sites)
+                                 [--isoforms-out out.isoforms.tsv [--isoform-min-count N] [--isoform-min-junctions N]]   (allele-specific isoform table: haplotype x intron chain)
 """
 import argparse
 import json
@@ -67,6 +68,9 @@ def main():
     ap.add_argument("--somatic-purity", type=float, default=0.3, help="fraction of a somatic haplotype's reads that carry the allele, in (0, 1]")
     ap.add_argument("--somatic-min-baseq", type=int, default=0, help="base quality an entry needs to be counted in --somatic-out (0 - 30)")
     ap.add_argument("--somatic-min-score", type=float, default=0.0, help="records with a somatic score below it are LowQual")
+    ap.add_argument("--isoforms-out", help="write the allele-specific isoform table: one row per intron chain held by enough tagged reads, with its haplotype x presence table")
+    ap.add_argument("--isoform-min-count", type=int, default=10, help="reads that must hold a chain exactly for it to be kept, and a table needs to be written")
+    ap.add_argument("--isoform-min-junctions", type=int, default=1, help="a read takes part with AT LEAST this many junctions (>= 1)")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -88,6 +92,8 @@ def main():
         ap.error("--somatic-purity must lie in (0, 1]")
     if not 0 <= a.somatic_min_baseq <= 30:
         ap.error("--somatic-min-baseq must lie in 0 - 30 (the fragment matrix clamps qualities to 30)")
+    if a.isoform_min_count < 0 or a.isoform_min_junctions < 1:
+        ap.error("--isoform-min-count must be >= 0 and --isoform-min-junctions >= 1 (an unspliced read has no chain)")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -106,7 +112,8 @@ def main():
                       annotation=a.annotation, exon_only=a.exon_only, packed_upload=a.packed_upload, haplotag=a.haplotag,
                       ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, hap_coverage_out=a.hap_coverage_out,
                       somatic_out=a.somatic_out, somatic_purity=a.somatic_purity, somatic_min_baseq=a.somatic_min_baseq,
-                      somatic_min_score=a.somatic_min_score, **extra)
+                      somatic_min_score=a.somatic_min_score,
+                      isoforms_out=a.isoforms_out, isoform_min_count=a.isoform_min_count, isoform_min_junctions=a.isoform_min_junctions, **extra)
     print(json.dumps(st))
 
 
