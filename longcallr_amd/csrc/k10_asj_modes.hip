@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k10_support_uniq(const int32_t* __r
     __syncthreads();
     uint32_t nxt = 0xffffffffu;
     for (int c = c0 + tid; c < c1; c += LCR_BLOCK) { const uint32_t v = sup[c]; if (v > cur) nxt = min(nxt, v); }
-    nxt = k7_wave_min(nxt);
+    nxt = wave_min_u32(nxt);
     if ((tid & 63) == 0 && nxt != 0xffffffffu) atomicMin(&sh_next, nxt);
     __syncthreads();
     const uint32_t next = sh_next;

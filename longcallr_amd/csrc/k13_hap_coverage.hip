@@ -5,7 +5,7 @@
 //   k13_blocks   sixteen lanes per read over its CIGAR (k6_walk's layout).  A read's covered set is a union of intervals that only an N op
 //                of length >= 1 breaks, so the walk emits one +1 where a covered run starts and one -1 where it ends -- not two per op --,
 //                clipped to the window, into the difference plane of the read's class.  u32 adds that wrap; start and end adds commute.
-//                What a wave sends to one address is summed in the wave first (k13_wave_add)                                  -> planes
+//                What a wave sends to one address is summed in the wave first (k13_grouped_add)                                  -> planes
 //   k13_scan     one workgroup per region: the inclusive scan of the three planes in steps of K13_TILE columns, in place (the planes
 //                hold depths afterwards), and in the same pass the region's sums, maxima, reads per class and run starts       -> reg, nseg
 //   (scan)       the run starts to segment offsets (launch_scan_i32); k13_offsets hands them and the region records to pinned memory
@@ -31,7 +31,7 @@ __device__ __forceinline__ int k13_class(const BatchView& b, const int32_t* __re
 
 // Every lane of the wave calls.  The active lanes' adds (delta = 1 or 0xffffffff) are grouped by address: one atomic per distinct
 // address and wave, none where the group's sum is 0.
-__device__ __forceinline__ void k13_wave_add(bool active, uint32_t* addr, uint32_t delta) {
+__device__ __forceinline__ void k13_grouped_add(bool active, uint32_t* addr, uint32_t delta) {
   const int lane = threadIdx.x & 63;
   unsigned long long pend = __ballot(active);
   while (pend) {   // (wave-uniform)
@@ -80,30 +80,14 @@ __global__ void __launch_bounds__(LCR_BLOCK) k13_blocks(BatchView b, const int32
     const long long s = ref_cur + ir - dr;                   // the op's first column
     const bool start = cov && pk == 2, end = gap && pk == 1;  // a run starts behind a gap, and ends where a gap begins
     const bool active = (start || end) && s < wlen;           // (a run wholly left of the window: +1 and -1 meet at column 0)
-    k13_wave_add(active, plane + (s > 0 ? s : 0), start ? 1u : 0xffffffffu);
+    k13_grouped_add(active, plane + (s > 0 ? s : 0), start ? 1u : 0xffffffffu);
     const unsigned int all = mc | mg;
     if (all) prev_kind = ((mc >> (31 - __clz((int)all))) & 1u) ? 1 : 2;
     ref_cur += __shfl(ir, rbase + 15, 64);
   }
   // the read's last run ends with the read; an end on the window's end is not written
   const bool active = live && l16 == 0 && prev_kind == 1 && ref_cur < wlen;
-  k13_wave_add(active, plane + (ref_cur > 0 ? ref_cur : 0), 0xffffffffu);
-}
-
-__device__ __forceinline__ uint32_t k13_wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t k13_wave_max32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned long long k13_wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (unsigned long long)__shfl_xor(v, d, 64);
-  return v;
+  k13_grouped_add(active, plane + (ref_cur > 0 ? ref_cur : 0), 0xffffffffu);
 }
 
 // One workgroup per region.  Step by step: four consecutive columns per thread, their running sums, the workgroup's exclusive scan of the
@@ -162,11 +146,11 @@ __global__ void __launch_bounds__(LCR_BLOCK) k13_scan(BatchView b, const int32_t
   }
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    const unsigned long long s = k13_wave_sum64(sum[k]);
-    const uint32_t m = k13_wave_max32(mx[k]), n = k13_wave_sum32(nr[k]);
+    const unsigned long long s = wave_sum_u64(sum[k]);
+    const uint32_t m = wave_max_u32(mx[k]), n = wave_sum_u32(nr[k]);
     if (lane == 0) { s_sum[k][wv] = s; s_max[k][wv] = m; s_nr[k][wv] = n; }
   }
-  starts = k13_wave_sum32(starts);
+  starts = wave_sum_u32(starts);
   if (lane == 0) s_st[wv] = starts;
   __syncthreads();
   if (tid != 0) return;

@@ -206,14 +206,11 @@ __device__ __forceinline__ int k15_present(const unsigned long long* __restrict_
 }
 
 // One workgroup per kept chain.  The region's participating rows are sorted by pos: those from the first with pos > a on cannot span and
-// are cut off by a binary search.  The phase sets of the spanning rows are visited in ascending order, one sweep over the rows each, as in
-// k6_tables: "most rows, ties to the smallest value" is a strict > against the best so far; presence is tested once per row, in the sweep
-// of its phase set.
+// are cut off by a binary search.  The spanning rows go through the four-cell sweep of k6_walk.h, as k6_tables' overlapping rows do.
 __global__ void __launch_bounds__(LCR_BLOCK) k15_tables(BatchView b, const int32_t* __restrict__ part_off, const K15Row* __restrict__ rows,
                                                          const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ chain,
                                                          int32_t n_kept, lcr_isoform* __restrict__ iso, lcr_isoform* __restrict__ host_iso) {
   __shared__ int sh_end;
-  __shared__ uint32_t sh_next, sh_found, sh_cnt[4];
   const int j = blockIdx.x, tid = threadIdx.x;
   if (j >= n_kept) return;
   const lcr_isoform rec = iso[j];
@@ -227,33 +224,13 @@ __global__ void __launch_bounds__(LCR_BLOCK) k15_tables(BatchView b, const int32
     sh_end = lo;
   }
   __syncthreads();
-  const int p_end = sh_end;
-  bool have_cur = false;
-  uint32_t cur = 0, n_sets = 0, best_ps = 0, best_tot = 0, best[4] = {0, 0, 0, 0};
-  for (;;) {   // (every value of the loop's state is the same in all threads)
-    if (tid == 0) { sh_next = 0xffffffffu; sh_found = 0; sh_cnt[0] = sh_cnt[1] = sh_cnt[2] = sh_cnt[3] = 0; }
-    __syncthreads();
-    for (int p = p0 + tid; p < p_end; p += LCR_BLOCK) {
-      const K15Row row = rows[p];
-      if ((long long)row.rend < e) continue;   // spanning: pos <= a && rend >= e
-      if (have_cur && row.ps == cur) atomicAdd(&sh_cnt[(row.hap - 1) * 2 + k15_present(keys + row.first, row.n, ch, k, a, e)], 1u);
-      if (!have_cur || row.ps > cur) { atomicMin(&sh_next, row.ps); atomicOr(&sh_found, 1u); }
-    }
-    __syncthreads();
-    const uint32_t nxt = sh_next, found = sh_found, c0 = sh_cnt[0], c1 = sh_cnt[1], c2 = sh_cnt[2], c3 = sh_cnt[3];
-    __syncthreads();
-    if (have_cur) {
-      n_sets++;
-      const uint32_t tot = c0 + c1 + c2 + c3;
-      if (tot > best_tot) { best_tot = tot; best_ps = cur; best[0] = c0; best[1] = c1; best[2] = c2; best[3] = c3; }
-    }
-    if (!found) break;
-    cur = nxt; have_cur = true;
-  }
+  const K6Cells best = sweep_phase_set_cells(
+      rows, p0, sh_end, [&](const K15Row& row) { return (long long)row.rend >= e; },   // spanning: pos <= a && rend >= e
+      [&](const K15Row& row) { return (row.hap - 1) * 2 + k15_present(keys + row.first, row.n, ch, k, a, e); });
   if (tid == 0) {
     lcr_isoform o = rec;
-    o.phase_set = best_ps; o.n_phase_sets = n_sets;
-    o.h1_absent = best[0]; o.h1_present = best[1]; o.h2_absent = best[2]; o.h2_present = best[3];
+    o.phase_set = best.ps; o.n_phase_sets = best.n_sets;
+    o.h1_absent = best.n[0]; o.h1_present = best.n[1]; o.h2_absent = best.n[2]; o.h2_present = best.n[3];
     iso[j] = o; host_iso[j] = o;
   }
 }

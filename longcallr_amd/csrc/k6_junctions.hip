@@ -121,8 +121,6 @@ __global__ void k6_compact(const unsigned long long* __restrict__ tbl_key, const
   ck[j] = tbl_key[t]; cc[j] = tbl_cnt[t]; cgr[j] = lo;
 }
 
-__device__ __forceinline__ uint8_t k6_upper(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
-
 // A kept junction's place is its rank among the region's kept keys, found by counting the smaller ones: kept junctions per region are
 // the splice sites of a gene with min_count reads each -- tens to a few hundred, next to thousands of rows -- so the quadratic count is
 // a few thousand coalesced loads per junction.  A region with more is still ordered correctly, only more slowly.
@@ -135,30 +133,18 @@ __global__ void k6_rank(BatchView b, const unsigned long long* __restrict__ ck, 
   int rank = 0;
   for (int k = lo; k < hi; k++) rank += ck[k] < key ? 1 : 0;
   const int32_t s = (int32_t)(key >> 32), l = (int32_t)(key & 0xffffffffu);
-  const long long sl = (long long)s - b.start0[g];
-  uint8_t motif = 0;
-  if (l >= 2 && sl >= 0 && sl + l <= (long long)b.len[g]) {
-    const uint8_t* __restrict__ w = b.ref + b.col_off[g];
-    const uint8_t d0 = k6_upper(w[sl]), d1 = k6_upper(w[sl + 1]), a0 = k6_upper(w[sl + l - 2]), a1 = k6_upper(w[sl + l - 1]);
-    if (d0 == 'G' && d1 == 'T' && a0 == 'A' && a1 == 'G') motif = 1;
-    else if (d0 == 'C' && d1 == 'T' && a0 == 'A' && a1 == 'C') motif = 2;
-  }
   lcr_junction o{};
-  o.region = g; o.motif = motif; o.start0 = s; o.len = l; o.n_reads = cc[j];
+  o.region = g; o.motif = splice_motif(b, g, s, l); o.start0 = s; o.len = l; o.n_reads = cc[j];
   out[lo + rank] = o;
 }
 
 // One workgroup per kept junction.  The region's participating rows are sorted by pos: those from the first with pos >= s + l on cannot
-// overlap and are cut off by a binary search.  The phase sets of the overlapping rows are visited in ascending order, one sweep over the
-// rows each: sweep k counts the four cells of the k-th smallest value and finds the next one (the first sweep only finds the smallest).
-// "Most rows, ties to the smallest value" is then a strict > against the best so far.  A region has a handful of phase sets -- one per
-// group of linked heterozygous sites --, so this is two to four sweeps; presence (a scan of the row's own keys) is tested once per row,
-// in the sweep of its phase set.
+// overlap and are cut off by a binary search.  The overlapping rows go through the four-cell sweep of k6_walk.h; presence is a scan of
+// the row's own keys.
 __global__ void __launch_bounds__(LCR_BLOCK) k6_tables(BatchView b, const int32_t* __restrict__ part_off, const K6Row* __restrict__ rows,
                                                         const unsigned long long* __restrict__ keys, int32_t n_kept,
                                                         lcr_junction* __restrict__ junc, lcr_junction* __restrict__ host_junc) {
   __shared__ int sh_end;
-  __shared__ uint32_t sh_next, sh_found, sh_cnt[4];
   const int j = blockIdx.x, tid = threadIdx.x;
   if (j >= n_kept) return;
   const lcr_junction rec = junc[j];
@@ -173,37 +159,17 @@ __global__ void __launch_bounds__(LCR_BLOCK) k6_tables(BatchView b, const int32_
     sh_end = lo;
   }
   __syncthreads();
-  const int p_end = sh_end;
-  bool have_cur = false;
-  uint32_t cur = 0, n_sets = 0, best_ps = 0, best_tot = 0, best[4] = {0, 0, 0, 0};
-  for (;;) {   // (every value of the loop's state is the same in all threads)
-    if (tid == 0) { sh_next = 0xffffffffu; sh_found = 0; sh_cnt[0] = sh_cnt[1] = sh_cnt[2] = sh_cnt[3] = 0; }
-    __syncthreads();
-    for (int p = p0 + tid; p < p_end; p += LCR_BLOCK) {
-      const K6Row row = rows[p];
-      if (!((long long)row.pos < jend && row.rend > s)) continue;   // overlap: pos < s + l && rend > s
-      if (have_cur && row.ps == cur) {
+  const K6Cells best = sweep_phase_set_cells(
+      rows, p0, sh_end, [&](const K6Row& row) { return (long long)row.pos < jend && row.rend > s; },   // overlap: pos < s + l && rend > s
+      [&](const K6Row& row) {
         int present = 0;
         for (int k = 0; k < row.n; k++) present |= keys[row.first + k] == key ? 1 : 0;
-        atomicAdd(&sh_cnt[(row.hap - 1) * 2 + present], 1u);
-      }
-      if (!have_cur || row.ps > cur) { atomicMin(&sh_next, row.ps); atomicOr(&sh_found, 1u); }
-    }
-    __syncthreads();
-    const uint32_t nxt = sh_next, found = sh_found, c0 = sh_cnt[0], c1 = sh_cnt[1], c2 = sh_cnt[2], c3 = sh_cnt[3];
-    __syncthreads();
-    if (have_cur) {
-      n_sets++;
-      const uint32_t tot = c0 + c1 + c2 + c3;
-      if (tot > best_tot) { best_tot = tot; best_ps = cur; best[0] = c0; best[1] = c1; best[2] = c2; best[3] = c3; }
-    }
-    if (!found) break;
-    cur = nxt; have_cur = true;
-  }
+        return (row.hap - 1) * 2 + present;
+      });
   if (tid == 0) {
     lcr_junction o = rec;
-    o.phase_set = best_ps; o.n_phase_sets = n_sets;
-    o.h1_absent = best[0]; o.h1_present = best[1]; o.h2_absent = best[2]; o.h2_present = best[3];
+    o.phase_set = best.ps; o.n_phase_sets = best.n_sets;
+    o.h1_absent = best.n[0]; o.h1_present = best.n[1]; o.h2_absent = best.n[2]; o.h2_present = best.n[3];
     junc[j] = o; host_junc[j] = o;
   }
 }

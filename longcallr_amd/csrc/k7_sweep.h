@@ -3,17 +3,6 @@
 #pragma once
 #include "lcr_dev.h"
 
-__device__ __forceinline__ uint32_t k7_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t k7_wave_min(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor(v, d, 64));
-  return v;
-}
-
 struct K7Pick { uint32_t ps, n_sets, h1, h2; };   // the phase set with the most counting rows (0 = none), distinct sets, its rows per haplotype
 
 // Called by every thread of one workgroup.  Over the rows [r0, r1) that `keep(r)` lets through: sweep k counts h1 / h2 of the k-th smallest
@@ -38,7 +27,7 @@ __device__ __forceinline__ K7Pick k7_sweep_phase_sets(const lcr_read_record* __r
       if (rr.phase_set == cur) { if (rr.assignment == 1) c1++; else c2++; }
       else if (rr.phase_set > cur) nxt = min(nxt, rr.phase_set);
     }
-    c1 = k7_wave_sum(c1); c2 = k7_wave_sum(c2); nxt = k7_wave_min(nxt);
+    c1 = wave_sum_u32(c1); c2 = wave_sum_u32(c2); nxt = wave_min_u32(nxt);
     if ((tid & 63) == 0) {
       if (c1) atomicAdd(&sh[1], c1);
       if (c2) atomicAdd(&sh[2], c2);

@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k8_pairs(const int32_t* __restrict_
     __syncthreads();
     int32_t nxt = INT_MAX;
     for (int r = r0 + tid; r < r1; r += LCR_BLOCK) { const int32_t k = rg[r]; if (k > cur) nxt = min(nxt, k); }
-    nxt = (int32_t)k7_wave_min((uint32_t)nxt);   // (gene indices above cur >= -1 are not negative)
+    nxt = (int32_t)wave_min_u32((uint32_t)nxt);   // (gene indices above cur >= -1 are not negative)
     if ((tid & 63) == 0 && nxt != INT_MAX) atomicMin(&sh_next, nxt);
     __syncthreads();
     const int32_t k = sh_next;

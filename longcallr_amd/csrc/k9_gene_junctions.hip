@@ -25,7 +25,7 @@
 // come from counts in read order, not from arrival.
 #include <algorithm>
 
-#include "k7_sweep.h"
+#include "k6_walk.h"
 
 namespace {
 
@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k9_pairs(const int32_t* __restrict_
     __syncthreads();
     int32_t nxt = INT_MAX;
     for (int r = r0 + tid; r < r1; r += LCR_BLOCK) { const int32_t k = gene[r]; if (part_flag[r] && k > cur) nxt = min(nxt, k); }
-    nxt = (int32_t)k7_wave_min((uint32_t)nxt);   // (a participating read's gene is not negative)
+    nxt = (int32_t)wave_min_u32((uint32_t)nxt);   // (a participating read's gene is not negative)
     if (lane == 0 && nxt != INT_MAX) atomicMin(&sh_next, nxt);
     __syncthreads();
     const int32_t k = sh_next;
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) k9_pairs(const int32_t* __restrict_
         n_rows += total;
         __syncthreads();
       }
-      occ = k7_wave_sum(occ);
+      occ = wave_sum_u32(occ);
       if (lane == 0 && occ) atomicAdd(&sh_occ, occ);
       __syncthreads();
       if (tid == 0) { pair_region[p] = g; pair_gene[p] = k; pair_row0[p] = base; pair_rows[p] = n_rows; pair_occ[p] = (int32_t)sh_occ; }
@@ -215,8 +215,6 @@ __global__ void k9_compact(const unsigned long long* __restrict__ tbl_key, const
   ck[j] = tbl_key[t]; cc[j] = tbl_cnt[t]; cp[j] = lo;
 }
 
-__device__ __forceinline__ uint8_t k9_upper(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
-
 // A kept junction's place is its rank among the pair's kept keys, found by counting the smaller ones (k6_rank's argument: tens to a few
 // hundred kept junctions per gene).  The pair's kept junctions are [koff[tbl_off[p]], koff[tbl_off[p + 1]]).
 __global__ void k9_rank(BatchView b, const unsigned long long* __restrict__ ck, const uint32_t* __restrict__ cc, const int32_t* __restrict__ cp,
@@ -230,16 +228,8 @@ __global__ void k9_rank(BatchView b, const unsigned long long* __restrict__ ck, 
   int rank = 0;
   for (int k = lo; k < hi; k++) rank += ck[k] < key ? 1 : 0;
   const int32_t s = (int32_t)(key >> 32), l = (int32_t)(key & 0xffffffffu);
-  const long long sl = (long long)s - b.start0[g];
-  uint8_t motif = 0;
-  if (l >= 2 && sl >= 0 && sl + l <= (long long)b.len[g]) {
-    const uint8_t* __restrict__ w = b.ref + b.col_off[g];
-    const uint8_t d0 = k9_upper(w[sl]), d1 = k9_upper(w[sl + 1]), a0 = k9_upper(w[sl + l - 2]), a1 = k9_upper(w[sl + l - 1]);
-    if (d0 == 'G' && d1 == 'T' && a0 == 'A' && a1 == 'G') motif = 1;
-    else if (d0 == 'C' && d1 == 'T' && a0 == 'A' && a1 == 'C') motif = 2;
-  }
   lcr_junction_gene o{};
-  o.region = g; o.motif = motif; o.start0 = s; o.len = l; o.n_reads = cc[j]; o.gene = pair_gene[p];
+  o.region = g; o.motif = splice_motif(b, g, s, l); o.start0 = s; o.len = l; o.n_reads = cc[j]; o.gene = pair_gene[p];
   out[lo + rank] = o;
   out_pair[lo + rank] = p;
 }
@@ -251,7 +241,6 @@ __global__ void __launch_bounds__(LCR_BLOCK) k9_tables(const int32_t* __restrict
                                                         const unsigned long long* __restrict__ keys, int32_t n_kept,
                                                         lcr_junction_gene* __restrict__ junc, lcr_junction_gene* __restrict__ host_junc) {
   __shared__ int sh_end;
-  __shared__ uint32_t sh_next, sh_found, sh_cnt[4];
   const int j = blockIdx.x, tid = threadIdx.x;
   if (j >= n_kept) return;
   const lcr_junction_gene rec = junc[j];
@@ -266,38 +255,19 @@ __global__ void __launch_bounds__(LCR_BLOCK) k9_tables(const int32_t* __restrict
     sh_end = lo;
   }
   __syncthreads();
-  const int p_end = sh_end;
-  bool have_cur = false;
-  uint32_t cur = 0, n_sets = 0, best_ps = 0, best_tot = 0, best[4] = {0, 0, 0, 0};
-  for (;;) {   // (every value of the loop's state is the same in all threads)
-    if (tid == 0) { sh_next = 0xffffffffu; sh_found = 0; sh_cnt[0] = sh_cnt[1] = sh_cnt[2] = sh_cnt[3] = 0; }
-    __syncthreads();
-    for (int q = p0 + tid; q < p_end; q += LCR_BLOCK) {
-      const K9Row row = rows[q];
-      if (!(row.hap & 4)) continue;                                   // not counted: no shared base with the gene's exons
-      if (!((long long)row.pos < jend && row.rend > s)) continue;     // overlap: pos < s + l && rend > s
-      if (have_cur && row.ps == cur) {
+  const K6Cells best = sweep_phase_set_cells(
+      rows, p0, sh_end,
+      // counted (a shared base with the gene's exons) and overlap: pos < s + l && rend > s
+      [&](const K9Row& row) { return (row.hap & 4) && (long long)row.pos < jend && row.rend > s; },
+      [&](const K9Row& row) {
         int present = 0;
         for (int k = 0; k < row.n; k++) present |= keys[row.first + k] == key ? 1 : 0;
-        atomicAdd(&sh_cnt[((row.hap & 3) - 1) * 2 + present], 1u);
-      }
-      if (!have_cur || row.ps > cur) { atomicMin(&sh_next, row.ps); atomicOr(&sh_found, 1u); }
-    }
-    __syncthreads();
-    const uint32_t nxt = sh_next, found = sh_found, c0 = sh_cnt[0], c1 = sh_cnt[1], c2 = sh_cnt[2], c3 = sh_cnt[3];
-    __syncthreads();
-    if (have_cur) {
-      n_sets++;
-      const uint32_t tot = c0 + c1 + c2 + c3;
-      if (tot > best_tot) { best_tot = tot; best_ps = cur; best[0] = c0; best[1] = c1; best[2] = c2; best[3] = c3; }
-    }
-    if (!found) break;
-    cur = nxt; have_cur = true;
-  }
+        return ((row.hap & 3) - 1) * 2 + present;
+      });
   if (tid == 0) {
     lcr_junction_gene o = rec;
-    o.phase_set = best_ps; o.n_phase_sets = n_sets;
-    o.h1_absent = best[0]; o.h1_present = best[1]; o.h2_absent = best[2]; o.h2_present = best[3];
+    o.phase_set = best.ps; o.n_phase_sets = best.n_sets;
+    o.h1_absent = best.n[0]; o.h1_present = best.n[1]; o.h2_absent = best.n[2]; o.h2_present = best.n[3];
     junc[j] = o; host_junc[j] = o;
   }
 }

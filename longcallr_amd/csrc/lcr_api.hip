@@ -172,10 +172,12 @@ int lcr_ctx_create(int device, lcr_ctx** out) {
   for (int k = 0; k < LCR_NTIMERS; k++)
     for (int j = 0; j < 2; j++)
       if (hipEventCreate(&c->ev[k][j]) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
-  for (hipEvent_t* e : {&c->ev_ctl, &c->ev_sv, &c->ev_cand, &c->ev_nnz, &c->ev_imp, &c->ev_junc, &c->ev_ase, &c->ev_genes, &c->ev_agene, &c->jgene.ev, &c->ajgene.ev, &c->ev_hap})
+  for (hipEvent_t* e : {&c->ev_ctl, &c->ev_sv, &c->ev_cand, &c->ev_nnz, &c->ev_imp, &c->ev_genes})
     if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
-  for (GeneJunctions* g : {&c->jgene, &c->ajgene})
-    for (hipEvent_t& e : g->ev_t) if (hipEventCreate(&e) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
+  for (CallState* st : c->post_calls()) {
+    if (hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
+    for (hipEvent_t& e : st->ev_t) if (hipEventCreate(&e) != hipSuccess) { lcr_ctx_destroy(c); return LCR_E_DEVICE; }
+  }
   *out = c;
   return LCR_OK;
 }
@@ -189,14 +191,10 @@ void lcr_ctx_destroy(lcr_ctx* c) {
   if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
   for (auto& u : c->up) if (u.ev) (void)hipEventDestroy(u.ev);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  for (hipEvent_t e : {c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp, c->ev_junc, c->ev_ase, c->ev_genes, c->ev_agene, c->ev_hap, c->ev_hap_t[0], c->ev_hap_t[1]}) if (e) (void)hipEventDestroy(e);
-  for (GeneJunctions* g : {&c->jgene, &c->ajgene}) for (hipEvent_t e : {g->ev, g->ev_t[0], g->ev_t[1]}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_nnz, c->ev_cand, c->ev_sv, c->ev_ctl, c->ev_imp, c->ev_genes}) if (e) (void)hipEventDestroy(e);
+  for (CallState* st : c->post_calls()) for (hipEvent_t e : {st->ev, st->ev_t[0], st->ev_t[1]}) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2 * lcr_ctx::UP_LANES; k++) if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
   for (hipEvent_t e : c->ev_mask_t) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {c->ev_sc, c->ev_sc_t[0], c->ev_sc_t[1]}) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {c->ev_hc, c->ev_hc_t[0], c->ev_hc_t[1]}) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {c->ev_som, c->ev_som_t[0], c->ev_som_t[1]}) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {c->ev_iso, c->ev_iso_t[0], c->ev_iso_t[1]}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_unpack_t) if (e) (void)hipEventDestroy(e);
   c->phase.release();
   for (int k = 0; k < LCR_NTIMERS; k++) for (int j = 0; j < 2; j++) if (c->ev[k][j]) (void)hipEventDestroy(c->ev[k][j]);

@@ -33,15 +33,13 @@ int lcr_ase(lcr_ctx* c, const lcr_ase_params* p, int32_t mem, int32_t n_sites, c
     int32_t* d_bad = nullptr;
     HIPCHK(c, c->h_ase_bad.dev(&d_bad));
     launch_k7_check(d_pos, d_pat, d_mat, n_sites, d_bad, s);
-    HIPCHK(c, hipEventRecord(c->ev_ase, s));
-    HIPCHK(c, hipEventSynchronize(c->ev_ase));
-    HIPCHK(c, hipGetLastError());
+    { int rc = stream_wait(c, c->ase.ev); if (rc) return rc; }
     if (*(volatile int32_t*)bad) {
       c->err = "lcr_ase: parental sites must be sorted by position without duplicates, pat and mat one of ACGT each and different";
       return LCR_E_ARG;
     }
   }
-  c->ase_valid = false;   // (from here on the last call's records are overwritten)
+  c->ase.valid = false;   // (from here on the last call's records are overwritten)
   HIPCHK(c, c->d_ase.reserve((size_t)std::max(ng, 1) * sizeof(lcr_ase_region)));
   HIPCHK(c, c->h_ase.reserve((size_t)std::max(ng, 1) * sizeof(lcr_ase_region)));
   lcr_ase_region* d_hase = nullptr;
@@ -65,18 +63,14 @@ int lcr_ase(lcr_ctx* c, const lcr_ase_params* p, int32_t mem, int32_t n_sites, c
       launch_k7_export(d_ase, ng, d_hase, s);
     }
   }
-  HIPCHK(c, hipEventRecord(c->ev_ase, s));     // lcr_get_ase waits for it
-  HIPCHK(c, hipGetLastError());
-  c->ase_ng = ng; c->ase_valid = true;
-  return LCR_OK;
+  c->ase_ng = ng;
+  return call_end(c, c->ase);     // lcr_get_ase waits for its event
 }
 
 int lcr_get_ase(lcr_ctx* c, lcr_ase_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->ase_valid) { c->err = "lcr_get_ase before lcr_ase (its records die with the phase stage's results)"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_ase));
-  HIPCHK(c, hipGetLastError());
+  if (c->stage < ST_PHASED || !c->ase.valid) { c->err = "lcr_get_ase before lcr_ase (its records die with the phase stage's results)"; return LCR_E_STATE; }
+  { int rc = call_wait(c, c->ase); if (rc) return rc; }
   out->n_regions = c->ase_ng;
   out->rec = c->ase_ng ? c->h_ase.as<lcr_ase_region>() : nullptr;
   out->dev_rec = c->ase_ng ? c->d_ase.as<lcr_ase_region>() : nullptr;

@@ -40,7 +40,7 @@ int lcr_asj_genes(lcr_ctx* c, const lcr_asj_params* p, int32_t mem, const lcr_ge
   { int rc = annotation_queue(c, g.ann, a, mem, g.h_bad, &d, &d_bad); if (rc) return rc; }
   if (n_genes > 0 || n_dna > 0) {
     launch_k10_dna_check(d_dna, n_dna, d_bad + 1, s);
-    { int rc = annotation_verdict(c, g.h_bad, g.ev, "lcr_asj_genes"); if (rc) return rc; }
+    { int rc = annotation_verdict(c, g.h_bad, g.st.ev, "lcr_asj_genes"); if (rc) return rc; }
     if (g.h_bad.as<volatile int32_t>()[1]) { c->err = "lcr_asj_genes: dna_pos0 must be ascending without duplicates"; return LCR_E_ARG; }
   }
   { int rc = gj_begin(c, g); if (rc) return rc; }   // (from here on the last call's tables are overwritten)
@@ -53,7 +53,7 @@ int lcr_asj_genes(lcr_ctx* c, const lcr_asj_params* p, int32_t mem, const lcr_ge
   HIPCHK(c, m.h_xoff.dev(&d_hxoff));
   const auto finish_empty = [&]() { no_records(g.h_off, ng, &g.n); no_records(m.h_xoff, ng, &m.nx); return gj_finish(c, g); };
   if (nr == 0 || ng == 0 || n_genes == 0) return finish_empty();   // (not at n_rows == 0: the coverage counts reads)
-  Bracket t(c, g);
+  Bracket t(c, g.st);
   // 1. K9's counts; beside them the interior blocks per participating read, their sums per pair and the exon table's segments, and the
   // coverage, which is complete here
   { int rc = gj_counts(c, g, p->min_junctions); if (rc) return rc; }
@@ -106,7 +106,7 @@ int lcr_asj_genes(lcr_ctx* c, const lcr_asj_params* p, int32_t mem, const lcr_ge
     launch_k10_emit(b, part, nblk, pr.read_pair, xtbl_off, m.x.tbl_key.as<uint64_t>(), m.x.tbl_cnt.as<uint32_t>(), s);
     { int rc = gj_keep(c, m.x, pair_off, xtbl_off, p->min_count, d_hxoff, d_ctl + 4); if (rc) return rc; }
   }
-  { int rc = stream_wait(c, g.ev); if (rc) return rc; }   // the numbers of kept junctions and exons size the records and the last kernels' grids
+  { int rc = stream_wait(c, g.st.ev); if (rc) return rc; }   // the numbers of kept junctions and exons size the records and the last kernels' grids
   const int32_t n_kept = h_ctl[2], n_xkept = n_xslots > 0 ? h_ctl[6] : 0;
   // 3. K9's tables; the exon records
   if (n_kept <= 0) no_records(g.h_off, ng, &g.n);
@@ -128,7 +128,7 @@ int lcr_asj_genes(lcr_ctx* c, const lcr_asj_params* p, int32_t mem, const lcr_ge
 
 int lcr_get_asj_genes(lcr_ctx* c, lcr_asj_gene_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->ajgene.valid) {
+  if (c->stage < ST_PHASED || !c->ajgene.st.valid) {
     c->err = "lcr_get_asj_genes before lcr_asj_genes (its tables die with the phase stage's results and with the gene assignment)";
     return LCR_E_STATE;
   }

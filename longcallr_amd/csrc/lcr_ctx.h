@@ -8,9 +8,11 @@
 // (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks;
 // lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) and lcr_hap_coverage.hip (lcr_hap_coverage,
 // lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
-// lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth.
+// lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth.  Every call behind the phase
+// stage keeps its bookkeeping in one CallState (below): lcr_ctx::post_calls() lists them for lcr_ctx_create / lcr_ctx_destroy / rewind_to.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstring>
 
 #include "lcr_dev.h"
@@ -19,6 +21,20 @@
 // How far the bound batch has come.  Every driver asks for the stage it reads (stage >= X) and moves the value with rewind_to() /
 // by assignment at its successful end: nothing else says which buffers hold what.
 enum Stage { ST_NONE, ST_LOADED, ST_PILED, ST_CALLED, ST_FRAGGED, ST_PHASED };
+
+// What every call behind the phase stage keeps beside its buffers: whether its last results belong to the phase results of the bound batch
+// (rewind_to), the event behind its last kernel, and HIP events around its kernels when timing is on (not a slot of lcr_kernel_ms,
+// include/lcr.h).  All three events live from lcr_ctx_create to lcr_ctx_destroy.  The helpers follow lcr_ctx.
+struct CallState {
+  bool valid = false;        // the getter may hand the last call's results out
+  bool timed = false;        // ev_t brackets the last call's kernels
+  hipEvent_t ev = nullptr;   // behind the call's host waits, then behind its last kernel: the getter waits for it (no timing)
+  hipEvent_t ev_t[2] = {};   // first kernel to last of the last call
+};
+
+// The per-candidate segments of the fragment matrix (col_segments.h), shared by lcr_site_counts and lcr_somatic: both run on the context's
+// stream, and nothing reads them behind a call's last kernel
+struct ColSegs { DevBuf cnt, off, seg; };   // entries per candidate (counted up, then back down); their 64-bit offsets; a word per entry, by candidate
 
 // A gene annotation's five arrays in HBM: where a call copies a host annotation (annotation_queue)
 struct AnnotationCopy { DevBuf span_s, span_e, exon_off, exon_s, exon_e; };
@@ -35,8 +51,8 @@ struct SlotTable {
 // The per-gene junction table of one call (lcr_junctions_genes.hip: the gj_* steps).  The context holds two, lcr_junctions_genes' and
 // lcr_asj_genes', so each call keeps its table across the other's.
 struct GeneJunctions {
-  bool valid = false;    // the getter: the last call's table belongs to the phase results and the gene assignment of the bound batch (rewind_to)
-  bool timed = false;    // ev_t brackets the last call's kernels
+  CallState st;          // valid: the last call's table belongs to the phase results and the gene assignment of the bound batch (rewind_to);
+                         // ev: behind the verdict's kernels, the two size waits, then the call's last kernel; ev_t: the list's kernel_ms
   int32_t n = 0, ng = 0;
   AnnotationCopy ann;
   DevBuf part, nocc, part_off, occ_off, cnt, pair_off, read_pair, row_slot, pregion, pgene, prow0, prows, pocc, tsz, tbl_off, rows, keys, jpair;
@@ -46,8 +62,6 @@ struct GeneJunctions {
   HostBuf h_ctl;           // pinned sizes: [0] participating rows, [1] occurrences, [2] kept junctions, [3] pairs; K10: [4..7] the same for blocks / exons
   HostBuf h_bad;           // pinned verdicts: [0] the annotation's; K10: [1] the DNA sites'
   int32_t *d_off = nullptr, *d_ctl = nullptr;   // h_off and h_ctl as the device sees them (gj_begin)
-  hipEvent_t ev = nullptr;      // behind the verdict's kernels, the two size waits, then the call's last kernel
-  hipEvent_t ev_t[2] = {};      // timing enabled: first kernel to last of the last call (the list's kernel_ms; no lcr_kernel_ms slot)
   K9Pairs pairs() const {
     return {read_pair.as<int32_t>(), row_slot.as<int32_t>(), pregion.as<int32_t>(), pgene.as<int32_t>(), prow0.as<int32_t>(), prows.as<int32_t>(), pocc.as<int32_t>()};
   }
@@ -195,59 +209,43 @@ struct lcr_ctx {
 
   // K11 (lcr_haplotag, in place of lcr_phase): it fills what the phase stage fills -- the candidate records, PhaseHost's pinned result blocks
   // and read records -- and owns the site arrays, the per-candidate site byte / phase set, and the site records
-  bool hap_valid = false;    // lcr_get_haplotag_sites: the last lcr_haplotag's site records belong to the phase results of the bound batch (rewind_to)
-  bool hap_pending = false;  // its kernels may be in flight: haplotag_settle waits for ev_hap and copies the candidate mirror into h_cand
-  bool hap_timed = false;    // ev_hap_t brackets the last call's kernels
+  CallState hap;             // lcr_get_haplotag_sites; ev: behind the sites' check, then behind the call's last kernel
+  bool hap_pending = false;  // its kernels may be in flight: haplotag_settle waits for hap.ev and copies the candidate mirror into h_cand
   int32_t hap_ncand = 0;
   DevBuf ht_pos, ht_h1, ht_h2, ht_ps, ht_site, ht_site_ps, d_hsite;   // host sites copied to HBM; a byte and a word per candidate; the records
   HostBuf h_hsite, h_hap_bad;            // pinned: the site records; the verdict on the sites
-  hipEvent_t ev_hap = nullptr;           // behind the sites' check, then behind the call's last kernel
-  hipEvent_t ev_hap_t[2] = {};           // timing enabled: around the kernels behind the check, created on first use
 
   // K6 (lcr_junctions): scratch and results of its own -- no other stage or getter reads them
-  bool junc_valid = false;   // lcr_get_junctions: the last lcr_junctions' table belongs to the phase results of the bound batch (rewind_to)
+  CallState junc;            // lcr_get_junctions (timed by LCR_K_JUNCTIONS: ev_t is not used)
   int32_t junc_n = 0, junc_ng = 0;
   DevBuf j_part, j_npair, j_part_off, j_pair_off, j_tsz, j_tbl_off, j_rows, j_keys, j_tbl_key, j_tbl_cnt, j_flag, j_koff, j_ck, j_cc, j_cg, j_off, d_junc;
   HostBuf h_junc_ctl, h_junc, h_junc_off;   // pinned: {participating rows, pairs, kept junctions}; the records; their offsets per region
-  hipEvent_t ev_junc = nullptr;             // behind the stage's last kernel
 
   // K7 (lcr_ase): scratch and results of its own -- no other stage or getter reads them
-  bool ase_valid = false;    // lcr_get_ase: the last lcr_ase's records belong to the phase results of the bound batch (rewind_to)
+  CallState ase;             // lcr_get_ase; ev: behind the sites' check, then behind the call's last kernel (timed by LCR_K_ASE: ev_t is not used)
   int32_t ase_ng = 0;
   DevBuf a_pos, a_pat, a_mat, a_tag, a_site, d_ase;   // host sites copied to HBM; a word per row, a byte per candidate; the records
   HostBuf h_ase, h_ase_bad;                            // pinned: the records; the verdict on the parental sites
-  hipEvent_t ev_ase = nullptr;                         // behind the sites' check, then behind the call's last kernel
 
-  // K12 (lcr_site_counts): scratch and results of its own -- no other stage or getter reads them
-  bool sc_valid = false;     // lcr_get_site_counts: the last lcr_site_counts' records belong to the phase results of the bound batch (rewind_to)
-  bool sc_timed = false;     // ev_sc_t brackets the last call's kernels
+  // K12 (lcr_site_counts) and K14 (lcr_somatic): the segments they share; results of their own -- no other stage or getter reads them
+  ColSegs colsegs;
+  CallState sc;              // lcr_get_site_counts
   int32_t sc_ncand = 0;
-  DevBuf sc_cnt, sc_off, sc_seg, d_sc;   // entries per candidate (counted up, then back down); their 64-bit offsets; a word per entry, by candidate; the records
-  HostBuf h_sc;                          // pinned: the records
-  hipEvent_t ev_sc = nullptr;            // behind the call's last kernel; created on first use
-  hipEvent_t ev_sc_t[2] = {};            // timing enabled: around the call's kernels, created on first use
+  DevBuf d_sc;               // the records
+  HostBuf h_sc;              // pinned: the records
+  CallState som;             // lcr_get_somatic
+  int32_t som_ncand = 0;
+  DevBuf d_som;              // the records
+  HostBuf h_som;             // pinned: the records
 
   // K13 (lcr_hap_coverage): scratch and results of its own -- no other stage or getter reads them
-  bool hc_valid = false;     // lcr_get_hap_coverage: the last lcr_hap_coverage's records belong to the phase results of the bound batch (rewind_to)
-  bool hc_timed = false;     // ev_hc_t brackets the last call's kernels
+  CallState hc;              // lcr_get_hap_coverage; ev: behind the count pass, then behind the call's last kernel
   int32_t hc_ng = 0, hc_n = 0;
   DevBuf hc_planes, hc_nseg, hc_off, hc_send, d_hc_seg, d_hc_reg;   // three u32 planes (differences, then depths); run starts per region; their offsets; a segment's end column; the records
   HostBuf h_hc_seg, h_hc_off, h_hc_reg;   // pinned: the segments; their offsets per region; the region records
-  hipEvent_t ev_hc = nullptr;             // behind the count pass, then behind the call's last kernel; created on first use
-  hipEvent_t ev_hc_t[2] = {};             // timing enabled: around the call's kernels, created on first use
-
-  // K14 (lcr_somatic): scratch and results of its own -- no other stage or getter reads them
-  bool som_valid = false;    // lcr_get_somatic: the last lcr_somatic's records belong to the phase results of the bound batch (rewind_to)
-  bool som_timed = false;    // ev_som_t brackets the last call's kernels
-  int32_t som_ncand = 0;
-  DevBuf som_cnt, som_off, som_seg, d_som;   // entries per candidate (counted up, then back down); their 64-bit offsets; a word per entry, by candidate; the records
-  HostBuf h_som;                             // pinned: the records
-  hipEvent_t ev_som = nullptr;               // behind the call's last kernel; created on first use
-  hipEvent_t ev_som_t[2] = {};               // timing enabled: around the call's kernels, created on first use
 
   // K15 (lcr_isoforms): scratch and results of its own -- no other stage or getter reads them
-  bool iso_valid = false;    // lcr_get_isoforms: the last lcr_isoforms' records belong to the phase results of the bound batch (rewind_to)
-  bool iso_timed = false;    // ev_iso_t brackets the last call's kernels
+  CallState iso;             // lcr_get_isoforms; ev: behind the two size waits, then behind the call's last kernel
   int32_t iso_ng = 0, iso_n = 0, iso_nchain = 0, iso_nrows = 0;
   int dbg_iso_hash_bits = 64;   // lcr_debug_set("iso_hash_bits"): the low bits of a chain's hash that route it; identity never depends on them
   DevBuf iso_part, iso_npair, iso_part_off, iso_pair_off, iso_tsz, iso_tbl_off;   // per read: participates, junctions, their running sums; per region: its table segment
@@ -256,8 +254,6 @@ struct lcr_ctx {
   DevBuf iso_off, iso_pbase, iso_cslot, iso_crank;                                // per region: kept chains / pool entries in front; per kept slot: its slot, its record
   DevBuf d_iso, d_iso_chain, d_iso_row;                                           // the records, the pool, row_isoform
   HostBuf h_iso_ctl, h_iso, h_iso_off, h_iso_chain, h_iso_row;   // pinned: {participating rows, pairs, kept chains, pool entries}; the four outputs
-  hipEvent_t ev_iso = nullptr;            // behind the two size waits, then behind the call's last kernel; created on first use
-  hipEvent_t ev_iso_t[2] = {};            // timing enabled: around the call's kernels, created on first use
 
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
@@ -266,16 +262,18 @@ struct lcr_ctx {
   DevBuf g_pmax, d_gene, d_gene_ov;        // running maximum of the spans' ends; the result
   HostBuf h_gene, h_gene_ov, h_gene_bad;   // pinned: the result; the verdict on the annotation
   hipEvent_t ev_genes = nullptr;           // behind the annotation's check, then behind the copies of the result
-  bool agene_valid = false;  // lcr_get_ase_genes: the last lcr_ase_genes' records belong to the phase results and the gene assignment of the bound batch
+  CallState agene;           // lcr_get_ase_genes: the records belong to the phase results and the gene assignment of the bound batch (timed by LCR_K_ASE_GENES)
   int32_t agene_ng = 0, agene_n = 0;
   DevBuf ag_pos, ag_pat, ag_mat, ag_cnt, ag_off, ag_tag, ag_site, ag_site_ps, d_agene;
   HostBuf h_agene, h_agene_off, h_agene_ctl, h_agene_bad;   // pinned: the records; their offsets per region; the number of pairs; the verdict on the parental sites
-  hipEvent_t ev_agene = nullptr;
 
   // K9 (lcr_junctions_genes) and K10 (lcr_asj_genes): one per-gene junction table each (GeneJunctions: the same steps fill both), and beside
   // K10's what its other modes add (AsjModes) -- scratch and results of their own, no other stage or getter reads them, each other's included
   GeneJunctions jgene, ajgene;
   AsjModes asj;
+
+  // every call behind the phase stage: their events are created and destroyed, and their results invalidated, through this list
+  std::array<CallState*, 10> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &jgene.st, &ajgene.st}; }
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;
@@ -309,16 +307,8 @@ inline void rewind_to(lcr_ctx* c, Stage to) {
     c->cand_used = false;      // the records lcr_phase rewrote are replaced by the next candidate stage
   }
   if (to < ST_FRAGGED) c->ds_rows_set = false;   // a sample names the rows of ONE fragment stage
-  if (to < ST_PHASED) c->junc_valid = false;     // the junction table counts the rows of ONE phase stage
-  if (to < ST_PHASED) c->ase_valid = false;      // ... and so do the haplotype / parent-of-origin counts
-  if (to < ST_PHASED) c->agene_valid = false;    // ... per region and per (region, gene) pair
-  if (to < ST_PHASED) c->hap_valid = false;      // lcr_haplotag's site records go with the phase results they describe
-  if (to < ST_PHASED) c->jgene.valid = c->ajgene.valid = false;   // ... and the per-gene junction tables
-  if (to < ST_PHASED) c->sc_valid = false;       // ... and the per-site allele x haplotype counts
-  if (to < ST_PHASED) c->hc_valid = false;       // ... and the per-haplotype coverage segments
-  if (to < ST_PHASED) c->som_valid = false;      // ... and the per-site somatic records
-  if (to < ST_PHASED) c->iso_valid = false;      // ... and the haplotype x intron-chain records
-  if (to < ST_LOADED) c->genes_valid = c->agene_valid = c->jgene.valid = c->ajgene.valid = false;   // read -> gene names the reads of ONE bound batch
+  if (to < ST_PHASED) for (CallState* st : c->post_calls()) st->valid = false;   // every table and record list behind the phase stage counts the rows of ONE phase stage
+  if (to < ST_LOADED) c->genes_valid = false;    // read -> gene names the reads of ONE bound batch (what was built on it -- agene, jgene, ajgene -- went above)
   // Deliberately not here: res_valid / res_ng (the last phase's results outlive load and pileup of the next batch and die at the next
   // candidate stage: cand_begin), sv_cap_guess (a size guess, good across batches), phase_slot (names the batch of a stage in flight),
   // cand_pending / nnz_pending (hand-overs of copies in flight: their settle functions are only reached through a valid stage), and
@@ -382,6 +372,38 @@ inline int stream_wait(lcr_ctx* c, hipEvent_t ev) {
   return LCR_OK;
 }
 
+// The bookkeeping of a call behind the phase stage (CallState).  A driver clears valid where it begins to overwrite the last call's results.
+// Bracket: the timing events around the call's kernels, closed before call_end.  call_end: the event the getter waits for; valid.  call_wait: the
+// getter's wait.  call_ms: the body of lcr_<call>_ms.
+struct Bracket {
+  lcr_ctx* c; CallState& st;
+  Bracket(lcr_ctx* c_, CallState& st_) : c(c_), st(st_) { if (c->timing) (void)hipEventRecord(st.ev_t[0], c->stream); }
+  ~Bracket() { if (c->timing) { (void)hipEventRecord(st.ev_t[1], c->stream); st.timed = true; } }
+};
+inline int call_end(lcr_ctx* c, CallState& st) {
+  HIPCHK(c, hipEventRecord(st.ev, c->stream));
+  HIPCHK(c, hipGetLastError());
+  st.valid = true;
+  return LCR_OK;
+}
+inline int call_wait(lcr_ctx* c, CallState& st) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(st.ev));
+  HIPCHK(c, hipGetLastError());
+  return LCR_OK;
+}
+inline int call_ms(lcr_ctx* c, CallState& st, const char* fn_ms, const char* fn, float* ms) {
+  if (!c->timing || !st.timed) { c->err = std::string(fn_ms) + ": no " + fn + " with timing enabled"; return LCR_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(st.ev_t[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, st.ev_t[0], st.ev_t[1]));
+  return LCR_OK;
+}
+
+// The per-candidate segments of the bound batch's fragment matrix, queued for n_cand > 0 candidates (lcr_site_counts.hip): reserve, clear,
+// count, scan -> the counters (to be counted back down by the caller's fill), the 64-bit offsets, the words' buffer
+int colseg_queue(lcr_ctx* c, int32_t n_cand, uint32_t** cnt, int64_t** off, uint64_t** seg);
+
 // A gene annotation on its way to the kernels (lcr_genes.hip; lcr_assign_genes, lcr_junctions_genes, lcr_asj_genes).  annotation_queue:
 // copied (host) or read in place (device) -> *d, and k8_check queued on it into word 0 of the pinned verdict block, whose two words are
 // zeroed here (-> *d_bad, the block as the device sees it; no kernel for an annotation without genes).  The caller queues what else
@@ -390,12 +412,8 @@ int annotation_queue(lcr_ctx* c, AnnotationCopy& to, const lcr_gene_annotation* 
 int annotation_verdict(lcr_ctx* c, const HostBuf& h_bad, hipEvent_t ev, const char* fn);
 
 // The steps that fill a GeneJunctions, in the order of their launches (lcr_junctions_genes.hip).  lcr_junctions_genes is these and nothing
-// else; lcr_asj_genes queues K10's kernels between them.  The host waits twice in between: gj_wait_counts and a stream_wait.
-struct Bracket {   // HIP events around a call's kernels when timing is on: not a slot of lcr_kernel_ms (include/lcr.h)
-  lcr_ctx* c; GeneJunctions& g;
-  Bracket(lcr_ctx* c_, GeneJunctions& g_) : c(c_), g(g_) { if (c->timing) (void)hipEventRecord(g.ev_t[0], c->stream); }
-  ~Bracket() { if (c->timing) { (void)hipEventRecord(g.ev_t[1], c->stream); g.timed = true; } }
-};
+// else; lcr_asj_genes queues K10's kernels between them.  The host waits twice in between: gj_wait_counts and a stream_wait.  Their
+// kernels stand inside a Bracket on g.st.
 int gj_begin(lcr_ctx* c, GeneJunctions& g);   // from here on the last table is overwritten: valid = false, the pinned blocks reserved and quiet, h_ctl zeroed
 int gj_counts(lcr_ctx* c, GeneJunctions& g, uint32_t min_junctions);   // junctions per read, participating reads, the pairs, their table segments -> h_ctl[0], [1], [3]
 int gj_wait_counts(lcr_ctx* c, GeneJunctions& g, const char* fn, bool* empty);   // the first wait -> no participating row or no occurrence; LCR_E_ARG beyond 2^28 of them
@@ -407,17 +425,15 @@ void no_records(const HostBuf& h_off, int32_t ng, int32_t* n);         // a tabl
 int gj_finish(lcr_ctx* c, GeneJunctions& g);                           // the event the getter waits for; valid
 template <class List>   // lcr_junction_gene_list, lcr_asj_gene_list: the getter's wait, the fields both lists have, kernel_ms
 int gj_get(lcr_ctx* c, GeneJunctions& g, List* out) {
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(g.ev));
-  HIPCHK(c, hipGetLastError());
+  { int rc = call_wait(c, g.st); if (rc) return rc; }
   out->n_regions = g.ng; out->n_junctions = g.n;
   out->junc = g.n ? g.h_junc.as<lcr_junction_gene>() : nullptr;
   out->junc_region_off = g.h_off.as<int32_t>();
   out->dev_junc = g.n ? g.d_junc.as<lcr_junction_gene>() : nullptr;
   out->kernel_ms = -1.f;
-  if (c->timing && g.timed) {
-    HIPCHK(c, hipEventSynchronize(g.ev_t[1]));
-    HIPCHK(c, hipEventElapsedTime(&out->kernel_ms, g.ev_t[0], g.ev_t[1]));
+  if (c->timing && g.st.timed) {
+    HIPCHK(c, hipEventSynchronize(g.st.ev_t[1]));
+    HIPCHK(c, hipEventElapsedTime(&out->kernel_ms, g.st.ev_t[0], g.st.ev_t[1]));
   }
   return LCR_OK;
 }

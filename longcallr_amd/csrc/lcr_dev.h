@@ -355,21 +355,21 @@ void launch_k11_rows(int32_t n_rows, const int64_t* row_ptr, const int32_t* col,
 void launch_k11_finish(lcr_candidate* cand, int32_t n_cand, const uint8_t* site, const lcr_haplotag_site* acc, lcr_candidate* host_cand /* pinned */,
                        lcr_haplotag_site* host_acc /* pinned */, hipStream_t s);
 
-// k12_site_counts.hip: allele x haplotype counts per candidate over the fragment matrix (lcr_site_counts)
-void launch_k12_count(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, int32_t n_cand, uint32_t* cnt /* n_cand, zeroed */, hipStream_t s);
+// k12_site_counts.hip: allele x haplotype counts per candidate over the fragment matrix (lcr_site_counts).  The per-candidate segments
+// (col_segments.h) are shared with k14_somatic.hip: launch_colseg_count and launch_scan_i32_to_i64 size them, each unit's fill orders them
+void launch_colseg_count(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, int32_t n_cand, uint32_t* cnt /* n_cand, zeroed */, hipStream_t s);
 void launch_k12_fill(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const lcr_read_record* rec, uint32_t min_baseq,
-                     int32_t n_cand, uint32_t* cnt /* k12_count's: counted back down to 0 */, const int64_t* off /* n_cand + 1 */, uint64_t* seg /* nnz */, hipStream_t s);
+                     int32_t n_cand, uint32_t* cnt /* launch_colseg_count's: counted back down to 0 */, const int64_t* off /* n_cand + 1 */, uint64_t* seg /* nnz */, hipStream_t s);
 void launch_k12_sites(const lcr_candidate* cand, int32_t n_cand, const int64_t* off, const uint64_t* seg, lcr_site_count* out,
                       lcr_site_count* host_out /* pinned (device pointer) */, hipStream_t s);
 
-// k14_somatic.hip: reference / heterozygous / somatic per haplotype at every candidate (lcr_somatic); the entry counts and offsets are
-// launch_k12_count's and launch_scan_i32_to_i64's
+// k14_somatic.hip: reference / heterozygous / somatic per haplotype at every candidate (lcr_somatic), over the same segments
 struct K14Tables {
   int64_t tab[4 * 31];   // fe, f1e, fs_ref, fs_alt by q: llround(log10(x) * 2^40) (include/lcr.h); 992 bytes, a kernel argument
   int64_t prior[3];      // ref, het, som
 };
 void launch_k14_fill(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, const lcr_read_record* rec, const lcr_candidate* cand,
-                     int32_t n_cand, uint32_t* cnt /* launch_k12_count's: counted back down to 0 */, const int64_t* off /* n_cand + 1 */, uint64_t* seg /* nnz */, hipStream_t s);
+                     int32_t n_cand, uint32_t* cnt /* launch_colseg_count's: counted back down to 0 */, const int64_t* off /* n_cand + 1 */, uint64_t* seg /* nnz */, hipStream_t s);
 void launch_k14_sites(const lcr_candidate* cand, int32_t n_cand, const int64_t* off, const uint64_t* seg, const K14Tables& t, uint32_t min_baseq,
                       lcr_somatic_site* out, lcr_somatic_site* host_out /* pinned (device pointer) */, hipStream_t s);
 
@@ -524,6 +524,28 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
   v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
+  return v;
+}
+
+// wave64 reductions by xor shuffles: every lane gets the result.  (A 64-bit shuffle is two 32-bit ones; the adds wrap as unsigned.)
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor(v, d, 64));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d, 64));
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += (unsigned long long)__shfl_xor(v, d, 64);
   return v;
 }
 

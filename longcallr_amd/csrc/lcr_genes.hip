@@ -54,8 +54,8 @@ int lcr_assign_genes(lcr_ctx* c, int32_t mem, const lcr_gene_annotation* a) {
     { int rc = annotation_verdict(c, c->h_gene_bad, c->ev_genes, "lcr_assign_genes"); if (rc) return rc; }
   }
   c->genes_valid = false;   // (from here on the last call's result is overwritten)
-  c->agene_valid = false;   // (... and the pair records of lcr_ase_genes counted the rows of that assignment)
-  c->jgene.valid = c->ajgene.valid = false;   // (... and so did the junction tables of lcr_junctions_genes and lcr_asj_genes)
+  c->agene.valid = false;   // (... and the pair records of lcr_ase_genes counted the rows of that assignment)
+  c->jgene.st.valid = c->ajgene.st.valid = false;   // (... and so did the junction tables of lcr_junctions_genes and lcr_asj_genes)
   const size_t n1 = (size_t)std::max(nr, 1);
   HIPCHK(c, c->d_gene.reserve(n1 * 4)); HIPCHK(c, c->d_gene_ov.reserve(n1 * 4));
   HIPCHK(c, c->h_gene.reserve(n1 * 4)); HIPCHK(c, c->h_gene_ov.reserve(n1 * 4));
@@ -116,15 +116,13 @@ int lcr_ase_genes(lcr_ctx* c, const lcr_ase_params* p, int32_t mem, int32_t n_si
     int32_t* d_bad = nullptr;
     HIPCHK(c, c->h_agene_bad.dev(&d_bad));
     launch_k7_check(d_pos, d_pat, d_mat, n_sites, d_bad, s);
-    HIPCHK(c, hipEventRecord(c->ev_agene, s));
-    HIPCHK(c, hipEventSynchronize(c->ev_agene));
-    HIPCHK(c, hipGetLastError());
+    { int rc = stream_wait(c, c->agene.ev); if (rc) return rc; }
     if (*(volatile int32_t*)bad) {
       c->err = "lcr_ase_genes: parental sites must be sorted by position without duplicates, pat and mat one of ACGT each and different";
       return LCR_E_ARG;
     }
   }
-  c->agene_valid = false;   // (from here on the last call's records are overwritten)
+  c->agene.valid = false;   // (from here on the last call's records are overwritten)
   const lcr_read_record* rec = c->phase.d_read_rec.as<lcr_read_record>();
   const int32_t* rro = c->row_region_off.as<int32_t>();
   const int32_t* gene = c->d_gene.as<int32_t>();
@@ -136,16 +134,14 @@ int lcr_ase_genes(lcr_ctx* c, const lcr_ase_params* p, int32_t mem, int32_t n_si
   HIPCHK(c, c->h_agene_ctl.dev(&d_ctl));
   HIPCHK(c, c->h_agene_off.dev(&d_hoff));
   h_ctl[0] = 0;
-  if (ng == 0) { h_off[0] = 0; c->agene_n = 0; c->agene_ng = 0; c->agene_valid = true; HIPCHK(c, hipEventRecord(c->ev_agene, s)); return LCR_OK; }
+  if (ng == 0) { h_off[0] = 0; c->agene_n = 0; c->agene_ng = 0; c->agene.valid = true; HIPCHK(c, hipEventRecord(c->agene.ev, s)); return LCR_OK; }
   int32_t* pair_off = c->ag_off.as<int32_t>();
   Timer t(c, LCR_K_ASE_GENES);
   // 1. pairs per region, their offsets; the host sizes the records from their number (the call's one wait beside the sites' verdict)
   launch_k8_pair_count(b, rro, rec, gene, c->ag_cnt.as<int32_t>(), s);
   launch_scan_i32(c->scan_tmp, c->ag_cnt.as<int32_t>(), pair_off, ng, pair_off + ng, s);
   launch_k8_pair_offsets(pair_off, ng, d_hoff, d_ctl, s);
-  HIPCHK(c, hipEventRecord(c->ev_agene, s));
-  HIPCHK(c, hipEventSynchronize(c->ev_agene));
-  HIPCHK(c, hipGetLastError());
+  { int rc = stream_wait(c, c->agene.ev); if (rc) return rc; }
   const int32_t n_pairs = h_ctl[0];
   if (n_pairs > (1 << 28)) { c->err = "lcr_ase_genes: more than 2^28 (region, gene) pairs in one batch; split it"; return LCR_E_ARG; }
   // 2. the records: to HBM and, by the call's last kernel, to pinned host memory
@@ -169,21 +165,17 @@ int lcr_ase_genes(lcr_ctx* c, const lcr_ase_params* p, int32_t mem, int32_t n_si
       launch_k8_export(d_rec, n_pairs, d_hrec, s);
     }
   }
-  HIPCHK(c, hipEventRecord(c->ev_agene, s));     // lcr_get_ase_genes waits for it
-  HIPCHK(c, hipGetLastError());
-  c->agene_n = n_pairs; c->agene_ng = ng; c->agene_valid = true;
-  return LCR_OK;
+  c->agene_n = n_pairs; c->agene_ng = ng;
+  return call_end(c, c->agene);     // lcr_get_ase_genes waits for its event
 }
 
 int lcr_get_ase_genes(lcr_ctx* c, lcr_ase_gene_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->agene_valid) {
+  if (c->stage < ST_PHASED || !c->agene.valid) {
     c->err = "lcr_get_ase_genes before lcr_ase_genes (its records die with the phase stage's results and with the gene assignment)";
     return LCR_E_STATE;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_agene));
-  HIPCHK(c, hipGetLastError());
+  { int rc = call_wait(c, c->agene); if (rc) return rc; }
   out->n_regions = c->agene_ng; out->n_pairs = c->agene_n;
   out->rec = c->agene_n ? c->h_agene.as<lcr_ase_gene>() : nullptr;
   out->pair_region_off = c->h_agene_off.as<int32_t>();

@@ -17,9 +17,7 @@ int lcr_hap_coverage(lcr_ctx* c) {
   const int ng = b.n_regions;
   const int64_t n_cols = c->n_cols;
   hipStream_t s = c->stream;
-  if (!c->ev_hc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_hc, hipEventDisableTiming));
-  if (c->timing && !c->ev_hc_t[0]) { HIPCHK(c, hipEventCreate(&c->ev_hc_t[0])); HIPCHK(c, hipEventCreate(&c->ev_hc_t[1])); }
-  c->hc_valid = false;   // (from here on the last call's records are overwritten)
+  c->hc.valid = false;   // (from here on the last call's records are overwritten)
   const size_t ng1 = (size_t)std::max(ng, 1);
   HIPCHK(c, c->hc_planes.reserve((size_t)std::max<int64_t>(n_cols, 1) * 12));
   HIPCHK(c, c->hc_nseg.reserve(ng1 * 4));
@@ -32,9 +30,8 @@ int lcr_hap_coverage(lcr_ctx* c) {
   lcr_hap_cov_region* d_hreg = nullptr;
   HIPCHK(c, c->h_hc_off.dev(&d_hoff));
   HIPCHK(c, c->h_hc_reg.dev(&d_hreg));
-  if (c->timing) HIPCHK(c, hipEventRecord(c->ev_hc_t[0], s));
   int32_t n_seg = 0;
-  if (ng > 0) {
+  if (Bracket t(c, c->hc); ng > 0) {
     uint32_t* planes = c->hc_planes.as<uint32_t>();
     int32_t* off = c->hc_off.as<int32_t>();
     const int32_t* rro = c->row_region_off.as<int32_t>();
@@ -45,9 +42,7 @@ int lcr_hap_coverage(lcr_ctx* c) {
     launch_k13_scan(b, rro, rec, n_cols, planes, c->d_hc_reg.as<lcr_hap_cov_region>(), c->hc_nseg.as<int32_t>(), s);
     launch_scan_i32(c->scan_tmp, c->hc_nseg.as<int32_t>(), off, ng, off + ng, s);
     launch_k13_offsets(ng, off, c->d_hc_reg.as<lcr_hap_cov_region>(), d_hoff, d_hreg, s);
-    HIPCHK(c, hipEventRecord(c->ev_hc, s));
-    HIPCHK(c, hipEventSynchronize(c->ev_hc));   // the number of segments sizes the records
-    HIPCHK(c, hipGetLastError());
+    { int rc = stream_wait(c, c->hc.ev); if (rc) return rc; }   // the number of segments sizes the records
     n_seg = h_off[ng];
     for (int g = 0; g < ng; g++)
       if (h_off[g + 1] < h_off[g]) { c->err = "lcr_hap_coverage: more than 2^31 - 1 segments in one batch; split it"; return LCR_E_ARG; }
@@ -64,19 +59,14 @@ int lcr_hap_coverage(lcr_ctx* c) {
   } else {
     h_off[0] = 0;
   }
-  if (c->timing) { HIPCHK(c, hipEventRecord(c->ev_hc_t[1], s)); c->hc_timed = true; }
-  HIPCHK(c, hipEventRecord(c->ev_hc, s));     // lcr_get_hap_coverage waits for it
-  HIPCHK(c, hipGetLastError());
-  c->hc_ng = ng; c->hc_n = n_seg; c->hc_valid = true;
-  return LCR_OK;
+  c->hc_ng = ng; c->hc_n = n_seg;
+  return call_end(c, c->hc);     // lcr_get_hap_coverage waits for its event
 }
 
 int lcr_get_hap_coverage(lcr_ctx* c, lcr_hap_cov_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->hc_valid) { c->err = "lcr_get_hap_coverage before lcr_hap_coverage (its records die with the phase results)"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_hc));
-  HIPCHK(c, hipGetLastError());
+  if (c->stage < ST_PHASED || !c->hc.valid) { c->err = "lcr_get_hap_coverage before lcr_hap_coverage (its records die with the phase results)"; return LCR_E_STATE; }
+  { int rc = call_wait(c, c->hc); if (rc) return rc; }
   out->n_regions = c->hc_ng; out->n_segments = c->hc_n;
   out->seg = c->hc_n ? c->h_hc_seg.as<lcr_hap_cov_segment>() : nullptr;
   out->seg_region_off = c->h_hc_off.as<int32_t>();
@@ -88,11 +78,7 @@ int lcr_get_hap_coverage(lcr_ctx* c, lcr_hap_cov_list* out) {
 
 int lcr_hap_coverage_ms(lcr_ctx* c, float* ms) {
   if (!c || !ms) return LCR_E_ARG;
-  if (!c->timing || !c->hc_timed) { c->err = "lcr_hap_coverage_ms: no lcr_hap_coverage with timing enabled"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_hc_t[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->ev_hc_t[0], c->ev_hc_t[1]));
-  return LCR_OK;
+  return call_ms(c, c->hc, "lcr_hap_coverage_ms", "lcr_hap_coverage", ms);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 int haplotag_settle(lcr_ctx* c) {
   if (!c->hap_pending) return LCR_OK;
   c->hap_pending = false;
-  HIPCHK(c, hipEventSynchronize(c->ev_hap));
+  HIPCHK(c, hipEventSynchronize(c->hap.ev));
   HIPCHK(c, hipGetLastError());
   if ((int32_t)c->h_cand.size() == c->hap_ncand && c->hap_ncand > 0)
     memcpy(c->h_cand.data(), c->phase.h_cand_obj.p, (size_t)c->hap_ncand * sizeof(lcr_candidate));
@@ -49,7 +49,7 @@ int lcr_haplotag(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t n_sites, 
     int32_t* d_bad = nullptr;
     HIPCHK(c, c->h_hap_bad.dev(&d_bad));
     launch_k11_check(st, d_bad, s);
-    { int rc = stream_wait(c, c->ev_hap); if (rc) return rc; }
+    { int rc = stream_wait(c, c->hap.ev); if (rc) return rc; }
     if (*(volatile int32_t*)bad) {
       c->err = "lcr_haplotag: sites must be sorted by position without duplicates, h1 and h2 one of ACGT each and different, phase_set non-zero";
       return LCR_E_ARG;
@@ -67,21 +67,20 @@ int lcr_haplotag(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t n_sites, 
   HIPCHK(c, c->d_hsite.reserve(nc1 * sizeof(lcr_haplotag_site))); HIPCHK(c, c->h_hsite.reserve(nc1 * sizeof(lcr_haplotag_site)));
   uint8_t* d_res = nullptr; lcr_candidate* d_hc = nullptr; lcr_haplotag_site* d_hs = nullptr;
   HIPCHK(c, ph.h_res.dev(&d_res)); HIPCHK(c, ph.h_cand_obj.dev(&d_hc)); HIPCHK(c, c->h_hsite.dev(&d_hs));
-  if (c->timing && !c->ev_hap_t[0]) { HIPCHK(c, hipEventCreate(&c->ev_hap_t[0])); HIPCHK(c, hipEventCreate(&c->ev_hap_t[1])); }
   // from here on the candidate records and the last result blocks are rewritten
   c->cand_used = true;
-  c->hap_valid = false;
+  c->hap.valid = false;
   c->ds_rows_set = false;   // (a sample given for "the next lcr_phase" is not kept for a later one)
   lcr_candidate* cand = c->d_cand.as<lcr_candidate>();
   const K11Rows rows{(int8_t*)(d_res + res_tag), d_res + res_asg, (uint32_t*)(d_res + res_ps), ph.d_read_rec.as<uint32_t>()};
-  if (c->timing) HIPCHK(c, hipEventRecord(c->ev_hap_t[0], s));
-  launch_k11_sites(cand, n_cand, st, c->ht_site.as<uint8_t>(), c->ht_site_ps.as<uint32_t>(), c->d_hsite.as<lcr_haplotag_site>(), s);
-  launch_k11_rows(n_rows, c->row_ptr.as<int64_t>(), c->col.as<int32_t>(), c->val.as<uint8_t>(), c->ht_site.as<uint8_t>(), c->ht_site_ps.as<uint32_t>(),
-                  phase_lut_dev(), p->min_linkers, p->read_assign_cutoff, rows, c->d_hsite.as<lcr_haplotag_site>(), s);
-  launch_k11_finish(cand, n_cand, c->ht_site.as<uint8_t>(), c->d_hsite.as<lcr_haplotag_site>(), d_hc, d_hs, s);
-  if (c->timing) { HIPCHK(c, hipEventRecord(c->ev_hap_t[1], s)); c->hap_timed = true; }
-  HIPCHK(c, hipEventRecord(c->ev_hap, s));   // haplotag_settle and lcr_get_haplotag_sites wait for it
-  HIPCHK(c, hipGetLastError());
+  {
+    Bracket t(c, c->hap);
+    launch_k11_sites(cand, n_cand, st, c->ht_site.as<uint8_t>(), c->ht_site_ps.as<uint32_t>(), c->d_hsite.as<lcr_haplotag_site>(), s);
+    launch_k11_rows(n_rows, c->row_ptr.as<int64_t>(), c->col.as<int32_t>(), c->val.as<uint8_t>(), c->ht_site.as<uint8_t>(), c->ht_site_ps.as<uint32_t>(),
+                    phase_lut_dev(), p->min_linkers, p->read_assign_cutoff, rows, c->d_hsite.as<lcr_haplotag_site>(), s);
+    launch_k11_finish(cand, n_cand, c->ht_site.as<uint8_t>(), c->d_hsite.as<lcr_haplotag_site>(), d_hc, d_hs, s);
+  }
+  { int rc = call_end(c, c->hap); if (rc) return rc; }   // haplotag_settle and lcr_get_haplotag_sites wait for its event
   // what the getters of the phase stage hand out: the per-row results are read in place, no optimiser ran
   ph.r_haplotag = (const int8_t*)(ph.h_res.as<uint8_t>() + res_tag); ph.r_assignment = ph.h_res.as<uint8_t>() + res_asg;
   ph.r_phase_set = (const uint32_t*)(ph.h_res.as<uint8_t>() + res_ps);
@@ -89,7 +88,7 @@ int lcr_haplotag(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t n_sites, 
   memset(ph.tie_census, 0, sizeof(ph.tie_census));
   ph.chain_desc.clear();   // (lcr_get_ld_blocks: no region built blocks)
   ph.ds_applied.assign((size_t)ng, 0); ph.ds_any = false; ph.ds_ng = ng; ph.ds_nrow = n_rows;   // (lcr_get_downsample: no region was down-sampled)
-  c->hap_ncand = n_cand; c->hap_pending = true; c->hap_valid = true;
+  c->hap_ncand = n_cand; c->hap_pending = true;
   c->stage = ST_PHASED;
   c->res_valid = true; c->res_ng = ng;
   c->phase_slot = c->bound_slot >= 0 ? c->bound_slot : (c->bound_host ? -2 : -1);
@@ -98,11 +97,10 @@ int lcr_haplotag(lcr_ctx* c, const lcr_params* p, int32_t mem, int32_t n_sites, 
 
 int lcr_get_haplotag_sites(lcr_ctx* c, int32_t* n_cand, const lcr_haplotag_site** rec, const lcr_haplotag_site** dev_rec) {
   if (!c || !n_cand || !rec || !dev_rec) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->hap_valid) { c->err = "lcr_get_haplotag_sites before lcr_haplotag (its records die with the phase results)"; return LCR_E_STATE; }
+  if (c->stage < ST_PHASED || !c->hap.valid) { c->err = "lcr_get_haplotag_sites before lcr_haplotag (its records die with the phase results)"; return LCR_E_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = phase_settle(c); if (rc) return rc; }
-  HIPCHK(c, hipEventSynchronize(c->ev_hap));
-  HIPCHK(c, hipGetLastError());
+  { int rc = call_wait(c, c->hap); if (rc) return rc; }
   *n_cand = c->hap_ncand;
   *rec = c->hap_ncand ? c->h_hsite.as<lcr_haplotag_site>() : nullptr;
   *dev_rec = c->hap_ncand ? c->d_hsite.as<lcr_haplotag_site>() : nullptr;
@@ -111,11 +109,7 @@ int lcr_get_haplotag_sites(lcr_ctx* c, int32_t* n_cand, const lcr_haplotag_site*
 
 int lcr_haplotag_ms(lcr_ctx* c, float* ms) {
   if (!c || !ms) return LCR_E_ARG;
-  if (!c->timing || !c->hap_timed) { c->err = "lcr_haplotag_ms: no lcr_haplotag with timing enabled"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_hap_t[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->ev_hap_t[0], c->ev_hap_t[1]));
-  return LCR_OK;
+  return call_ms(c, c->hap, "lcr_haplotag_ms", "lcr_haplotag", ms);
 }
 
 }  // extern "C"

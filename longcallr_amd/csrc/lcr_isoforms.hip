@@ -28,7 +28,7 @@ int iso_queue(lcr_ctx* c, const lcr_isoform_params* p, int32_t* d_ctl, int32_t* 
   launch_scan_i32(c->scan_tmp, c->iso_npair.as<int32_t>(), pair_off, nr, pair_off + nr, s);
   launch_k15_sizes(b, part_off, pair_off, c->iso_tsz.as<int32_t>(), d_ctl, s);
   launch_scan_i32(c->scan_tmp, c->iso_tsz.as<int32_t>(), tbl_off, ng, tbl_off + ng, s);
-  { int rc = stream_wait(c, c->ev_iso); if (rc) return rc; }   // the host sizes the row records, the keys and the table from the two totals
+  { int rc = stream_wait(c, c->iso.ev); if (rc) return rc; }   // the host sizes the row records, the keys and the table from the two totals
   const int32_t n_part = h_ctl[0], n_pairs = h_ctl[1];
   if (n_part <= 0 || n_pairs <= 0) return LCR_OK;
   if (n_pairs > (1 << 28)) { c->err = "lcr_isoforms: more than 2^28 junction occurrences in one batch; split it"; return LCR_E_ARG; }
@@ -56,7 +56,7 @@ int iso_queue(lcr_ctx* c, const lcr_isoform_params* p, int32_t* d_ctl, int32_t* 
   launch_scan_i32(c->scan_tmp, c->iso_flag.as<int32_t>(), koff, n_slots, koff + n_slots, s);
   launch_scan_i32(c->scan_tmp, c->iso_plen.as<int32_t>(), poff, n_slots, poff + n_slots, s);
   launch_k15_offsets(tbl_off, koff, poff, ng, n_slots, c->iso_off.as<int32_t>(), d_hoff, c->iso_pbase.as<int32_t>(), d_ctl, s);
-  { int rc = stream_wait(c, c->ev_iso); if (rc) return rc; }   // kept chains and pool entries size the records, the pool and the last kernels' grids
+  { int rc = stream_wait(c, c->iso.ev); if (rc) return rc; }   // kept chains and pool entries size the records, the pool and the last kernels' grids
   const int32_t n_kept = h_ctl[2], n_pool = h_ctl[3];
   if (n_kept <= 0) return LCR_OK;
   // 4. order, pool, row_isoform, tables: the results go to HBM and, by the same kernels, to pinned host memory
@@ -91,9 +91,7 @@ int lcr_isoforms(lcr_ctx* c, const lcr_isoform_params* p) {
   const int ng = c->bv.n_regions;
   const int32_t n_rows = c->n_rows;
   hipStream_t s = c->stream;
-  if (!c->ev_iso) HIPCHK(c, hipEventCreateWithFlags(&c->ev_iso, hipEventDisableTiming));
-  if (c->timing && !c->ev_iso_t[0]) { HIPCHK(c, hipEventCreate(&c->ev_iso_t[0])); HIPCHK(c, hipEventCreate(&c->ev_iso_t[1])); }
-  c->iso_valid = false;   // (from here on the last call's records are overwritten)
+  c->iso.valid = false;   // (from here on the last call's records are overwritten)
   HIPCHK(c, c->h_iso_ctl.reserve(64));
   HIPCHK(c, c->h_iso_off.reserve(((size_t)std::max(ng, 0) + 1) * 4));
   HIPCHK(c, c->h_iso_row.reserve((size_t)std::max(n_rows, 1) * 4));
@@ -107,24 +105,21 @@ int lcr_isoforms(lcr_ctx* c, const lcr_isoform_params* p) {
   HIPCHK(c, hipStreamSynchronize(s));   // (an earlier call's last kernels write the pinned blocks that are reused from here on)
   h_ctl[0] = h_ctl[1] = h_ctl[2] = h_ctl[3] = 0;
   for (int g = 0; g <= ng; g++) h_off[g] = 0;                    // (k15_offsets overwrites them when the call gets that far)
-  if (c->timing) HIPCHK(c, hipEventRecord(c->ev_iso_t[0], s));
-  if (n_rows > 0) HIPCHK(c, lcr_fill_async(c->d_iso_row.p, 0xff, (size_t)n_rows * 4, s));   // -1: k15_rows overwrites the rows that hold a kept chain
   int32_t n_kept = 0, n_pool = 0;
-  { int rc = iso_queue(c, p, d_ctl, d_hoff, &n_kept, &n_pool); if (rc) return rc; }
-  launch_k15_export(n_rows, c->d_iso_row.as<int32_t>(), d_hrow, s);   // (also when nothing is kept: every row's -1)
-  if (c->timing) { HIPCHK(c, hipEventRecord(c->ev_iso_t[1], s)); c->iso_timed = true; }
-  HIPCHK(c, hipEventRecord(c->ev_iso, s));     // lcr_get_isoforms waits for it
-  HIPCHK(c, hipGetLastError());
-  c->iso_ng = ng; c->iso_n = n_kept; c->iso_nchain = n_pool; c->iso_nrows = n_rows; c->iso_valid = true;
-  return LCR_OK;
+  {
+    Bracket t(c, c->iso);
+    if (n_rows > 0) HIPCHK(c, lcr_fill_async(c->d_iso_row.p, 0xff, (size_t)n_rows * 4, s));   // -1: k15_rows overwrites the rows that hold a kept chain
+    { int rc = iso_queue(c, p, d_ctl, d_hoff, &n_kept, &n_pool); if (rc) return rc; }
+    launch_k15_export(n_rows, c->d_iso_row.as<int32_t>(), d_hrow, s);   // (also when nothing is kept: every row's -1)
+  }
+  c->iso_ng = ng; c->iso_n = n_kept; c->iso_nchain = n_pool; c->iso_nrows = n_rows;
+  return call_end(c, c->iso);     // lcr_get_isoforms waits for its event
 }
 
 int lcr_get_isoforms(lcr_ctx* c, lcr_isoform_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->iso_valid) { c->err = "lcr_get_isoforms before lcr_isoforms (its records die with the phase results)"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_iso));
-  HIPCHK(c, hipGetLastError());
+  if (c->stage < ST_PHASED || !c->iso.valid) { c->err = "lcr_get_isoforms before lcr_isoforms (its records die with the phase results)"; return LCR_E_STATE; }
+  { int rc = call_wait(c, c->iso); if (rc) return rc; }
   out->n_regions = c->iso_ng; out->n_isoforms = c->iso_n; out->n_chain = c->iso_nchain; out->n_rows = c->iso_nrows;
   out->iso = c->iso_n ? c->h_iso.as<lcr_isoform>() : nullptr;
   out->iso_region_off = c->h_iso_off.as<int32_t>();
@@ -138,11 +133,7 @@ int lcr_get_isoforms(lcr_ctx* c, lcr_isoform_list* out) {
 
 int lcr_isoforms_ms(lcr_ctx* c, float* ms) {
   if (!c || !ms) return LCR_E_ARG;
-  if (!c->timing || !c->iso_timed) { c->err = "lcr_isoforms_ms: no lcr_isoforms with timing enabled"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_iso_t[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->ev_iso_t[0], c->ev_iso_t[1]));
-  return LCR_OK;
+  return call_ms(c, c->iso, "lcr_isoforms_ms", "lcr_isoforms", ms);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@ int lcr_junctions(lcr_ctx* c, const lcr_junction_params* p) {
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = phase_settle(c); if (rc) return rc; }       // an asynchronous phase stage in flight writes the read records
   static_assert(sizeof(lcr_junction) == 48, "lcr_junction is 48 bytes");
-  c->junc_valid = false;   // (from here on the last call's table is overwritten)
+  c->junc.valid = false;   // (from here on the last call's table is overwritten)
   const BatchView& b = c->bv;
   const int nr = b.n_reads, ng = b.n_regions;
   hipStream_t s = c->stream;
@@ -27,7 +27,7 @@ int lcr_junctions(lcr_ctx* c, const lcr_junction_params* p) {
   h_ctl[0] = h_ctl[1] = h_ctl[2] = 0;
   const auto finish_empty = [&]() {   // no participating row, no pair or no kept junction
     for (int g = 0; g <= ng; g++) h_off[g] = 0;
-    c->junc_n = 0; c->junc_ng = ng; c->junc_valid = true;
+    c->junc_n = 0; c->junc_ng = ng; c->junc.valid = true;
     return LCR_OK;
   };
   if (nr == 0 || ng == 0 || c->n_rows == 0) return finish_empty();
@@ -46,9 +46,7 @@ int lcr_junctions(lcr_ctx* c, const lcr_junction_params* p) {
   launch_scan_i32(c->scan_tmp, c->j_npair.as<int32_t>(), pair_off, nr, pair_off + nr, s);
   launch_k6_sizes(b, part_off, pair_off, c->j_tsz.as<int32_t>(), d_ctl, s);
   launch_scan_i32(c->scan_tmp, c->j_tsz.as<int32_t>(), tbl_off, ng, tbl_off + ng, s);
-  HIPCHK(c, hipEventRecord(c->ev_junc, s));
-  HIPCHK(c, hipEventSynchronize(c->ev_junc));   // the host sizes the row records, the keys and the table from the two totals
-  HIPCHK(c, hipGetLastError());
+  { int rc = stream_wait(c, c->junc.ev); if (rc) return rc; }   // the host sizes the row records, the keys and the table from the two totals
   const int32_t n_part = h_ctl[0], n_pairs = h_ctl[1];
   if (n_part <= 0 || n_pairs <= 0) return finish_empty();
   if (n_pairs > (1 << 28)) { c->err = "lcr_junctions: more than 2^28 junction occurrences in one batch; split it"; return LCR_E_ARG; }
@@ -68,9 +66,7 @@ int lcr_junctions(lcr_ctx* c, const lcr_junction_params* p) {
   launch_k6_flag(c->j_tbl_key.as<uint64_t>(), c->j_tbl_cnt.as<uint32_t>(), n_slots, p->min_count, c->j_flag.as<int32_t>(), s);
   launch_scan_i32(c->scan_tmp, c->j_flag.as<int32_t>(), koff, n_slots, koff + n_slots, s);
   launch_k6_offsets(tbl_off, koff, ng, n_slots, c->j_off.as<int32_t>(), d_hoff, d_ctl, s);
-  HIPCHK(c, hipEventRecord(c->ev_junc, s));
-  HIPCHK(c, hipEventSynchronize(c->ev_junc));   // the number of kept junctions sizes the records and the last kernels' grids
-  HIPCHK(c, hipGetLastError());
+  { int rc = stream_wait(c, c->junc.ev); if (rc) return rc; }   // the number of kept junctions sizes the records and the last kernels' grids
   const int32_t n_kept = h_ctl[2];
   if (n_kept <= 0) return finish_empty();
   // 4. order, motif, tables: the records go to HBM and, by the last kernel, to pinned host memory
@@ -82,18 +78,14 @@ int lcr_junctions(lcr_ctx* c, const lcr_junction_params* p) {
   launch_k6_place(b, c->j_tbl_key.as<uint64_t>(), c->j_tbl_cnt.as<uint32_t>(), c->j_flag.as<int32_t>(), koff, tbl_off, n_slots, c->j_off.as<int32_t>(),
                   n_kept, c->j_ck.as<uint64_t>(), c->j_cc.as<uint32_t>(), c->j_cg.as<int32_t>(), c->d_junc.as<lcr_junction>(), s);
   launch_k6_tables(b, part_off, c->j_rows.p, c->j_keys.as<uint64_t>(), n_kept, c->d_junc.as<lcr_junction>(), d_hjunc, s);
-  HIPCHK(c, hipEventRecord(c->ev_junc, s));     // lcr_get_junctions waits for it
-  HIPCHK(c, hipGetLastError());
-  c->junc_n = n_kept; c->junc_ng = ng; c->junc_valid = true;
-  return LCR_OK;
+  c->junc_n = n_kept; c->junc_ng = ng;
+  return call_end(c, c->junc);     // lcr_get_junctions waits for its event
 }
 
 int lcr_get_junctions(lcr_ctx* c, lcr_junction_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->junc_valid) { c->err = "lcr_get_junctions before lcr_junctions (its table dies with the phase stage's results)"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_junc));
-  HIPCHK(c, hipGetLastError());
+  if (c->stage < ST_PHASED || !c->junc.valid) { c->err = "lcr_get_junctions before lcr_junctions (its table dies with the phase stage's results)"; return LCR_E_STATE; }
+  { int rc = call_wait(c, c->junc); if (rc) return rc; }
   out->n_regions = c->junc_ng; out->n_junctions = c->junc_n;
   out->junc = c->junc_n ? c->h_junc.as<lcr_junction>() : nullptr;
   out->junc_region_off = c->h_junc_off.as<int32_t>();

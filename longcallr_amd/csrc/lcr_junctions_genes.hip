@@ -9,7 +9,7 @@
 #include "lcr_asj_args.h"
 
 int gj_begin(lcr_ctx* c, GeneJunctions& g) {
-  g.valid = g.timed = false;
+  g.st.valid = g.st.timed = false;
   HIPCHK(c, g.h_ctl.reserve(64));
   HIPCHK(c, g.h_off.reserve((size_t)(c->bv.n_regions + 1) * 4));
   HIPCHK(c, g.h_junc.reserve(sizeof(lcr_junction_gene)));
@@ -47,7 +47,7 @@ int gj_counts(lcr_ctx* c, GeneJunctions& g, uint32_t min_junctions) {
 }
 
 int gj_wait_counts(lcr_ctx* c, GeneJunctions& g, const char* fn, bool* empty) {
-  { int rc = stream_wait(c, g.ev); if (rc) return rc; }   // the host sizes the row records, the keys and the table from the two totals
+  { int rc = stream_wait(c, g.st.ev); if (rc) return rc; }   // the host sizes the row records, the keys and the table from the two totals
   const int32_t n_part = g.h_ctl.as<int32_t>()[0], n_occ = g.h_ctl.as<int32_t>()[1];
   *empty = n_part <= 0 || n_occ <= 0;
   if (!*empty && n_occ > (1 << 28)) { c->err = std::string(fn) + ": more than 2^28 junction occurrences in one batch; split it"; return LCR_E_ARG; }
@@ -107,10 +107,8 @@ void no_records(const HostBuf& h_off, int32_t ng, int32_t* n) {
 }
 
 int gj_finish(lcr_ctx* c, GeneJunctions& g) {
-  HIPCHK(c, hipEventRecord(g.ev, c->stream));
-  HIPCHK(c, hipGetLastError());
-  g.ng = c->bv.n_regions; g.valid = true;
-  return LCR_OK;
+  g.ng = c->bv.n_regions;
+  return call_end(c, g.st);
 }
 
 extern "C" {
@@ -137,18 +135,18 @@ int lcr_junctions_genes(lcr_ctx* c, const lcr_junction_params* p, int32_t mem, c
   lcr_gene_annotation d{};
   int32_t* d_bad = nullptr;
   { int rc = annotation_queue(c, g.ann, a, mem, g.h_bad, &d, &d_bad); if (rc) return rc; }
-  if (a->n_genes > 0) { int rc = annotation_verdict(c, g.h_bad, g.ev, "lcr_junctions_genes"); if (rc) return rc; }
+  if (a->n_genes > 0) { int rc = annotation_verdict(c, g.h_bad, g.st.ev, "lcr_junctions_genes"); if (rc) return rc; }
   { int rc = gj_begin(c, g); if (rc) return rc; }
   const auto finish_empty = [&]() { no_records(g.h_off, ng, &g.n); return gj_finish(c, g); };   // no participating row, no occurrence or no kept junction
   if (c->bv.n_reads == 0 || ng == 0 || c->n_rows == 0 || a->n_genes == 0) return finish_empty();
-  Bracket t(c, g);
+  Bracket t(c, g.st);
   { int rc = gj_counts(c, g, p->min_junctions); if (rc) return rc; }
   bool empty = false;
   { int rc = gj_wait_counts(c, g, "lcr_junctions_genes", &empty); if (rc) return rc; }
   if (empty) return finish_empty();
   { int rc = gj_rows(c, g, d); if (rc) return rc; }
   { int rc = gj_keep(c, g.t, g.pair_off.as<int32_t>(), g.tbl_off.as<int32_t>(), p->min_count, g.d_off, g.d_ctl); if (rc) return rc; }
-  { int rc = stream_wait(c, g.ev); if (rc) return rc; }   // the number of kept junctions sizes the records and the last kernels' grids
+  { int rc = stream_wait(c, g.st.ev); if (rc) return rc; }   // the number of kept junctions sizes the records and the last kernels' grids
   const int32_t n_kept = g.h_ctl.as<int32_t>()[2];
   if (n_kept <= 0) return finish_empty();
   { int rc = gj_tables(c, g, n_kept); if (rc) return rc; }
@@ -157,7 +155,7 @@ int lcr_junctions_genes(lcr_ctx* c, const lcr_junction_params* p, int32_t mem, c
 
 int lcr_get_junctions_genes(lcr_ctx* c, lcr_junction_gene_list* out) {
   if (!c || !out) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->jgene.valid) {
+  if (c->stage < ST_PHASED || !c->jgene.st.valid) {
     c->err = "lcr_get_junctions_genes before lcr_junctions_genes (its table dies with the phase stage's results and with the gene assignment)";
     return LCR_E_STATE;
   }

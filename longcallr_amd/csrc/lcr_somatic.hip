@@ -1,7 +1,7 @@
 // lcr_somatic.hip — the host driver of K14 (k14_somatic.hip): the three-class model per haplotype at every candidate over the fragment
 // matrix, its getter and its timer.  A call of its own behind lcr_phase / lcr_haplotag, shaped like lcr_site_counts: it reads the fragment
 // stage's CSR, the candidate records and the phase stage's read records, and writes buffers no other stage or getter reads (lcr_ctx:
-// som_*, d_som, h_som).  The tables are built here per call and travel as a kernel argument, so a repeated call with other params waits
+// d_som, h_som) beside the segments it shares with lcr_site_counts (colsegs, colseg_queue).  The tables are built here per call and travel as a kernel argument, so a repeated call with other params waits
 // for nothing.  Six launches (clear, count, two of the scan, fill, sites), no host wait of its own: the entry count is the fragment stage's.
 #include <cmath>
 
@@ -47,43 +47,28 @@ int lcr_somatic(lcr_ctx* c, const lcr_somatic_params* p) {
   static_assert(sizeof(lcr_somatic_site) == 80, "lcr_somatic_site is 80 bytes");
   const K14Tables t = somatic_tables(*p);
   const int n_rows = c->n_rows, n_cand = (int)c->h_cand.size();
-  const int64_t nnz = c->nnz;
   hipStream_t s = c->stream;
-  if (!c->ev_som) HIPCHK(c, hipEventCreateWithFlags(&c->ev_som, hipEventDisableTiming));
-  if (c->timing && !c->ev_som_t[0]) { HIPCHK(c, hipEventCreate(&c->ev_som_t[0])); HIPCHK(c, hipEventCreate(&c->ev_som_t[1])); }
-  c->som_valid = false;   // (from here on the last call's records are overwritten)
+  c->som.valid = false;   // (from here on the last call's records are overwritten)
   const size_t nc1 = (size_t)std::max(n_cand, 1);
-  HIPCHK(c, c->som_cnt.reserve(nc1 * 4));
-  HIPCHK(c, c->som_off.reserve((nc1 + 1) * 8));
-  HIPCHK(c, c->som_seg.reserve((size_t)std::max<int64_t>(nnz, 1) * 8));
   HIPCHK(c, c->d_som.reserve(nc1 * sizeof(lcr_somatic_site)));
   HIPCHK(c, c->h_som.reserve(nc1 * sizeof(lcr_somatic_site)));
   lcr_somatic_site* d_hsom = nullptr;
   HIPCHK(c, c->h_som.dev(&d_hsom));
-  if (c->timing) HIPCHK(c, hipEventRecord(c->ev_som_t[0], s));
-  if (n_cand > 0) {
-    uint32_t* cnt = c->som_cnt.as<uint32_t>();
-    int64_t* off = c->som_off.as<int64_t>();
-    HIPCHK(c, lcr_fill_async(cnt, 0, (size_t)n_cand * 4, s));
-    launch_k12_count(n_rows, c->row_ptr.as<int64_t>(), c->col.as<int32_t>(), n_cand, cnt, s);
-    launch_scan_i32_to_i64(c->scan_tmp, (const int32_t*)cnt, off, n_cand, s);   // (a column has fewer than 2^31 entries: one per row; the offsets are 64 bits)
+  if (Bracket br(c, c->som); n_cand > 0) {
+    uint32_t* cnt; int64_t* off; uint64_t* seg;
+    { int rc = colseg_queue(c, n_cand, &cnt, &off, &seg); if (rc) return rc; }
     launch_k14_fill(n_rows, c->row_ptr.as<int64_t>(), c->col.as<int32_t>(), c->val.as<uint8_t>(), c->phase.d_read_rec.as<lcr_read_record>(),
-                    c->d_cand.as<lcr_candidate>(), n_cand, cnt, off, c->som_seg.as<uint64_t>(), s);
-    launch_k14_sites(c->d_cand.as<lcr_candidate>(), n_cand, off, c->som_seg.as<uint64_t>(), t, p->min_baseq, c->d_som.as<lcr_somatic_site>(), d_hsom, s);
+                    c->d_cand.as<lcr_candidate>(), n_cand, cnt, off, seg, s);
+    launch_k14_sites(c->d_cand.as<lcr_candidate>(), n_cand, off, seg, t, p->min_baseq, c->d_som.as<lcr_somatic_site>(), d_hsom, s);
   }
-  if (c->timing) { HIPCHK(c, hipEventRecord(c->ev_som_t[1], s)); c->som_timed = true; }
-  HIPCHK(c, hipEventRecord(c->ev_som, s));     // lcr_get_somatic waits for it
-  HIPCHK(c, hipGetLastError());
-  c->som_ncand = n_cand; c->som_valid = true;
-  return LCR_OK;
+  c->som_ncand = n_cand;
+  return call_end(c, c->som);     // lcr_get_somatic waits for its event
 }
 
 int lcr_get_somatic(lcr_ctx* c, int32_t* n_cand, const lcr_somatic_site** rec, const lcr_somatic_site** dev_rec) {
   if (!c || !n_cand || !rec || !dev_rec) return LCR_E_ARG;
-  if (c->stage < ST_PHASED || !c->som_valid) { c->err = "lcr_get_somatic before lcr_somatic (its records die with the phase results)"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_som));
-  HIPCHK(c, hipGetLastError());
+  if (c->stage < ST_PHASED || !c->som.valid) { c->err = "lcr_get_somatic before lcr_somatic (its records die with the phase results)"; return LCR_E_STATE; }
+  { int rc = call_wait(c, c->som); if (rc) return rc; }
   *n_cand = c->som_ncand;
   *rec = c->som_ncand ? c->h_som.as<lcr_somatic_site>() : nullptr;
   *dev_rec = c->som_ncand ? c->d_som.as<lcr_somatic_site>() : nullptr;
@@ -92,11 +77,7 @@ int lcr_get_somatic(lcr_ctx* c, int32_t* n_cand, const lcr_somatic_site** rec, c
 
 int lcr_somatic_ms(lcr_ctx* c, float* ms) {
   if (!c || !ms) return LCR_E_ARG;
-  if (!c->timing || !c->som_timed) { c->err = "lcr_somatic_ms: no lcr_somatic with timing enabled"; return LCR_E_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_som_t[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->ev_som_t[0], c->ev_som_t[1]));
-  return LCR_OK;
+  return call_ms(c, c->som, "lcr_somatic_ms", "lcr_somatic", ms);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@ tests/test_site_counts_gpu.py does (its regions are reused); a site is made a lo
 candidate record in HBM, as a caller of the C ABI who holds the records could -- the candidate stage's own flag is exercised behind
 lcr_phase.  The contract's worked instance, wave boundaries, an empty haplotype, the quality threshold and q = 0, the phase-set rules and
 their equality with lcr_site_counts, LCR_SOM_ALLELES / dense / RNA-edit candidates, no call without the flag, both outcomes of the rescue,
-purity, independence from the batch, and the call's order and lifetime on one context.  LCR_SOM_DEEP needs 2^20 + 1 entries on one
+purity, independence from the batch, the call's order and lifetime on one context, and the segment scratch it shares with
+lcr_site_counts.  LCR_SOM_DEEP needs 2^20 + 1 entries on one
 haplotype: not a shape for this suite; the restatement's branch is covered in tests/test_somatic_host.py."""
 import ctypes as C
 
@@ -335,3 +336,61 @@ def test_order_and_lifetime(engine_cls):
     T.load_batch(b1).run_all()
     assert T.somatic().tobytes() == first.tobytes() and T.somatic_ms() > 0.0
     T.close()
+
+
+# ---- 5. lcr_site_counts and lcr_somatic fill the same per-candidate segments on one context ---------------------------------------------
+def shared_engine(engine_cls):
+    """test_site_counts_gpu's seven-row worked instance and its depth region (129 / 65 / 64 / 63 / 1 / 0 entries: a segment on either side
+    of the 64 lanes of its wave) in one batch, behind lcr_haplotag"""
+    (w0, wref, wrs), (d0, dref, drs) = sc.worked_region(), sc.depth_region()
+    sites = {w0 + c: (wref[c], tj.ALT[wref[c]], 100 if c in sc.W_SET100 else 200) for c in sc.W_SET100 + sc.W_SET200}
+    sites.update({d0 + c: (dref[c], tj.ALT[dref[c]], 500) for c in sc.DEPTH_COLS})
+    E = engine_cls(0, _abi.make_params("hifi-masseq", seed=5, dist_to_end=0))
+    sc.imported(E, tj.batch_of([(w0, wref, wrs), (d0, dref, drs)]), [sc.W_SET100 + sc.W_SET200 + (sc.W_X,), sc.DEPTH_COLS], [w0, d0])
+    E.haplotag(th.site_arrays(sites))
+    return E
+
+
+def queue_site_counts(E, q):
+    p = _abi.LcrSiteCountParams(q)
+    assert E.lib.lcr_site_counts(E.h, C.byref(p)) == 0
+
+
+def queue_somatic(E, q):
+    p = _abi.LcrSomaticParams(0.3, 5e-6, 5e-4, q, 0)
+    assert E.lib.lcr_somatic(E.h, C.byref(p)) == 0
+
+
+def fetched(E, which):
+    """the records of the calls named in `which` as their getters hand them out, pinned host memory and HBM, as bytes"""
+    out = {}
+    for name, getter, dtype, dev in (("site_counts", E.lib.lcr_get_site_counts, _abi.SITE_COUNT_DTYPE, sc.dev_records),
+                                     ("somatic", E.lib.lcr_get_somatic, _abi.SOMATIC_SITE_DTYPE, dev_records)):
+        if name in which:
+            n, rec, d = C.c_int32(), C.c_void_p(), C.c_void_p()
+            assert getter(E.h, C.byref(n), C.byref(rec), C.byref(d)) == 0 and n.value > 0
+            out[name] = (C.string_at(rec.value, n.value * dtype.itemsize), dev(E).tobytes())
+    return out
+
+
+def test_shared_segments_with_site_counts(engine_cls):
+    # every call alone on a fresh context
+    alone = {}
+    for key, queue, q in (("sc13", queue_site_counts, 13), ("sc0", queue_site_counts, 0), ("som13", queue_somatic, 13)):
+        A = shared_engine(engine_cls)
+        queue(A, q)
+        (alone[key],) = fetched(A, ("somatic",) if key == "som13" else ("site_counts",)).values()
+        assert alone[key][0] == alone[key][1]
+        A.close()
+    assert alone["sc13"] != alone["sc0"]                       # (column 100 of the depth region holds q = 12 entries)
+    n_entries = np.frombuffer(alone["sc13"][0], dtype=_abi.SITE_COUNT_DTYPE)["n_entries"].tolist()
+    assert len(n_entries) == 13 and n_entries[3] == 7 and n_entries[7:] == [129, 65, 64, 63, 1, 0]       # (column 350 of the instance; the depth columns)
+    E = shared_engine(engine_cls)
+    both = ("site_counts", "somatic")
+    queue_site_counts(E, 13); queue_somatic(E, 13)             # one behind the other, both fetched afterwards
+    assert fetched(E, both) == {"site_counts": alone["sc13"], "somatic": alone["som13"]}
+    queue_somatic(E, 13); queue_site_counts(E, 13)             # the other order
+    assert fetched(E, both) == {"site_counts": alone["sc13"], "somatic": alone["som13"]}
+    queue_site_counts(E, 13); queue_somatic(E, 13); queue_site_counts(E, 0)       # ... and again with another threshold
+    assert fetched(E, both) == {"site_counts": alone["sc0"], "somatic": alone["som13"]}
+    E.close()
