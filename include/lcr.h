@@ -710,6 +710,75 @@ int lcr_get_isoforms(lcr_ctx*, lcr_isoform_list* out);
  * waits for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
 int lcr_isoforms_ms(lcr_ctx*, float* ms);
 
+/* Allele-specific transcript ends (K16): the haplotype x TSS / TES site table -- where do each haplotype's transcripts start and end --,
+ * counted on the GPU from what lcr_phase or lcr_haplotag left there.  DESIGN.md section 1o.  Defined per region, as lcr_junctions.  Row r
+ * of region g is a row of lcr_get_fragmat: its read is row_read[r], its haplotype assignment[r], its phase set phase_set[r] (0 = none).
+ *   ends of a read        left = pos; right = rend - 1, where rend = pos + the lengths of all M, D, N, = and X ops (exclusive, exactly
+ *       lcr_junctions' rend).  Soft and hard clips play no part.
+ *   transcript strand t   of a read (util.rs:803-819), from its flags: rev = bit 0, ts = bits 1-2.  ts == 1 ('+'): t = '+' if !rev, else
+ *       '-'.  ts == 2 ('-'): t = '-' if !rev, else '+'.  ts == 0 (no tag; ts == 3 counts as no tag too): with strand_mode ==
+ *       LCR_ENDS_STRAND_TS (0, the default) the read has no strand; with LCR_ENDS_STRAND_READ (1: direct RNA, where the read's strand is
+ *       the transcript's) t = '+' if !rev, else '-'.  In the records 1 = '+', 2 = '-'.
+ *   kind of an end        the left end of a '+' read and the right end of a '-' read are 5' ends (kind 0, "TSS"); the other two are 3'
+ *       ends (kind 1, "TES").
+ *   participating rows    assignment 1 or 2, and a strand.  Unspliced reads take part.  Every other read takes no part, neither as present
+ *       nor as absent.
+ *   histogram             for region g, strand t and side d (0 left, 1 right), c(g, t, d, x) = participating rows of g with strand t whose
+ *       side-d end is column x.  x is a contig coordinate; ends outside the region's window count like any other.  The four (t, d) classes
+ *       of a region never mix.
+ *   peaks                 non-maximum suppression with the window W = `window`: x with c(x) > 0 is a peak iff, for every other y of the
+ *       same (g, t, d) with c(y) > 0 and |y - x| <= W, either c(x) > c(y), or c(x) == c(y) and x < y.  That order is strict and total, so
+ *       two peaks of a class are always more than W apart, and every non-empty class has at least one peak.  W == 0 makes every distinct
+ *       coordinate a peak.  Deliberately not single-linkage clustering: with the ragged 5' ends of cDNA reads single linkage chains a whole
+ *       exon into one cluster.
+ *   assignment            an end at x belongs to the nearest peak p of its class with |p - x| <= W; a tie (p = x - k and p' = x + k) goes
+ *       to the smaller coordinate.  If no peak lies within W (a shoulder of a shoulder) the end is unassigned and counts for no site.
+ *   sites, kept sites     a site is a peak.  n_reads = rows assigned to it, over every phase set; n_h1 / n_h2 the same per haplotype;
+ *       n_peak = c(p), the rows ending exactly at the peak; min0 / max0 = the smallest and largest assigned coordinate.  Kept iff
+ *       n_reads >= min_count.
+ *   present / absent      at a kept site (g, t, d, p) only the participating rows of g with strand t are looked at.  PRESENT: the row's
+ *       side-d end is assigned to this site.  ABSENT: the row is not present and its alignment covers the site's whole window,
+ *       pos <= p - W && rend >= p + W + 1 (signed 64-bit arithmetic; a window reaching below column 0 is covered by no row): a read-through
+ *       at a TES, a transcript that started further upstream at a TSS.  Presence is asked first, so an absent row is never also present (a
+ *       row whose end lies exactly W from p and is assigned to p is present, whatever it covers).  A row that ends inside the window but
+ *       is assigned elsewhere or unassigned is neither; so is a row that stops short of the window.  Only the extent counts: a read whose
+ *       intron spans the window is absent, which is the alternative to terminating at an intronic site.
+ *   phase set             lcr_junctions' rule over the present and absent rows: count them per value of ps; phase_set is the value with
+ *       the most rows, ties to the smallest value, 0 a value like any other; n_phase_sets = distinct values; h1_absent, h1_present,
+ *       h2_absent, h2_present count the rows of that phase set only.
+ *   order                 by region, then p, then strand ('+' first), then side (left first); independent of the batch's composition and of
+ *       the order in which atomics land.  All arithmetic is integer adds: bit-reproducible.
+ *   row_site              two int32 per fragment row of the batch, [2 r] for the left end and [2 r + 1] for the right: the index of the
+ *       kept record the end is assigned to, or -1.  (What a TSS / TES tag in the phased BAM would consume.)
+ *   totals                n_part = participating rows; n_assigned = ends assigned to a kept site.
+ * Not here: clip-length or poly-A-sequence evidence, annotation matching, a per-gene form, smoothing of the histogram.
+ * lcr_transcript_ends needs the bound batch with the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed;
+ * params == NULL, window > 4096 or strand_mode > 1: LCR_E_ARG, the last call's records stay valid; min_count == 0 is treated as 1; more
+ * than 2^27 participating rows in a batch: LCR_E_ARG), collects an asynchronous phase stage in flight first, queues a fixed number of
+ * kernels on the context's stream around at most two host waits on sizes, writes no buffer another stage or getter reads, and may be
+ * repeated with other params.  The records die with the phase results: at the next candidate stage and at lcr_load_batch /
+ * lcr_bind_batch; lcr_get_transcript_ends answers LCR_E_STATE then.  site / site_region_off (n_regions + 1) / row_site: pinned host
+ * memory, valid until the next lcr_transcript_ends -- the call's last kernels' stores (the zero offsets of a call that keeps nothing are the
+ * host's) --; dev_*: the same bytes in HBM.  site / dev_site are NULL without a record, row_site / dev_row_site without a fragment row. */
+enum { LCR_ENDS_STRAND_TS = 0, LCR_ENDS_STRAND_READ = 1 };
+typedef struct { uint32_t min_count, window, strand_mode, pad_; } lcr_end_params;      /* defaults 10, 10, LCR_ENDS_STRAND_TS */
+typedef struct {                 /* 64 bytes */
+  int32_t region; uint8_t strand, side, kind, pad_;
+  int64_t peak0;
+  int32_t min0, max0;
+  uint32_t n_reads, n_h1, n_h2, n_peak;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1_absent, h1_present, h2_absent, h2_present;
+} lcr_end_site;
+typedef struct { int32_t n_regions, n_sites, n_rows, n_part; int64_t n_assigned;
+                 const lcr_end_site* site; const int32_t* site_region_off; const int32_t* row_site;
+                 const lcr_end_site* dev_site; const int32_t* dev_row_site; } lcr_end_list;
+int lcr_transcript_ends(lcr_ctx*, const lcr_end_params*);
+int lcr_get_transcript_ends(lcr_ctx*, lcr_end_list* out);
+/* HIP-event time (ms) from the first to the last kernel of the last lcr_transcript_ends with timing enabled (lcr_enable_timing), the host's
+ * waits for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_transcript_ends_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.
@@ -1084,7 +1153,9 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * library's fill kernels), "fill_selftest" (checks those kernels against the host; LCR_E_DEVICE on a difference), "host_trace" (1: a
  * "[host]" line of wall-clock marks per lcr_phase on stderr; process-wide like own_fill), "iso_hash_bits" (0 .. 64, default 64: lcr_isoforms
  * routes a chain by the low n bits of its hash only -- 0 sends every chain of a region down one probe sequence; the results are the same
- * bytes for every n, which is how the comparison of whole chains is tested).  Unknown key: LCR_E_ARG.  The defaults are the
+ * bytes for every n, which is how the comparison of whole chains is tested), "ends_hash_bits" (0 .. 32, default 32: lcr_transcript_ends
+ * routes an end's key by the low n bits of its hash only -- 0 makes every key of a region probe from its segment's first slot; the same
+ * bytes for every n).  Unknown key: LCR_E_ARG.  The defaults are the
  * product behaviour. */
 int lcr_debug_set(lcr_ctx*, const char* key, int64_t value);
 

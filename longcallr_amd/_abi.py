@@ -201,6 +201,27 @@ class LcrIsoformList(C.Structure):   # include/lcr.h: lcr_isoform_list
                 ("dev_iso", C.c_void_p), ("dev_chain", C.c_void_p), ("dev_row_isoform", C.c_void_p)]
 
 
+LCR_ENDS_STRAND_TS, LCR_ENDS_STRAND_READ = 0, 1   # include/lcr.h: lcr_end_params.strand_mode
+
+
+class LcrEndParams(C.Structure):   # include/lcr.h: lcr_end_params (defaults 10, 10, LCR_ENDS_STRAND_TS)
+    _fields_ = [("min_count", C.c_uint32), ("window", C.c_uint32), ("strand_mode", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+# lcr_end_site (include/lcr.h): one kept transcript-end site of a region -- the peak of a (strand, side) class of read ends, what was
+# assigned to it -- with its haplotype x presence table
+END_SITE_DTYPE = np.dtype([("region", "<i4"), ("strand", "u1"), ("side", "u1"), ("kind", "u1"), ("pad_", "u1"), ("peak0", "<i8"), ("min0", "<i4"),
+                           ("max0", "<i4"), ("n_reads", "<u4"), ("n_h1", "<u4"), ("n_h2", "<u4"), ("n_peak", "<u4"), ("phase_set", "<u4"),
+                           ("n_phase_sets", "<u4"), ("h1_absent", "<u4"), ("h1_present", "<u4"), ("h2_absent", "<u4"), ("h2_present", "<u4")],
+                          align=True)
+assert END_SITE_DTYPE.itemsize == 64, END_SITE_DTYPE.itemsize
+
+
+class LcrEndList(C.Structure):   # include/lcr.h: lcr_end_list
+    _fields_ = [("n_regions", C.c_int32), ("n_sites", C.c_int32), ("n_rows", C.c_int32), ("n_part", C.c_int32), ("n_assigned", C.c_int64),
+                ("site", C.c_void_p), ("site_region_off", C.c_void_p), ("row_site", C.c_void_p), ("dev_site", C.c_void_p), ("dev_row_site", C.c_void_p)]
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

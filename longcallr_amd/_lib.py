@@ -26,6 +26,7 @@ SYMBOLS = [
     "lcr_hap_coverage", "lcr_get_hap_coverage", "lcr_hap_coverage_ms",
     "lcr_somatic", "lcr_get_somatic", "lcr_somatic_ms",
     "lcr_isoforms", "lcr_get_isoforms", "lcr_isoforms_ms",
+    "lcr_transcript_ends", "lcr_get_transcript_ends", "lcr_transcript_ends_ms",
 ]
 
 _lib = None
@@ -155,5 +156,8 @@ def load():
     l.lcr_isoforms.argtypes = [vp, C.POINTER(_abi.LcrIsoformParams)]
     l.lcr_get_isoforms.argtypes = [vp, C.POINTER(_abi.LcrIsoformList)]
     l.lcr_isoforms_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_transcript_ends.argtypes = [vp, C.POINTER(_abi.LcrEndParams)]
+    l.lcr_get_transcript_ends.argtypes = [vp, C.POINTER(_abi.LcrEndList)]
+    l.lcr_transcript_ends_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

@@ -444,6 +444,34 @@ class Engine:
         self._chk(self.lib.lcr_isoforms_ms(self.h, C.byref(ms)), "lcr_isoforms_ms")
         return float(ms.value)
 
+    def transcript_ends(self, min_count=10, window=10, strand="ts"):
+        """lcr_transcript_ends + lcr_get_transcript_ends after phase() or haplotag(): the kept transcript-end sites of every region --
+        where each haplotype's transcripts start (TSS) and end (TES) -- with their haplotype x presence tables (include/lcr.h).  strand:
+        "ts" takes a read's transcript strand from its ts tag only, "read" falls back to the read's own strand (direct RNA) -> (records
+        as a structured array of _abi.END_SITE_DTYPE, ordered by region, peak, strand and side; site_region_off, n_regions + 1; row_site
+        as an (n_rows, 2) array, per row of fragmat() the records its left and right end are assigned to or -1; totals, a dict of n_part
+        and n_assigned), all copied.  Waits for an asynchronous phase stage in flight; may be repeated with other parameters."""
+        modes = {"ts": _abi.LCR_ENDS_STRAND_TS, "read": _abi.LCR_ENDS_STRAND_READ}
+        if strand not in modes:
+            raise ValueError("transcript_ends: strand is 'ts' or 'read', not %r" % (strand,))
+        p = _abi.LcrEndParams(int(min_count), int(window), modes[strand], 0)
+        self._chk(self.lib.lcr_transcript_ends(self.h, C.byref(p)), "lcr_transcript_ends")
+        o = self._end_list()
+        return (_view(o.site, _abi.END_SITE_DTYPE, o.n_sites), _view(o.site_region_off, np.int32, o.n_regions + 1),
+                _view(o.row_site, np.int32, 2 * o.n_rows).reshape(-1, 2), dict(n_part=int(o.n_part), n_assigned=int(o.n_assigned)))
+
+    def _end_list(self):
+        """lcr_get_transcript_ends: the last transcript_ends()'s list (pinned host and HBM pointers)"""
+        o = _abi.LcrEndList()
+        self._chk(self.lib.lcr_get_transcript_ends(self.h, C.byref(o)), "lcr_get_transcript_ends")
+        return o
+
+    def transcript_ends_ms(self):
+        """lcr_transcript_ends_ms: HIP-event time of the last transcript_ends()'s kernels, its host waits included (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_transcript_ends_ms(self.h, C.byref(ms)), "lcr_transcript_ends_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

@@ -8,8 +8,9 @@
 // (lcr_haplotag, lcr_get_haplotag_sites, lcr_haplotag_ms) stands where the phase entry stands and fills the phase stage's result blocks;
 // lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) and lcr_hap_coverage.hip (lcr_hap_coverage,
 // lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
-// lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth.  Every call behind the phase
-// stage keeps its bookkeeping in one CallState (below): lcr_ctx::post_calls() lists them for lcr_ctx_create / lcr_ctx_destroy / rewind_to.
+// lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth, lcr_ends.hip (lcr_transcript_ends,
+// lcr_get_transcript_ends, lcr_transcript_ends_ms) a fifth.  Every call behind the phase stage keeps its bookkeeping in one CallState
+// (below): lcr_ctx::post_calls() lists them for lcr_ctx_create / lcr_ctx_destroy / rewind_to.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -255,6 +256,17 @@ struct lcr_ctx {
   DevBuf d_iso, d_iso_chain, d_iso_row;                                           // the records, the pool, row_isoform
   HostBuf h_iso_ctl, h_iso, h_iso_off, h_iso_chain, h_iso_row;   // pinned: {participating rows, pairs, kept chains, pool entries}; the four outputs
 
+  // K16 (lcr_transcript_ends): scratch and results of its own -- no other stage or getter reads them
+  CallState ends;            // lcr_get_transcript_ends; ev: behind the two size waits, then behind the call's last kernel
+  int32_t ends_ng = 0, ends_n = 0, ends_nrows = 0, ends_npart = 0;
+  int dbg_ends_hash_bits = 32;   // lcr_debug_set("ends_hash_bits"): the low bits of a key's hash that route it; the results never depend on them
+  DevBuf e_part, e_part_off, e_tsz, e_tbl_off;        // per read: participates, the running sum; per region: its table segment
+  DevBuf e_rows;                                      // per participating row: its record (ends' slots, then their records)
+  DevBuf e_tbl_key, e_tbl_cnt, e_slot, e_flag, e_koff;   // per slot: key, c_h1 / c_h2, peak / target / the peak's sums, kept, kept in front
+  DevBuf e_off, e_cslot, e_crank, e_nasg;             // per region: kept sites in front; per kept slot: its slot, its record; n_assigned
+  DevBuf d_end, d_end_row;                            // the records, row_site
+  HostBuf h_end_ctl, h_end, h_end_off, h_end_row;     // pinned: {participating rows, kept sites, n_assigned (64 bit)}; the three outputs
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -273,7 +285,7 @@ struct lcr_ctx {
   AsjModes asj;
 
   // every call behind the phase stage: their events are created and destroyed, and their results invalidated, through this list
-  std::array<CallState*, 10> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &jgene.st, &ajgene.st}; }
+  std::array<CallState*, 11> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &jgene.st, &ajgene.st}; }
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;

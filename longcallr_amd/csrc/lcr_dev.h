@@ -406,6 +406,31 @@ void launch_k15_export(int32_t n_rows, const int32_t* row_iso, int32_t* host_row
 void launch_k15_tables(const BatchView& b, const int32_t* part_off, const void* rows, const uint64_t* keys, const uint64_t* chain, int32_t n_kept,
                        lcr_isoform* iso, lcr_isoform* host_iso /* pinned (device pointer) */, hipStream_t s);
 
+// k16_ends.hip: haplotype x transcript-end sites over the phased rows (lcr_transcript_ends).  hash_mask: the bits of a key's hash that route it
+void launch_k16_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, uint32_t strand_mode, int32_t* part_flag /* n_reads */,
+                      hipStream_t s);
+void launch_k16_sizes(const BatchView& b, const int32_t* part_off /* n_reads + 1 */, int32_t* tsz /* n_regions */,
+                      int32_t* host_ctl /* pinned (device pointer): [0] participating rows */, hipStream_t s);
+size_t launch_k16_row_bytes();    // bytes of a participating row's record
+size_t launch_k16_slot_bytes();   // bytes of a slot's record behind the insertion
+void launch_k16_walk(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, uint32_t strand_mode, uint32_t hash_mask,
+                     const int32_t* part_flag, const int32_t* part_off, const int32_t* tbl_off /* n_regions + 1 */, void* rows,
+                     uint64_t* tbl_key /* 0xff-filled */, uint32_t* tbl_cnt /* two per slot, zeroed */, hipStream_t s);
+void launch_k16_peaks(const uint64_t* tbl_key, const uint32_t* tbl_cnt, const int32_t* tbl_off, int32_t ng, int32_t n_slots, uint32_t window,
+                      uint32_t hash_mask, void* slots /* n_slots records: k16_peaks writes all of them, k16_assign (the second launch) the peaks' sums */,
+                      hipStream_t s);
+void launch_k16_flag(const void* slots, int32_t n_slots, uint32_t min_count, int32_t* flag, hipStream_t s);
+void launch_k16_offsets(const int32_t* tbl_off, const int32_t* koff /* n_slots + 1 */, int32_t ng, int32_t n_slots, int32_t* off, int32_t* host_off,
+                        int32_t* host_ctl /* [1] kept sites */, hipStream_t s);
+void launch_k16_place(const uint64_t* tbl_key, const void* slots, const int32_t* flag, const int32_t* koff, int32_t n_slots, const int32_t* off,
+                      int32_t n_kept, int32_t* cslot /* n_kept */, int32_t* crank /* n_kept */, lcr_end_site* site, hipStream_t s);
+void launch_k16_rows(int32_t n_part, void* rows, const void* slots, const int32_t* flag, const int32_t* koff, const int32_t* crank,
+                     int32_t* row_site /* 2 x n_rows, 0xff-filled */, uint64_t* n_assigned /* zeroed */, hipStream_t s);
+void launch_k16_export(int32_t n_rows, const int32_t* row_site, int32_t* host_row_site, const uint64_t* n_assigned,
+                       uint64_t* host_n_assigned /* pinned (device pointers) */, hipStream_t s);
+void launch_k16_tables(const BatchView& b, const int32_t* part_off, const void* rows, uint32_t window, int32_t n_kept, lcr_end_site* site,
+                       lcr_end_site* host_site /* pinned (device pointer) */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import _abi, annotation, api, ase, asj, bamio, coverage, isoforms, somatic, vcf
+from . import _abi, annotation, api, ase, asj, bamio, coverage, ends, isoforms, somatic, vcf
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -122,7 +122,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         asj_cluster_with_exons=False, asj_dna_vcf=None, asj_gene_coverage=False, annotation=None, exon_only=False, packed_upload=False,
         haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, hap_coverage_out=None,
         somatic_out=None, somatic_purity=0.3, somatic_min_baseq=0, somatic_min_score=0.0,
-        isoforms_out=None, isoform_min_count=10, isoform_min_junctions=1, **param_overrides):
+        isoforms_out=None, isoform_min_count=10, isoform_min_junctions=1,
+        ends_out=None, ends_min_count=10, ends_window=10, ends_strand="ts", **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -231,7 +232,15 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     Reads with fewer than isoform_min_junctions junctions take no part (at least 1: ValueError otherwise).  Every chunk calls
     Engine.isoforms behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Adds the
     stats isoforms (kept records, summed over chunks) and isoform_reads (fragment rows that hold a kept chain).  No other output depends
-    on it; without isoforms_out nothing changes."""
+    on it; without isoforms_out nothing changes.
+    ends_out / ends_min_count / ends_window / ends_strand: the allele-specific transcript-end table (include/lcr.h: lcr_transcript_ends;
+    ends.format_tsv), written to ends_out: one row per TSS / TES site -- a peak of the tagged reads' 5' or 3' ends that at least
+    ends_min_count ends within ends_window columns are assigned to -- with the reads per haplotype and the absent / present table of the
+    reads that end there or cover the site's window, tested like a junction's.  ends_strand: "ts" takes a read's transcript strand from
+    its ts tag only, "read" from the read's own strand where the tag is missing (direct RNA).  ends_window above 4096 or another
+    ends_strand is a ValueError before any GPU work.  Every chunk calls Engine.transcript_ends behind phase() / haplotag() and the other
+    table calls; that call waits for the phase stage, like theirs.  Adds the stats end_sites (kept records, summed over chunks) and
+    end_reads (ends assigned to a kept site).  No other output depends on it; without ends_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -250,6 +259,12 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         for what, v, least in (("isoform_min_count", isoform_min_count, 0), ("isoform_min_junctions", isoform_min_junctions, 1)):
             if isinstance(v, bool) or int(v) != v or not least <= int(v) < 1 << 32:
                 raise ValueError("%s must be an integer in [%d, 2^32), got %r" % (what, least, v))
+    if ends_out is not None:
+        for what, v, most in (("ends_min_count", ends_min_count, (1 << 32) - 1), ("ends_window", ends_window, 4096)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= most:
+                raise ValueError("%s must be an integer in [0, %d], got %r" % (what, most, v))
+        if ends_strand not in ("ts", "read"):
+            raise ValueError("ends_strand is 'ts' or 'read', got %r" % (ends_strand,))
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -326,14 +341,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     # for the stage in flight), its pileup is queued, THEN the previous chunk's results are collected (lcr_collect_phase: the getter that
     # outlives the binding) and turned into VCF text / read tags while this chunk's kernels run, then candidates / fragments / phase.
     results = {}            # chunk index -> dict(text, n_cand[, hp, ps, names])
-    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records, somatic records, isoform results) of the chunk whose phase stage runs
+    in_flight = [None] * len(engines)   # per engine: (chunk index, name, batch, want_reads, fragmat info, junction records, expression records, site records, coverage records, somatic records, isoform results, end-site results) of the chunk whose phase stage runs
     n_slot = [0] * len(engines)
     for E in engines:
         E.set_async_phase(async_phase)
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -374,6 +389,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                               int(np.count_nonzero(flagged & (som["status"] == somatic.SOM_OK))), int(np.count_nonzero(som["call"])))
         if iso is not None:     # (Engine.isoforms copied them out of the context's buffers)
             out["iso"] = (name, iso[0], iso[2], batch.start0, batch.len, int(np.count_nonzero(iso[3] >= 0)))
+        if tends is not None:   # (Engine.transcript_ends copied them out of the context's buffers)
+            out["ends"] = (name, tends[0], batch.start0, batch.len, tends[3]["n_assigned"])
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -431,7 +448,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             hcov = E.hap_coverage() if hap_coverage_out is not None else None                                 # (waits for the phase stage)
             som = E.somatic(purity=somatic_purity, min_baseq=somatic_min_baseq) if somatic_out is not None else None   # (waits for the phase stage)
             iso = E.isoforms(isoform_min_count, isoform_min_junctions) if isoforms_out is not None else None           # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso)
+            tends = E.transcript_ends(ends_min_count, ends_window, ends_strand) if ends_out is not None else None     # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends)
         finally:
             with free_lock:
                 free.append(k)
@@ -588,6 +606,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["isoform_reads"] = sum(r["iso"][5] for r in results)
         with open(isoforms_out, "w") as f:
             f.write(isoforms.format_tsv([r["iso"][:5] for r in results], isoform_min_count))
+    if ends_out is not None:
+        stats["end_sites"] = sum(int(r["ends"][1].size) for r in results)
+        stats["end_reads"] = sum(r["ends"][4] for r in results)
+        with open(ends_out, "w") as f:
+            f.write(ends.format_tsv([r["ends"][:4] for r in results], ends_min_count))
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

@@ -71,6 +71,10 @@ def main():
     ap.add_argument("--isoforms-out", help="write the allele-specific isoform table: one row per intron chain held by enough tagged reads, with its haplotype x presence table")
     ap.add_argument("--isoform-min-count", type=int, default=10, help="reads that must hold a chain exactly for it to be kept, and a table needs to be written")
     ap.add_argument("--isoform-min-junctions", type=int, default=1, help="a read takes part with AT LEAST this many junctions (>= 1)")
+    ap.add_argument("--ends-out", help="write the allele-specific transcript-end table: one row per TSS / TES site that enough tagged reads start or end at, with its haplotype x presence table")
+    ap.add_argument("--ends-min-count", type=int, default=10, help="read ends a site needs to be kept, and a table needs to be written")
+    ap.add_argument("--ends-window", type=int, default=10, help="columns around a peak whose ends belong to it (0 - 4096)")
+    ap.add_argument("--ends-strand", choices=("ts", "read"), default="ts", help="transcript strand from the ts tag only, or from the read's own strand where the tag is missing (direct RNA)")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -94,6 +98,8 @@ def main():
         ap.error("--somatic-min-baseq must lie in 0 - 30 (the fragment matrix clamps qualities to 30)")
     if a.isoform_min_count < 0 or a.isoform_min_junctions < 1:
         ap.error("--isoform-min-count must be >= 0 and --isoform-min-junctions >= 1 (an unspliced read has no chain)")
+    if a.ends_min_count < 0 or not 0 <= a.ends_window <= 4096:
+        ap.error("--ends-min-count must be >= 0 and --ends-window lie in 0 - 4096")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -113,7 +119,8 @@ def main():
                       ase_sites_out=a.ase_sites_out, ase_sites_min_baseq=a.ase_sites_min_baseq, hap_coverage_out=a.hap_coverage_out,
                       somatic_out=a.somatic_out, somatic_purity=a.somatic_purity, somatic_min_baseq=a.somatic_min_baseq,
                       somatic_min_score=a.somatic_min_score,
-                      isoforms_out=a.isoforms_out, isoform_min_count=a.isoform_min_count, isoform_min_junctions=a.isoform_min_junctions, **extra)
+                      isoforms_out=a.isoforms_out, isoform_min_count=a.isoform_min_count, isoform_min_junctions=a.isoform_min_junctions,
+                      ends_out=a.ends_out, ends_min_count=a.ends_min_count, ends_window=a.ends_window, ends_strand=a.ends_strand, **extra)
     print(json.dumps(st))
 
 
