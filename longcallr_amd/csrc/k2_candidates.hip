@@ -88,6 +88,7 @@ __global__ void __launch_bounds__(LCR_BLOCK) scan_phase3(OutT* __restrict__ out,
 // Phases 2 + 3 + the total in one kernel for scans of up to SCAN_FUSED_BLOCKS blocks (every scan of the stage calls): a block adds up
 // the sums of the blocks before it itself (a few hundred coalesced words) instead of waiting for a one-block kernel to scan them --
 // five tiny kernels per scan-and-gather become three (each is ~5 us of queue whatever it does).
+// (tests/test_scan_regime_cases_gpu.py covers both sides of this limit through launch_scan_i32; launch_scan_i32_to_i64 shares scan_phase1/2 but needs > 2 M rows to get past it: untested.)
 #define SCAN_FUSED_BLOCKS 2048
 template <typename OutT>
 __global__ void __launch_bounds__(LCR_BLOCK) scan_phase3x(OutT* __restrict__ out, int32_t n, const long long* __restrict__ block_sum, int32_t n_blocks,

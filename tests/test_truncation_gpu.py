@@ -1,5 +1,7 @@
 """lcr_discover_regions_truncated on the GPU against the loop restatement of util.rs:236-332 (tests/truncation_ref.py): regions and
-the count of columns above the cap, at the smallest shapes at which the kernels can go wrong."""
+the count of columns above the cap, at the smallest shapes at which the kernels can go wrong.  (The prefix scan under them has size
+limits of its own, at windows of hundreds of thousands and of millions of columns: tests/test_scan_regime_cases_gpu.py.  The depth
+builders of this file live in tests/scan_regime_cases.py, where the CPU test of the windowed reference shares them.)"""
 import ctypes as C
 import os
 
@@ -9,21 +11,11 @@ import pytest
 import helpers
 import truncation_ref as tr
 from longcallr_amd import _abi, bamio
+from scan_regime_cases import HAND_BUILT, TRUNC_CAP as CAP, depth_to_spans, hand_built, random_case, tiny_islands
 
 pytestmark = pytest.mark.gpu
 
-CAP = 3
 DEMO_LEN = 64444167
-
-
-def depth_to_spans(depth):
-    """spans whose depth vector is `depth`: one span per run of columns with depth >= level, for every level"""
-    depth = np.asarray(depth, dtype=np.int64)
-    spans = []
-    for level in range(1, int(depth.max()) + 1):
-        edges = np.flatnonzero(np.diff(np.concatenate(([0], (depth >= level).view(np.int8), [0]))))
-        spans += list(zip(edges[0::2].tolist(), edges[1::2].tolist()))
-    return spans
 
 
 def arrays(spans):
@@ -68,40 +60,7 @@ def check_off(E, spans, contig_len, max_depth):
     assert E.discover_regions(rs, re_, contig_len) == base
 
 
-def hand_built(variant, tail):
-    """depth of a contig of 4096 whose first covered column is 7 (w: window-relative -> contig position), cap = CAP"""
-    L, off = 4096, 7
-    d = np.zeros(L, dtype=np.int64)
-    w = lambda r: r + off
-    d[7:10] = 5            # an over-deep stretch on the first covered column: counts for the first region
-    d[10:20] = CAP         # exactly the cap: kept
-    d[20:22] = CAP + 1     # one above: break; column 20 closes (10, 10) and counts for it, column 21 for the next region
-    d[22] = 2              # a single kept column between two over-deep stretches: stays pending ...
-    d[23:30] = 6
-    d[30:50] = 1           # ... and starts the region that ends here: max over column 21, the column, the stretch, the island
-    d[60:70] = 2
-    d[70:75] = 9           # two over-deep stretches one kept column apart
-    d[75] = 1
-    d[76:80] = 7
-    d[80:90] = 2
-    if variant == 0:       # an island ends at window column 1023, the next starts at 1025
-        d[w(1000):w(1024)] = 2; d[w(1024)] = 4; d[w(1025):w(1040)] = 1
-    elif variant == 1:     # start at 1023, end at 1024
-        d[w(1000):w(1022)] = 2; d[w(1022)] = 4; d[w(1023):w(1025)] = 3; d[w(1025):w(1030)] = 5
-    else:                  # start at 1024, end at 1025
-        d[w(1000):w(1023)] = 2; d[w(1023)] = 0; d[w(1024):w(1026)] = 1; d[w(1026)] = 8; d[w(1027):w(1040)] = 2
-    # an over-deep stretch over more than two whole 1024-column blocks, largest in the middle one; it is the "break run in front" of the island behind it
-    d[w(1100):w(3200)] = 5
-    d[w(2500)] = 8
-    d[w(3200):w(3300)] = 2
-    if tail == "deep":     # an over-deep stretch on the contig's last column: counts for nothing
-        d[3900:4000] = 1; d[4000:4096] = 6
-    else:                  # an island that reaches the contig's last column: emitted after the loop
-        d[3990:4000] = 4; d[4000:4096] = 2
-    return d, L
-
-
-@pytest.mark.parametrize("variant,tail", [(0, "deep"), (1, "island"), (2, "deep")])
+@pytest.mark.parametrize("variant,tail", HAND_BUILT)
 def test_hand_built_spans(engine_cls, variant, tail):
     d, L = hand_built(variant, tail)
     assert 3200 - 1100 >= 2049
@@ -135,16 +94,7 @@ def test_degenerate_cases(engine_cls):
 def test_many_tiny_islands(engine_cls):
     """depth alternating around the cap every one or two columns over 6000 columns: more islands than a block has threads, islands of
     one column next to each other, every thread's four columns holding several runs"""
-    rng = np.random.default_rng(21)
-    L, first = 9000, 1500
-    d = np.zeros(L, dtype=np.int64)
-    i, kept, n_isl = first, True, 0
-    while i < first + 6000:
-        n = int(rng.integers(1, 3))
-        d[i:i + n] = rng.integers(CAP - 1, CAP + 1) if kept else rng.integers(CAP + 1, CAP + 4)
-        n_isl += kept
-        i += n
-        kept = not kept
+    d, L, n_isl = tiny_islands()
     assert n_isl > 1024
     spans = depth_to_spans(d)
     E = engine_cls(0, _abi.make_params())
@@ -153,13 +103,6 @@ def test_many_tiny_islands(engine_cls):
     check(E, spans, L, CAP + 1)
     check_off(E, spans, L, int(d.max()))
     E.close()
-
-
-def random_case():
-    rng = np.random.default_rng(3)
-    st = np.sort(rng.integers(0, 200000, size=300))
-    ln = rng.integers(1, 400, size=300)
-    return list(zip(st.tolist(), (st + ln).tolist())), 200100
 
 
 def covered_depths(spans, L):

@@ -5,7 +5,10 @@ longcallr_amd.bamio and of oracle_np.discover_regions (which restates the functi
 One liberty, for contigs of tens of megabases: the depth vector and the column loop cover only [lo, hi], lo the first covered
 column and hi the column behind the last covered one (if the contig has it).  Every column outside has depth 0 and is a break
 whatever the cap; in front of lo nothing is pending and max_coverage is 0, so those iterations change no state, and behind hi
-the pending region has been emitted at hi (or is emitted after the loop, with the same state), so neither do those."""
+the pending region has been emitted at hi (or is emitted after the loop, with the same state), so neither do those.
+
+discover_np is the same function over whole arrays, for windows of millions of columns (tests/scan_regime_cases.py), where the
+column loop takes seconds per call; tests/test_scan_regime_cases.py holds it to the loop on every small case."""
 import numpy as np
 
 
@@ -46,3 +49,46 @@ def discover(spans, ref_len, truncation=False, truncation_coverage=200000):
     if region_end > region_start:            # util.rs:320-330
         out.append((region_start, region_end - region_start + 1, max_coverage))
     return out, n_truncated
+
+
+def window_depth(spans, ref_len):
+    """(lo, depth): the int64 depth of the columns [lo, hi] of `discover` (a difference array and its cumsum), or None without a valid span"""
+    a = np.asarray(spans, dtype=np.int64).reshape(-1, 2)
+    s, e = np.maximum(a[:, 0], 0), np.minimum(a[:, 1], ref_len)
+    ok = s < e
+    s, e = s[ok], e[ok]
+    if s.size == 0:
+        return None
+    lo = int(s.min())
+    n = min(int(e.max()), ref_len - 1) - lo + 1           # e - lo <= n: the difference array has n + 1 entries
+    diff = np.bincount(s - lo, minlength=n + 1).astype(np.int64) - np.bincount(e - lo, minlength=n + 1)
+    return lo, np.cumsum(diff)[:n]
+
+
+def regions_of_depth(depth, lo, truncation=False, truncation_coverage=200000):
+    """the column loop of `discover` over the window's depth vector (depth[i] = column lo + i), island by island -> (regions, n_truncated)"""
+    depth = np.asarray(depth, dtype=np.int64)
+    kept = depth > 0
+    n_truncated = 0
+    if truncation:
+        kept &= depth <= truncation_coverage
+        n_truncated = int((depth > truncation_coverage).sum())
+    edges = np.flatnonzero(np.diff(np.concatenate(([0], kept.view(np.int8), [0]))))
+    out = []
+    pend, first = -1, 0          # start of the pending region; first column behind the last emission (max_coverage runs from there)
+    for s, e in zip(edges[0::2].tolist(), (edges[1::2] - 1).tolist()):      # islands, both ends included
+        if pend < 0:
+            pend = s
+        if e > pend:             # region_end > region_start: emitted at the first break behind the island, or after the loop
+            at = min(e + 1, depth.size - 1)
+            out.append((pend + lo, e - pend + 1, int(depth[first:at + 1].max())))
+            pend, first = -1, at + 1
+    return out, n_truncated
+
+
+def discover_np(spans, ref_len, truncation=False, truncation_coverage=200000):
+    """`discover` without the column loop: the same arguments, the same (regions, n_truncated)"""
+    w = window_depth(spans, ref_len)
+    if w is None:
+        return [], 0
+    return regions_of_depth(w[1], w[0], truncation, truncation_coverage)
