@@ -1149,7 +1149,9 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * preset allows, -1 = never); round 6: "chain_ties" (0: chain regions of workgroup scope keep the tie contract of round 5: sigma ties
  * only), "redo_lds" (bytes of dynamic LDS of the enumeration branch's repair pass; 0: its matrices in global memory), "fuse_filter",
  * "spec_compact" (0: lcr_candidates waits for the survivors' number before it queues their compaction), "lean_planes" (0: lcr_pileup always stores
- * the planes of the tiles with records -- and, on the ONT presets, the filter flags -- instead of handing the filter's survivors to lcr_candidates), "own_fill" (0: hipMemsetAsync instead of the
+ * the planes of the tiles with records -- and, on the ONT presets, the filter flags -- instead of handing the filter's survivors to lcr_candidates), "fold_indels" (0: the CIGAR
+ * decode gives every 1-base insertion / deletion a record of its own instead of a flag of the aligned block in front of it; same results, more
+ * records: lcr_pileup_records), "own_fill" (0: hipMemsetAsync instead of the
  * library's fill kernels), "fill_selftest" (checks those kernels against the host; LCR_E_DEVICE on a difference), "host_trace" (1: a
  * "[host]" line of wall-clock marks per lcr_phase on stderr; process-wide like own_fill), "iso_hash_bits" (0 .. 64, default 64: lcr_isoforms
  * routes a chain by the low n bits of its hash only -- 0 sends every chain of a region down one probe sequence; the results are the same
@@ -1183,6 +1185,11 @@ int lcr_kernel_ms(lcr_ctx*, int kernel, float* ms);
  * number if lcr_candidates has not run yet.  Planes stored later for a getter are not counted.  See DESIGN.md. */
 int lcr_pileup_bytes(lcr_ctx*, int64_t* bytes);
 int lcr_pileup_stage_bytes(lcr_ctx*, int64_t* bytes);
+/* What the last lcr_pileup's CIGAR decode produced: `items` = the M / D / I / N ops that count somewhere (the N above), `records` = the 8-byte
+ * records it cut them into for the tally -- one per tile an item touches, none for a 1-base insertion or deletion that directly follows an
+ * aligned block of its read and travels as a flag of that block's record ("K0").  Both are the words lcr_pileup has
+ * fetched anyway: no wait, no copy.  LCR_E_STATE before lcr_pileup. */
+int lcr_pileup_records(lcr_ctx*, int64_t* items, int64_t* records);
 
 /* Memory given back by contexts (lcr_ctx_destroy, buffers that grow) is kept in a process-wide cache per device -- at most 24 GiB of HBM
  * and 2 GiB of page-locked host memory each -- and handed to the next context: a worker that recreates its context per task does not

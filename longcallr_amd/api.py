@@ -34,7 +34,7 @@ def _view_nocopy(ptr, dtype, n):
 
 _DEBUG_ENV = {"LCR_PHASE_PROF": "phase_prof", "LCR_GRID_MIN_ENTRIES": "grid_min_entries",
               "LCR_GRID_GENERIC": "grid_generic", "LCR_GRID_SPEC_LANES": "grid_spec_lanes", "LCR_GRID_SPEC_BATCH": "grid_spec_batch", "LCR_POST_HALF": "post_half", "LCR_ENUM_FORCE_BIG": "enum_force_big",
-              "LCR_ENUM_FORCE_STREAM": "enum_force_stream", "LCR_ENUM_ELIDE": "enum_elide", "LCR_HIST_TILES": "hist_tiles", "LCR_TIE_ARITH": "tie_arith", "LCR_CHAIN_TIES": "chain_ties", "LCR_K3_HITS": "k3_hits", "LCR_K3_LIST_BLOCKS": "k3_list_blocks", "LCR_FUSE_FILTER": "fuse_filter", "LCR_ASYNC_PHASE": "async_phase", "LCR_HOST_TRACE": "host_trace", "LCR_OWN_FILL": "own_fill", "LCR_REDO_LDS": "redo_lds", "LCR_SPEC_COMPACT": "spec_compact", "LCR_LEAN_PLANES": "lean_planes"}
+              "LCR_ENUM_FORCE_STREAM": "enum_force_stream", "LCR_ENUM_ELIDE": "enum_elide", "LCR_HIST_TILES": "hist_tiles", "LCR_TIE_ARITH": "tie_arith", "LCR_CHAIN_TIES": "chain_ties", "LCR_K3_HITS": "k3_hits", "LCR_K3_LIST_BLOCKS": "k3_list_blocks", "LCR_FUSE_FILTER": "fuse_filter", "LCR_ASYNC_PHASE": "async_phase", "LCR_HOST_TRACE": "host_trace", "LCR_OWN_FILL": "own_fill", "LCR_REDO_LDS": "redo_lds", "LCR_SPEC_COMPACT": "spec_compact", "LCR_LEAN_PLANES": "lean_planes", "LCR_FOLD_INDELS": "fold_indels"}
 
 
 class Engine:
@@ -676,6 +676,12 @@ class Engine:
         b = C.c_int64()
         self._chk(self.lib.lcr_pileup_stage_bytes(self.h, C.byref(b)), "lcr_pileup_stage_bytes")
         return int(b.value)
+
+    def pileup_records(self):
+        """(items, records) of the last pileup: counting CIGAR ops, and the tile records K0 cut them into."""
+        items, recs = C.c_int64(), C.c_int64()
+        self._chk(self.lib.lcr_pileup_records(self.h, C.byref(items), C.byref(recs)), "lcr_pileup_records")
+        return int(items.value), int(recs.value)
 
 
 def host_register(*arrays):

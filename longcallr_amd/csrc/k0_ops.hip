@@ -9,6 +9,12 @@
 //   N-run      (tile column, length)                    util.rs:930-942; only in the tiles where an intron starts or
 //              ends -- the tiles it covers entirely get +1 in a tile-level difference array (tile_ndiff) instead.
 // ONT end trimming (util.rs:745-751) is applied here by clipping M blocks to the untrimmed read interval.
+// Fold (lcr_dev.h: REC_F_INS / REC_F_DEL; lcr_debug_set("fold_indels", 0) turns it off): an I, or a D of length 1, directly behind an M op of
+// its read -- 41 % of an ONT batch's records -- is not a record of its own but a flag of that M op's record in the M's last tile.  The M op
+// decides (it owns the geometry): its kept end is its own end, the point / the deleted column lies inside the region, the deleted column in
+// the same tile; the next op is not another read's first and lies in the same wave's ops (a register, or one shuffle at a thread border).
+// Anything else -- a longer D, a D on the next tile's first column, a trimmed or clipped M, the second of M I D -- keeps its record.  The
+// folded op still counts as an item; only the record count falls.
 //
 // Design (DESIGN.md §4 "K0").  The unit of work is the CIGAR *op*, not the read: the flat CIGAR array of the batch is
 // cut into blocks of K0_OPB consecutive ops (a workgroup each), whatever reads they belong to.
@@ -137,10 +143,12 @@ __device__ __forceinline__ void wave_lds_sync() {
 // Thread t owns the OPT consecutive ops [j0 + OPT t, j0 + OPT (t + 1)) of its block (one 16-byte load for OPT = 4): the
 // prefix sums need ONE wave scan per quantity (thread-local sums first), and "the previous op" is a register, or the
 // neighbour lane's last op.
+// (waves per SIMD: the kernel ran at seven -- 67 VGPRs -- before the fold's code word; left alone the compiler takes 73, one more than seven
+// waves allow.  With the target it fits 72 without a spill.)
 template <int OPT>
-__global__ void __launch_bounds__(K0_THREADS)
+__global__ void __launch_bounds__(K0_THREADS) __attribute__((amdgpu_waves_per_eu(7)))
 k0_ops(BatchView b, const ReadBin* __restrict__ rbin, const int32_t* __restrict__ blk_first_read, uint64_t cig0, uint32_t n_ops,
-       int ont, int D, int32_t n_tiles, int32_t* __restrict__ tile_fill, int32_t* __restrict__ tile_nchunks, int32_t* __restrict__ tile_ndiff,
+       int ont, int D, int fold, int32_t n_tiles, int32_t* __restrict__ tile_fill, int32_t* __restrict__ tile_nchunks, int32_t* __restrict__ tile_ndiff,
        K0Ctl* __restrict__ ctl, unsigned int* __restrict__ acct, unsigned int pool_sub, unsigned long long* __restrict__ recs,
        unsigned int desc_sub, uint32_t* __restrict__ desc_tile, uint2* __restrict__ desc_val, int2* __restrict__ read_scan) {
   constexpr int OPB = OPT * K0_THREADS, WOPS = OPT * 64;
@@ -189,7 +197,7 @@ k0_ops(BatchView b, const ReadBin* __restrict__ rbin, const int32_t* __restrict_
     x.vec = h.vec; x.ftile = h.ftile; x.seq_off = h.seq_off; x.reb = h.reb; x.rel_pos = h.rel_pos;
     const int strand = h.flags & 1, ts = (h.flags >> 1) & 3;
     const uint32_t tscls = ts == 0 ? 0u : ((strand == 0) == (ts == 1) ? 1u : 2u);
-    x.hi = ((uint32_t)strand << 28) | (tscls << 29);
+    x.hi = ((uint32_t)strand << REC_HI_STRAND_SHIFT) | (tscls << REC_HI_TS_SHIFT);
     const uint64_t cb = h.cig_off - cig0;
     x.cend = (int32_t)min<int64_t>((int64_t)cb + h.n_cig - (int64_t)j0, INT_MAX);
     *cb_out = cb; *ncig_out = h.n_cig;
@@ -230,9 +238,11 @@ k0_ops(BatchView b, const ReadBin* __restrict__ rbin, const int32_t* __restrict_
   if (K0_ABL == 1) return;
   // ---- 2. scan: exclusive prefixes of the reference / query advance over the block, read of every op
   int dr[OPT], dq[OPT], xr[OPT], xq[OPT], rid[OPT], mark[OPT];
+  unsigned int nxc;   // two bits per op of this thread: the fold code of the op behind it (0: nothing to fold)
   {
     bool bad_op = false;
     int tr = 0, tq = 0, tm = 0;
+    unsigned int selfc = 0u;
     const uint2 mk = *reinterpret_cast<const uint2*>(&ridh[OPT * tid]);   // (OPT == 4: four marks in one read)
 #pragma unroll
     for (int k = 0; k < OPT; k++) {
@@ -245,6 +255,13 @@ k0_ops(BatchView b, const ReadBin* __restrict__ rbin, const int32_t* __restrict_
       xr[k] = tr; xq[k] = tq;          // thread-local exclusive
       tr += dr[k]; tq += dq[k];
       tm = max(tm, mark[k]); rid[k] = tm;
+      // fold: what this op is for the M op in front of it -- 1: an I with bases, 2: a D of length 1, of the same read (no head mark)
+      if (fold && mark[k] == 0) selfc |= (op == 1 && len > 0 ? 1u : op == 2 && len == 1 ? 2u : 0u) << (2 * k);
+    }
+    {   // ... and the same about the op BEHIND each of this thread's: the last one's from the neighbour lane, none across a wave's end
+      unsigned int c0n = (unsigned int)__shfl_down((int)(selfc & 3u), 1, 64);
+      if (lane == 63) c0n = 0u;
+      nxc = (selfc >> 2) | (c0n << (2 * (OPT - 1)));
     }
     if (bad_op) atomicExch(&ctl->error, 1);
     const int ir = wave_incl_scan(tr), iq = wave_incl_scan(tq), im = wave_incl_max(tm);
@@ -294,9 +311,19 @@ k0_ops(BatchView b, const ReadBin* __restrict__ rbin, const int32_t* __restrict_
     int kd = ((m || d || isn) && len > 0 && ee > aa) ? (m ? 1 : d ? 2 : 4) : 0;
     if (ins && len > 0 && rs >= 1 && rs < H.vec) { kd = 3; aa = rs - 1; ee = rs; }
     kind[k] = kd; a[k] = aa; e[k] = ee; tb[k] = H.ftile;
+    // fold: the next op of the same read (no head mark, before the read's end, inside this wave's ops) is an I, or a D of length 1, and this M's
+    // kept end is its own end (neither clipped nor trimmed).  The indel's count then lies on this M's last column (I) or on the column behind it
+    // (D: in the same tile only) and is carried as a flag of the M's record in its last tile; the successor drops its own record below.  The
+    // conditions on `end` are the successor's own for having a record (ins / d above with rs = end).
+    unsigned int fl = 0u;
+    if (kd == 1 && ee == rs + len && ee < H.vec && p + 1 < H.cend) {   // (kd == 1: ee >= 1)
+      const unsigned int cn = (nxc >> (2 * k)) & 3u;
+      if (cn == 1u) fl = REC_HI_F_INS;
+      else if (cn == 2u && ((unsigned int)ee % (unsigned int)LCR_TILE) != 0u) fl = REC_HI_F_DEL;
+    }
     if (kd == 1) {   // byte offset of the base that would sit on column 0 of the region; the record adds its first column
       const unsigned long long o0 = H.seq_off + (unsigned long long)(long long)(qs - rs);
-      rlo[k] = (unsigned int)o0; rhi[k] = ((unsigned int)(o0 >> 32) & 0xffu) | H.hi;
+      rlo[k] = (unsigned int)o0; rhi[k] = ((unsigned int)(o0 >> 32) & 0xffu) | H.hi | fl;   // (the flags: for the record of the op's last tile, make_rec)
     } else {
       rlo[k] = kd == 2 ? (unsigned int)REC_KIND_D : kd == 3 ? (unsigned int)REC_KIND_I : (unsigned int)REC_KIND_N;
       rhi[k] = 0xffu;
@@ -312,16 +339,26 @@ k0_ops(BatchView b, const ReadBin* __restrict__ rbin, const int32_t* __restrict_
     }
   }
 
+  // a folded op leaves no record: it was counted as an item above, its count travels with its M's record
+  {
+    constexpr unsigned int FM = REC_HI_F_INS | REC_HI_F_DEL;
+    unsigned int fp = (unsigned int)__shfl_up((int)(kind[OPT - 1] == 1 ? rhi[OPT - 1] & FM : 0u), 1, 64);
+    if (lane == 0) fp = 0u;   // (lane 63 never folds)
+#pragma unroll
+    for (int k = OPT - 1; k >= 0; k--) if ((k == 0 ? fp : (kind[k - 1] == 1 ? rhi[k - 1] & FM : 0u)) != 0u) kind[k] = 0;
+  }
+
   if (K0_ABL == 3) { int x = 0; for (int k = 0; k < OPT; k++) x += a[k] + e[k] + tb[k] + kind[k] + (int)rlo[k] + (int)rhi[k]; if (x == 0x7fffffff) ctl->error = 9; return; }
   // record of op k in tile t (global tile index): columns [max(a, c0), min(e, c0 + LCR_TILE)) with c0 = (t - tb) * LCR_TILE
   auto make_rec = [&](int k, int t) -> unsigned long long {
     const int c0 = (t - tb[k]) * LCR_TILE;
     const int c_lo = max(a[k], c0), c_hi = min(e[k], c0 + LCR_TILE);
-    unsigned int lo = rlo[k], hi = rhi[k] | ((unsigned int)(c_lo - c0) << 8) | ((unsigned int)(c_hi - c_lo - 1) << 18);
+    unsigned int lo = rlo[k], hi = rhi[k] | ((unsigned int)(c_lo - c0) << REC_HI_COL_SHIFT) | ((unsigned int)(c_hi - c_lo - 1) << REC_HI_LEN_SHIFT);
     if (kind[k] == 1) {   // 40-bit add of the column
       const unsigned int s = lo + (unsigned int)c_lo;
       hi = (hi & ~0xffu) | (((hi & 0xffu) + (s < lo ? 1u : 0u)) & 0xffu);
       lo = s;
+      if (c_hi != e[k]) hi &= ~(REC_HI_F_INS | REC_HI_F_DEL);   // (only the record of the op's last tile carries its folded successor)
     }
     return ((unsigned long long)hi << 32) | lo;
   };
@@ -505,13 +542,13 @@ void launch_k0_desc_bin(const K0Ctl* ctl, const unsigned int* acct, unsigned int
                      chunk_off, cursor, (uint2*)sorted);
 }
 
-void launch_k0_ops(const BatchView& b, const ReadBin* rb, const int32_t* blk_first_read, uint64_t cig0, uint32_t n_ops, int ont, int D,
+void launch_k0_ops(const BatchView& b, const ReadBin* rb, const int32_t* blk_first_read, uint64_t cig0, uint32_t n_ops, int ont, int D, int fold,
                    int32_t n_tiles, int32_t* tile_fill, int32_t* tile_nchunks, int32_t* tile_ndiff, K0Ctl* ctl, unsigned int* acct,
                    unsigned int pool_sub, unsigned long long* recs, unsigned int desc_sub, uint32_t* desc_tile, void* desc_val, void* read_scan,
                    hipStream_t s) {
   if (b.n_reads == 0) return;
   if (n_ops == 0) { hipLaunchKernelGGL(k0_empty_reads, dim3((b.n_reads + LCR_BLOCK - 1) / LCR_BLOCK), dim3(LCR_BLOCK), 0, s, b, rb, ctl); return; }
   const int opb = launch_k0_opb();
-  hipLaunchKernelGGL(k0_ops<K0_OPT>, dim3((n_ops + opb - 1) / opb), dim3(K0_THREADS), 0, s, b, rb, blk_first_read, cig0, n_ops, ont, D, n_tiles,
+  hipLaunchKernelGGL(k0_ops<K0_OPT>, dim3((n_ops + opb - 1) / opb), dim3(K0_THREADS), 0, s, b, rb, blk_first_read, cig0, n_ops, ont, D, fold, n_tiles,
                      tile_fill, tile_nchunks, tile_ndiff, ctl, acct, pool_sub, recs, desc_sub, desc_tile, (uint2*)desc_val, (int2*)read_scan);
 }

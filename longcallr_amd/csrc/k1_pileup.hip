@@ -7,7 +7,8 @@
 //       belong to, emits per pileup tile (LCR_TILE columns of one region) compact 8-byte records:  M-segment (tile column,
 //       length, byte offset of its first read base, strand, transcript-strand class), D-run (column, length), I-point (the
 //       column in front of the insertion), N-run (column, length).  ONT end trimming (util.rs:745-751) is applied there by
-//       clipping M blocks to the untrimmed read interval.  An intron leaves an N-run record in its first and in its last tile
+//       clipping M blocks to the untrimmed read interval.  A 1-base insertion or deletion directly behind an M op of its read is
+//       a flag of that op's record, not a record (REC_F_INS / REC_F_DEL, lcr_dev.h).  An intron leaves an N-run record in its first and in its last tile
 //       only; the tiles it covers entirely get +1 in a tile-level difference array (tile_ndiff), whose prefix sum K1 adds as
 //       tile_nbase.  A block's records lie back to back in the pool, grouped by tile; k0_desc_bin sorts the (block, tile) chunk
 //       descriptors by tile and cuts them into entries of at most 16 records, which K1 walks.  What this file keeps of K0 are
@@ -15,7 +16,8 @@
 //       (ReadBin) and the first read of every op block (k0_bind_a / k0_bind_b and the single-purpose kernels they fuse).
 //   K1  one workgroup owns one tile and keeps all its counters in LDS.  It never sees a CIGAR:
 //       threads take one record each (coalesced 8-byte loads); whole M-segments and D-runs are
-//       difference-array range updates (2 LDS atomics per record, prefix-scanned at the end); then
+//       difference-array range updates (2 LDS atomics per record, prefix-scanned at the end), a flagged M-segment's
+//       folded indel one or two atomics more; then
 //       the segments' read bases are cut into 16-byte aligned pieces, one piece per thread, loaded
 //       with one 16-byte global load each (512 independent loads in flight per workgroup) and XORed
 //       against the tile's reference bytes in LDS: a piece that equals the reference is finished
@@ -360,20 +362,22 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
       const int slot = tid * K1_RPB + x;
       const unsigned long long rec = rec_cur[x];
       const bool hasrec = (has_cur >> x) & 1;
-      const unsigned long long off = rec & REC_OFF_MASK;
-      const int col0 = (int)((rec >> 40) & 1023u), len = (int)((rec >> 50) & 1023u) + 1;
+      const unsigned long long off = rec_off(rec);
+      const int col0 = rec_col(rec), len = rec_len(rec);
       int npieces = 0;
+      // (the insertion plane has no reader on the device: the lean form, which stores no plane, does not count it -- the full form replayed over
+      // the same records does, lcr_pileup.hip: planes_tally)
       if (hasrec) {
         if (off == REC_KIND_D) {          // util.rs:905-917: +1 per deleted reference position
           atomicAdd(&pl[P_DIFF_D * TSTRIDE + col0], 1u);
           atomicAdd(&pl[P_DIFF_D * TSTRIDE + col0 + len], 0xFFFFFFFFu);
         } else if (off == REC_KIND_I) {   // util.rs:918-929
-          atomicAdd(&pl[P_NI * TSTRIDE + col0], 1u);
+          if (!LEAN) atomicAdd(&pl[P_NI * TSTRIDE + col0], 1u);
         } else if (off == REC_KIND_N) {   // util.rs:930-942: +1 per intron position (the part of the run inside this tile)
           atomicAdd(&pl[P_DIFF_N * TSTRIDE + col0], 1u);
           atomicAdd(&pl[P_DIFF_N * TSTRIDE + col0 + len], 0xFFFFFFFFu);
         } else {                          // M-segment: range update now, per-base corrections in phase 2
-          const int strand = (int)((rec >> 60) & 1u), tscls = (int)((rec >> 61) & 3u);
+          const int strand = rec_strand(rec), tscls = rec_tscls(rec);
           uint32_t* dp = pl + (strand ? P_DIFF_DEPTH_R : P_DIFF_DEPTH_F) * TSTRIDE;
           atomicAdd(&dp[col0], 1u);
           atomicAdd(&dp[col0 + len], 0xFFFFFFFFu);
@@ -382,6 +386,13 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
             atomicAdd(&tp[col0], 1u);
             atomicAdd(&tp[col0 + len], 0xFFFFFFFFu);
           }
+          // the 1-base indel K0 folded into this record: a deletion of the column behind the segment (K0: col0 + len < LCR_TILE, so the end
+          // marker fits TSTRIDE), an insertion point on its last column
+          if (rec_f_del(rec)) {
+            atomicAdd(&pl[P_DIFF_D * TSTRIDE + col0 + len], 1u);
+            atomicAdd(&pl[P_DIFF_D * TSTRIDE + col0 + len + 1], 0xFFFFFFFFu);
+          }
+          if (!LEAN && rec_f_ins(rec)) atomicAdd(&pl[P_NI * TSTRIDE + col0 + len - 1], 1u);
           npieces = (len + 15) >> 4;   // 16-byte pieces from the segment's first base on (dword-unaligned 16-byte loads are fine on gfx950)
         }
       }
@@ -420,10 +431,9 @@ k1_pileup(BatchView b, DevParams prm, const int32_t* __restrict__ tile_region, c
       if (pstride == 1) lo = pown[p];
       else { lo = pown[p / pstride]; while (pstart[lo + 1] <= p) lo++; }
       const unsigned long long rc = rec_s[lo];
-      const uint32_t rhi = (uint32_t)(rc >> 32);
-      const long long soff = (long long)(rc & REC_OFF_MASK);
-      const int scol = (int)((rhi >> 8) & 1023u), slen = (int)((rhi >> 18) & 1023u) + 1;
-      q.strand = (int)((rhi >> 28) & 1u);
+      const long long soff = (long long)rec_off(rc);
+      const int scol = rec_col(rc), slen = rec_len(rc);
+      q.strand = rec_strand(rc);
       const int d16 = 16 * (p - pstart[lo]);                              // piece d16 / 16 of the segment
       const long long A = soff + d16;                                     // byte address of the piece
       q.k_lo = 0; q.k_hi = min(16, slen - d16);                           // valid bytes

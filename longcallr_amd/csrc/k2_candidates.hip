@@ -388,9 +388,9 @@ k2_hist_tiles(BatchView b, const int32_t* __restrict__ tile_col0, const int32_t*
       const unsigned long long rec = nx;
       nx = nx2;
       nx2 = fetch(j + 2 * (HT_BLOCK / HT_LANES));
-      const unsigned long long off = rec & REC_OFF_MASK;
-      const bool live = off < REC_KIND_N;          // (else: idle slot, D / I / N record: no base -- an empty range, no branch)
-      const int col0 = (int)((rec >> 40) & 1023u), len = (int)((rec >> 50) & 1023u) + 1;
+      const unsigned long long off = rec_off(rec);
+      const bool live = rec_is_m(rec);             // (else: idle slot, D / I / N record: no base -- an empty range, no branch)
+      const int col0 = rec_col(rec), len = rec_len(rec);
       const int d_lo = max(0, c_lo - col0), d_hi = live ? min(len - 1, c_hi - col0) : -1;
       // (no branch before the atomic: a switch on the base and early returns cost twice as many scalar as vector instructions here)
       auto tally = [&](int dd, bool in, uint32_t base, uint32_t qual) {

@@ -240,6 +240,13 @@ int lcr_pileup_bytes(lcr_ctx* c, int64_t* bytes) {
   return rc;
 }
 
+int lcr_pileup_records(lcr_ctx* c, int64_t* items, int64_t* records) {
+  if (!c || !items || !records) return LCR_E_ARG;
+  if (c->stage < ST_PILED) { c->err = "lcr_pileup_records before lcr_pileup"; return LCR_E_STATE; }
+  *items = c->pile_items; *records = c->pile_recs;
+  return LCR_OK;
+}
+
 int lcr_pileup_stage_bytes(lcr_ctx* c, int64_t* bytes) {
   if (!c || !bytes) return LCR_E_ARG;
   int64_t staged = 0;
@@ -515,6 +522,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "fuse_filter") c->dbg_fuse_filter = value != 0;
   else if (k == "spec_compact") c->dbg_spec_compact = value != 0;
   else if (k == "lean_planes") c->dbg_lean_planes = value != 0;
+  else if (k == "fold_indels") c->dbg_fold_indels = value != 0;
   else if (k == "poison_planes") c->dbg_poison_planes = value != 0;
   else if (k == "iso_hash_bits") c->dbg_iso_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
   else if (k == "ends_hash_bits") c->dbg_ends_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 32));

@@ -110,7 +110,8 @@ struct lcr_ctx {
   DevBuf blk_first_read, read_scan, cig_compact, cig_off_new, cig_new_off32;   // K0 op blocks (k0_ops.hip)
   uint64_t cig0 = 0;      // index of the batch's first op in bv.cigar
   uint32_t n_ops = 0;     // ops of the batch (one flat op space)
-  int64_t n_items = 0;
+  int64_t pile_items = 0, pile_recs = 0;   // the last lcr_pileup: M / D / I / N items with a count, records K0 emitted for them (lcr_pileup_records)
+  int dbg_fold_indels = 1;   // lcr_debug_set("fold_indels"): 0 = K0 emits a record of its own for every item (no REC_F_INS / REC_F_DEL)
 
   // K1
   // Which planes exist after lcr_pileup ("Which planes exist when"):

@@ -69,15 +69,46 @@ struct DevParams {
   int32_t dbg;  // (unused; the K1 ablation switches are compile-time, see k1_pileup.hip)
 };
 
-// pass-1 survivor of the candidate filters (one per column that reaches the likelihood block)
 // K0's per-tile records (k0_ops.hip writes them, k1_pileup.hip and k2_hist_tiles read them), 64 bit:
-// [0,40) byte offset of the first read base | [40,50) tile column | [50,60) length-1 | [60] reverse strand |
-// [61,63) transcript-strand class (0 none, 1 -> [0], 2 -> [1]); D / I / N records carry a marker in the offset field
+// [0,40) byte offset of the first read base | [40,48) tile column | [48,56) length-1 | [56] REC_F_INS | [57] REC_F_DEL | [58,60) spare |
+// [60] reverse strand | [61,63) transcript-strand class (0 none, 1 -> [0], 2 -> [1]); D / I / N records carry a marker in the offset field.
+// The two flags are set on M records only (k0_ops.hip, "fold"): a 1-base indel that directly follows an M op of its read is not a record of
+// its own but a flag of that op's record in its last tile --
+//   REC_F_INS  one insertion point counted on the record's last column            (the I record it replaces: column col + len - 1)
+//   REC_F_DEL  a deletion of length 1 on the column behind the record's last one  (the D record it replaces: column col + len, length 1;
+//              K0 folds only where that column lies in the same tile)
+// Every reader goes through the accessors below.
+static_assert(LCR_TILE <= 256, "a record keeps its tile column and its length - 1 in 8 bits each");
 #define REC_OFF_MASK 0xFFFFFFFFFFull
 #define REC_KIND_D 0xFFFFFFFFFFull  // offset field of a D-run record
 #define REC_KIND_I 0xFFFFFFFFFEull  // offset field of an I-point record
 #define REC_KIND_N 0xFFFFFFFFFDull  // offset field of an N-run record (the part of an intron inside its first / last tile)
+// the fields above bit 32 as K0 assembles them in a record's high word
+#define REC_HI_COL_SHIFT 8
+#define REC_HI_LEN_SHIFT 16
+#define REC_HI_F_INS (1u << 24)
+#define REC_HI_F_DEL (1u << 25)
+#define REC_HI_STRAND_SHIFT 28
+#define REC_HI_TS_SHIFT 29
+#define REC_F_INS ((unsigned long long)REC_HI_F_INS << 32)
+#define REC_F_DEL ((unsigned long long)REC_HI_F_DEL << 32)
+#ifdef __HIPCC__
+__device__ __forceinline__ unsigned long long rec_off(unsigned long long rec) { return rec & REC_OFF_MASK; }
+__device__ __forceinline__ int rec_col(unsigned long long rec) { return (int)((uint32_t)(rec >> 40) & 255u); }
+__device__ __forceinline__ int rec_len(unsigned long long rec) { return (int)((uint32_t)(rec >> 48) & 255u) + 1; }
+__device__ __forceinline__ int rec_strand(unsigned long long rec) { return (int)((uint32_t)(rec >> 60) & 1u); }
+__device__ __forceinline__ int rec_tscls(unsigned long long rec) { return (int)((uint32_t)(rec >> 61) & 3u); }
+__device__ __forceinline__ bool rec_f_ins(unsigned long long rec) { return (rec & REC_F_INS) != 0; }
+__device__ __forceinline__ bool rec_f_del(unsigned long long rec) { return (rec & REC_F_DEL) != 0; }
+// kind of a record: 1 M-segment, 2 D-run, 3 I-point, 4 N-run (K0's numbering); an M-segment is whatever carries no marker
+__device__ __forceinline__ bool rec_is_m(unsigned long long rec) { return rec_off(rec) < REC_KIND_N; }
+__device__ __forceinline__ int rec_kind(unsigned long long rec) {
+  const unsigned long long off = rec_off(rec);
+  return off == REC_KIND_D ? 2 : off == REC_KIND_I ? 3 : off == REC_KIND_N ? 4 : 1;
+}
+#endif
 
+// pass-1 survivor of the candidate filters (one per column that reaches the likelihood block)
 struct Survivor {
   int64_t gcol;      // global column index (col_off[region] + column)
   int32_t region;
@@ -204,6 +235,7 @@ void launch_k0_cig_compact(const uint32_t* cigar, const uint64_t* cig_off, const
 int launch_k0_opb();   // ops per K0 workgroup
 void launch_k0_block_reads(const ReadBin* rbin, int32_t nr, uint64_t cig0, int32_t opb, int32_t n_blocks, int32_t* blk_first_read, hipStream_t s);
 void launch_k0_ops(const BatchView& b, const ReadBin* rb, const int32_t* blk_first_read, uint64_t cig0, uint32_t n_ops, int ont, int D,
+                   int fold /* 1-base indels behind an M op travel as flags of its record (REC_F_INS / REC_F_DEL); 0: every op its own record */,
                    int32_t n_tiles, int32_t* tile_fill, int32_t* tile_nchunks, int32_t* tile_ndiff, K0Ctl* ctl, unsigned int* acct /* launch_k0_acct_words() zeroed words */,
                    unsigned int pool_sub /* slots per shard */, unsigned long long* recs, unsigned int desc_sub, uint32_t* desc_tile, void* desc_val /* uint2 */,
                    void* read_scan /* n_reads x int2 scratch */, hipStream_t s);

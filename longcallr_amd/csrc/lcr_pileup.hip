@@ -63,7 +63,7 @@ int pile_queue_k0(lcr_ctx* c, const PileScratch& L, const PilePools& P, bool& ga
   // in front of it runs early)
   if (!gated) { HIPCHK(c, c->phase.gate_stream(c->stream)); gated = true; }
   Timer t(c, LCR_K_SPANS);
-  launch_k0_ops(c->bv, c->read_bin.as<ReadBin>(), c->blk_first_read.as<int32_t>(), c->cig0, c->n_ops, c->dp.ont, c->dp.dist_to_end, c->n_tiles,
+  launch_k0_ops(c->bv, c->read_bin.as<ReadBin>(), c->blk_first_read.as<int32_t>(), c->cig0, c->n_ops, c->dp.ont, c->dp.dist_to_end, c->dbg_fold_indels, c->n_tiles,
                 fill, fill + L.nch, fill + L.ndiff, reinterpret_cast<K0Ctl*>(fill + L.ctl), (unsigned int*)(fill + L.acct), P.pool_sub, c->k0_items.as<unsigned long long>(),
                 P.desc_sub, c->desc_tile.as<uint32_t>(), c->desc_val.p, c->read_scan.p, c->stream);
   return LCR_OK;
@@ -211,7 +211,7 @@ int lcr_pileup(lcr_ctx* c, const lcr_params* p) {
       P.desc_cap64 = std::max<size_t>(P.desc_cap64 * 2, ((size_t)ctl.desc_top + 1024) * P.n_shards);
     }
   }
-  c->n_items = (int32_t)ctl.n_recs;
+  c->pile_items = (int64_t)ctl.n_items; c->pile_recs = (int64_t)ctl.n_recs;
   // bytes K1 itself has to move: read bases once + 8-byte records + reference byte per column, 13 u32
   // planes written per column of a tile with records (the record-free tiles' planes are not written by this stage)
   // (8 bytes per M / D / I / N item: the extra records of items that cross a tile boundary are overhead, not algorithm)

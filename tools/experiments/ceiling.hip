@@ -69,9 +69,8 @@ __global__ void __launch_bounds__(256) k_compare(const uint8_t* __restrict__ bas
       const unsigned long long rc[2] = {((unsigned long long)v.y << 32) | v.x, ((unsigned long long)v.w << 32) | v.z};
 #pragma unroll
       for (int x = 0; x < 2; x++) {
-        const uint32_t hi = (uint32_t)(rc[x] >> 32);
-        const int col0 = (int)((hi >> 8) & 255u), len = (int)min((hi >> 18) & 1023u, (uint32_t)(LCR_TILE - 1 - col0)) + 1;
-        const int strand = (hi >> 28) & 1, ts = (hi >> 29) & 3;
+        const int col0 = rec_col(rc[x]), len = min(rec_len(rc[x]), LCR_TILE - col0);   // (record layout: lcr_dev.h)
+        const int strand = rec_strand(rc[x]), ts = rec_tscls(rc[x]);
         uint32_t* dp = pl + strand * TSTRIDE;
         atomicAdd(&dp[col0], 1u); atomicAdd(&dp[col0 + len], 0xFFFFFFFFu);
         if (ts) { uint32_t* tp = pl + (ts == 2 ? 3 : 2) * TSTRIDE; atomicAdd(&tp[col0], 1u); atomicAdd(&tp[col0 + len], 0xFFFFFFFFu); }
