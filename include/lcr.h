@@ -779,6 +779,63 @@ int lcr_get_transcript_ends(lcr_ctx*, lcr_end_list* out);
  * waits for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
 int lcr_transcript_ends_ms(lcr_ctx*, float* ms);
 
+/* Allele-specific intron retention (K17): the haplotype x {spliced, retained} table per intron -- which haplotype leaves an intron in its
+ * transcripts --, counted on the GPU from what lcr_phase or lcr_haplotag left there.  DESIGN.md section 1p.  Defined per region, as
+ * lcr_junctions.  Row r of region g is a row of lcr_get_fragmat: its read is row_read[r], its haplotype assignment[r], its phase set
+ * phase_set[r] (0 = none).
+ *   junctions, extent, blocks   of a read: the junction (s, l) of every N op with l >= 1, and rend, are exactly lcr_junctions'.  The
+ *       read's aligned blocks are the maximal stretches of [pos, rend) that hold none of those N ops: M, =, X and D all cover
+ *       (lcr_hap_coverage's rule); I, S, H, P and zero-length ops change nothing.
+ *   participating rows    assignment 1 or 2, and nothing else: there is no junction minimum, unspliced reads take part.  Every other read
+ *       takes no part in any count.
+ *   introns, kept introns n_spliced(g, s, l) = participating rows of g that hold the junction (s, l).  Kept iff n_spliced >= min_count
+ *       (min_count == 0 is treated as 1): an intron that no tagged read splices is not an event here.
+ *   classes               of a participating row at a kept intron [s, e), e = s + l, with the anchor a = `anchor`.  The row is looked at only
+ *       if it overlaps: pos < e && rend > s (signed 64-bit arithmetic throughout).
+ *         SPLICED   one of the row's junctions is exactly (s, l).
+ *         RETAINED  the row is not spliced, and one of its aligned blocks [bs, be) has bs <= s - a && be >= e + a; equivalently
+ *                   pos <= s - a, rend >= e + a and none of the row's N ops (s_i, l_i) has s_i < e + a && s_i + l_i > s - a.  s - a < 0
+ *                   is covered by no row.
+ *         OTHER     any other overlapping row: another donor or acceptor, a nested junction, a read that ends inside the intron, anchors
+ *                   that are too short.
+ *       SPLICED is asked first, so no row is in two classes.
+ *   record                n_spliced, n_retained, n_other: the rows of each class over every phase set.  motif: lcr_junctions' (1 = GT-AG,
+ *       2 = CT-AC, 0 = neither).  phase_set, n_phase_sets: lcr_junctions' rule over the SPLICED and RETAINED rows only -- count them per
+ *       value of ps; phase_set is the value with the most rows, ties to the smallest value, 0 a value like any other; n_phase_sets =
+ *       distinct values.  h1_spliced, h1_retained, h2_spliced, h2_retained count the rows of that phase set only.
+ *   order                 by region, then s, then l; independent of the batch's composition and of the order in which atomics land.  All
+ *       arithmetic is integer adds: bit-reproducible.
+ *   row_retained          one int32 per fragment row of the batch: the number of kept introns the row is RETAINED at, 0 for rows that
+ *       retain none or take no part.  (What a retention tag in the phased BAM would consume.)
+ *   totals                n_part = participating rows; n_retained_total = the sum of row_retained (64 bit) = the sum of n_retained.
+ * Not here: annotated introns or a per-gene form, partial retention (a read that covers part of the intron is OTHER), a cap on the length
+ * of D ops inside the intron, skipped exons, tags in the phased BAM.
+ * lcr_intron_retention needs the bound batch with the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed;
+ * params == NULL or anchor > 4096: LCR_E_ARG, the last call's records stay valid; more than 2^28 junction occurrences of participating
+ * rows in a batch: LCR_E_ARG), collects an asynchronous phase stage in flight first, queues a fixed number of kernels on the context's
+ * stream around at most two host waits on sizes, writes no buffer another stage or getter reads, and may be repeated with other params.
+ * The records die with the phase results: at the next candidate stage and at lcr_load_batch / lcr_bind_batch; lcr_get_intron_retention
+ * answers LCR_E_STATE then.  intron / intron_region_off (n_regions + 1) / row_retained: pinned host memory, valid until the next
+ * lcr_intron_retention -- the call's last kernels' stores (the zero offsets of a call that keeps nothing are the host's) --; dev_*: the same
+ * bytes in HBM.  intron / dev_intron are NULL without a record, row_retained / dev_row_retained without a fragment row. */
+typedef struct { uint32_t min_count, anchor, pad_[2]; } lcr_retention_params;      /* defaults 10, 10 */
+typedef struct {                 /* 56 bytes */
+  int32_t region; uint8_t motif; uint8_t pad_[3];
+  int64_t start0;                /* s: contig coordinate of the first skipped base */
+  int32_t len;                   /* l */
+  uint32_t n_spliced, n_retained, n_other;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1_spliced, h1_retained, h2_spliced, h2_retained;
+} lcr_retained_intron;
+typedef struct { int32_t n_regions, n_introns, n_rows, n_part; int64_t n_retained_total;
+                 const lcr_retained_intron* intron; const int32_t* intron_region_off; const int32_t* row_retained;
+                 const lcr_retained_intron* dev_intron; const int32_t* dev_row_retained; } lcr_retention_list;
+int lcr_intron_retention(lcr_ctx*, const lcr_retention_params*);
+int lcr_get_intron_retention(lcr_ctx*, lcr_retention_list* out);
+/* HIP-event time (ms) from the first to the last kernel of the last lcr_intron_retention with timing enabled (lcr_enable_timing), the
+ * host's waits for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_intron_retention_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.
@@ -1157,7 +1214,7 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * routes a chain by the low n bits of its hash only -- 0 sends every chain of a region down one probe sequence; the results are the same
  * bytes for every n, which is how the comparison of whole chains is tested), "ends_hash_bits" (0 .. 32, default 32: lcr_transcript_ends
  * routes an end's key by the low n bits of its hash only -- 0 makes every key of a region probe from its segment's first slot; the same
- * bytes for every n).  Unknown key: LCR_E_ARG.  The defaults are the
+ * bytes for every n), "ir_hash_bits" (0 .. 32, default 32: the same for lcr_intron_retention's junction keys).  Unknown key: LCR_E_ARG.  The defaults are the
  * product behaviour. */
 int lcr_debug_set(lcr_ctx*, const char* key, int64_t value);
 

@@ -222,6 +222,24 @@ class LcrEndList(C.Structure):   # include/lcr.h: lcr_end_list
                 ("site", C.c_void_p), ("site_region_off", C.c_void_p), ("row_site", C.c_void_p), ("dev_site", C.c_void_p), ("dev_row_site", C.c_void_p)]
 
 
+class LcrRetentionParams(C.Structure):   # include/lcr.h: lcr_retention_params (defaults 10, 10)
+    _fields_ = [("min_count", C.c_uint32), ("anchor", C.c_uint32), ("pad_", C.c_uint32 * 2)]
+
+
+# lcr_retained_intron (include/lcr.h): one kept intron of a region -- a junction that min_count tagged rows splice -- with the rows that
+# splice it, retain it or do neither, and its haplotype x {spliced, retained} table
+RETAINED_INTRON_DTYPE = np.dtype([("region", "<i4"), ("motif", "u1"), ("pad_", "u1", 3), ("start0", "<i8"), ("len", "<i4"), ("n_spliced", "<u4"),
+                                  ("n_retained", "<u4"), ("n_other", "<u4"), ("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("h1_spliced", "<u4"),
+                                  ("h1_retained", "<u4"), ("h2_spliced", "<u4"), ("h2_retained", "<u4")], align=True)
+assert RETAINED_INTRON_DTYPE.itemsize == 56, RETAINED_INTRON_DTYPE.itemsize
+
+
+class LcrRetentionList(C.Structure):   # include/lcr.h: lcr_retention_list
+    _fields_ = [("n_regions", C.c_int32), ("n_introns", C.c_int32), ("n_rows", C.c_int32), ("n_part", C.c_int32), ("n_retained_total", C.c_int64),
+                ("intron", C.c_void_p), ("intron_region_off", C.c_void_p), ("row_retained", C.c_void_p), ("dev_intron", C.c_void_p),
+                ("dev_row_retained", C.c_void_p)]
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

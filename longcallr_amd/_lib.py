@@ -27,6 +27,7 @@ SYMBOLS = [
     "lcr_somatic", "lcr_get_somatic", "lcr_somatic_ms",
     "lcr_isoforms", "lcr_get_isoforms", "lcr_isoforms_ms",
     "lcr_transcript_ends", "lcr_get_transcript_ends", "lcr_transcript_ends_ms",
+    "lcr_intron_retention", "lcr_get_intron_retention", "lcr_intron_retention_ms",
 ]
 
 _lib = None
@@ -160,5 +161,8 @@ def load():
     l.lcr_transcript_ends.argtypes = [vp, C.POINTER(_abi.LcrEndParams)]
     l.lcr_get_transcript_ends.argtypes = [vp, C.POINTER(_abi.LcrEndList)]
     l.lcr_transcript_ends_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_intron_retention.argtypes = [vp, C.POINTER(_abi.LcrRetentionParams)]
+    l.lcr_get_intron_retention.argtypes = [vp, C.POINTER(_abi.LcrRetentionList)]
+    l.lcr_intron_retention_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

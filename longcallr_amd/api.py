@@ -472,6 +472,31 @@ class Engine:
         self._chk(self.lib.lcr_transcript_ends_ms(self.h, C.byref(ms)), "lcr_transcript_ends_ms")
         return float(ms.value)
 
+    def intron_retention(self, min_count=10, anchor=10):
+        """lcr_intron_retention + lcr_get_intron_retention after phase() or haplotag(): the kept introns of every region -- the junctions
+        that at least min_count tagged rows splice -- with the rows that splice them, retain them (one aligned block covers the intron
+        and `anchor` columns on either side) or do neither, and their haplotype x {spliced, retained} tables (include/lcr.h) -> (records
+        as a structured array of _abi.RETAINED_INTRON_DTYPE, ordered by region, start and length; intron_region_off, n_regions + 1;
+        row_retained, per row of fragmat() the number of kept introns it retains; totals, a dict of n_part and n_retained), all
+        copied.  Waits for an asynchronous phase stage in flight; may be repeated with other parameters."""
+        p = _abi.LcrRetentionParams(int(min_count), int(anchor))
+        self._chk(self.lib.lcr_intron_retention(self.h, C.byref(p)), "lcr_intron_retention")
+        o = self._retention_list()
+        return (_view(o.intron, _abi.RETAINED_INTRON_DTYPE, o.n_introns), _view(o.intron_region_off, np.int32, o.n_regions + 1),
+                _view(o.row_retained, np.int32, o.n_rows), dict(n_part=int(o.n_part), n_retained=int(o.n_retained_total)))
+
+    def _retention_list(self):
+        """lcr_get_intron_retention: the last intron_retention()'s list (pinned host and HBM pointers)"""
+        o = _abi.LcrRetentionList()
+        self._chk(self.lib.lcr_get_intron_retention(self.h, C.byref(o)), "lcr_get_intron_retention")
+        return o
+
+    def intron_retention_ms(self):
+        """lcr_intron_retention_ms: HIP-event time of the last intron_retention()'s kernels, its host waits included (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_intron_retention_ms(self.h, C.byref(ms)), "lcr_intron_retention_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

@@ -9,7 +9,8 @@
 // lcr_site_counts.hip (lcr_site_counts, lcr_get_site_counts, lcr_site_counts_ms) and lcr_hap_coverage.hip (lcr_hap_coverage,
 // lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
 // lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth, lcr_ends.hip (lcr_transcript_ends,
-// lcr_get_transcript_ends, lcr_transcript_ends_ms) a fifth.  Every call behind the phase stage keeps its bookkeeping in one CallState
+// lcr_get_transcript_ends, lcr_transcript_ends_ms) a fifth, lcr_retention.hip (lcr_intron_retention, lcr_get_intron_retention,
+// lcr_intron_retention_ms) a sixth.  Every call behind the phase stage keeps its bookkeeping in one CallState
 // (below): lcr_ctx::post_calls() lists them for lcr_ctx_create / lcr_ctx_destroy / rewind_to.
 #pragma once
 #include <algorithm>
@@ -268,6 +269,17 @@ struct lcr_ctx {
   DevBuf d_end, d_end_row;                            // the records, row_site
   HostBuf h_end_ctl, h_end, h_end_off, h_end_row;     // pinned: {participating rows, kept sites, n_assigned (64 bit)}; the three outputs
 
+  // K17 (lcr_intron_retention): scratch and results of its own -- no other stage or getter reads them
+  CallState ret;             // lcr_get_intron_retention; ev: behind the two size waits, then behind the call's last kernel
+  int32_t ret_ng = 0, ret_n = 0, ret_nrows = 0, ret_npart = 0;
+  int dbg_ir_hash_bits = 32;     // lcr_debug_set("ir_hash_bits"): the low bits of a key's hash that route it; the results never depend on them
+  DevBuf r_part, r_npair, r_part_off, r_pair_off, r_tsz, r_tbl_off;   // per read: participates, junctions, their running sums; per region: its table segment
+  DevBuf r_rows, r_keys;                                              // per participating row: its record; its junction keys
+  DevBuf r_tbl_key, r_tbl_cnt, r_flag, r_koff;                        // per slot: key, rows that hold it, kept, kept in front
+  DevBuf r_off, r_ck, r_cc, r_cg, r_ntot;                             // per region: kept introns in front; per kept slot: key, count, region; n_retained_total
+  DevBuf d_ret, d_ret_row;                                            // the records, row_retained
+  HostBuf h_ret_ctl, h_ret, h_ret_off, h_ret_row;     // pinned: {participating rows, pairs, kept introns, -, n_retained_total (64 bit)}; the three outputs
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -286,7 +298,7 @@ struct lcr_ctx {
   AsjModes asj;
 
   // every call behind the phase stage: their events are created and destroyed, and their results invalidated, through this list
-  std::array<CallState*, 11> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &jgene.st, &ajgene.st}; }
+  std::array<CallState*, 12> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &ret, &jgene.st, &ajgene.st}; }
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;

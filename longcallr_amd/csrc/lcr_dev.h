@@ -463,6 +463,27 @@ void launch_k16_export(int32_t n_rows, const int32_t* row_site, int32_t* host_ro
 void launch_k16_tables(const BatchView& b, const int32_t* part_off, const void* rows, uint32_t window, int32_t n_kept, lcr_end_site* site,
                        lcr_end_site* host_site /* pinned (device pointer) */, hipStream_t s);
 
+// k17_retention.hip: haplotype x intron retention over the phased rows (lcr_intron_retention).  hash_mask: the bits of a key's hash that route it
+void launch_k17_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, int32_t* part_flag /* n_reads */,
+                      int32_t* npair /* n_reads: junctions of a participating row */, hipStream_t s);
+void launch_k17_sizes(const BatchView& b, const int32_t* part_off /* n_reads + 1 */, const int32_t* pair_off /* n_reads + 1 */, int32_t* tsz /* n_regions */,
+                      int32_t* host_ctl /* pinned (device pointer): [0] participating rows, [1] pairs */, hipStream_t s);
+size_t launch_k17_row_bytes();   // bytes of a participating row's record
+void launch_k17_emit(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, uint32_t hash_mask, const int32_t* part_flag,
+                     const int32_t* part_off, const int32_t* pair_off, const int32_t* tbl_off /* n_regions + 1; a segment may be empty */, void* rows,
+                     uint64_t* keys, uint64_t* tbl_key /* 0xff-filled */, uint32_t* tbl_cnt /* zeroed */, hipStream_t s);
+void launch_k17_flag(const uint64_t* tbl_key, const uint32_t* tbl_cnt, int32_t n_slots, uint32_t min_count, int32_t* flag, hipStream_t s);
+void launch_k17_offsets(const int32_t* tbl_off, const int32_t* koff /* n_slots + 1 */, int32_t ng, int32_t n_slots, int32_t* off, int32_t* host_off,
+                        int32_t* host_ctl /* [2] kept introns */, hipStream_t s);
+void launch_k17_place(const BatchView& b, const uint64_t* tbl_key, const uint32_t* tbl_cnt, const int32_t* flag, const int32_t* koff,
+                      const int32_t* tbl_off, int32_t n_slots, const int32_t* off, int32_t n_kept, uint64_t* ck, uint32_t* cc, int32_t* cgr /* n_kept each */,
+                      lcr_retained_intron* intron, hipStream_t s);
+void launch_k17_tables(const BatchView& b, const int32_t* part_off, const void* rows, const uint64_t* keys, uint32_t anchor, int32_t n_kept,
+                       lcr_retained_intron* intron, lcr_retained_intron* host_intron /* pinned (device pointer) */, int32_t* row_retained /* n_rows, zeroed */,
+                       uint64_t* n_total /* zeroed */, hipStream_t s);
+void launch_k17_export(int32_t n_rows, const int32_t* row_retained, int32_t* host_row_retained, const uint64_t* n_total,
+                       uint64_t* host_n_total /* pinned (device pointers) */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

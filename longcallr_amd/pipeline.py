@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import _abi, annotation, api, ase, asj, bamio, coverage, ends, isoforms, somatic, vcf
+from . import _abi, annotation, api, ase, asj, bamio, coverage, ends, isoforms, retention, somatic, vcf
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -123,7 +123,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         haplotag=False, ase_sites_out=None, ase_sites_min_baseq=13, hap_coverage_out=None,
         somatic_out=None, somatic_purity=0.3, somatic_min_baseq=0, somatic_min_score=0.0,
         isoforms_out=None, isoform_min_count=10, isoform_min_junctions=1,
-        ends_out=None, ends_min_count=10, ends_window=10, ends_strand="ts", **param_overrides):
+        ends_out=None, ends_min_count=10, ends_window=10, ends_strand="ts",
+        retention_out=None, retention_min_count=10, retention_anchor=10, retention_min_retained=1, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -240,7 +241,16 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     its ts tag only, "read" from the read's own strand where the tag is missing (direct RNA).  ends_window above 4096 or another
     ends_strand is a ValueError before any GPU work.  Every chunk calls Engine.transcript_ends behind phase() / haplotag() and the other
     table calls; that call waits for the phase stage, like theirs.  Adds the stats end_sites (kept records, summed over chunks) and
-    end_reads (ends assigned to a kept site).  No other output depends on it; without ends_out nothing changes."""
+    end_reads (ends assigned to a kept site).  No other output depends on it; without ends_out nothing changes.
+    retention_out / retention_min_count / retention_anchor / retention_min_retained: the allele-specific intron-retention table
+    (include/lcr.h: lcr_intron_retention; retention.format_tsv), written to retention_out: one row per intron that at least
+    retention_min_count tagged reads of a region splice, with the tagged reads that splice it, retain it -- one aligned block covers the
+    intron and retention_anchor columns on either side -- or do neither, the spliced / retained table per haplotype, tested like a
+    junction's, and the percent-intron-retention per haplotype.  Written are the introns whose table sums to retention_min_count and
+    whose retained cells sum to retention_min_retained.  A retention_anchor above 4096 or a negative value is a ValueError before any GPU
+    work.  Every chunk calls Engine.intron_retention behind phase() / haplotag() and the other table calls; that call waits for the phase
+    stage, like theirs.  Adds the stats retention_introns (kept records, summed over chunks) and retention_reads (fragment rows that
+    retain a kept intron).  No other output depends on it; without retention_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -265,6 +275,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                 raise ValueError("%s must be an integer in [0, %d], got %r" % (what, most, v))
         if ends_strand not in ("ts", "read"):
             raise ValueError("ends_strand is 'ts' or 'read', got %r" % (ends_strand,))
+    if retention_out is not None:
+        for what, v, most in (("retention_min_count", retention_min_count, (1 << 32) - 1), ("retention_anchor", retention_anchor, 4096),
+                              ("retention_min_retained", retention_min_retained, (1 << 32) - 1)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= most:
+                raise ValueError("%s must be an integer in [0, %d], got %r" % (what, most, v))
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -348,7 +363,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -391,6 +406,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["iso"] = (name, iso[0], iso[2], batch.start0, batch.len, int(np.count_nonzero(iso[3] >= 0)))
         if tends is not None:   # (Engine.transcript_ends copied them out of the context's buffers)
             out["ends"] = (name, tends[0], batch.start0, batch.len, tends[3]["n_assigned"])
+        if ret is not None:     # (Engine.intron_retention copied them out of the context's buffers)
+            out["retention"] = (name, ret[0], batch.start0, batch.len, int(np.count_nonzero(ret[2] > 0)))
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -449,7 +466,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             som = E.somatic(purity=somatic_purity, min_baseq=somatic_min_baseq) if somatic_out is not None else None   # (waits for the phase stage)
             iso = E.isoforms(isoform_min_count, isoform_min_junctions) if isoforms_out is not None else None           # (waits for the phase stage)
             tends = E.transcript_ends(ends_min_count, ends_window, ends_strand) if ends_out is not None else None     # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends)
+            ret = E.intron_retention(retention_min_count, retention_anchor) if retention_out is not None else None   # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret)
         finally:
             with free_lock:
                 free.append(k)
@@ -611,6 +629,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["end_reads"] = sum(r["ends"][4] for r in results)
         with open(ends_out, "w") as f:
             f.write(ends.format_tsv([r["ends"][:4] for r in results], ends_min_count))
+    if retention_out is not None:
+        stats["retention_introns"] = sum(int(r["retention"][1].size) for r in results)
+        stats["retention_reads"] = sum(r["retention"][4] for r in results)
+        with open(retention_out, "w") as f:
+            f.write(retention.format_tsv([r["retention"][:4] for r in results], retention_min_count, retention_min_retained))
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

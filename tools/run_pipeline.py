@@ -75,6 +75,10 @@ def main():
     ap.add_argument("--ends-min-count", type=int, default=10, help="read ends a site needs to be kept, and a table needs to be written")
     ap.add_argument("--ends-window", type=int, default=10, help="columns around a peak whose ends belong to it (0 - 4096)")
     ap.add_argument("--ends-strand", choices=("ts", "read"), default="ts", help="transcript strand from the ts tag only, or from the read's own strand where the tag is missing (direct RNA)")
+    ap.add_argument("--retention-out", help="write the allele-specific intron-retention table: one row per intron that enough tagged reads splice, with the reads that splice or retain it per haplotype")
+    ap.add_argument("--retention-min-count", type=int, default=10, help="tagged reads that must splice an intron for it to be kept, and a table needs to be written")
+    ap.add_argument("--retention-anchor", type=int, default=10, help="columns on either side of the intron a retaining read's aligned block must cover (0 - 4096)")
+    ap.add_argument("--retention-min-retained", type=int, default=1, help="retaining reads a table needs to be written")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -100,6 +104,8 @@ def main():
         ap.error("--isoform-min-count must be >= 0 and --isoform-min-junctions >= 1 (an unspliced read has no chain)")
     if a.ends_min_count < 0 or not 0 <= a.ends_window <= 4096:
         ap.error("--ends-min-count must be >= 0 and --ends-window lie in 0 - 4096")
+    if a.retention_min_count < 0 or a.retention_min_retained < 0 or not 0 <= a.retention_anchor <= 4096:
+        ap.error("--retention-min-count and --retention-min-retained must be >= 0 and --retention-anchor lie in 0 - 4096")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -120,7 +126,9 @@ def main():
                       somatic_out=a.somatic_out, somatic_purity=a.somatic_purity, somatic_min_baseq=a.somatic_min_baseq,
                       somatic_min_score=a.somatic_min_score,
                       isoforms_out=a.isoforms_out, isoform_min_count=a.isoform_min_count, isoform_min_junctions=a.isoform_min_junctions,
-                      ends_out=a.ends_out, ends_min_count=a.ends_min_count, ends_window=a.ends_window, ends_strand=a.ends_strand, **extra)
+                      ends_out=a.ends_out, ends_min_count=a.ends_min_count, ends_window=a.ends_window, ends_strand=a.ends_strand,
+                      retention_out=a.retention_out, retention_min_count=a.retention_min_count, retention_anchor=a.retention_anchor,
+                      retention_min_retained=a.retention_min_retained, **extra)
     print(json.dumps(st))
 
 
