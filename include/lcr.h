@@ -836,6 +836,79 @@ int lcr_get_intron_retention(lcr_ctx*, lcr_retention_list* out);
  * host's waits for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
 int lcr_intron_retention_ms(lcr_ctx*, float* ms);
 
+/* Phased small indels (K18): the insertions and deletions of a few bases that sit on one haplotype's reads -- a pileup count cannot tell a
+ * real 1-base deletion from homopolymer noise; the haplotype of every fragment row can --, normalised, counted and classed on the GPU from
+ * what lcr_phase or lcr_haplotag left there.  DESIGN.md section 1q.  Defined per region g with the window [w0, w1) = [start0, start0 + len),
+ * as lcr_junctions.  All arithmetic is signed 64 bit; the window's reference is compared without regard to case.  Row r of region g is a
+ * row of lcr_get_fragmat: its read is row_read[r], its haplotype assignment[r], its phase set phase_set[r] (0 = none).
+ *   participating rows    every fragment row of g, whatever its assignment (row k is the region's k-th read).  n_part is their number.
+ *   gaps of a row         walking the CIGAR from pos: every I, D and N op of length L >= 1 is a gap; its raw column s is the reference
+ *       column at the op, its reference length Lr is L for D and N and 0 for I.  Aligned blocks and rend are lcr_intron_retention's (M, =,
+ *       X and D cover; only an N of length >= 1 breaks a block).  An I or D op with s <= pos or s + Lr >= rend has no aligned base on one
+ *       side and is ignored entirely: it is no gap.  A row's gaps are in walk order; their starts and their ends (s + Lr) both ascend.
+ *   events                a D gap with L <= max_del is an event iff its raw placement has s >= w0 + 1 && s + Lr <= w1; an I gap with
+ *       L <= max_ins on the same condition, and only if its inserted bases (the L bases at the op's query offset: M, I, S, = and X consume
+ *       the query, from offset 0) are all A, C, G or T, either case.  Every other gap -- an over-long I or D, an insertion that holds
+ *       another letter, a placement outside the window, every N -- is a gap only.
+ *   left shift            DEL: while s > w0 + 1 && ref[s-1] == ref[s+L-1]: s -= 1.  INS with bases q: while s > w0 + 1 && ref[s-1] ==
+ *       q[L-1]: q = ref[s-1] + q[:L-1], s -= 1.  A reference letter outside ACGT stops the shift, and so do 1024 steps.  -> s_left and,
+ *       for INS, the rotated q.
+ *   right shift           from the left-shifted form, for the extent only.  DEL: while s + L < w1 && ref[s] == ref[s+L]: s += 1.  INS:
+ *       while s < w1 && ref[s] == q[0]: q = q[1:] + ref[s], s += 1.  The same stops, at most 1024 steps.  -> s_right; shift = s_right -
+ *       s_left.  The extent is [lo, hi) with lo = s_left and hi = s_right + L (DEL) or s_right (INS).
+ *   key                   (uint32)s_left << 32 | type << 31 | payload, payload = L (DEL) or L << 24 | seq (INS; seq: 2 bits per base of the
+ *       rotated q, A C G T = 0..3, first base lowest).  The key is exact: hashes only route, identity is the key's equality.  Hence
+ *       max_ins <= 12 and max_del <= 65535.
+ *   depth(g, x)           participating rows with an aligned block that holds column x (M, =, X and D cover, N does not).
+ *   kept events           cnt = participating rows that hold the key.  A row may hold a key twice -- two 1-base deletions inside one
+ *       homopolymer normalise to one placement --; it is counted once.  Kept iff cnt >= max(min_count, 1) && cnt * 1000 >=
+ *       (uint64)min_permille * depth(g, s_left - 1)  (s_left - 1 >= w0: the anchor base lies inside the window).
+ *   classes               of a participating row at a kept event, with lo_f = lo - flank, hi_f = hi + flank.  The row is looked at iff
+ *       pos < hi_f && rend > lo_f.
+ *         PRESENT   one of the row's event keys is the key.  Asked first.
+ *         ABSENT    not PRESENT, pos <= lo_f && rend >= hi_f, and none of the row's gaps -- those that are no events included -- touches
+ *                   [lo_f, hi_f]: a D or N gap touches iff s <= hi_f && s + L >= lo_f, an I gap iff lo_f <= s <= hi_f.  So: one clean
+ *                   aligned block over the whole extent plus flanks.  (lo_f < 0 is covered by no row.)
+ *         OTHER     every other row that is looked at.
+ *   record                n_present, n_absent, n_other: the rows of each class over all participating rows.  depth = depth(g, s_left - 1).
+ *       hrun: the length of the run of equal reference letters that starts at column s_left, inside the window, at most 255 (0 for an
+ *       insertion at w1).  phase_set, n_phase_sets: lcr_junctions' rule over the PRESENT and ABSENT rows with assignment 1 or 2 -- the
+ *       value with the most rows, ties to the smallest, 0 a value like any other; distinct values --; h1_present, h1_absent, h2_present,
+ *       h2_absent count those rows of that phase set only.
+ *   order                 by region, then by the key's numeric value (s_left, deletions before insertions, then L, then seq);
+ *       independent of the batch's composition and of the order in which atomics land.  All arithmetic is integer adds: bit-reproducible.
+ *   row_indels            one int32 per fragment row of the batch: the number of kept events the row is PRESENT at.
+ *   totals                n_part; n_events = event occurrences over all participating rows (a key a row holds twice counts twice here);
+ *       n_present_total = the sum of row_indels (64 bit) = the sum of n_present.
+ * Not here: indels in regions without fragment rows, insertions above 12 bases, multi-allelic merging, realignment, BAM tags.
+ * lcr_indels needs the bound batch with the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed; params ==
+ * NULL, flank > 4096, max_ins > 12, max_del > 65535 or more than 2^31 - 2 window columns plus regions: LCR_E_ARG, the last call's records
+ * stay valid; more than 2^28 gaps or event occurrences of participating rows in a batch: LCR_E_ARG), collects an asynchronous phase stage
+ * in flight first, queues a fixed number of kernels on the context's stream around at most two host waits on sizes, writes no buffer
+ * another stage or getter reads, and may be repeated with other params.  The records die with the phase results: at the next candidate
+ * stage and at lcr_load_batch / lcr_bind_batch; lcr_get_indels answers LCR_E_STATE then.  indel / indel_region_off (n_regions + 1) /
+ * row_indels: pinned host memory, valid until the next lcr_indels -- the call's last kernels' stores (the zero offsets of a call that keeps
+ * nothing are the host's) --; dev_*: the same bytes in HBM.  indel / dev_indel are NULL without a record, row_indels / dev_row_indels
+ * without a fragment row. */
+typedef struct { uint32_t min_count, min_permille, flank, max_ins, max_del, pad_[3]; } lcr_indel_params;  /* defaults 10, 150, 5, 12, 50 */
+typedef struct {                     /* 64 bytes */
+  int32_t region; uint8_t type;      /* 0 = DEL, 1 = INS */
+  uint8_t hrun; uint16_t shift;
+  int64_t start0;                    /* s_left */
+  int32_t len; uint32_t seq;         /* INS: 2 bits per base (A C G T = 0..3), first base in the lowest bits; DEL: 0 */
+  uint32_t depth, n_present, n_absent, n_other;
+  uint32_t phase_set, n_phase_sets;
+  uint32_t h1_present, h1_absent, h2_present, h2_absent;
+} lcr_indel;
+typedef struct { int32_t n_regions, n_indels, n_rows, n_part; int64_t n_events, n_present_total;
+                 const lcr_indel* indel; const int32_t* indel_region_off; const int32_t* row_indels;
+                 const lcr_indel* dev_indel; const int32_t* dev_row_indels; } lcr_indel_list;
+int lcr_indels(lcr_ctx*, const lcr_indel_params*);
+int lcr_get_indels(lcr_ctx*, lcr_indel_list* out);
+/* HIP-event time (ms) from the first to the last kernel of the last lcr_indels with timing enabled (lcr_enable_timing), the host's waits
+ * for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
+int lcr_indels_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.
@@ -1214,7 +1287,8 @@ int lcr_ctx_set_lock_dir(lcr_ctx*, const char* dir);
  * routes a chain by the low n bits of its hash only -- 0 sends every chain of a region down one probe sequence; the results are the same
  * bytes for every n, which is how the comparison of whole chains is tested), "ends_hash_bits" (0 .. 32, default 32: lcr_transcript_ends
  * routes an end's key by the low n bits of its hash only -- 0 makes every key of a region probe from its segment's first slot; the same
- * bytes for every n), "ir_hash_bits" (0 .. 32, default 32: the same for lcr_intron_retention's junction keys).  Unknown key: LCR_E_ARG.  The defaults are the
+ * bytes for every n), "ir_hash_bits" (0 .. 32, default 32: the same for lcr_intron_retention's junction keys), "indel_hash_bits"
+ * (0 .. 32, default 32: the same for lcr_indels' event keys).  Unknown key: LCR_E_ARG.  The defaults are the
  * product behaviour. */
 int lcr_debug_set(lcr_ctx*, const char* key, int64_t value);
 

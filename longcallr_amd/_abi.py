@@ -240,6 +240,25 @@ class LcrRetentionList(C.Structure):   # include/lcr.h: lcr_retention_list
                 ("dev_row_retained", C.c_void_p)]
 
 
+class LcrIndelParams(C.Structure):   # include/lcr.h: lcr_indel_params (defaults 10, 150, 5, 12, 50)
+    _fields_ = [("min_count", C.c_uint32), ("min_permille", C.c_uint32), ("flank", C.c_uint32), ("max_ins", C.c_uint32), ("max_del", C.c_uint32),
+                ("pad_", C.c_uint32 * 3)]
+
+
+# lcr_indel (include/lcr.h): one kept small indel of a region in its left-shifted form, with the rows that hold it, lack it or do neither,
+# and its haplotype x {present, absent} table
+INDEL_DTYPE = np.dtype([("region", "<i4"), ("type", "u1"), ("hrun", "u1"), ("shift", "<u2"), ("start0", "<i8"), ("len", "<i4"), ("seq", "<u4"),
+                        ("depth", "<u4"), ("n_present", "<u4"), ("n_absent", "<u4"), ("n_other", "<u4"), ("phase_set", "<u4"),
+                        ("n_phase_sets", "<u4"), ("h1_present", "<u4"), ("h1_absent", "<u4"), ("h2_present", "<u4"), ("h2_absent", "<u4")], align=True)
+assert INDEL_DTYPE.itemsize == 64, INDEL_DTYPE.itemsize
+
+
+class LcrIndelList(C.Structure):   # include/lcr.h: lcr_indel_list
+    _fields_ = [("n_regions", C.c_int32), ("n_indels", C.c_int32), ("n_rows", C.c_int32), ("n_part", C.c_int32), ("n_events", C.c_int64),
+                ("n_present_total", C.c_int64), ("indel", C.c_void_p), ("indel_region_off", C.c_void_p), ("row_indels", C.c_void_p),
+                ("dev_indel", C.c_void_p), ("dev_row_indels", C.c_void_p)]
+
+
 class LcrGeneAnnotation(C.Structure):   # include/lcr.h: lcr_gene_annotation (one contig's genes, 0-based half-open)
     _fields_ = [("n_genes", C.c_int32), ("n_exons", C.c_int32), ("span_start0", C.c_void_p), ("span_end0", C.c_void_p),
                 ("exon_off", C.c_void_p), ("exon_start0", C.c_void_p), ("exon_end0", C.c_void_p)]

@@ -28,6 +28,7 @@ SYMBOLS = [
     "lcr_isoforms", "lcr_get_isoforms", "lcr_isoforms_ms",
     "lcr_transcript_ends", "lcr_get_transcript_ends", "lcr_transcript_ends_ms",
     "lcr_intron_retention", "lcr_get_intron_retention", "lcr_intron_retention_ms",
+    "lcr_indels", "lcr_get_indels", "lcr_indels_ms",
 ]
 
 _lib = None
@@ -164,5 +165,8 @@ def load():
     l.lcr_intron_retention.argtypes = [vp, C.POINTER(_abi.LcrRetentionParams)]
     l.lcr_get_intron_retention.argtypes = [vp, C.POINTER(_abi.LcrRetentionList)]
     l.lcr_intron_retention_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_indels.argtypes = [vp, C.POINTER(_abi.LcrIndelParams)]
+    l.lcr_get_indels.argtypes = [vp, C.POINTER(_abi.LcrIndelList)]
+    l.lcr_indels_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

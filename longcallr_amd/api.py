@@ -497,6 +497,32 @@ class Engine:
         self._chk(self.lib.lcr_intron_retention_ms(self.h, C.byref(ms)), "lcr_intron_retention_ms")
         return float(ms.value)
 
+    def indels(self, min_count=10, min_permille=150, flank=5, max_ins=12, max_del=50):
+        """lcr_indels + lcr_get_indels after phase() or haplotag(): the kept small indels of every region -- the normalised insertions and
+        deletions that at least min_count fragment rows hold, and at least min_permille per mille of the depth at their anchor base --
+        with the rows that hold them, lack them (one clean aligned block over the event's extent and `flank` columns on either side) or do
+        neither, and their haplotype x {present, absent} tables (include/lcr.h) -> (records as a structured array of _abi.INDEL_DTYPE,
+        ordered by region and key; indel_region_off, n_regions + 1; row_indels, per row of fragmat() the number of kept events it holds;
+        totals, a dict of n_part, n_events and n_present), all copied.  Waits for an asynchronous phase stage in flight; may be repeated
+        with other parameters."""
+        p = _abi.LcrIndelParams(int(min_count), int(min_permille), int(flank), int(max_ins), int(max_del))
+        self._chk(self.lib.lcr_indels(self.h, C.byref(p)), "lcr_indels")
+        o = self._indel_list()
+        return (_view(o.indel, _abi.INDEL_DTYPE, o.n_indels), _view(o.indel_region_off, np.int32, o.n_regions + 1),
+                _view(o.row_indels, np.int32, o.n_rows), dict(n_part=int(o.n_part), n_events=int(o.n_events), n_present=int(o.n_present_total)))
+
+    def _indel_list(self):
+        """lcr_get_indels: the last indels()'s list (pinned host and HBM pointers)"""
+        o = _abi.LcrIndelList()
+        self._chk(self.lib.lcr_get_indels(self.h, C.byref(o)), "lcr_get_indels")
+        return o
+
+    def indels_ms(self):
+        """lcr_indels_ms: HIP-event time of the last indels()'s kernels, its host waits included (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_indels_ms(self.h, C.byref(ms)), "lcr_indels_ms")
+        return float(ms.value)
+
     def _ase_call(self, fn, what, sites, min_baseq, min_phase_score):
         """lcr_ase / lcr_ase_genes with the parental sites marshalled: None, numpy arrays (converted) or device tensors (read in place)"""
         p = _abi.LcrAseParams(int(min_baseq), float(self.params.min_phase_score if min_phase_score is None else min_phase_score))

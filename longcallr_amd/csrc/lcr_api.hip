@@ -527,6 +527,7 @@ int lcr_debug_set(lcr_ctx* c, const char* key, int64_t value) {
   else if (k == "iso_hash_bits") c->dbg_iso_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
   else if (k == "ends_hash_bits") c->dbg_ends_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 32));
   else if (k == "ir_hash_bits") c->dbg_ir_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 32));
+  else if (k == "indel_hash_bits") c->dbg_indel_hash_bits = (int)std::max<int64_t>(0, std::min<int64_t>(value, 32));
   else if (k == "grid_spec_batch") d.spec_batch = (int)value;
   else if (k == "grid_spec_lanes") d.spec_lanes = (int)std::max<int64_t>(1, std::min<int64_t>(value, 16));
   else { c->err = "lcr_debug_set: unknown key " + k; return LCR_E_ARG; }

@@ -10,7 +10,7 @@
 // lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
 // lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth, lcr_ends.hip (lcr_transcript_ends,
 // lcr_get_transcript_ends, lcr_transcript_ends_ms) a fifth, lcr_retention.hip (lcr_intron_retention, lcr_get_intron_retention,
-// lcr_intron_retention_ms) a sixth.  Every call behind the phase stage keeps its bookkeeping in one CallState
+// lcr_intron_retention_ms) a sixth, lcr_indels.hip (lcr_indels, lcr_get_indels, lcr_indels_ms) a seventh.  Every call behind the phase stage keeps its bookkeeping in one CallState
 // (below): lcr_ctx::post_calls() lists them for lcr_ctx_create / lcr_ctx_destroy / rewind_to.
 #pragma once
 #include <algorithm>
@@ -280,6 +280,19 @@ struct lcr_ctx {
   DevBuf d_ret, d_ret_row;                                            // the records, row_retained
   HostBuf h_ret_ctl, h_ret, h_ret_off, h_ret_row;     // pinned: {participating rows, pairs, kept introns, -, n_retained_total (64 bit)}; the three outputs
 
+  // K18 (lcr_indels): scratch and results of its own -- no other stage or getter reads them
+  CallState indel;           // lcr_get_indels; ev: behind the two size waits, then behind the call's last kernel
+  int32_t ind_ng = 0, ind_n = 0, ind_nrows = 0, ind_npart = 0;
+  int64_t ind_nev = 0;
+  int dbg_indel_hash_bits = 32;  // lcr_debug_set("indel_hash_bits"): the low bits of a key's hash that route it; the results never depend on them
+  DevBuf i_part, i_ngap, i_nev, i_part_off, i_gap_off, i_ev_off, i_tsz, i_tbl_off;   // per read: participates, gaps, events, their running sums; per region: its table segment
+  DevBuf i_rows, i_gaps, i_gap_read;                                  // per participating row: its record; per gap: its record, its read
+  DevBuf i_diff, i_dscan;                                             // per window column (+ 1 per region): block-end differences, their exclusive scan
+  DevBuf i_tbl_key, i_tbl_cnt, i_flag, i_koff;                        // per slot: key, rows that hold it, kept, kept in front
+  DevBuf i_off, i_ck, i_cc, i_cg, i_ntot;                             // per region: kept events in front; per kept slot: key, count, region; n_present_total
+  DevBuf d_ind, d_ind_row;                                            // the records, row_indels
+  HostBuf h_ind_ctl, h_ind, h_ind_off, h_ind_row;     // pinned: {participating rows, gaps, kept events, event occurrences, n_present_total (64 bit)}; the three outputs
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -298,7 +311,7 @@ struct lcr_ctx {
   AsjModes asj;
 
   // every call behind the phase stage: their events are created and destroyed, and their results invalidated, through this list
-  std::array<CallState*, 12> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &ret, &jgene.st, &ajgene.st}; }
+  std::array<CallState*, 13> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &ret, &indel, &jgene.st, &ajgene.st}; }
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;

@@ -484,6 +484,33 @@ void launch_k17_tables(const BatchView& b, const int32_t* part_off, const void* 
 void launch_k17_export(int32_t n_rows, const int32_t* row_retained, int32_t* host_row_retained, const uint64_t* n_total,
                        uint64_t* host_n_total /* pinned (device pointers) */, hipStream_t s);
 
+// k18_indels.hip: phased small indels over the fragment rows (lcr_indels).  hash_mask: the bits of a key's hash that route it.  diff / dscan:
+// the per-column difference array and its exclusive scan, a segment of len[g] + 1 words per region at col_off[g] + g (dscan: one word more)
+void launch_k18_count(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, uint32_t max_ins, uint32_t max_del,
+                      int32_t* part_flag, int32_t* ngap, int32_t* nev /* n_reads each */, hipStream_t s);
+void launch_k18_sizes(const BatchView& b, const int32_t* part_off, const int32_t* gap_off, const int32_t* ev_off /* n_reads + 1 each */, int32_t* tsz /* n_regions */,
+                      int32_t* host_ctl /* pinned (device pointer): [0] participating rows, [1] gaps, [3] event occurrences */, hipStream_t s);
+size_t launch_k18_row_bytes();   // bytes of a participating row's record
+size_t launch_k18_gap_bytes();   // bytes of a gap's record
+void launch_k18_emit(const BatchView& b, const int32_t* row_region_off, const lcr_read_record* rec, uint32_t max_ins, uint32_t max_del,
+                     const int32_t* part_flag, const int32_t* part_off, const int32_t* gap_off, void* rows, void* gaps, int32_t* gap_read /* n_gaps */,
+                     int32_t* diff /* zeroed */, hipStream_t s);
+void launch_k18_insert(const BatchView& b, const void* gaps, const int32_t* gap_read, const int32_t* gap_off, int32_t n_gaps,
+                       const int32_t* tbl_off /* n_regions + 1; a segment may be empty */, uint32_t hash_mask, uint64_t* tbl_key /* 0xff-filled */,
+                       uint32_t* tbl_cnt /* zeroed */, hipStream_t s);
+void launch_k18_flag(const BatchView& b, const uint64_t* tbl_key, const uint32_t* tbl_cnt, int32_t n_slots, const int32_t* tbl_off, const int32_t* dscan,
+                     uint32_t min_count, uint32_t min_permille, int32_t* flag, hipStream_t s);
+void launch_k18_offsets(const int32_t* tbl_off, const int32_t* koff /* n_slots + 1 */, int32_t ng, int32_t n_slots, int32_t* off, int32_t* host_off,
+                        int32_t* host_ctl /* [2] kept events */, hipStream_t s);
+void launch_k18_place(const BatchView& b, const uint64_t* tbl_key, const uint32_t* tbl_cnt, const int32_t* flag, const int32_t* koff,
+                      const int32_t* tbl_off, int32_t n_slots, const int32_t* off, const int32_t* dscan, int32_t n_kept, uint64_t* ck, uint32_t* cc,
+                      int32_t* cgr /* n_kept each */, lcr_indel* indel, hipStream_t s);
+void launch_k18_tables(const BatchView& b, const int32_t* part_off, const void* rows, const void* gaps, uint32_t flank, int32_t n_kept, lcr_indel* indel,
+                       lcr_indel* host_indel /* pinned (device pointer) */, int32_t* row_indels /* n_rows, zeroed */, uint64_t* n_total /* zeroed */,
+                       hipStream_t s);
+void launch_k18_export(int32_t n_rows, const int32_t* row_indels, int32_t* host_row_indels, const uint64_t* n_total,
+                       uint64_t* host_n_total /* pinned (device pointers) */, hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

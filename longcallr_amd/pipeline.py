@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import _abi, annotation, api, ase, asj, bamio, coverage, ends, isoforms, retention, somatic, vcf
+from . import _abi, annotation, api, ase, asj, bamio, coverage, ends, indels, isoforms, retention, somatic, vcf
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -124,7 +124,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         somatic_out=None, somatic_purity=0.3, somatic_min_baseq=0, somatic_min_score=0.0,
         isoforms_out=None, isoform_min_count=10, isoform_min_junctions=1,
         ends_out=None, ends_min_count=10, ends_window=10, ends_strand="ts",
-        retention_out=None, retention_min_count=10, retention_anchor=10, retention_min_retained=1, **param_overrides):
+        retention_out=None, retention_min_count=10, retention_anchor=10, retention_min_retained=1,
+        indels_out=None, indel_min_count=10, indel_min_permille=150, indel_flank=5, indel_max_ins=12, indel_max_del=50, **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -250,7 +251,16 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     whose retained cells sum to retention_min_retained.  A retention_anchor above 4096 or a negative value is a ValueError before any GPU
     work.  Every chunk calls Engine.intron_retention behind phase() / haplotag() and the other table calls; that call waits for the phase
     stage, like theirs.  Adds the stats retention_introns (kept records, summed over chunks) and retention_reads (fragment rows that
-    retain a kept intron).  No other output depends on it; without retention_out nothing changes."""
+    retain a kept intron).  No other output depends on it; without retention_out nothing changes.
+    indels_out / indel_min_count / indel_min_permille / indel_flank / indel_max_ins / indel_max_del: the phased small-indel calls
+    (include/lcr.h: lcr_indels; indels.format_vcf), written to indels_out: a VCF with the run's header plus the tags HRUN, SHIFT, AD, HC
+    and PV, and one record per kept event -- a normalised insertion of at most indel_max_ins (<= 12) or deletion of at most
+    indel_max_del (<= 65535) bases that at least indel_min_count fragment rows of a region hold, and at least indel_min_permille per
+    mille of the depth at its anchor base -- genotyped from the rows of each haplotype that hold it or cover it cleanly with indel_flank
+    (<= 4096) columns on either side (indels.genotype).  A value outside its range is a ValueError before any GPU work.  Every chunk
+    calls Engine.indels behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Adds
+    the stats indel_events (kept records, summed over chunks) and indel_calls (records written with PASS).  No other output depends on
+    it; without indels_out nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -278,6 +288,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     if retention_out is not None:
         for what, v, most in (("retention_min_count", retention_min_count, (1 << 32) - 1), ("retention_anchor", retention_anchor, 4096),
                               ("retention_min_retained", retention_min_retained, (1 << 32) - 1)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= most:
+                raise ValueError("%s must be an integer in [0, %d], got %r" % (what, most, v))
+    if indels_out is not None:
+        for what, v, most in (("indel_min_count", indel_min_count, (1 << 32) - 1), ("indel_min_permille", indel_min_permille, (1 << 32) - 1),
+                              ("indel_flank", indel_flank, 4096), ("indel_max_ins", indel_max_ins, 12), ("indel_max_del", indel_max_del, 65535)):
             if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= most:
                 raise ValueError("%s must be an integer in [0, %d], got %r" % (what, most, v))
     if exon_only and annotation is None:
@@ -363,7 +378,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret, ind = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -408,6 +423,8 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["ends"] = (name, tends[0], batch.start0, batch.len, tends[3]["n_assigned"])
         if ret is not None:     # (Engine.intron_retention copied them out of the context's buffers)
             out["retention"] = (name, ret[0], batch.start0, batch.len, int(np.count_nonzero(ret[2] > 0)))
+        if ind is not None:     # (Engine.indels copied them out of the context's buffers)
+            out["indels"] = (name, ind[0], [indels.alleles(r, batch.start0, batch.col_off, batch.ref) for r in ind[0]])
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -467,7 +484,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             iso = E.isoforms(isoform_min_count, isoform_min_junctions) if isoforms_out is not None else None           # (waits for the phase stage)
             tends = E.transcript_ends(ends_min_count, ends_window, ends_strand) if ends_out is not None else None     # (waits for the phase stage)
             ret = E.intron_retention(retention_min_count, retention_anchor) if retention_out is not None else None   # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret)
+            ind = (E.indels(indel_min_count, indel_min_permille, indel_flank, indel_max_ins, indel_max_del)
+                   if indels_out is not None else None)   # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret, ind)
         finally:
             with free_lock:
                 free.append(k)
@@ -634,6 +653,11 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["retention_reads"] = sum(r["retention"][4] for r in results)
         with open(retention_out, "w") as f:
             f.write(retention.format_tsv([r["retention"][:4] for r in results], retention_min_count, retention_min_retained))
+    if indels_out is not None:
+        text, n_pass = indels.format_vcf([r["indels"] for r in results], [name for name, _ in contig_lengths])
+        stats["indel_events"] = sum(int(r["indels"][1].size) for r in results)
+        stats["indel_calls"] = n_pass
+        write_vcf(indels_out, contig_lengths, [text], indels.INFO_LINES)
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

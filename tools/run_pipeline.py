@@ -79,6 +79,12 @@ def main():
     ap.add_argument("--retention-min-count", type=int, default=10, help="tagged reads that must splice an intron for it to be kept, and a table needs to be written")
     ap.add_argument("--retention-anchor", type=int, default=10, help="columns on either side of the intron a retaining read's aligned block must cover (0 - 4096)")
     ap.add_argument("--retention-min-retained", type=int, default=1, help="retaining reads a table needs to be written")
+    ap.add_argument("--indels-out", help="write the phased small-indel calls: a VCF with one record per normalised insertion or deletion that enough reads of a region hold, genotyped per haplotype")
+    ap.add_argument("--indel-min-count", type=int, default=10, help="reads that must hold an indel for it to be kept")
+    ap.add_argument("--indel-min-permille", type=int, default=150, help="... and their share of the depth at its anchor base, per mille")
+    ap.add_argument("--indel-flank", type=int, default=5, help="clean columns on either side of an indel's extent a read without it must cover (0 - 4096)")
+    ap.add_argument("--indel-max-ins", type=int, default=12, help="longest insertion that is an event (0 - 12)")
+    ap.add_argument("--indel-max-del", type=int, default=50, help="longest deletion that is an event (0 - 65535)")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -106,6 +112,9 @@ def main():
         ap.error("--ends-min-count must be >= 0 and --ends-window lie in 0 - 4096")
     if a.retention_min_count < 0 or a.retention_min_retained < 0 or not 0 <= a.retention_anchor <= 4096:
         ap.error("--retention-min-count and --retention-min-retained must be >= 0 and --retention-anchor lie in 0 - 4096")
+    if (a.indel_min_count < 0 or a.indel_min_permille < 0 or not 0 <= a.indel_flank <= 4096 or not 0 <= a.indel_max_ins <= 12
+            or not 0 <= a.indel_max_del <= 65535):
+        ap.error("--indel-min-count and --indel-min-permille must be >= 0, --indel-flank lie in 0 - 4096, --indel-max-ins in 0 - 12 and --indel-max-del in 0 - 65535")
     if a.asj_annotation and not a.asj_out:
         ap.error("--asj-annotation needs --asj-out")
     if (a.asj_cluster_with_exons or a.asj_dna_vcf or a.asj_gene_coverage) and not a.asj_annotation:
@@ -128,7 +137,9 @@ def main():
                       isoforms_out=a.isoforms_out, isoform_min_count=a.isoform_min_count, isoform_min_junctions=a.isoform_min_junctions,
                       ends_out=a.ends_out, ends_min_count=a.ends_min_count, ends_window=a.ends_window, ends_strand=a.ends_strand,
                       retention_out=a.retention_out, retention_min_count=a.retention_min_count, retention_anchor=a.retention_anchor,
-                      retention_min_retained=a.retention_min_retained, **extra)
+                      retention_min_retained=a.retention_min_retained,
+                      indels_out=a.indels_out, indel_min_count=a.indel_min_count, indel_min_permille=a.indel_min_permille, indel_flank=a.indel_flank,
+                      indel_max_ins=a.indel_max_ins, indel_max_del=a.indel_max_del, **extra)
     print(json.dumps(st))
 
 
