@@ -909,6 +909,51 @@ int lcr_get_indels(lcr_ctx*, lcr_indel_list* out);
  * for the sizes included; LCR_E_STATE without one.  Not a slot of lcr_kernel_ms: that list is closed. */
 int lcr_indels_ms(lcr_ctx*, float* ms);
 
+/* Read-backed linkage of nearby sites (K19): per pair of nearby candidates, how many rows of the fragment matrix carry which base at the
+ * first site AND which base at the second -- the count behind multi-nucleotide variants (two or three SNVs of one codon on one haplotype)
+ * and behind a check of the phase that consults neither lcr_phase's decisions nor the rows' haplotags --, counted on the GPU from what
+ * lcr_phase or lcr_haplotag left there.  DESIGN.md section 1r.  Candidate c is an index into lcr_get_candidates.
+ *   eligible site      LCR_PAIRS_ALL: a candidate without LCR_F_DENSE (a dense candidate has no entries).  LCR_PAIRS_PHASED: additionally
+ *       variant_type == 1, haplotype != 0 and phase_set != 0.
+ *   pairs              e_0 < e_1 < ... the eligible candidates of one region in candidate order: (a, b) = (e_i, e_{i+k}) is a pair iff
+ *       1 <= k <= max_partners (at most LCR_PAIRS_MAX_PARTNERS), both sites are in the same region and, with max_dist != 0,
+ *       pos[b] - pos[a] <= max_dist (inclusive; 0 = no distance limit).  k is a difference of ELIGIBLE RANKS -- not of candidate indices
+ *       and not the adjacency of entries inside a row: a candidate that is not eligible between two eligible ones takes no partner slot,
+ *       and a row without an entry at an intermediate site still counts for the outer pair.
+ *   joint row          a row with a CSR entry at a and one at b; any row: assignment and phase set are not consulted.  n_rows is their
+ *       number.  A joint row in which either entry has q = val & 31 < min_baseq goes to n_lowq; every other one adds 1 to n[x][y], x and y
+ *       the base codes A, C, G, T (val >> 6) at a and b.  min_baseq 0 counts everything; above 30 is LCR_E_ARG.
+ *   invariant          the sixteen cells and n_lowq add up to n_rows.
+ *   order              one record per pair, pairs with n_rows == 0 included, ordered by a, then b.  pair_off has n_cand + 1 entries: the
+ *       pairs whose first site is candidate c are [pair_off[c], pair_off[c + 1]), empty for a c that is not eligible.  Integer adds only:
+ *       bit-reproducible; a region processed alone gives the same records as inside any batch, apart from the candidate indices' offset.
+ * Instance: one region with non-dense het sites at columns 10, 11, 13, 40 (candidates 0..3), reference A and alternate G at each; ALL,
+ * max_partners 2, max_dist 3, min_baseq 13.  Pairs (10,11), (10,13), (11,13) and pair_off = [0, 2, 3, 3, 3]: (11,40) and (13,40) fail the
+ * distance, (10,40) is rank 3.  Row r0 has the reference base everywhere and adds n[A][A] to all three; r1 has G at 10 and 11 and a third
+ * base at 13 (no entry there): n[G][G] of (10,11) only; r2 has G at all three with quality 5 at column 11: n_lowq of (10,11) and (11,13),
+ * n[G][G] of (10,13).  With max_dist 2, (10,13) is gone and pair_off = [0, 1, 2, 2, 2].  PHASED with site 11 homozygous, max_partners 1
+ * and max_dist 0: the pairs are (10,13) and (13,40).
+ * lcr_site_pairs needs the phase results of lcr_phase or lcr_haplotag (LCR_E_STATE otherwise, nothing changed).  LCR_E_ARG, with the last
+ * call's records still valid: params == NULL, an unknown mode, max_partners 0 or above 8, min_baseq > 30, n_cand x max_partners above
+ * 2^31 - 1.  It collects an asynchronous phase stage in flight first, queues a fixed number of kernels on the context's stream without a
+ * host wait of its own (its buffers are sized from n_cand x max_partners; the last kernel leaves n_eligible and n_pairs in pinned memory,
+ * read behind the call's event in lcr_get_site_pairs), writes no buffer another stage or getter reads, and may be repeated with other
+ * parameters.  The records die with the phase results: at the next candidate stage and at lcr_load_batch / lcr_bind_batch;
+ * lcr_get_site_pairs answers LCR_E_STATE then.  pair / pair_off: pinned host memory the call's last kernel wrote, valid until the next
+ * lcr_site_pairs (pair is NULL without a pair); dev_pair / dev_pair_off: the same bytes in HBM. */
+enum { LCR_PAIRS_ALL = 0, LCR_PAIRS_PHASED = 1 };
+#define LCR_PAIRS_MAX_PARTNERS 8
+typedef struct { uint32_t mode, max_partners, max_dist, min_baseq; } lcr_site_pair_params;     /* defaults ALL, 2, 2, 13 */
+typedef struct { int32_t a, b; uint32_t n_rows, n_lowq; uint32_t n[4][4]; } lcr_site_pair;    /* 80 bytes */
+typedef struct { int32_t n_cand, n_eligible, n_pairs, pad_;
+                 const lcr_site_pair* pair; const int32_t* pair_off;
+                 const lcr_site_pair* dev_pair; const int32_t* dev_pair_off; } lcr_site_pair_list;
+int lcr_site_pairs(lcr_ctx*, const lcr_site_pair_params*);
+int lcr_get_site_pairs(lcr_ctx*, lcr_site_pair_list* out);
+/* HIP-event time (ms) of the last lcr_site_pairs' kernels with timing enabled (lcr_enable_timing); LCR_E_STATE without one.  Not a
+ * slot of lcr_kernel_ms: that list is closed. */
+int lcr_site_pairs_ms(lcr_ctx*, float* ms);
+
 /* Read -> gene (K8): the gene assignment of reads of the allele-specific scripts (allele_specific/longcallR-ase.py: assign_reads_to_gene
  * :197-305, repeated in longcallR-asj.py :238-272), on the GPU from the CIGARs and positions of the bound batch, and the per-gene form of
  * the K7 counts on top of it (lcr_ase_genes).  All coordinates 0-based half-open; DESIGN.md section 1d.

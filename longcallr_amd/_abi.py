@@ -159,6 +159,23 @@ SITE_COUNT_DTYPE = np.dtype([("phase_set", "<u4"), ("n_phase_sets", "<u4"), ("n_
 assert SITE_COUNT_DTYPE.itemsize == 64, SITE_COUNT_DTYPE.itemsize
 
 
+PAIRS_ALL, PAIRS_PHASED, PAIRS_MAX_PARTNERS = 0, 1, 8   # include/lcr.h: LCR_PAIRS_*
+
+
+class LcrSitePairParams(C.Structure):   # include/lcr.h: lcr_site_pair_params (defaults ALL, 2, 2, 13)
+    _fields_ = [("mode", C.c_uint32), ("max_partners", C.c_uint32), ("max_dist", C.c_uint32), ("min_baseq", C.c_uint32)]
+
+
+# lcr_site_pair (include/lcr.h): the joint rows of candidates a < b; n[x][y]: x / y = the base code ACGT at a / b
+SITE_PAIR_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("n_rows", "<u4"), ("n_lowq", "<u4"), ("n", "<u4", (4, 4))], align=True)
+assert SITE_PAIR_DTYPE.itemsize == 80, SITE_PAIR_DTYPE.itemsize
+
+
+class LcrSitePairList(C.Structure):   # include/lcr.h: lcr_site_pair_list
+    _fields_ = [("n_cand", C.c_int32), ("n_eligible", C.c_int32), ("n_pairs", C.c_int32), ("pad_", C.c_int32),
+                ("pair", C.c_void_p), ("pair_off", C.c_void_p), ("dev_pair", C.c_void_p), ("dev_pair_off", C.c_void_p)]
+
+
 # lcr_hap_cov_segment / lcr_hap_cov_region (include/lcr.h): a run of window columns with one depth triple n[k] (k = 0 unassigned, 1 / 2 the
 # haplotypes); a region's reads, maxima and covered bases per class
 HAP_COV_SEGMENT_DTYPE = np.dtype([("region", "<i4"), ("len", "<i4"), ("start0", "<i8"), ("n", "<u4", (3,)), ("pad_", "<u4")], align=True)

@@ -29,6 +29,7 @@ SYMBOLS = [
     "lcr_transcript_ends", "lcr_get_transcript_ends", "lcr_transcript_ends_ms",
     "lcr_intron_retention", "lcr_get_intron_retention", "lcr_intron_retention_ms",
     "lcr_indels", "lcr_get_indels", "lcr_indels_ms",
+    "lcr_site_pairs", "lcr_get_site_pairs", "lcr_site_pairs_ms",
 ]
 
 _lib = None
@@ -168,5 +169,8 @@ def load():
     l.lcr_indels.argtypes = [vp, C.POINTER(_abi.LcrIndelParams)]
     l.lcr_get_indels.argtypes = [vp, C.POINTER(_abi.LcrIndelList)]
     l.lcr_indels_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    l.lcr_site_pairs.argtypes = [vp, C.POINTER(_abi.LcrSitePairParams)]
+    l.lcr_get_site_pairs.argtypes = [vp, C.POINTER(_abi.LcrSitePairList)]
+    l.lcr_site_pairs_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = l
     return l

@@ -378,6 +378,32 @@ class Engine:
         self._chk(self.lib.lcr_site_counts_ms(self.h, C.byref(ms)), "lcr_site_counts_ms")
         return float(ms.value)
 
+    def site_pairs(self, mode="all", max_partners=2, max_dist=2, min_baseq=13):
+        """lcr_site_pairs + lcr_get_site_pairs after phase() or haplotag(): per pair of nearby eligible candidates of candidates() how
+        many rows carry which base at the first site and which at the second (include/lcr.h) -> (records as a structured array of
+        _abi.SITE_PAIR_DTYPE, ordered by a, then b; pair_off, n_cand + 1; n_eligible), copied.  mode: "all" (every candidate that is not
+        dense) or "phased" (phased hets only); max_dist 0: no distance limit.  Waits for an asynchronous phase stage in flight; may be
+        repeated with other parameters."""
+        modes = {"all": _abi.PAIRS_ALL, "phased": _abi.PAIRS_PHASED}
+        if mode not in modes:
+            raise ValueError("site_pairs: mode must be 'all' or 'phased', got %r" % (mode,))
+        p = _abi.LcrSitePairParams(modes[mode], int(max_partners), int(max_dist), int(min_baseq))
+        self._chk(self.lib.lcr_site_pairs(self.h, C.byref(p)), "lcr_site_pairs")
+        o = self.site_pairs_list()
+        return _view(o.pair, _abi.SITE_PAIR_DTYPE, o.n_pairs), _view(o.pair_off, np.int32, o.n_cand + 1), int(o.n_eligible)
+
+    def site_pairs_list(self):
+        """lcr_get_site_pairs: the last site_pairs()'s list (pinned host and HBM pointers)"""
+        o = _abi.LcrSitePairList()
+        self._chk(self.lib.lcr_get_site_pairs(self.h, C.byref(o)), "lcr_get_site_pairs")
+        return o
+
+    def site_pairs_ms(self):
+        """lcr_site_pairs_ms: HIP-event time of the last site_pairs()'s kernels (timing on)"""
+        ms = C.c_float()
+        self._chk(self.lib.lcr_site_pairs_ms(self.h, C.byref(ms)), "lcr_site_pairs_ms")
+        return float(ms.value)
+
     def hap_coverage(self):
         """lcr_hap_coverage + lcr_get_hap_coverage after phase() or haplotag(): the covered depth of every window column per haplotype
         class (0 unassigned, 1 / 2 as the HP tag) as run-length segments, and per region the reads, maxima and covered bases per class

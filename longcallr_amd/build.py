@@ -15,7 +15,8 @@ SOURCES = ["k0_ops.hip", "k0_unpack.hip", "k1_pileup.hip", "k2_candidates.hip", 
            "k15_isoforms.hip", "lcr_isoforms.hip",
            "k16_ends.hip", "lcr_ends.hip",
            "k17_retention.hip", "lcr_retention.hip",
-           "k18_indels.hip", "lcr_indels.hip"]   # (new units go to the end: the link order moves the bench line)
+           "k18_indels.hip", "lcr_indels.hip",
+           "k19_site_pairs.hip", "lcr_site_pairs.hip"]   # (new units go to the end: the link order moves the bench line)
 HEADERS = ["lcr_dev.h", "k0_unpack.h", "lcr_ctx.h", "lcr_phase_host.h", "k4_dev.h", "k4_types.h", "k4_grid.h", "k4_grid_batch.h", "k4_kernels.h", "k4_post.h", "k2_eval.h", "k7_sweep.h", "lcr_asj_args.h", "k13_hap_coverage.h", "k6_walk.h", "k18_walk.h", "col_segments.h", os.path.join("..", "..", "include", "lcr.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function"]

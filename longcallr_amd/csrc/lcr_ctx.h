@@ -10,7 +10,7 @@
 // lcr_get_hap_coverage, lcr_hap_coverage_ms) are two more calls behind either of them, lcr_somatic.hip (lcr_somatic, lcr_get_somatic,
 // lcr_somatic_ms) a third, lcr_isoforms.hip (lcr_isoforms, lcr_get_isoforms, lcr_isoforms_ms) a fourth, lcr_ends.hip (lcr_transcript_ends,
 // lcr_get_transcript_ends, lcr_transcript_ends_ms) a fifth, lcr_retention.hip (lcr_intron_retention, lcr_get_intron_retention,
-// lcr_intron_retention_ms) a sixth, lcr_indels.hip (lcr_indels, lcr_get_indels, lcr_indels_ms) a seventh.  Every call behind the phase stage keeps its bookkeeping in one CallState
+// lcr_intron_retention_ms) a sixth, lcr_indels.hip (lcr_indels, lcr_get_indels, lcr_indels_ms) a seventh, lcr_site_pairs.hip (lcr_site_pairs, lcr_get_site_pairs, lcr_site_pairs_ms) an eighth.  Every call behind the phase stage keeps its bookkeeping in one CallState
 // (below): lcr_ctx::post_calls() lists them for lcr_ctx_create / lcr_ctx_destroy / rewind_to.
 #pragma once
 #include <algorithm>
@@ -293,6 +293,13 @@ struct lcr_ctx {
   DevBuf d_ind, d_ind_row;                                            // the records, row_indels
   HostBuf h_ind_ctl, h_ind, h_ind_off, h_ind_row;     // pinned: {participating rows, gaps, kept events, event occurrences, n_present_total (64 bit)}; the three outputs
 
+  // K19 (lcr_site_pairs): scratch and results of its own -- no other stage or getter reads them
+  CallState pairs;           // lcr_get_site_pairs; ev: behind the call's last kernel (the call has no host wait)
+  int32_t sp_ncand = 0;
+  DevBuf sp_elig, sp_rank, sp_list, sp_erank, sp_m, sp_ctl;   // per candidate: eligible, its rank, rank -> candidate, rank or -1, pairs it starts; n_eligible
+  DevBuf sp_off, d_sp;                                        // pair_off (n_cand + 1); the records
+  HostBuf h_sp, h_sp_off, h_sp_ctl;                           // pinned: the records; pair_off; {n_eligible, n_pairs}
+
   // K8 (lcr_assign_genes): read -> gene of the bound batch; (lcr_ase_genes): the per-gene counts -- scratch and results of their own
   bool genes_valid = false;  // lcr_get_read_genes / lcr_ase_genes: the last lcr_assign_genes' result belongs to the bound batch (rewind_to)
   int32_t genes_nr = 0, genes_n_genes = 0;   // reads of that batch; genes of that annotation (lcr_junctions_genes takes the annotation again)
@@ -311,7 +318,7 @@ struct lcr_ctx {
   AsjModes asj;
 
   // every call behind the phase stage: their events are created and destroyed, and their results invalidated, through this list
-  std::array<CallState*, 13> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &ret, &indel, &jgene.st, &ajgene.st}; }
+  std::array<CallState*, 14> post_calls() { return {&hap, &junc, &ase, &agene, &sc, &hc, &som, &iso, &ends, &ret, &indel, &pairs, &jgene.st, &ajgene.st}; }
 
   // region discovery (N3)
   DevBuf rd_start, rd_end, rd_diff, rd_ex, rd_cnt, rd_off, rd_s, rd_e, rd_max;

@@ -511,6 +511,19 @@ void launch_k18_tables(const BatchView& b, const int32_t* part_off, const void* 
 void launch_k18_export(int32_t n_rows, const int32_t* row_indels, int32_t* host_row_indels, const uint64_t* n_total,
                        uint64_t* host_n_total /* pinned (device pointers) */, hipStream_t s);
 
+// k19_site_pairs.hip: base x base counts of nearby site pairs over the fragment matrix (lcr_site_pairs), in the order of their launches; the
+// two scans between them are launch_scan_i32.  elig / rank / list / erank / m: n_cand words each; off: n_cand + 1; pair: n_cand x max_partners
+void launch_k19_elig(const lcr_candidate* cand, int32_t n_cand, uint32_t mode, int32_t* elig, hipStream_t s);
+void launch_k19_list(const int32_t* elig, const int32_t* rank, int32_t n_cand, int32_t* list, int32_t* erank, hipStream_t s);
+void launch_k19_count(const lcr_candidate* cand, int32_t n_cand, const int32_t* erank, const int32_t* list, const int32_t* n_elig, uint32_t max_partners,
+                      uint32_t max_dist, int32_t* m, hipStream_t s);
+void launch_k19_init(int32_t n_cand, uint32_t max_partners, const int32_t* erank, const int32_t* list, const int32_t* off, lcr_site_pair* pair, hipStream_t s);
+void launch_k19_rows(int32_t n_rows, const int64_t* row_ptr, const int32_t* col, const uint8_t* val, int32_t n_cand, const int32_t* erank,
+                     const int32_t* off, uint32_t min_baseq, lcr_site_pair* pair, hipStream_t s);
+void launch_k19_export(int32_t n_cand, uint32_t max_partners, const int32_t* n_elig /* the first scan's total */, const int32_t* off, lcr_site_pair* pair,
+                       lcr_site_pair* host_pair, int32_t* host_off, int32_t* host_ctl /* pinned (device pointers): records, n_cand + 1 offsets, {n_eligible, n_pairs} */,
+                       hipStream_t s);
+
 // k8_genes.hip: read -> gene over the bound batch (lcr_assign_genes) and the per-gene counts on top of it (lcr_ase_genes)
 void launch_k8_check(const lcr_gene_annotation& a /* device arrays */, int32_t* bad /* zeroed */, hipStream_t s);
 void launch_k8_prefix_max(const lcr_gene_annotation& a, int64_t* pmax /* n_genes: running maximum of span_end0 */, hipStream_t s);

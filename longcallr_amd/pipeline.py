@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from . import _abi, annotation, api, ase, asj, bamio, coverage, ends, indels, isoforms, retention, somatic, vcf
+from . import pairs as _pairs   # (run() has a local of that name)
 
 _ann = annotation    # (run() has a parameter of the module's name, as the reference's -a)
 
@@ -125,7 +126,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         isoforms_out=None, isoform_min_count=10, isoform_min_junctions=1,
         ends_out=None, ends_min_count=10, ends_window=10, ends_strand="ts",
         retention_out=None, retention_min_count=10, retention_anchor=10, retention_min_retained=1,
-        indels_out=None, indel_min_count=10, indel_min_permille=150, indel_flank=5, indel_max_ins=12, indel_max_del=50, **param_overrides):
+        indels_out=None, indel_min_count=10, indel_min_permille=150, indel_flank=5, indel_max_ins=12, indel_max_del=50,
+        pairs_out=None, pairs_partners=2, pairs_min_count=10, pairs_min_baseq=13, mnv_out=None, mnv_max_dist=2, mnv_min_count=3, mnv_min_frac=0.8,
+        **param_overrides):
     """BAM + FASTA (+ .fai) -> phased VCF and, with out_bam, the phased BAM.  Returns a dict of counts.
     devices: GPUs to use (default [device]); a contig's regions are cut into chunks (chunk_regions) that the engines --
     one context and one host thread per device -- take in turn (regions are independent units, thread.rs:77; the BAM
@@ -260,7 +263,20 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
     (<= 4096) columns on either side (indels.genotype).  A value outside its range is a ValueError before any GPU work.  Every chunk
     calls Engine.indels behind phase() / haplotag() and the other table calls; that call waits for the phase stage, like theirs.  Adds
     the stats indel_events (kept records, summed over chunks) and indel_calls (records written with PASS).  No other output depends on
-    it; without indels_out nothing changes."""
+    it; without indels_out nothing changes.
+    pairs_out / pairs_partners / pairs_min_count / pairs_min_baseq: the read-backed check of the phase (include/lcr.h: lcr_site_pairs;
+    pairs.format_pairs_tsv), written to pairs_out: one row per pair of phased het sites of eligible rank difference 1..pairs_partners
+    (1..8; no distance limit) that at least pairs_min_count rows hold with both qualities >= pairs_min_baseq (0..30) -- the 2 x 2 table
+    of their bases, the reads' own orientation (cis / trans / tie), whether the phase agrees, and a Fisher p-value.
+    mnv_out / mnv_max_dist / mnv_min_count / mnv_min_frac: the multi-nucleotide variants (pairs.mnv_records), written to mnv_out as a
+    second VCF with the run's header plus the tags SITES and RB: runs of two or three PASS calls of the main VCF at most mnv_max_dist
+    (>= 1) apart, all 1/1 or all on one haplotype of one phase set, merged where at least mnv_min_count rows, and at least mnv_min_frac
+    (0..1) of the rows with an ALT base at either site, carry the ALT base at both.  The main VCF keeps the constituent sites.  A value
+    outside its range is a ValueError before any GPU work.  Every chunk calls Engine.site_pairs("phased", pairs_partners, 0,
+    pairs_min_baseq) and / or Engine.site_pairs("all", 2, mnv_max_dist, pairs_min_baseq) behind phase() / haplotag() and the other table
+    calls; the call waits for the phase stage, like theirs.  Adds the stats site_pairs (records, summed over chunks) and
+    phase_disagreements (rows of the table whose phase is contradicted) with pairs_out, mnv_records with mnv_out.  No other output
+    depends on them; without the two options nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     import threading
     truncation = bool(truncation)
@@ -295,6 +311,14 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
                               ("indel_flank", indel_flank, 4096), ("indel_max_ins", indel_max_ins, 12), ("indel_max_del", indel_max_del, 65535)):
             if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= most:
                 raise ValueError("%s must be an integer in [0, %d], got %r" % (what, most, v))
+    if pairs_out is not None or mnv_out is not None:
+        for what, v, least, most in (("pairs_partners", pairs_partners, 1, _abi.PAIRS_MAX_PARTNERS), ("pairs_min_count", pairs_min_count, 0, (1 << 32) - 1),
+                                     ("pairs_min_baseq", pairs_min_baseq, 0, 30), ("mnv_max_dist", mnv_max_dist, 1, (1 << 32) - 1),
+                                     ("mnv_min_count", mnv_min_count, 0, (1 << 32) - 1)):
+            if isinstance(v, bool) or int(v) != v or not least <= int(v) <= most:
+                raise ValueError("%s must be an integer in [%d, %d], got %r" % (what, least, most, v))
+        if isinstance(mnv_min_frac, bool) or not 0.0 <= float(mnv_min_frac) <= 1.0:      # (NaN fails both comparisons)
+            raise ValueError("mnv_min_frac must be a number in [0, 1], got %r" % (mnv_min_frac,))
     if exon_only and annotation is None:
         raise ValueError("exon_only is set, but annotation file is not provided")      # main.rs:436-438
     gene_clusters, gene_cds = _ann.calling_annotation(annotation) if annotation is not None else (None, None)
@@ -378,7 +402,7 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
 
     def finish(k):          # collect engine k's chunk in flight
         E = engines[k]
-        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret, ind = in_flight[k]
+        idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret, ind, prs, mnv = in_flight[k]
         in_flight[k] = None
         res = E.collect_phase()
         cands = res["cand"]
@@ -425,6 +449,10 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             out["retention"] = (name, ret[0], batch.start0, batch.len, int(np.count_nonzero(ret[2] > 0)))
         if ind is not None:     # (Engine.indels copied them out of the context's buffers)
             out["indels"] = (name, ind[0], [indels.alleles(r, batch.start0, batch.col_off, batch.ref) for r in ind[0]])
+        if prs is not None:     # (Engine.site_pairs copied them out of the context's buffers; cands is the context's buffer)
+            out["pairs"] = (name, cands.copy(), prs[0])
+        if mnv is not None:
+            out["mnv"] = (name, _pairs.mnv_records(cands, mnv[0], mnv[1], refs[name], 0, min_ps, mnv_max_dist, mnv_min_count, mnv_min_frac, 2))
         results[idx] = out
 
     def work(idx, batch, name, want_reads, imp, mask, hs=None):   # one chunk on whichever engine is free (imp: its sites, or None: call candidates; mask: its CDS lists, or None; hs: its phased sites, or None: phase())
@@ -486,7 +514,9 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
             ret = E.intron_retention(retention_min_count, retention_anchor) if retention_out is not None else None   # (waits for the phase stage)
             ind = (E.indels(indel_min_count, indel_min_permille, indel_flank, indel_max_ins, indel_max_del)
                    if indels_out is not None else None)   # (waits for the phase stage)
-            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret, ind)
+            prs = E.site_pairs("phased", pairs_partners, 0, pairs_min_baseq) if pairs_out is not None else None   # (waits for the phase stage)
+            mnv = E.site_pairs("all", 2, mnv_max_dist, pairs_min_baseq) if mnv_out is not None else None          # (waits for the phase stage)
+            in_flight[k] = (idx, name, batch, want_reads, fm, junc, arec, srec, hcov, som, iso, tends, ret, ind, prs, mnv)
         finally:
             with free_lock:
                 free.append(k)
@@ -658,6 +688,15 @@ def run(bam_path, ref_path, out_vcf, out_bam=None, preset="hifi-masseq", contigs
         stats["indel_events"] = sum(int(r["indels"][1].size) for r in results)
         stats["indel_calls"] = n_pass
         write_vcf(indels_out, contig_lengths, [text], indels.INFO_LINES)
+    if pairs_out is not None:
+        text = _pairs.format_pairs_tsv([r["pairs"] for r in results], pairs_min_count, min_ps)
+        stats["site_pairs"] = sum(int(r["pairs"][2].size) for r in results)
+        stats["phase_disagreements"] = sum(1 for line in text.splitlines()[1:] if line.split("\t")[18] == "disagree")
+        with open(pairs_out, "w") as f:
+            f.write(text)
+    if mnv_out is not None:
+        text, stats["mnv_records"] = _pairs.format_mnv_vcf([r["mnv"] for r in results], [name for name, _ in contig_lengths])
+        write_vcf(mnv_out, contig_lengths, [text], _pairs.INFO_LINES)
     if out_bam is not None:
         hp = np.concatenate([r["hp"] for r in results]) if results else np.zeros(0, np.int32)
         ps = np.concatenate([r["ps"] for r in results]) if results else np.zeros(0, np.uint32)

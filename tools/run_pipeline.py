@@ -16,6 +16,8 @@
                                  [--hap-coverage-out PREFIX]   (PREFIX.h1 / .h2 / .unassigned.bedgraph: covered depth per HP tag)
                                  [--somatic-out out.somatic.vcf [--somatic-purity P] [--somatic-min-baseq N] [--somatic-min-score S]]   (haplotype-resolved somatic calls at low-fraction sites)
                                  [--isoforms-out out.isoforms.tsv [--isoform-min-count N] [--isoform-min-junctions N]]   (allele-specific isoform table: haplotype x intron chain)
+                                 [--pairs-out out.pairs.tsv [--pairs-partners K] [--pairs-min-count N] [--pairs-min-baseq N]]   (read-backed check of the phase: cis / trans rows per pair of phased sites)
+                                 [--mnv-out out.mnv.vcf [--mnv-max-dist D] [--mnv-min-count N] [--mnv-min-frac F]]   (adjacent calls on one haplotype merged into multi-nucleotide variants)
 """
 import argparse
 import json
@@ -85,6 +87,14 @@ def main():
     ap.add_argument("--indel-flank", type=int, default=5, help="clean columns on either side of an indel's extent a read without it must cover (0 - 4096)")
     ap.add_argument("--indel-max-ins", type=int, default=12, help="longest insertion that is an event (0 - 12)")
     ap.add_argument("--indel-max-del", type=int, default=50, help="longest deletion that is an event (0 - 65535)")
+    ap.add_argument("--pairs-out", help="write the read-backed check of the phase: a TSV with one row per pair of nearby phased het sites, the 2 x 2 table of the bases their shared reads carry, cis / trans, and whether the phase agrees")
+    ap.add_argument("--pairs-partners", type=int, default=2, help="following phased sites every site is paired with (1 - 8)")
+    ap.add_argument("--pairs-min-count", type=int, default=10, help="counted shared reads a pair needs for a row")
+    ap.add_argument("--pairs-min-baseq", type=int, default=13, help="base quality both entries of a read need to be counted in --pairs-out / --mnv-out (0 - 30)")
+    ap.add_argument("--mnv-out", help="write the multi-nucleotide variants: a second VCF with one record per run of two or three adjacent PASS calls on one haplotype (or all 1/1) that the reads carry together")
+    ap.add_argument("--mnv-max-dist", type=int, default=2, help="largest distance of consecutive sites of a run (>= 1)")
+    ap.add_argument("--mnv-min-count", type=int, default=3, help="reads that must carry the ALT base at both sites of every pair of a run")
+    ap.add_argument("--mnv-min-frac", type=float, default=0.8, help="... and their share of the reads with an ALT base at either site (0 - 1)")
     ap.add_argument("--read-assign-cutoff", type=float, default=None, help="min_read_assignment_diff (preset: 0.0)")
     a = ap.parse_args()
     if a.haplotag and not a.input_vcf:
@@ -112,6 +122,9 @@ def main():
         ap.error("--ends-min-count must be >= 0 and --ends-window lie in 0 - 4096")
     if a.retention_min_count < 0 or a.retention_min_retained < 0 or not 0 <= a.retention_anchor <= 4096:
         ap.error("--retention-min-count and --retention-min-retained must be >= 0 and --retention-anchor lie in 0 - 4096")
+    if (not 1 <= a.pairs_partners <= 8 or a.pairs_min_count < 0 or not 0 <= a.pairs_min_baseq <= 30 or a.mnv_max_dist < 1 or a.mnv_min_count < 0
+            or not 0.0 <= a.mnv_min_frac <= 1.0):
+        ap.error("--pairs-partners must lie in 1 - 8, --pairs-min-baseq in 0 - 30 and --mnv-min-frac in 0 - 1, --mnv-max-dist be >= 1, --pairs-min-count and --mnv-min-count >= 0")
     if (a.indel_min_count < 0 or a.indel_min_permille < 0 or not 0 <= a.indel_flank <= 4096 or not 0 <= a.indel_max_ins <= 12
             or not 0 <= a.indel_max_del <= 65535):
         ap.error("--indel-min-count and --indel-min-permille must be >= 0, --indel-flank lie in 0 - 4096, --indel-max-ins in 0 - 12 and --indel-max-del in 0 - 65535")
@@ -139,7 +152,9 @@ def main():
                       retention_out=a.retention_out, retention_min_count=a.retention_min_count, retention_anchor=a.retention_anchor,
                       retention_min_retained=a.retention_min_retained,
                       indels_out=a.indels_out, indel_min_count=a.indel_min_count, indel_min_permille=a.indel_min_permille, indel_flank=a.indel_flank,
-                      indel_max_ins=a.indel_max_ins, indel_max_del=a.indel_max_del, **extra)
+                      indel_max_ins=a.indel_max_ins, indel_max_del=a.indel_max_del,
+                      pairs_out=a.pairs_out, pairs_partners=a.pairs_partners, pairs_min_count=a.pairs_min_count, pairs_min_baseq=a.pairs_min_baseq,
+                      mnv_out=a.mnv_out, mnv_max_dist=a.mnv_max_dist, mnv_min_count=a.mnv_min_count, mnv_min_frac=a.mnv_min_frac, **extra)
     print(json.dumps(st))
 
 
